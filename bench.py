@@ -10,9 +10,18 @@ adds the sampler-level exchange of config 5 (an all-gather of the per-chain log-
 P steps, mirroring MC3's SwapPeriod, app/Main.hs:477); it is off by default because it is not part
 of the likelihood path.
 
-Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel against HBM (north_star);
-`cpu_baseline` times the CPU oracle (a restatement of the reference's algebra -- the Haskell
-toolchain is absent) on a bounded sample on rank 0's host core.
+Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel against HBM (north_star) from
+the timed steps themselves.  A plain run does only that: set up, warm up, time `--steps` steps, write
+the outputs if asked, print the line.  `--full` adds what takes runs of its own: the check of the
+log-density batch against a separate evaluation by the column sweep, the secondary Metropolis-Hastings
+lines (`mh`, `mh_config5_share`, `mh_sparse`), `full_gpu`, and `cpu_baseline` (the CPU oracle, a
+restatement of the reference's algebra -- the Haskell toolchain is absent -- timed on a bounded sample on
+rank 0's host cores).
+
+`--dump-outputs DIR` writes, after the timed steps, the arrays the timed path handed back in its last
+steps as DIR/<name>.npy (float64; rank r > 0 adds `_rank<r>`; at most 64 MB in all, larger outputs
+as a fixed, seeded sample of their rows).  The inputs depend only on the arguments, so two builds can
+be compared output for output.
 """
 import argparse
 import json
@@ -28,6 +37,26 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 FP64_PEAK_TFLOPS = 78.6    # vector fp64 FMA peak (256 CU x 4 SIMD x 16 lanes x 2 flop x 2.4 GHz)
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays, rank=0, world=1):
+    """--dump-outputs: every array as float64 DIR/<name>.npy (DIR/<name>_rank<r>.npy for r > 0).  If the run's outputs exceed
+    64 MB in all, each keeps the same fraction of its rows, drawn once by a fixed seed, so that two runs stay comparable."""
+    os.makedirs(directory, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        if hasattr(a, "detach"):
+            a = a.detach().cpu().numpy()
+        host[name] = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+    budget = DUMP_BUDGET_BYTES // max(1, world)
+    total = sum(a.nbytes for a in host.values())
+    suffix = f"_rank{rank}" if rank > 0 else ""
+    for name, a in host.items():
+        if total > budget and a.ndim >= 1 and a.shape[0] > 1:
+            keep = max(1, (a.shape[0] * budget) // total)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(directory, name + suffix + ".npy"), a)
 
 
 def algorithmic_bytes_per_eval(n: int, batch: int) -> float:
@@ -93,7 +122,7 @@ def cpu_baseline(n, mu, sigma, X, budget_s=12.0):
 
 
 def mh_measure(dev_index, n, B, steps, warm, seed=3, rank=0, world=1, swap_period=0, swap_steps=0, rehearsal=False, sparse=False, repeats=1,
-               tune_periods=0):
+               tune_periods=0, outputs=None):
     """Lock-step Metropolis-Hastings on the device (the metric's "= MCMC steps/sec x chains" reading):
     a synthetic tree of dimension n (255 for --n 256: 2L - 3 is odd), the reference's whole proposal cycle
     (app/Definitions.hs:127-278) in its shuffled order, B chains per GPU stepping together; one step = one proposal of the cycle,
@@ -106,7 +135,8 @@ def mh_measure(dev_index, n, B, steps, warm, seed=3, rank=0, world=1, swap_perio
     warm-up, T periods of one iteration of the cycle each followed by `mcmc`'s auto-tuning (mcd_mh_tune) -- the reference always samples
     with tuned proposals (burnIn = BurnInWithCustomAutoTuning, app/Definitions.hs:420-424); the untuned default accepts most proposals,
     which is the expensive case for the persistent kernels (a proposal drawn ahead is thrown away after an acceptance).  The line says
-    which acceptance rate the timed steps had.  Returns a dict for the JSON line."""
+    which acceptance rate the timed steps had.  Returns a dict for the JSON line; a dict passed as `outputs` receives the chains' states
+    and ln posteriors after the timed steps (--dump-outputs)."""
     import torch
 
     import mcmc_date_amd as M
@@ -196,6 +226,11 @@ def mh_measure(dev_index, n, B, steps, warm, seed=3, rank=0, world=1, swap_perio
     _, n_acc, n_try = smp.tuning()
     post = smp.posterior()
     assert np.all(np.isfinite(post)), "non-finite ln posterior after the Metropolis-Hastings run"
+    if outputs is not None:
+        st = smp.state()
+        outputs.update({"heights": st.heights, "rates": st.rates, "time_height": st.time_height, "rate_mean": st.rate_mean,
+                        "rate_variance": st.rate_variance, "time_birth_rate": st.time_birth_rate, "time_death_rate": st.time_death_rate,
+                        "ln_posterior_terms": post})
     if mc3 is not None:
         rk = mc3.rank
         assert all(sorted(rk[g * 4:(g + 1) * 4].tolist()) == [0, 1, 2, 3] for g in range(len(rk) // 4)), "temperature ranks are not a permutation"
@@ -254,10 +289,11 @@ def full_gpu_measure(dev_index, n, chains=8192, launches=200):
                          "hbm_gbs": hbm, "hbm_frac": hbm / HBM_PEAK_GBS}}
 
 
-def sparse_measure(dev_index, n, B, steps, warm, band=3, extra=4):
+def sparse_measure(dev_index, n, B, steps, warm, band=3, extra=4, check=True, outputs=None):
     """The sparse form (csrc/k_sparse.hip; logDensitySparseMultivariateNormal, app/Probability.hs:178-184): a synthetic symmetric,
     diagonally dominant precision matrix with a band and `extra` random entries per row -- the density a graphical-lasso estimate of a
-    large tree has -- B chains, device resident.  HBM-priced: the CSR stream (12 bytes per nonzero) once per launch plus the chain vectors."""
+    large tree has -- B chains, device resident.  HBM-priced: the CSR stream (12 bytes per nonzero) once per launch plus the chain vectors.
+    check: the batch against scipy.sparse after the clock (--full); a dict passed as `outputs` receives the log-densities."""
     import torch
 
     import mcmc_date_amd as M
@@ -287,11 +323,14 @@ def sparse_measure(dev_index, n, B, steps, warm, band=3, extra=4):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     per = e0.elapsed_time(e1) * 1e-3 / steps
-    dx = X.cpu().numpy() - mu
-    Pc = P.tocsr()
-    ref = -n * 0.9189385332046727 - 0.5 * np.einsum("bi,bi->b", dx, (Pc @ dx.T).T)
-    err = float(np.max(np.abs(ll.cpu().numpy() - ref) / np.abs(ref)))
-    assert err <= 1e-12, f"sparse form differs from scipy.sparse: {err}"
+    if outputs is not None:
+        outputs["loglik"] = ll
+    if check:
+        dx = X.cpu().numpy() - mu
+        Pc = P.tocsr()
+        ref = -n * 0.9189385332046727 - 0.5 * np.einsum("bi,bi->b", dx, (Pc @ dx.T).T)
+        err = float(np.max(np.abs(ll.cpu().numpy() - ref) / np.abs(ref)))
+        assert err <= 1e-12, f"sparse form differs from scipy.sparse: {err}"
     alg = 12.0 * sp.nnz + 4.0 * (n + 1) + 8.0 * n + B * (8.0 * n + 8.0)
     flops = (2.0 * sp.nnz + 3.0 * n) * B / per / 1e12
     return dt, per, {"n": int(n), "nnz": int(sp.nnz), "chains": int(B), "chains_per_tile": int({True: 16}.get(False, 0)) or None,
@@ -308,7 +347,7 @@ def haskell_toolchain():
     return {t: shutil.which(t) for t in ("ghc", "cabal", "stack")}
 
 
-def e2e_measure(dev_index, chains=128, iterations=8000, period=2, seed=21, cpu_budget_s=15.0):
+def e2e_measure(dev_index, chains=128, iterations=8000, period=2, seed=21, cpu_budget_s=15.0, outputs=None):
     """The reference's ONLY published timing, end to end: the posterior analysis of the 7-taxon mtCDNApri data --
     `./run -s -f analysis.conf -c ul s r`: sparse multivariate normal likelihood (graphical lasso 0.1), uncorrelated log-normal clock,
     calibrations from the MCMCtree-style tree, the burn-in schedule with auto tuning (app/Definitions.hs:420-424) + 8000 iterations
@@ -317,7 +356,7 @@ def e2e_measure(dev_index, chains=128, iterations=8000, period=2, seed=21, cpu_b
     step on the device through the NATIVE sparse handle (mcd_mh_create_sparse: every proposal inside a segment launch), the chains'
     states fetched every 2 iterations as the monitors would; the node ages against the reference's committed samples
     (tests/golden/mtCDNApri_post_samples.json; must stay within 1 %).  Beside it the CPU twin (oracle/mh_oracle.c, a restatement) timed on
-    a bounded sample on this box's host cores."""
+    a bounded sample on this box's host cores.  A dict passed as `outputs` receives the monitored node ages and the final ln posteriors."""
     import tempfile
 
     import mcmc_date_amd as M
@@ -361,6 +400,8 @@ def e2e_measure(dev_index, chains=128, iterations=8000, period=2, seed=21, cpu_b
     run_device()                                            # (untimed: code objects, allocations)
     smp, tr, burn_s, run_s = run_device()
     ages = tr.ages()[:, :, post["nodes"]].reshape(-1, len(post["nodes"]))
+    if outputs is not None:
+        outputs.update({"node_ages": ages, "ln_posterior_terms": smp.posterior()})
     ref = {k: np.array(v) for k, v in post["pooled"].items()}
     dev = np.abs(ages.mean(axis=0) - ref["mean"]) / ref["mean"]
     assert np.all(dev <= 0.01), f"node ages off the reference's committed samples: {dev}"
@@ -506,6 +547,10 @@ def main():
     ap.add_argument("--no-mh", action="store_true", help="skip the secondary Metropolis-Hastings measurement of the default run")
     ap.add_argument("--sparse", action="store_true", help="--kind mh: the likelihood over a sparse precision matrix (mcd_mh_create_sparse), the reference's "
                     "production configuration; any --dim up to 2046")
+    ap.add_argument("--full", action="store_true", help="also what takes runs of its own: the check against the column sweep (--kind logpdf) or "
+                    "scipy.sparse (--kind sparse), the secondary Metropolis-Hastings lines, full_gpu and cpu_baseline (default: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed as DIR/<name>.npy "
+                    "(float64, at most 64 MB in all)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -546,8 +591,11 @@ def main():
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
+        outputs = {} if args.dump_outputs else None
         r = mh_measure(dev_index, n, B, K, W, seed=3, rank=rank, world=world, swap_period=args.swap_period, swap_steps=args.swap_steps, tune_periods=args.tune_periods,
-                       rehearsal=rehearsal, sparse=args.sparse)
+                       rehearsal=rehearsal, sparse=args.sparse, outputs=outputs)
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs, rank, world)
         elapsed = K * r["us_per_lockstep"] * 1e-6
         ranks = rank_report(dist, world, rank, elapsed, K, ctl_dev, rehearsal, r.get("rccl_comm_ranks"))
         if world > 1:
@@ -594,7 +642,10 @@ def main():
         if world > 1:
             raise SystemExit("bench.py --kind e2e runs on one GPU (the analysis is one batch of chains)")
         chains = args.chains if args.chains != 512 else 128
-        r = e2e_measure(dev_index, chains=chains)
+        outputs = {} if args.dump_outputs else None
+        r = e2e_measure(dev_index, chains=chains, outputs=outputs)
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         n_it = r["iterations"] + r["burn_in_iterations"]
         print(json.dumps({
             "metric": "MVN log-likelihood evals/sec (= MCMC steps/sec \u00d7 chains) at N=256 nodes", "value": r["proposal_steps_per_s"],
@@ -608,7 +659,10 @@ def main():
         return
     if args.kind == "sparse":
         K, W = args.steps, args.warmup
-        dt, per, r = sparse_measure(dev_index, n, B, K, W)
+        outputs = {} if args.dump_outputs else None
+        dt, per, r = sparse_measure(dev_index, n, B, K, W, check=args.full, outputs=outputs)
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs, rank, world)
         if rank == 0:
             r.pop("chains_per_tile")
             print(json.dumps({
@@ -695,6 +749,20 @@ def main():
                                                       st.time_height.data_ptr(), st.rate_mean.data_ptr(), B, 1,
                                                       torch.cuda.current_stream().cuda_stream, ll.data_ptr(), gH.data_ptr(),
                                                       gR.data_ptr(), gt.data_ptr(), gm.data_ptr()))
+
+    # what a caller of the timed path receives (--dump-outputs); logpdf alternates two batches, each with its own output
+    if args.kind == "logpdf":
+        outputs = {"loglik": ll, "loglik_alt": ll2}
+    elif args.kind == "grad":
+        outputs = {"loglik": ll, "grad": G}
+    elif args.kind == "tree":
+        outputs = {"loglik": ll, "log_jacobian": lj}
+    elif args.kind == "tree_grad":
+        outputs = {"loglik": ll, "grad_heights": gH, "grad_rates": gR, "grad_time_height": gt, "grad_rate_mean": gm}
+    elif args.kind == "prior":
+        outputs = {"logprior": lp}
+    else:
+        outputs = {"logprior": lp, "loglik": ll, "log_jacobian": lj}
 
     gathered = torch.empty(world * B, dtype=torch.float64, device=ctl_dev) if (world > 1 and args.swap_period > 0) else None
     # which form the launch takes (mirror of use_wide / use_wide_grad in csrc/k_logpdf.hip)
@@ -798,13 +866,15 @@ def main():
     # batches against a separate evaluation by the column sweep on another handle)
     ll_host = ll.cpu().numpy()
     assert np.all(np.isfinite(ll_host)) or os.environ.get("MCD_SPLIT_PROBE"), "non-finite log-likelihood in the bench batch"
-    if args.kind == "logpdf" and not os.environ.get("MCD_SPLIT_PROBE"):
+    if args.full and args.kind == "logpdf" and not os.environ.get("MCD_SPLIT_PROBE"):
         chk = M.MvnLikelihood.from_covariance(mu, sigma, device=dev_index)
         chk.set_form("sweep")
         for xs, out in ((X, ll), (X2, ll2)):
             ref = chk.logpdf(xs)
             err = float(((out - ref).abs() / ref.abs()).max())
             assert err <= 1e-11, f"bench batch differs from the sweep form: {err}"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs, rank, world)
 
     if rank == 0:
         evals = float(K) * B * world
@@ -856,7 +926,7 @@ def main():
                     out["roofline"]["traffic_source"] = "profiles/" + os.path.basename(fs[-1]) + "[pmc_traffic_n256_b8192] (committed rocprofv3 --pmc passes)"
                 except Exception:
                     pass
-        if world == 1 and args.kind == "logpdf" and not args.no_mh:
+        if args.full and world == 1 and args.kind == "logpdf" and not args.no_mh:
             # the metric's "= MCMC steps/sec x chains": real Metropolis-Hastings steps on a tree of this size (secondary field)
             out["mh"] = mh_measure(dev_index, n, B, 4000, 400, repeats=2)
             if n == 256 and B == 512:
@@ -876,9 +946,9 @@ def main():
                         out["mh_sparse"].append({k: rs[k] for k in ("value", "unit", "us_per_lockstep", "n_nodes", "dimension", "chains", "lock_steps", "likelihood", "lds_bytes_per_workgroup", "acceptance_rate", "what")})
                 except Exception as e:
                     out["mh_sparse"] = {"error": repr(e)}
-        if world == 1 and args.kind == "logpdf" and not args.no_mh and B <= 1024:
+        if args.full and world == 1 and args.kind == "logpdf" and not args.no_mh and B <= 1024:
             out["full_gpu"] = full_gpu_measure(dev_index, n)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(n, mu, sigma, X_host)
         print(json.dumps(out))
     if world > 1:

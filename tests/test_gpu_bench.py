@@ -113,3 +113,32 @@ def test_tuned_metropolis_hastings_line(gpu):
         assert "segments over a sparse precision matrix" in mh["what"]
         rates.append(mh["acceptance_rate"])
     assert 0.2 < rates[1] < 0.55 and abs(rates[1] - 0.35) < abs(rates[0] - 0.35) + 0.02, rates
+
+
+def test_full_and_dump_outputs_options_exist():
+    """`--full` (the measurements that take runs of their own) and `--dump-outputs DIR` are options of every run."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs" in p.stdout
+
+
+@pytest.mark.gpu
+def test_plain_line_is_lean_and_dumps_its_outputs(gpu, tmp_path):
+    """A plain run carries the headline only; --dump-outputs writes the timed path's log-densities (both alternating batches) as float64,
+    and the same arguments give the same inputs, hence the same outputs.  --full still runs the check against the column sweep."""
+    import numpy as np
+
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        line = _one_line(_run_bench(["--steps", "20", "--warmup", "5", "--dump-outputs", str(d)]))
+        assert line["steps"] == 20 and math.isfinite(line["ms_per_step"]) and line["ms_per_step"] > 0
+        for k in ("mh", "mh_config5_share", "mh_sparse", "full_gpu", "cpu_baseline"):
+            assert k not in line
+        arrs = {n: np.load(d / f"{n}.npy") for n in ("loglik", "loglik_alt")}
+        for a in arrs.values():
+            assert a.dtype == np.float64 and a.shape == (512,) and np.all(np.isfinite(a))
+        runs.append(arrs)
+    for n in runs[0]:
+        assert np.allclose(runs[0][n], runs[1][n], rtol=1e-12, atol=0), n
+    line = _one_line(_run_bench(["--steps", "20", "--warmup", "5", "--full", "--no-mh", "--no-cpu-baseline"]))
+    assert line["steps"] == 20 and "cpu_baseline" not in line and "mh" not in line

@@ -1,5 +1,6 @@
 """`prepare` (row f4, data contract): the product's host-side restatement against the oracle's independent
-one, on the reference's own tree lists.  Needs /root/reference (build container only): skipped elsewhere."""
+one, on the reference's own tree lists -- kept under tests/golden/inputs/ (the long tree lists xz-compressed)."""
+import lzma
 import os
 
 import numpy as np
@@ -8,8 +9,23 @@ import pytest
 import mcmc_date_amd as M
 from mcmc_date_amd import prepare as PP
 
-REF = "/root/reference/tests"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference inputs are not available on this machine")
+INPUTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "inputs")
+
+
+@pytest.fixture(scope="session")
+def ref(tmp_path_factory):
+    """The reference's test directories as `prepare` reads them: tests/golden/inputs/ with every `*.xz` unpacked."""
+    out = tmp_path_factory.mktemp("reference_tests")
+    for d, _, files in os.walk(INPUTS):
+        dst = out / os.path.relpath(d, INPUTS)
+        dst.mkdir(parents=True, exist_ok=True)
+        for f in files:
+            data = open(os.path.join(d, f), "rb").read()
+            if f.endswith(".xz"):
+                f, data = f[:-3], lzma.decompress(data)
+            (dst / f).write_bytes(data)
+    return str(out)
+
 
 CASES = {
     "06-leaves-constant-rate": ("data/test.treelist", "data/time.tree"),
@@ -19,9 +35,9 @@ CASES = {
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
-def test_prepare_matches_fixture_operands(golden, name, tmp_path):
+def test_prepare_matches_fixture_operands(golden, name, tmp_path, ref):
     tl, rt = CASES[name]
-    p = PP.prepare(os.path.join(REF, name, tl), os.path.join(REF, name, rt))
+    p = PP.prepare(os.path.join(ref, name, tl), os.path.join(ref, name, rt))
     fx = golden[name]
     assert p.n_trees - p.n_burn_in == int(fx["n_trees_kept"])
     assert np.array_equal(p.topology.parent, fx["parent"])
@@ -38,11 +54,11 @@ def test_prepare_matches_fixture_operands(golden, name, tmp_path):
     assert topo2.names[0] == "0" and all(n for n in topo2.names)
 
 
-def test_prepare_bastien_annotated_newick():
+def test_prepare_bastien_annotated_newick(ref):
     """25-leaves-bastien: BEAST-style annotated Newick ([&index=..] comments), 3001 trees."""
     import oracle.prepare as OP
 
-    d = os.path.join(REF, "25-leaves-bastien", "data")
+    d = os.path.join(ref, "25-leaves-bastien", "data")
     p = PP.prepare(os.path.join(d, "alignment.fasta.trees.only"), os.path.join(d, "time.tree"))
     assert len(p.mu) == 47 and p.n_trees == 3001 and p.n_burn_in == 500
     o = OP.prepare(os.path.join(d, "alignment.fasta.trees.only"), os.path.join(d, "time.tree"))
@@ -50,11 +66,11 @@ def test_prepare_bastien_annotated_newick():
     assert abs(p.lhd.logdet_sigma - o.logdet) < 1e-9 and np.all(np.linalg.eigvalsh(p.sigma) > 0)
 
 
-def test_prepare_reroots_when_needed(tmp_path):
+def test_prepare_reroots_when_needed(tmp_path, ref):
     """A rooted tree with another root: every tree of the list is re-rooted at its outgroup."""
     tl, rt = CASES["06-leaves-constant-rate"]
-    a = os.path.join(REF, "06-leaves-constant-rate", tl)
-    p0 = PP.prepare(a, os.path.join(REF, "06-leaves-constant-rate", rt))
+    a = os.path.join(ref, "06-leaves-constant-rate", tl)
+    p0 = PP.prepare(a, os.path.join(ref, "06-leaves-constant-rate", rt))
     alt = tmp_path / "alt.tree"
     alt.write_text("((a:1,b:1):1,(c:1,(d:1,(e:1,f:1):1):1):1);")
     p1 = PP.prepare(a, str(alt))
@@ -74,9 +90,9 @@ def test_prepare_reroots_when_needed(tmp_path):
         PP.prepare(a, str(bad))
 
 
-def test_prepare_other_specs(tmp_path):
+def test_prepare_other_specs(tmp_path, ref):
     tl, rt = CASES["06-leaves-constant-rate"]
-    a, b = os.path.join(REF, "06-leaves-constant-rate", tl), os.path.join(REF, "06-leaves-constant-rate", rt)
+    a, b = os.path.join(ref, "06-leaves-constant-rate", tl), os.path.join(ref, "06-leaves-constant-rate", rt)
     u = PP.prepare(a, b, "UnivariateNormal")
     assert isinstance(u.lhd, M.Univariate) and np.allclose(u.lhd.vs, np.diag(u.sigma))
     assert isinstance(PP.prepare(a, b, "NoLikelihood").lhd, M.NoData)
@@ -86,12 +102,12 @@ def test_prepare_other_specs(tmp_path):
         PP.prepare(a, b, "SomethingElse")
 
 
-def test_node_prior_loaders_match_fixtures(golden):
+def test_node_prior_loaders_match_fixtures(golden, ref):
     """calibrations.csv / constraints.csv / braces.json of the reference's test directories -> pre-order node ids."""
     for name in ("12-leaves-variable-rate", "24-leaves-braces"):
         fx = golden[name]
         topo = M.Topology(fx["parent"], list(fx["names"]))
-        d = os.path.join(REF, name, "data")
+        d = os.path.join(ref, name, "data")
         cals = M.load_calibrations(topo, os.path.join(d, "calibrations.csv"))
         assert [c.node for c in cals] == [int(r[0]) for r in fx["cal"]]
         assert [c.lower for c in cals] == [r[2] for r in fx["cal"]] and [c.upper for c in cals] == [r[5] for r in fx["cal"]]

@@ -19,8 +19,8 @@ for cfg in "n256:" "n1024:--n 1024" "tree255:--kind tree" "tree1023:--n 1024 --k
 done
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/mh_trace -- python3 $ROOT/bench.py --kind mh --steps 2000 --warmup 200 > $OUT/mh_bench.json 2> $OUT/mh_trace.log
 cd $ROOT
-python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.log
-python3 bench.py --n 1024 > $OUT/bench_n1024.json 2> $OUT/bench_n1024.log
+python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.log
+python3 bench.py --full --n 1024 > $OUT/bench_n1024.json 2> $OUT/bench_n1024.log
 python3 bench.py --kind mh --steps 4000 --warmup 400 > $OUT/bench_mh.json 2> $OUT/bench_mh.log
 python3 - "$OUT" <<'PY'
 import csv, glob, json, os, statistics, sys

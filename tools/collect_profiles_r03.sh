@@ -33,8 +33,8 @@ MCD_MH_SEGMENTS=0 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv 
 MCD_MH_SEGMENTS=0 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/cfg5ns_pmc_write -- $CFG5 > /dev/null 2> $OUT/cfg5ns_pmc_write.log
 echo "traces done"
 cd $ROOT
-python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.log
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.log
+python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.log
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.log
 python3 bench.py --kind mh --steps 8000 --warmup 800 > $OUT/bench_mh.json 2> $OUT/bench_mh.log
 python3 bench.py --kind mh --dim 1024 --chains 512 --swap-period 2 --steps 31826 --warmup 1000 > $OUT/bench_cfg5_1gpu.json 2> $OUT/bench_cfg5_1gpu.log
 python3 bench.py --kind sparse --dim 2011 --chains 512 --steps 300 --warmup 30 > $OUT/bench_sparse.json 2> $OUT/bench_sparse.log

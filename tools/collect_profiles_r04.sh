@@ -37,8 +37,8 @@ run3 cfg5 $CFG5
 run3 smh1025 $SMH1025
 run3 smh2013 $SMH2013
 cd $ROOT
-python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.log
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.log
+python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.log
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.log
 python3 bench.py --kind mh --steps 8000 --warmup 800 > $OUT/bench_mh.json 2> $OUT/bench_mh.log
 python3 bench.py --kind mh --dim 1024 --chains 512 --swap-period 2 --steps 31826 --warmup 1000 > $OUT/bench_cfg5_1gpu.json 2> $OUT/bench_cfg5_1gpu.log
 python3 bench.py --kind mh --sparse --dim 2012 --chains 512 --steps 8000 --warmup 800 > $OUT/bench_mh_sparse_2013.json 2> $OUT/bench_mh_sparse_2013.log
