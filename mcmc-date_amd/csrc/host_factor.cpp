@@ -5,6 +5,7 @@
 // the Cholesky factor of Sigma and the two scaled, packed triangular factors the kernels stream.
 // Inner products are accumulated in long double: this runs once per analysis, accuracy wins.
 #include "host_factor.h"
+#include "fc_layout.hpp"
 #include "split_sched.hpp"
 
 #include <cmath>
@@ -113,6 +114,29 @@ void pack_factors(int n, int R, const std::vector<double>& L, std::vector<double
             // backward: U = L^T; row j, column i  ->  U_ji / U_jj = L_ij / L_jj
             Ut[packed_index(R, j, i)] = lij * invdiag[j];
         }
+    }
+}
+
+void pack_compact_forward(int R, const std::vector<double>& Ft, std::vector<double>& Fc)
+{
+    const int CP = fc_cp(R), CPB = fc_cpb(R);
+    Fc.assign((size_t)fc_total_units(R) * 128, 0.0);
+    auto unit = [&](int pair, int k) { return &Ft[((size_t)pair * R + k) * 128]; };   // 64 lanes x 2 columns
+    for (int ci = 0; ci < fc_nchunk(R); ++ci) {
+        const int JB = ci / CPB, lc = ci % CPB;
+        double* c = &Fc[(size_t)fc_chunk_base(R, ci) * 128];
+        for (int p = 0; p < CP; ++p) {                     // diagonal part: lanes 2 p' + 1 .. 63 of each pair
+            const int pl = lc * CP + p;
+            const double* u = unit(32 * JB + pl, JB);
+            double* dst = c + 2 * (size_t)fc_diag_start(R, lc, p);
+            for (int l = 2 * pl + 1; l < 64; ++l, dst += 2) {
+                dst[0] = u[2 * l];
+                dst[1] = u[2 * l + 1];
+            }
+        }
+        double* o = c + (size_t)fc_diag_units(R, lc) * 128;
+        for (int p = 0; p < CP; ++p)                       // off-diagonal units
+            for (int k = JB + 1; k < R; ++k, o += 128) std::memcpy(o, unit(32 * JB + lc * CP + p, k), 128 * sizeof(double));
     }
 }
 
@@ -293,4 +317,72 @@ extern "C" double mcd_split_schedule_selftest_(int n, int G, unsigned seed)
         direct += z * z;
     }
     return (double)(fabsl(total - direct) / direct);
+}
+
+// Host-only self test of the compact forward stream (tests/test_compact_stream.py, no GPU): packs a random lower-triangular factor
+// of dimension n both ways (pack_factors' Ft, pack_compact_forward's Fc), then unpacks Fc chunk by chunk exactly as the sweep reads
+// it (a diagonal unit's lane l of pair p' from the diagonal part when l > 2 p', else zero; the off-diagonal units in order) and
+// compares every element with Ft at packed_index, and every nonzero with the dense scaled factor.  Returns the number of units of Fc
+// (256 at n = 256) if all of it agrees, < 0 for a fault.
+extern "C" int mcd_compact_stream_selftest_(int n, unsigned seed)
+{
+    if (n < 1 || n > 1024) return -1;
+    int R = 0;
+    for (int a : {1, 2, 3, 4, 6, 8, 12, 16})
+        if (R == 0 && (n + 63) / 64 <= a) R = a;
+    if (R == 0) return -1;
+    unsigned long long st = 0x9E3779B97F4A7C15ull ^ seed;
+    auto rnd = [&]() {
+        st = st * 6364136223846793005ull + 1442695040888963407ull;
+        return (double)((st >> 11) & ((1ull << 53) - 1)) / (double)(1ull << 53) + 0.5;
+    };
+    std::vector<double> L((size_t)n * n, 0.0), mu(n, 0.0), mu_pad, invdiag, Ft, Ut, Fc;
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j <= i; ++j) L[(size_t)i * n + j] = rnd();        // in [0.5, 1.5): every scaled entry is nonzero
+    mcd::pack_factors(n, R, L, mu_pad, mu.data(), invdiag, Ft, Ut);
+    mcd::pack_compact_forward(R, Ft, Fc);
+    const int CP = mcd::fc_cp(R), CPB = mcd::fc_cpb(R), NP = 64 * R;
+    if (Fc.size() != (size_t)mcd::fc_total_units(R) * 128) return -2;
+    std::vector<double> D((size_t)NP * NP, 0.0);          // Fc unpacked: D[row * NP + col]
+    std::vector<int> seen((size_t)NP * NP, 0);
+    for (int ci = 0; ci < mcd::fc_nchunk(R); ++ci) {
+        const int JB = ci / CPB, lc = ci % CPB, ND = mcd::fc_diag_units(R, lc);
+        const double* c = &Fc[(size_t)mcd::fc_chunk_base(R, ci) * 128];
+        for (int p = 0; p < CP; ++p) {
+            const int pl = lc * CP + p, col = 64 * JB + 2 * pl;
+            for (int k = JB; k < R; ++k)
+                for (int l = 0; l < 64; ++l) {
+                    const double* e = nullptr;
+                    static const double zero[2] = {0.0, 0.0};
+                    if (k == JB) {
+                        const int idx = mcd::fc_diag_start(R, lc, p) - (2 * pl + 1) + l;
+                        e = l > 2 * pl ? c + 2 * (size_t)idx : zero;
+                        if (l > 2 * pl && idx >= 64 * ND) return -3;
+                    } else {
+                        e = c + ((size_t)ND + (size_t)p * (R - 1 - JB) + (k - JB - 1)) * 128 + 2 * l;
+                    }
+                    for (int h = 0; h < 2; ++h) {
+                        const size_t at = (size_t)(64 * k + l) * NP + col + h;
+                        D[at] = e[h];
+                        ++seen[at];
+                    }
+                }
+        }
+    }
+    for (int row = 0; row < NP; ++row)
+        for (int col = 0; col < NP; ++col) {
+            const size_t at = (size_t)row * NP + col;
+            const bool below = row >= 64 * (col / 64);     // a row block the sweep applies to this column
+            if (seen[at] != (below ? 1 : 0)) return -4;
+            const double f = Ft[mcd::packed_index(R, row, col)];
+            if (!below) {
+                if (f != 0.0) return -5;                   // (Ft holds zeros above the diagonal block)
+                continue;
+            }
+            if (D[at] != f) return -6;
+            const double want = (row < n && col < row) ? L[(size_t)row * n + col] / L[(size_t)row * n + row] : 0.0;
+            if ((col < row && row < n) && (D[at] == 0.0 || std::fabs(D[at] - want) > 1e-15 * std::fabs(want))) return -7;
+            if (!(col < row && row < n) && D[at] != 0.0) return -8;
+        }
+    return mcd::fc_total_units(R);
 }

@@ -19,6 +19,8 @@ size_t packed_index(int R, int row, int col);
 // mu / invdiag padded to 64 R, forward factor L_ij/L_ii and backward factor L_ij/L_jj packed.
 void pack_factors(int n, int R, const std::vector<double>& L, std::vector<double>& mu_pad, const double* mu,
                   std::vector<double>& invdiag, std::vector<double>& Ft, std::vector<double>& Ut);
+// The compact forward stream (fc_layout.hpp) from the padded one: fc_total_units(R) units of 128 doubles.
+void pack_compact_forward(int R, const std::vector<double>& Ft, std::vector<double>& Fc);
 
 // W = L^-1 (row-major lower triangular, given) as the operand tiles k_wide.hip streams: row block ib (16 rows) holds the
 // k tiles kt = 0 .. 4 (ib + 1) - 1 (4 columns each) at tile index 2 ib (ib + 1) + kt; a tile is 64 doubles in lane

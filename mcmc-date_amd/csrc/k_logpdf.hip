@@ -6,22 +6,16 @@
 
 namespace mcd {
 
-template <int R, int BT, int CW, int LW>
+template <int R, int BT, int CW, int LW, int FS>
 __global__ void __launch_bounds__(64 * (CW + LW)) k_logpdf(MvnDev M, const double* __restrict__ X, int64_t ldx,
                                                            int64_t batch, double* __restrict__ ll)
 {
-    MCD_KERNEL_HEAD
+    MCD_KERNEL_HEAD_FS(FS)
     MCD_ACC_DECL
     MCD_T(0);
     if (wave >= CW) {                                      // loader role
-        Stage<R, LW> st;
         const int lw = wave - CW;
-        fwd_loader_prologue<R, LW>(M.Ft, ring, st, lw, lane);
-        MCD_T(1);
-        lds_barrier();
-        MCD_T(2);
-        fwd_loader_start<R, LW>(M.Ft, st, lw, lane);
-        fwd_loader<R, LW, 0>(M.Ft, ring, st, lw, lane, ncols MCD_ACC_ARGS);
+        fwd_loader_role<R, LW, FS>(M, ring, lw, lane, ncols MCD_ACC_ARGS);
         MCD_T(3);
         MCD_ACC_FLUSH(5);
         return;
@@ -31,7 +25,7 @@ __global__ void __launch_bounds__(64 * (CW + LW)) k_logpdf(MvnDev M, const doubl
     MCD_T(1);
     lds_barrier();
     MCD_T(2);
-    fwd_compute<R, BT, 0>(d, ring, lane, ncols MCD_ACC_ARGS);
+    fwd_compute<R, BT, 0, FS>(d, ring, lane, ncols MCD_ACC_ARGS);
     MCD_T(3);
     finish_ll<R, BT>(d, M, b0, batch, ll, lane);
     MCD_T(4);
@@ -43,7 +37,23 @@ static void launch_geom(const MvnDev& M, const double* X, int64_t ldx, int64_t b
 {
     const int64_t per_wg = (int64_t)CW * BT;
     const unsigned grid = (unsigned)((batch + per_wg - 1) / per_wg);
-    hipLaunchKernelGGL((k_logpdf<R, BT, CW, LW>), dim3(grid), dim3(64 * (CW + LW)), 0, st, M, X, ldx, batch, ll);
+    switch (fwd_stream<R>(CW)) {
+    case 1:
+        if constexpr (fwd_stream_compact(R)) {
+            hipLaunchKernelGGL((k_logpdf<R, BT, CW, LW, 1>), dim3(grid), dim3(64 * (CW + LW)), 0, st, M, X, ldx, batch, ll);
+            return;
+        }
+        break;
+    case 2:
+        if constexpr (fwd_stream_compact(R)) {
+            hipLaunchKernelGGL((k_logpdf<R, BT, CW, LW, 2>), dim3(grid), dim3(64 * (CW + LW)), 0, st, M, X, ldx, batch, ll);
+            return;
+        }
+        break;
+    default:
+        break;
+    }
+    hipLaunchKernelGGL((k_logpdf<R, BT, CW, LW, 0>), dim3(grid), dim3(64 * (CW + LW)), 0, st, M, X, ldx, batch, ll);
 }
 
 template <int R>

@@ -19,7 +19,7 @@ struct MhPriorJob {
 };
 struct NoJob {};
 
-template <int R, int BT, int CW, int LW, bool PRIOR>
+template <int R, int BT, int CW, int LW, bool PRIOR, int FS>
 __global__ void __launch_bounds__(64 * (CW + LW)) k_tree_logpdf(MvnDev M, TreeDev T, const double* __restrict__ H,
                                                                 const double* __restrict__ Rt, int64_t lds,
                                                                 const double* __restrict__ tH,
@@ -29,7 +29,7 @@ __global__ void __launch_bounds__(64 * (CW + LW)) k_tree_logpdf(MvnDev M, TreeDe
 {
     unsigned bid_off = 0;
     if constexpr (PRIOR) bid_off = (unsigned)J.n_wgs;
-    MCD_KERNEL_HEAD
+    MCD_KERNEL_HEAD_FS(FS)
     if constexpr (PRIOR) {
         if (blockIdx.x < bid_off) {                        // the prior role: a chain per wave (or per two), its state in a slice of the ring
             if (J.wpc == 2) {
@@ -48,12 +48,7 @@ __global__ void __launch_bounds__(64 * (CW + LW)) k_tree_logpdf(MvnDev M, TreeDe
     }
     MCD_ACC_DECL
     if (wave >= CW) {                                      // loader role
-        Stage<R, LW> st;
-        const int lw = wave - CW;
-        fwd_loader_prologue<R, LW>(M.Ft, ring, st, lw, lane);
-        lds_barrier();
-        fwd_loader_start<R, LW>(M.Ft, st, lw, lane);
-        fwd_loader<R, LW, 0>(M.Ft, ring, st, lw, lane, ncols MCD_ACC_ARGS);
+        fwd_loader_role<R, LW, FS>(M, ring, wave - CW, lane, ncols MCD_ACC_ARGS);
         return;
     }
     double d[R][BT], dist[R][BT];
@@ -71,8 +66,29 @@ __global__ void __launch_bounds__(64 * (CW + LW)) k_tree_logpdf(MvnDev M, TreeDe
             if (b0 + c < batch) logjac[b0 + c] = log(1.0 / dist[0][c]);  // app/Probability.hs:394, 409
     }
     lds_barrier();
-    fwd_compute<R, BT, 0>(d, ring, lane, ncols MCD_ACC_ARGS);
+    fwd_compute<R, BT, 0, FS>(d, ring, lane, ncols MCD_ACC_ARGS);
     finish_ll<R, BT>(d, M, b0, batch, ll, lane);
+}
+
+// one launch of k_tree_logpdf<R, BT, CW, LW, PRIOR, FS> with FS the forward stream in force (fwd_stream); the prior variant (the
+// Metropolis-Hastings step's likelihood launch) keeps the padded stream whatever MCD_FSTREAM says: its workgroups of both roles share
+// CUs two by two, which the LDS-DMA ring's four slots would not leave room for, and the compact stream staged through registers
+// measured no gain on the sweep
+template <int R, int BT, int CW, int LW, bool PRIOR, class... A>
+static void launch_tree_fs(unsigned grid, hipStream_t st, A... a)
+{
+    if constexpr (fwd_stream_compact(R) && !PRIOR) {
+        const int fs = fwd_stream<R>(CW);
+        if (fs == 1) {
+            hipLaunchKernelGGL((k_tree_logpdf<R, BT, CW, LW, PRIOR, 1>), dim3(grid), dim3(64 * (CW + LW)), 0, st, a...);
+            return;
+        }
+        if (fs == 2) {
+            hipLaunchKernelGGL((k_tree_logpdf<R, BT, CW, LW, PRIOR, 2>), dim3(grid), dim3(64 * (CW + LW)), 0, st, a...);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((k_tree_logpdf<R, BT, CW, LW, PRIOR, 0>), dim3(grid), dim3(64 * (CW + LW)), 0, st, a...);
 }
 
 template <int R, bool PRIOR, class JOB>
@@ -101,18 +117,18 @@ static hipError_t launch_tree_logpdf_R(const MvnDev& M, const TreeDev& T, const 
     };
     if (g.cw == 2) {
         const unsigned grid = (unsigned)((batch + 1) / 2) + prior_wgs(2 + LW);
-        hipLaunchKernelGGL((k_tree_logpdf<R, 1, 2, LW, PRIOR>), dim3(grid), dim3(64 * (2 + LW)), 0, st, M, T, H, Rt, lds, tH, rMu, batch, ll, logjac, J);
+        launch_tree_fs<R, 1, 2, LW, PRIOR>(grid, st, M, T, H, Rt, lds, tH, rMu, batch, ll, logjac, J);
     } else if (g.bt == 1) {
         const unsigned grid = (unsigned)((batch + 3) / 4) + prior_wgs(4 + LW);
-        hipLaunchKernelGGL((k_tree_logpdf<R, 1, 4, LW, PRIOR>), dim3(grid), dim3(64 * (4 + LW)), 0, st, M, T, H, Rt, lds, tH, rMu, batch, ll, logjac, J);
+        launch_tree_fs<R, 1, 4, LW, PRIOR>(grid, st, M, T, H, Rt, lds, tH, rMu, batch, ll, logjac, J);
     } else if constexpr (R >= 16) {
         // (two chains per compute wave do not fit the register file at R = 16: 1 188 spilled registers; such a batch -- more than 4096 chains on
         // the sweep -- is only reached with the form forced, the automatic choice takes the multiply form there)
         const unsigned grid = (unsigned)((batch + 3) / 4) + prior_wgs(4 + LW);
-        hipLaunchKernelGGL((k_tree_logpdf<R, 1, 4, LW, PRIOR>), dim3(grid), dim3(64 * (4 + LW)), 0, st, M, T, H, Rt, lds, tH, rMu, batch, ll, logjac, J);
+        launch_tree_fs<R, 1, 4, LW, PRIOR>(grid, st, M, T, H, Rt, lds, tH, rMu, batch, ll, logjac, J);
     } else {                                               // large batches: two chains per compute wave share every factor read
         const unsigned grid = (unsigned)((batch + 7) / 8) + prior_wgs(4 + LW);
-        hipLaunchKernelGGL((k_tree_logpdf<R, 2, 4, LW, PRIOR>), dim3(grid), dim3(64 * (4 + LW)), 0, st, M, T, H, Rt, lds, tH, rMu, batch, ll, logjac, J);
+        launch_tree_fs<R, 2, 4, LW, PRIOR>(grid, st, M, T, H, Rt, lds, tH, rMu, batch, ll, logjac, J);
     }
     return hipGetLastError();
 }

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/mcmcdate_mvn.h"
+#include "fc_layout.hpp"
 #include "host_factor.h"
 #include "mvn_kernels.h"
 
@@ -132,7 +133,7 @@ struct mcd_mvn {
     int n = 0, R = 0, device = 0;
     double logdet = 0.0;
     mcd::MvnDev dev{};
-    double *d_mu = nullptr, *d_invdiag = nullptr, *d_Ft = nullptr, *d_Ut = nullptr, *d_Wt = nullptr, *d_Wtb = nullptr, *d_Wc = nullptr;
+    double *d_mu = nullptr, *d_invdiag = nullptr, *d_Ft = nullptr, *d_Fc = nullptr, *d_Ut = nullptr, *d_Wt = nullptr, *d_Wtb = nullptr, *d_Wc = nullptr;
     std::vector<double> L;  // host copy of the factor (row-major lower)
     mutable WorkspacePool pool;
     mcd::SplitHost* split = nullptr;   // k_split.hip: schedules of the row-split form + scratch sets per stream
@@ -145,6 +146,7 @@ struct mcd_mvn {
         if (d_mu) (void)hipFree(d_mu);
         if (d_invdiag) (void)hipFree(d_invdiag);
         if (d_Ft) (void)hipFree(d_Ft);
+        if (d_Fc) (void)hipFree(d_Fc);
         if (d_Ut) (void)hipFree(d_Ut);
         if (d_Wt) (void)hipFree(d_Wt);
         mcd::split_host_destroy(split);
@@ -265,6 +267,12 @@ int mcd_mvn_create(mcd_mvn_t** out, int n, const double* mu, const double* mat, 
     HIP_TRY(hipMemcpy(h->d_invdiag, invdiag.data(), NP * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->d_Ft, Ft.data(), NP * NP * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->d_Ut, Ut.data(), NP * NP * sizeof(double), hipMemcpyHostToDevice));
+    if (mcd::fwd_stream_compact(h->R)) {   // the compact forward stream of the column sweep (fc_layout.hpp), read at R = 3, 4 only
+        std::vector<double> Fc;
+        mcd::pack_compact_forward(h->R, Ft, Fc);
+        HIP_TRY(hipMalloc((void**)&h->d_Fc, Fc.size() * sizeof(double)));
+        HIP_TRY(hipMemcpy(h->d_Fc, Fc.data(), Fc.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
 
     const int ch = mcd::sweep_chunk_columns(h->R);
     h->dev.n = n;
@@ -275,6 +283,7 @@ int mcd_mvn_create(mcd_mvn_t** out, int n, const double* mu, const double* mat, 
     h->dev.mu = h->d_mu;
     h->dev.invdiag = h->d_invdiag;
     h->dev.Ft = h->d_Ft;
+    h->dev.Fc = h->d_Fc;
     h->dev.Ut = h->d_Ut;
     {   // multiply form for large batches (k_wide.hip): W = L^-1 as MFMA operand tiles
         std::vector<double> Wt, Wtb;

@@ -34,6 +34,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "fc_layout.hpp"
 #include "mvn_kernels.h"
 #include "options.h"
 
@@ -167,6 +168,7 @@ struct Cfg {
     static constexpr int CPB = 32 / CP;                     // chunks per 64-column block
     static constexpr int NCHUNK = R * CPB;
     static constexpr int CCOLS = 2 * CP;                    // columns per chunk
+    static_assert(CP == fc_cp(R), "fc_layout.hpp: the same chunks");
 };
 
 constexpr int floordiv(int a, int b) { return (a >= 0) ? a / b : -((-a + b - 1) / b); }
@@ -214,6 +216,70 @@ __device__ __forceinline__ void stage_store(const Stage<R, LW>& st, d2* slot, in
     }
 }
 
+// ---- the compact stream Fc (fc_layout.hpp) -------------------------------------------------------------------------------
+// FS (factor stream) 0: Ft, register-staged, two ring slots; 1: Fc, register-staged, two slots; 2: Fc by LDS-DMA
+// (global_load_lds_dwordx4: a wave-instruction writes one lane-linear unit straight into its slot), NS slots.  With Fc a chunk
+// is fc_chunk_units consecutive units, copied as they are; the diagonal units' lanes on or above the diagonal are read from a
+// zero unit behind the slots (fwd_unit), written once before the first barrier.  Compact streams serve R <= 4 (every chunk's
+// diagonal part is a whole number of units there, and the loaders' schedule is compile-time: at most four chunks per block).
+template <int R, int FS>
+struct Ring {
+    // slots: LDS-DMA keeps two chunks in flight across a barrier beside the one being read and the one waited for, as register
+    // staging does (measured at N = 256 x 512 chains: 3 slots 7.20 us per step, 4 slots 7.18-7.20, 5 slots 7.78)
+    static constexpr int NS = FS == 2 ? 4 : 2;
+    static constexpr int STRIDE = FS == 2 ? fc_chunk_units(R, 0) : Cfg<R>::SU;   // units per slot (chunk 0 is the largest)
+    static constexpr int ZERO = NS * STRIDE * 64;                            // the zero unit (d2 index; FS > 0)
+    static constexpr int D2 = ZERO + (FS > 0 ? 64 : 0);
+    static_assert(FS == 0 || (R <= 4 && fc_chunk_units(R, 0) <= Cfg<R>::SU), "compact streams: R <= 4");
+};
+
+template <int R, int LW, int CI, int SET>
+__device__ __forceinline__ void stage_load_c(Stage<R, LW>& st, const double* __restrict__ Fc, int lw, int lane)
+{
+    constexpr int NU = fc_chunk_units(R, CI), B = fc_chunk_base(R, CI);
+#pragma unroll
+    for (int i = 0; i < (NU + LW - 1) / LW; ++i) {
+        int u = i * LW + lw;                              // wave-uniform
+        if constexpr (NU % LW != 0) u = u < NU ? u : NU - 1;
+        st.v[SET][i] = reinterpret_cast<const d2*>(Fc)[((size_t)B + u) * 64 + lane];
+    }
+}
+
+template <int R, int LW, int CI, int SET>
+__device__ __forceinline__ void stage_store_c(const Stage<R, LW>& st, d2* slot, int lw, int lane)
+{
+    constexpr int NU = fc_chunk_units(R, CI);
+#pragma unroll
+    for (int i = 0; i < (NU + LW - 1) / LW; ++i) {
+        const int u = i * LW + lw;
+        if constexpr (NU % LW != 0) {
+            if (u < NU) slot[u * 64 + lane] = st.v[SET][i];
+        } else {
+            slot[u * 64 + lane] = st.v[SET][i];
+        }
+    }
+}
+
+// Unit (pair p of the chunk, row block JB + k) of chunk LC of block JB, this lane's 16 bytes.  FS 0: the padded layout.  Compact:
+// the diagonal unit from the chunk's diagonal part where the lane is below the diagonal, else from the zero unit (one compare
+// and one select, issued with the LDS prefetch); the off-diagonal units behind the diagonal part.
+template <int R, int JB, int LC, int FS>
+__device__ __forceinline__ d2 fwd_unit(const d2* slot, const d2* zu, int p, int k, int lane)
+{
+    constexpr int NK = R - JB;
+    if constexpr (FS == 0) {
+        return slot[(p * NK + k) * 64 + lane];
+    } else {
+        constexpr int CP = Cfg<R>::CP;
+        if (k == 0) {
+            const int pl = LC * CP + p;
+            const d2* a = lane > 2 * pl ? slot + (fc_diag_start(R, LC, p) - (2 * pl + 1) + lane) : zu + lane;
+            return *a;
+        }
+        return slot[(fc_diag_units(R, LC) + p * (NK - 1) + (k - 1)) * 64 + lane];
+    }
+}
+
 // LDS -> VGPR prefetch distance (column pairs).  One wave per SIMD has nothing else to overlap the
 // ~100-cycle LDS latency with, so the factor values of pair p + LDS_PD are requested before pair p
 // is applied.
@@ -225,10 +291,11 @@ template <int R> struct LdsPd { static constexpr int PD = (R >= 16) ? 1 : 2; };
 // forward sweep
 // =======================================================================================
 // Apply one chunk (CP column pairs starting at column offset jj0 of block JB) from an LDS slot.
-template <int R, int BT, int JB, int JJ0>
-__device__ __forceinline__ void fwd_apply(double (&d)[R][BT], const d2* slot, int lane)
+template <int R, int BT, int JB, int JJ0, int FS>
+__device__ __forceinline__ void fwd_apply(double (&d)[R][BT], const d2* slot, const d2* zu, int lane)
 {
     constexpr int jj0 = JJ0;
+    constexpr int LC = JJ0 / Cfg<R>::CCOLS;
     constexpr int CP = Cfg<R>::CP;
     constexpr int NK = R - JB;
     constexpr int LDS_PD = LdsPd<R>::PD;
@@ -237,7 +304,7 @@ __device__ __forceinline__ void fwd_apply(double (&d)[R][BT], const d2* slot, in
 #pragma unroll
     for (int p = 0; p < LDS_PD && p < CP; ++p)
 #pragma unroll
-        for (int k = 0; k < NK; ++k) l[p % NBUF][k] = slot[(p * NK + k) * 64 + lane];
+        for (int k = 0; k < NK; ++k) l[p % NBUF][k] = fwd_unit<R, JB, LC, FS>(slot, zu, p, k, lane);
     double z[BT];
 #pragma unroll
     for (int b = 0; b < BT; ++b) z[b] = readlane64(d[JB][b], jj0);
@@ -245,7 +312,7 @@ __device__ __forceinline__ void fwd_apply(double (&d)[R][BT], const d2* slot, in
     for (int p = 0; p < CP; ++p) {
         if (p + LDS_PD < CP) {
 #pragma unroll
-            for (int k = 0; k < NK; ++k) l[(p + LDS_PD) % NBUF][k] = slot[((p + LDS_PD) * NK + k) * 64 + lane];
+            for (int k = 0; k < NK; ++k) l[(p + LDS_PD) % NBUF][k] = fwd_unit<R, JB, LC, FS>(slot, zu, p + LDS_PD, k, lane);
         }
         MCD_SB;
 #pragma unroll
@@ -286,7 +353,7 @@ __device__ __forceinline__ void fwd_apply(double (&d)[R][BT], const d2* slot, in
 // ---- compute role -------------------------------------------------------------------------
 // The chunk index is a compile-time constant so that every v_readlane has an immediate lane
 // select (a lane select in a freshly written SGPR costs ~9 cycles per column, lat2.hip).
-template <int R, int BT, int JB, int LC>
+template <int R, int BT, int JB, int LC, int FS>
 __device__ __forceinline__ bool fwd_compute_chunks(double (&d)[R][BT], const d2* ring, int lane, int ncols MCD_ACC_PARAMS)
 {
     using C = Cfg<R>;
@@ -294,22 +361,22 @@ __device__ __forceinline__ bool fwd_compute_chunks(double (&d)[R][BT], const d2*
         constexpr int CI = JB * C::CPB + LC;
         if (CI * C::CCOLS >= ncols) return false;        // workgroup-uniform
         MCD_ACC(-1);
-        fwd_apply<R, BT, JB, LC * C::CCOLS>(d, ring + (CI & 1) * C::SU * 64, lane);
+        fwd_apply<R, BT, JB, LC * C::CCOLS, FS>(d, ring + (CI % Ring<R, FS>::NS) * Ring<R, FS>::STRIDE * 64, ring + Ring<R, FS>::ZERO, lane);
         MCD_ACC(0);
         lds_barrier();
         MCD_ACC(1);
-        return fwd_compute_chunks<R, BT, JB, LC + 1>(d, ring, lane, ncols MCD_ACC_ARGS);
+        return fwd_compute_chunks<R, BT, JB, LC + 1, FS>(d, ring, lane, ncols MCD_ACC_ARGS);
     } else {
         return true;
     }
 }
 
-template <int R, int BT, int JB>
+template <int R, int BT, int JB, int FS = 0>
 __device__ __forceinline__ void fwd_compute(double (&d)[R][BT], const d2* ring, int lane, int ncols MCD_ACC_PARAMS)
 {
     if constexpr (JB < R) {
-        if (!fwd_compute_chunks<R, BT, JB, 0>(d, ring, lane, ncols MCD_ACC_ARGS)) return;
-        fwd_compute<R, BT, JB + 1>(d, ring, lane, ncols MCD_ACC_ARGS);
+        if (!fwd_compute_chunks<R, BT, JB, 0, FS>(d, ring, lane, ncols MCD_ACC_ARGS)) return;
+        fwd_compute<R, BT, JB + 1, FS>(d, ring, lane, ncols MCD_ACC_ARGS);
     }
 }
 
@@ -385,6 +452,143 @@ __device__ __forceinline__ void fwd_loader_start(const double* __restrict__ Ft, 
     using C = Cfg<R>;
     if constexpr (C::NCHUNK > 1) stage_load<R, LW, 1 / C::CPB, R, 1>(st, Ft, C::CP, lw, lane);
     if constexpr (C::NCHUNK > 2) stage_load<R, LW, 2 / C::CPB, R, 0>(st, Ft, 2 * C::CP, lw, lane);
+}
+
+// ---- loader role, compact stream ----------------------------------------------------------------------------------------
+// FS = 1: the schedule of fwd_loader above (chunk ci+1 written to its slot, ci+3 requested, one barrier per chunk) over Fc, every
+// chunk index compile-time.
+template <int R, int LW, int CI>
+__device__ __forceinline__ void fc_loader(const double* __restrict__ Fc, d2* ring, Stage<R, LW>& st, int lw, int lane,
+                                          int ncols MCD_ACC_PARAMS)
+{
+    using C = Cfg<R>;
+    if constexpr (CI < C::NCHUNK) {
+        if (CI * C::CCOLS >= ncols) return;
+        constexpr int S = (CI + 1) & 1;
+        MCD_ACC(-1);
+        if constexpr (CI + 1 < C::NCHUNK) stage_store_c<R, LW, CI + 1, S>(st, ring + S * C::SU * 64, lw, lane);
+        MCD_ACC(0);
+        if constexpr (CI + 3 < C::NCHUNK) stage_load_c<R, LW, CI + 3, S>(st, Fc, lw, lane);
+        MCD_ACC(2);
+        lds_barrier();
+        MCD_ACC(1);
+        fc_loader<R, LW, CI + 1>(Fc, ring, st, lw, lane, ncols MCD_ACC_ARGS);
+    }
+}
+
+// chunk 0 and the zero unit into the ring before the first barrier; chunks 1 and 2 requested after it (fc_loader_start)
+template <int R, int LW>
+__device__ __forceinline__ void fc_loader_prologue(const double* __restrict__ Fc, d2* ring, Stage<R, LW>& st, int lw, int lane)
+{
+    stage_load_c<R, LW, 0, 0>(st, Fc, lw, lane);
+    if (lw == 0) ring[Ring<R, 1>::ZERO + lane] = d2{0.0, 0.0};
+    stage_store_c<R, LW, 0, 0>(st, ring, lw, lane);
+}
+
+template <int R, int LW>
+__device__ __forceinline__ void fc_loader_start(const double* __restrict__ Fc, Stage<R, LW>& st, int lw, int lane)
+{
+    if constexpr (Cfg<R>::NCHUNK > 1) stage_load_c<R, LW, 1, 1>(st, Fc, lw, lane);
+    if constexpr (Cfg<R>::NCHUNK > 2) stage_load_c<R, LW, 2, 0>(st, Fc, lw, lane);
+}
+
+// FS = 2: LDS-DMA.  Chunk ci goes to slot ci % NS.  Between the barriers that publish chunks ci and ci+1 a loader requests chunk
+// ci + NS - 1 (into the slot of chunk ci-1, which every compute wave finished reading before the first of them), then waits with
+// a counted vmcnt for its share of chunk ci+1 and leaves the later chunks in flight across the barrier.  LDS-DMA writes count on
+// vmcnt only: the barrier is lds_barrier (lgkmcnt), never __syncthreads(), whose vmcnt(0) would drain the stream.
+template <int R, int LW, int FS, int CI>
+__device__ __forceinline__ void fc_dma_chunk(const double* __restrict__ Fc, d2* ring, int lw, int lane)
+{
+    if constexpr (CI < Cfg<R>::NCHUNK) {
+        constexpr int NU = fc_chunk_units(R, CI), B = fc_chunk_base(R, CI);
+        const __attribute__((address_space(1))) d2* src =
+            (const __attribute__((address_space(1))) d2*)reinterpret_cast<const d2*>(Fc) + ((size_t)B * 64 + lane);
+        d2* slot = ring + (CI % Ring<R, FS>::NS) * Ring<R, FS>::STRIDE * 64;
+#pragma unroll
+        for (int i = 0; i < (NU + LW - 1) / LW; ++i) {
+            const int u = i * LW + lw;                    // wave-uniform
+            if (NU % LW == 0 || u < NU)
+                __builtin_amdgcn_global_load_lds(src + u * 64, (__attribute__((address_space(3))) void*)(slot + u * 64), 16, 0, 0);
+        }
+    }
+}
+
+// the fewest LDS-DMAs any loader wave issues for chunks [c0, c1): a wave that issued more waits for a little more than it must
+constexpr int fc_dma_min(int R, int LW, int c0, int c1)
+{
+    int s = 0;
+    for (int c = c0; c < c1 && c < fc_nchunk(R); ++c) s += fc_chunk_units(R, c) / LW;
+    return s;
+}
+
+template <int N>
+__device__ __forceinline__ void wait_vmcnt()
+{
+    static_assert(N >= 0 && N < 64, "vmcnt");
+    __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));   // vmcnt(N), expcnt / lgkmcnt not waited for
+}
+
+template <int R, int LW, int FS, int CI>
+__device__ __forceinline__ void fc_dma_loader_chunks(const double* __restrict__ Fc, d2* ring, int lw, int lane, int ncols)
+{
+    using C = Cfg<R>;
+    constexpr int NS = Ring<R, FS>::NS;
+    if constexpr (CI < C::NCHUNK) {
+        if (CI * C::CCOLS >= ncols) return;
+        fc_dma_chunk<R, LW, FS, CI + NS - 1>(Fc, ring, lw, lane);
+        if constexpr (CI + 1 < C::NCHUNK) wait_vmcnt<fc_dma_min(R, LW, CI + 2, CI + NS)>();
+        lds_barrier();
+        fc_dma_loader_chunks<R, LW, FS, CI + 1>(Fc, ring, lw, lane, ncols);
+    }
+}
+
+template <int R, int LW, int FS, int C0, int C1>
+__device__ __forceinline__ void fc_dma_chunks(const double* __restrict__ Fc, d2* ring, int lw, int lane)
+{
+    if constexpr (C0 < C1) {
+        fc_dma_chunk<R, LW, FS, C0>(Fc, ring, lw, lane);
+        fc_dma_chunks<R, LW, FS, C0 + 1, C1>(Fc, ring, lw, lane);
+    }
+}
+
+// the whole loader role of FS = 2, first barrier included
+template <int R, int LW, int FS>
+__device__ __forceinline__ void fc_dma_loader(const double* __restrict__ Fc, d2* ring, int lw, int lane, int ncols)
+{
+    if (lw == 0) ring[Ring<R, FS>::ZERO + lane] = d2{0.0, 0.0};
+    fc_dma_chunk<R, LW, FS, 0>(Fc, ring, lw, lane);
+    wait_vmcnt<0>();
+    MCD_T(1);
+    lds_barrier();
+    MCD_T(2);
+    fc_dma_chunks<R, LW, FS, 1, Ring<R, FS>::NS - 1>(Fc, ring, lw, lane);
+    fc_dma_loader_chunks<R, LW, FS, 0>(Fc, ring, lw, lane, ncols);
+    wait_vmcnt<0>();                                       // (nothing in flight into the ring when the wave ends)
+}
+
+// The loader role of a forward sweep for stream FS, first barrier included (MCD_T: the milestones of the diagnostic builds).
+template <int R, int LW, int FS>
+__device__ __forceinline__ void fwd_loader_role(const MvnDev& M, d2* ring, int lw, int lane, int ncols MCD_ACC_PARAMS)
+{
+    if constexpr (FS == 2) {
+        fc_dma_loader<R, LW, FS>(M.Fc, ring, lw, lane, ncols);
+    } else if constexpr (FS == 1) {
+        Stage<R, LW> st;
+        fc_loader_prologue<R, LW>(M.Fc, ring, st, lw, lane);
+        MCD_T(1);
+        lds_barrier();
+        MCD_T(2);
+        fc_loader_start<R, LW>(M.Fc, st, lw, lane);
+        fc_loader<R, LW, 0>(M.Fc, ring, st, lw, lane, ncols MCD_ACC_ARGS);
+    } else {
+        Stage<R, LW> st;
+        fwd_loader_prologue<R, LW>(M.Ft, ring, st, lw, lane);
+        MCD_T(1);
+        lds_barrier();
+        MCD_T(2);
+        fwd_loader_start<R, LW>(M.Ft, st, lw, lane);
+        fwd_loader<R, LW, 0>(M.Ft, ring, st, lw, lane, ncols MCD_ACC_ARGS);
+    }
 }
 
 // =======================================================================================
@@ -673,12 +877,26 @@ __device__ __forceinline__ void finish_ll(const double (&d)[R][BT], const MvnDev
 #ifndef MCD_BID
 #define MCD_BID blockIdx.x
 #endif
-#define MCD_KERNEL_HEAD                                                         \
-    __shared__ d2 ring[2 * Cfg<R>::SU * 64];                                    \
+#define MCD_KERNEL_HEAD MCD_KERNEL_HEAD_FS(0)
+#define MCD_KERNEL_HEAD_FS(FS_)                                                 \
+    __shared__ d2 ring[Ring<R, (FS_)>::D2];                                     \
     const int lane = threadIdx.x & 63;                                          \
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);          \
     const int64_t b0 = ((int64_t)MCD_BID * CW + wave) * BT;                      \
     const int ncols = M.ncols;   /* swept columns: N rounded up to whole chunks (host: sweep_chunk_columns) */
+
+// The forward factor stream of the column sweep (host side; mcd_set_option "MCD_FSTREAM", A/B and tests): compact streams at 129 ..
+// 256 dimensions (R = 3, 4), the padded one elsewhere.  By default the compact stream by LDS-DMA where a workgroup has a CU to itself
+// anyway (two compute waves: up to 512 chains), and the padded stream with four compute waves: there two workgroups share a CU on
+// the two-slot ring, which the four DMA slots would not leave room for, and the compact stream staged through registers measured no
+// gain on the sweep; MCD_FSTREAM = 1 or 2 forces a compact stream in every geometry (tests).
+template <int R>
+static inline int fwd_stream(int cw)
+{
+    if constexpr (!fwd_stream_compact(R)) return 0;
+    const int f = opt_or(OPT_FSTREAM, cw == 2 ? 2 : 0);
+    return (f == 1 || f == 2) ? f : 0;
+}
 
 // launch geometry by batch size (host side)
 struct Geometry {

@@ -16,6 +16,8 @@ struct MvnDev {
     const double* mu;       // [NP], zero padded
     const double* invdiag;  // [NP], 1 / L_ii, one padded
     const double* Ft;       // forward factor  L[i][j]/L[i][i], pair-interleaved column layout, NP*NP
+    const double* Fc;       // the same factor as the compact stream of the sweep (fc_layout.hpp): no stored zeros on or above the diagonal;
+                            // NULL unless fwd_stream_compact(R)
     const double* Ut;       // backward factor L[i][r]/L[r][r], same layout, NP*NP
     const double* Wt;       // W = L^-1 as 16 x 4 MFMA operand tiles (host_factor.h: pack_w_tiles), for k_wide.hip
     const double* Wtb;      // the tiles of W^T for the gradient's second product (k_wide_grad.hip)
