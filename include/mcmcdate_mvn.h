@@ -359,20 +359,27 @@ int mcd_mh_get_posterior(const mcd_mh_t* m, double* post);
  * n_iter iterations of steps_per_iter proposals; schedule[n_iter * steps_per_iter] = proposal row per step (host).
  * accumulate != 0: after every iteration add the absolute node ages tH * h_v to the running sums.
  * trace_alpha / trace_accept (host, may be NULL): [n_iter * steps_per_iter][batch] ln acceptance ratio / decision.
- * Trees of at most 64 nodes: the whole schedule in one launch, the factor of Sigma in LDS; up to 514 nodes (N <= 512) and 1024 chains: the
- * same with the factor streamed through LDS once per step (default up to 258 nodes).  Trees of 259 .. 1026 nodes: every run of steps between
- * two proposals that move more than 192 branch distances in one launch, the chains' states in LDS (k_mh_segment.hip); such a dense
- * proposal by two launches.  Trees of up to 258 nodes with more than 1024 chains, and trees over a sparse likelihood: two launches per step -- accept the pending
- * proposal and propose the next one; then ln likelihood of the proposed states, which up to 256 dimensions also carries their ln
- * prior as workgroups of a second role (both depend on the proposal only); from 321 nodes the likelihood launch only for proposals that
- * move more than 32 distances (the others: columns of L^-1 on a kept z).  Knobs (mcd_set_option), for tests and timing:
- * MCD_MH_SEGMENTS=0 / MCD_MH_INCREMENTAL=0 switch the segments / every incremental evaluation off (the chains: same decisions and states),
- * MCD_MH_INC_SLOTS (consulted by mcd_mh_create) sets the number of moved distances up to which a proposal counts as sparse (at most 256),
- * MCD_MH_SPARSE_SLOTS the same for the whole-schedule kernel of 65 .. 258 nodes (at most 64), MCD_MH_CHAIN_LW=0 runs the small-tree kernel with
- * one wave per chain (the likelihood then after the prior instead of beside it: the same bits),
- * MCD_MH_PRIOR=0 evaluates the prior inside the first launch everywhere (the chains are the same bits either way),
- * MCD_MH_PER_PHASE=1 takes the two-launch path for small trees as well, MCD_MH_STEP_WG=1 / 0 forces / forbids the step kernel
- * with a workgroup per chain (default: trees of more than 320 nodes).
+ * Which launch structure a run takes (mcd_mh_last_path) is decided once, when the run starts, from the handle's shape and the knobs below:
+ * - trees of at most 64 nodes (dense likelihood): the whole schedule in one launch, the factor of Sigma in LDS (path 1, any batch);
+ * - 65 .. 258 nodes (N <= 256) at up to 1024 chains, unless the multiply form is forced: the same with the factor streamed through LDS once
+ *   per step (path 2);
+ * - 259 .. 1026 nodes: every run of steps between two proposals that move more than 192 branch distances in one launch, the chains' states
+ *   in LDS (k_mh_segment.hip); such a dense proposal by a likelihood launch (path 8, any batch);
+ * - a sparse likelihood (mcd_mh_create_sparse), 3 .. 2048 nodes: the same segments over the rows of the matrix (path 9);
+ * - otherwise two launches per step -- accept the pending proposal and propose the next one; then the ln likelihood of the proposed states:
+ *   65 .. 258 nodes beyond 1024 chains, the likelihood launch carrying the proposal's ln prior as workgroups of a second role where the
+ *   column sweep serves it (path 3; else path 4, e.g. from 2048 chains, where the multiply form takes over).
+ * Knobs (mcd_set_option), for tests and timing; the chains are the same bits on every path:
+ * MCD_MH_PER_PHASE=1 takes two launches per step instead of paths 1 and 2 (for path 1 it must be set before mcd_mh_create);
+ * MCD_MH_SEGMENTS=0 switches the segments off: 259 .. 320 nodes then take path 4, from 321 nodes the workgroup-per-chain step kernel with the
+ * likelihood launch only for proposals that move more than 32 distances (path 6), a sparse likelihood the step kernel + the sparse product
+ * at every step (path 7); MCD_MH_INCREMENTAL=0 switches every incremental evaluation off as well: path 2 sweeps every proposal, from 321
+ * nodes path 5 (a full product at every step), a sparse likelihood path 7;
+ * MCD_MH_STEP_WG=1 / 0 forces / forbids the workgroup-per-chain step kernel (default: trees of more than 320 nodes, 258 with the segments;
+ * the sparse driver refuses 0); MCD_MH_PRIOR=0 evaluates the prior inside the step kernel everywhere (path 4 instead of 3);
+ * MCD_MH_CHAIN_LW=0 runs path 1 with one wave per chain (the likelihood after the prior instead of beside it);
+ * MCD_MH_INC_SLOTS (read by mcd_mh_create) sets the number of moved distances up to which a proposal counts as sparse (at most 256),
+ * MCD_MH_SPARSE_SLOTS the same for path 2 (at most 64).
  */
 int mcd_mh_run(mcd_mh_t* m, const int32_t* schedule, int64_t n_iter, int32_t steps_per_iter, int accumulate,
                double* trace_alpha, int8_t* trace_accept);

@@ -127,17 +127,19 @@ int effective_form(const MvnDev& M)
     return own != 0 ? own : g_form.load(std::memory_order_relaxed);
 }
 
-bool use_wide(const MvnDev& M, int64_t batch)
+MvnFacts::MvnFacts(const MvnDev& M)
+    : n(M.n), R(M.R), form(effective_form(M)), split(M.split != nullptr), wide(M.Wt != nullptr), cols(M.Wc != nullptr) {}
+
+bool use_wide(const MvnFacts& M, int64_t batch)
 {
-    const int form = effective_form(M);
-    if (M.Wt == nullptr || form == 1) return false;
-    if (form == 2) return true;
+    if (!M.wide || M.form == 1) return false;
+    if (M.form == 2) return true;
     // measured crossovers (tools/bench_forms.py, profiles/r01_form_crossover.jsonl): at 1024 chains the sweep still wins
     // or ties for every N, at 2048 the multiply form wins from N = 127 up; small N only pays at 8192 chains
     return (M.n >= 96 && batch >= 2048) || (M.n >= 32 && batch >= 8192);
 }
 
-bool use_split(const MvnDev& M, int64_t batch)
+bool use_split(const MvnFacts& M, int64_t batch)
 {
     // measured window (tools/gpu/window.sh, window2.sh; profiles/r02_split_window.jsonl, r02_split_window_240.jsonl; raw x and
     // tree states alike): above N = 256 -- five or more 64-row blocks in the sweep's dependent chain -- the row split wins for every
@@ -146,7 +148,7 @@ bool use_split(const MvnDev& M, int64_t batch)
     // pays about two memory round trips for handing the partial sums over); at N = 200 and 224 (13 / 14 row blocks over 8 groups:
     // uneven) and below the sweep wins everywhere; from 2048 chains k_wide takes over
     const int force = opt_or(OPT_SPLIT, -1);               // tests and tuning (mcd_set_option "MCD_SPLIT"): 1 = wherever possible, 0 = never
-    if (effective_form(M) != 0 || M.split == nullptr || batch < 1 || batch > kSplitMaxBatch || force == 0) return false;
+    if (M.form != 0 || !M.split || batch < 1 || batch > kSplitMaxBatch || force == 0) return false;
     if (force == 1) return true;
     if (M.n > 256) return true;
     return M.n > 240 && batch <= 128;

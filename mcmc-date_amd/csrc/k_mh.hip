@@ -719,27 +719,25 @@ hipError_t launch_mh_draws(const MhDev& M, const int32_t* sched, int64_t idx0, i
     hipLaunchKernelGGL(k_mh_draws, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, M, sched, idx0, count, step0, seed);
     return hipGetLastError();
 }
-// does launch_mh_step take the workgroup-per-chain kernel for this handle (MCD_MH_STEP_WG: 1 = for every tree, 0 = never)?
 // dynamic LDS of k_mh_step_wg: four state vectors, two blocks of summands, the hand-over words, three index arrays
 static size_t mh_step_wg_lds(int n_nodes)
 {
     const size_t NS = (size_t)((n_nodes - 1 + 63) / 64) * 64;
     return sizeof(double) * (4 * (size_t)n_nodes + 2 * NS + 48) + sizeof(int) * 3 * (size_t)n_nodes;
 }
-bool mh_step_wg_active(const MhDev& M, int prior_inline, int min_nodes)
+bool mh_step_wg_fits(int n_nodes)
 {
-    const int force = opt_get(OPT_MH_STEP_WG);            // (mcd_set_option "MCD_MH_STEP_WG": 1 / 0 = for every tree / never)
-    const bool wg = force != MCD_OPT_UNSET ? force != 0 : (prior_inline && M.n_nodes > min_nodes);
-    return wg && M.n_nodes <= 2048 && mh_step_wg_lds(M.n_nodes) + sizeof(IncShared) <= 144 * 1024;   // (above 64 KiB: allowed at launch)
+    return n_nodes <= 2048 && mh_step_wg_lds(n_nodes) + sizeof(IncShared) <= 144 * 1024;   // (above 64 KiB: allowed at launch)
 }
 
 hipError_t launch_mh_step(const MhDev& M, const PriorDev& P, int p_acc, int jac_root_acc, int p_prop, const MhRow& r, int draw_slot,
                           uint64_t step_acc, uint64_t seed, int accumulate_now, double* trace_alpha, int8_t* trace_accept, int prior_inline,
-                          const TreeDev* T, int n_dim, double* X1, int64_t ldx, hipStream_t st, const MhInc* inc, const MvnDev* V, int summands_init)
+                          bool wg, const TreeDev* T, int n_dim, double* X1, int64_t ldx, hipStream_t st, const MhInc* inc, const MvnDev* V, int summands_init)
 {
     if (summands_init < 0) summands_init = p_acc < 0 ? 1 : 0;
     const PropRow row_{r.kind, r.node, r.n1, r.n2, r.jac_root, r.p0, r.p1};
-    if (mh_step_wg_active(M, prior_inline, X1 != nullptr ? 0 : 320)) {      // (a caller that wants the distances has asked mh_step_wg_active itself)
+    if (wg) {
+        if (!mh_step_wg_fits(M.n_nodes)) return hipErrorInvalidValue;
         const bool dist = T != nullptr && X1 != nullptr;
         const TreeDev Tv = dist ? *T : TreeDev{};
         double* Xv = dist ? X1 : (double*)nullptr;

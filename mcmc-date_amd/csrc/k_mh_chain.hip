@@ -299,7 +299,7 @@ size_t mh_chain_lds_bytes(int n, int n_prop, int wpb)
 
 hipError_t launch_mh_chain(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const double* Fp,
                            const int32_t* sched, int64_t n_steps, int32_t S, int accumulate, uint64_t step0, uint64_t seed,
-                           double* trace_alpha, int8_t* trace_accept, hipStream_t st)
+                           double* trace_alpha, int8_t* trace_accept, bool likelihood_wave, hipStream_t st)
 {
     if (n_steps <= 0) return hipSuccess;
     if (M.batch >= 1024) {
@@ -310,7 +310,7 @@ hipError_t launch_mh_chain(const MhDev& M, const MvnDev& V, const TreeDev& T, co
     } else {
         constexpr int WPB = 1;
         const size_t sh = mh_chain_lds_bytes(V.n, M.n_prop, WPB) + sizeof(double) * prior_node_tables_doubles(P.n_cal, P.n_con);
-        if (opt_is(OPT_MH_CHAIN_LW, 0))                   // (mcd_set_option "MCD_MH_CHAIN_LW" = 0: one wave per chain; tests, timing)
+        if (!likelihood_wave)
             hipLaunchKernelGGL((k_mh_chain<WPB, false>), dim3((unsigned)M.batch), dim3(64), sh, st, M, V, T, P, Fp, sched, n_steps, S, accumulate,
                                step0, seed, trace_alpha, trace_accept);
         else

@@ -973,13 +973,13 @@ __global__ __launch_bounds__(256, 1) void k_mh_chain_big(MhDev M, MvnDev V, Tree
 
 // trees of 65 .. 514 nodes whose factor the sweep holds in 2 .. 8 register blocks (N <= 512), a batch of at most two rounds of
 // workgroups (one workgroup per CU: 512 chains per round), state + tables + the 64 KiB ring within a CU's LDS
-bool mh_chain_big_available(const MhDev& M, const MvnDev& V)
+bool mh_chain_big_available(const MvnFacts& V, int n_nodes, int n_prop, int64_t batch)
 {
     // (R <= 4: up to 258 nodes.  Round 3 also built R = 6 and 8 -- 514 nodes -- which the segment kernel has superseded from 259 nodes and which
     // did not fit the register file: 204 / 420 bytes of scratch per lane; removed in round 4.  1024 chains: two rounds of workgroups, still
     // ahead of two launches per step)
-    if (V.R < 1 || V.R > 4 || M.n_nodes > 64 * V.R + 2 || M.batch > 1024) return false;
-    return mhb_lds_bytes(M.n_nodes, M.n_prop, V.R) + 64 * 1024 <= 160 * 1024;
+    if (V.R < 1 || V.R > 4 || n_nodes > 64 * V.R + 2 || batch > 1024) return false;
+    return mhb_lds_bytes(n_nodes, n_prop, V.R) + 64 * 1024 <= 160 * 1024;
 }
 
 template <int R>
@@ -1003,11 +1003,11 @@ static hipError_t launch_big_R(const MhDev& M, const MvnDev& V, const TreeDev& T
 
 hipError_t launch_mh_chain_big(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const int32_t* sched, int64_t n_steps,
                                int32_t S, int accumulate, uint64_t step0, uint64_t seed, double* trace_alpha, int8_t* trace_accept,
-                               hipStream_t st)
+                               bool incremental, hipStream_t st)
 {
     if (n_steps <= 0) return hipSuccess;
-    if (!mh_chain_big_available(M, V)) return hipErrorInvalidValue;
-    if (opt_is(OPT_MH_INCREMENTAL, 0)) {                     // (mcd_set_option "MCD_MH_INCREMENTAL" = 0: every proposal through the full sweep; tests, timing)
+    if (!mh_chain_big_available(V, M.n_nodes, M.n_prop, M.batch)) return hipErrorInvalidValue;
+    if (!incremental) {                                      // (every proposal through the full sweep)
         MvnDev V0 = V;
         V0.Wc = nullptr;
         switch (V.R) {

@@ -393,10 +393,10 @@ __global__ __launch_bounds__(HELP ? 512 : 256, 1) void k_mh_segment(MhDev M, Mvn
 
 // trees whose factor takes 6 .. 16 register blocks (259 .. 1026 nodes: below that the streaming chain kernel's in-kernel sweeps of
 // the dense proposals cost less than two launches), columns of L^-1 on the device, tables and two chains within a CU's LDS
-bool mh_segment_available(const MhDev& M, const MvnDev& V)
+bool mh_segment_available(const MvnFacts& V, int n_nodes, int64_t batch)
 {
-    if ((V.R != 6 && V.R != 8 && V.R != 12 && V.R != 16) || V.Wc == nullptr || M.n_nodes > 64 * V.R + 2 || M.n_nodes < 3 || M.batch > kSegMaxBatch) return false;
-    return seg_lds_bytes(M.n_nodes, 64 * V.R) <= 160 * 1024;
+    if ((V.R != 6 && V.R != 8 && V.R != 12 && V.R != 16) || !V.cols || n_nodes > 64 * V.R + 2 || n_nodes < 3 || batch > kSegMaxBatch) return false;
+    return seg_lds_bytes(n_nodes, 64 * V.R) <= 160 * 1024;
 }
 
 template <int R, bool HELP>
@@ -422,36 +422,30 @@ static hipError_t launch_segment_RH(const MhDev& M, const MvnDev& V, const TreeD
 template <int R>
 static hipError_t launch_segment_R(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const MhInc& I, const int32_t* sched,
                                    int64_t n_steps, int32_t S, int accumulate, uint64_t step0, uint64_t seed, double* trace_alpha,
-                                   int8_t* trace_accept, int64_t gs_base, int summands_kept, const MhSegPending& Q, hipStream_t st)
+                                   int8_t* trace_accept, int64_t gs_base, int summands_kept, const MhSegPending& Q, bool prior_waves, hipStream_t st)
 {
-    // (mcd_set_option "MCD_MH_PRIOR_WAVES" = 0: the chain wave evaluates the whole ln prior; tests, timing)
-    if (opt_is(OPT_MH_PRIOR_WAVES, 0))
+    if (!prior_waves)                                        // (the chain wave evaluates the whole ln prior)
         return launch_segment_RH<R, false>(M, V, T, P, I, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, gs_base, summands_kept, Q, st);
     return launch_segment_RH<R, true>(M, V, T, P, I, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, gs_base, summands_kept, Q, st);
 }
 
 // steps [0, n_steps) of `sched` (device memory), none of which moves more than kSegList distances; step0 = the step number of
 // sched[0], gs_base its position in the run's schedule (iterations close at multiples of S); summands_kept: MhDev::psum holds the
-// current states' summands; pending (may be null): a dense proposal whose likelihood has been evaluated and which is decided here
+// current states' summands; Q: the dense proposal whose likelihood has been evaluated and which is decided here (p_acc < 0: none), the one
+// the segment proposes after its last step (p_tail < 0: none), how the chain wave draws ahead; prior_waves: the kernel with its prior waves
 hipError_t launch_mh_segment(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const MhInc& I, const int32_t* sched,
                              int64_t n_steps, int32_t S, int accumulate, uint64_t step0, uint64_t seed, double* trace_alpha, int8_t* trace_accept,
-                             int64_t gs_base, int summands_kept, const MhSegPending* pending, hipStream_t st)
+                             int64_t gs_base, int summands_kept, const MhSegPending& Q, bool prior_waves, hipStream_t st)
 {
-    MhSegPending Q{};
-    Q.p_acc = -1;
-    Q.p_tail = -1;
-    if (pending) Q = *pending;
-    Q.ahead_from = opt_or(OPT_MH_AHEAD_FROM, kSegAheadFrom);
-    Q.prior_draws = (!opt_is(OPT_MH_PRIOR_DRAWS, 0) && !opt_is(OPT_MH_PRIOR_WAVES, 0)) ? 1 : 0;
     if (n_steps <= 0) return Q.p_acc >= 0 ? hipErrorInvalidValue : hipSuccess;
     if (Q.p_acc >= 0 && (Q.X1 == nullptr || (Q.z_in_zprop ? I.zprop == nullptr : I.zt == nullptr) || !summands_kept)) return hipErrorInvalidValue;
     if (Q.p_tail >= M.n_prop || (Q.p_tail >= 0 && (Q.X1_tail == nullptr || M.psum == nullptr || M.psel == nullptr))) return hipErrorInvalidValue;
     if (n_steps > (1 << 28)) return hipErrorInvalidValue;    // (the hand-over words count steps in 30 bits)
-    if (!mh_segment_available(M, V) || I.X0 == nullptr || I.zcur == nullptr || I.NPz != 64 * V.R) return hipErrorInvalidValue;
-    if (V.R == 6) return launch_segment_R<6>(M, V, T, P, I, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, gs_base, summands_kept, Q, st);
-    if (V.R == 8) return launch_segment_R<8>(M, V, T, P, I, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, gs_base, summands_kept, Q, st);
-    if (V.R == 12) return launch_segment_R<12>(M, V, T, P, I, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, gs_base, summands_kept, Q, st);
-    return launch_segment_R<16>(M, V, T, P, I, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, gs_base, summands_kept, Q, st);
+    if (!mh_segment_available(V, M.n_nodes, M.batch) || I.X0 == nullptr || I.zcur == nullptr || I.NPz != 64 * V.R) return hipErrorInvalidValue;
+    if (V.R == 6) return launch_segment_R<6>(M, V, T, P, I, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, gs_base, summands_kept, Q, prior_waves, st);
+    if (V.R == 8) return launch_segment_R<8>(M, V, T, P, I, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, gs_base, summands_kept, Q, prior_waves, st);
+    if (V.R == 12) return launch_segment_R<12>(M, V, T, P, I, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, gs_base, summands_kept, Q, prior_waves, st);
+    return launch_segment_R<16>(M, V, T, P, I, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, gs_base, summands_kept, Q, prior_waves, st);
 }
 
 }  // namespace mcd

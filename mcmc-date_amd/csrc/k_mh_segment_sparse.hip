@@ -502,11 +502,11 @@ __global__ __launch_bounds__(64 * CPW * (HELP ? 4 : 2), 1) void k_mh_segment_spa
 }
 
 // any tree of 3 .. 2048 nodes whose tables and one chain fit a CU's LDS, the symmetric part of the matrix on the device
-bool mh_segment_sparse_available(const MhDev& M, const SparseDev& Sp)
+bool mh_segment_sparse_available(const SparseFacts& Sp, int n_nodes, int64_t batch)
 {
-    if (Sp.s_rowptr == nullptr || M.n_nodes < 3 || M.n_nodes > 2048 || Sp.n != M.n_nodes - 2 || M.batch > 65536) return false;
+    if (!Sp.rows || n_nodes < 3 || n_nodes > 2048 || Sp.n != n_nodes - 2 || batch > 65536) return false;
     int cpw = 0, sz = 0;
-    sseg_geometry(M.n_nodes, (Sp.n + 63) / 64 * 64, cpw, sz);
+    sseg_geometry(n_nodes, (Sp.n + 63) / 64 * 64, cpw, sz);
     return cpw > 0;
 }
 int mh_segment_sparse_list() { return kSsegList; }
@@ -534,26 +534,23 @@ static hipError_t launch_sseg(const MhDev& M, const SparseDev& Sp, const TreeDev
 
 // steps [0, n_steps) of `sched` (device memory), none of which moves more than kSsegList distances; I: X0 = the current distances
 // [batch][n], zcur / zprop = the quadratic forms q [batch] of the current states / of the pending dense proposal (NPz = 1); list_all:
-// the tree's distance slots all fit the list, so a proposal that moves tH or rMu (every distance) may be part of a segment
+// the tree's distance slots all fit the list, so a proposal that moves tH or rMu (every distance) may be part of a segment; Q and
+// prior_waves as for launch_mh_segment
 hipError_t launch_mh_segment_sparse(const MhDev& M, const SparseDev& Sp, const TreeDev& T, const PriorDev& P, const MhInc& I, const int32_t* sched,
                                     int64_t n_steps, int32_t S, int accumulate, uint64_t step0, uint64_t seed, double* trace_alpha, int8_t* trace_accept,
-                                    int64_t gs_base, int summands_kept, const MhSegPending* pending, int list_all, hipStream_t st)
+                                    int64_t gs_base, int summands_kept, const MhSegPending& Q, int list_all, bool prior_waves, hipStream_t st)
 {
-    MhSegPending Q{};
-    Q.p_acc = -1;
-    Q.p_tail = -1;
-    if (pending) Q = *pending;
-    Q.ahead_from = opt_or(OPT_MH_AHEAD_FROM, kSegAheadFrom);
-    Q.prior_draws = (!opt_is(OPT_MH_PRIOR_DRAWS, 0) && !opt_is(OPT_MH_PRIOR_WAVES, 0)) ? 1 : 0;
     if (n_steps <= 0) return Q.p_acc >= 0 ? hipErrorInvalidValue : hipSuccess;
     if (Q.p_acc >= 0 && (Q.X1 == nullptr || I.zprop == nullptr || !summands_kept)) return hipErrorInvalidValue;
     if (Q.p_tail >= M.n_prop || (Q.p_tail >= 0 && (Q.X1_tail == nullptr || M.psum == nullptr || M.psel == nullptr))) return hipErrorInvalidValue;
-    if (n_steps > (1 << 22)) return hipErrorInvalidValue;    // (a slot's mark holds the step in 23 bits)
-    if (!mh_segment_sparse_available(M, Sp) || I.X0 == nullptr || I.zcur == nullptr || I.NPz != 1) return hipErrorInvalidValue;
+    // (a slot's mark is tag << 8 in an int32, the tags 2 (step + 1) + pass of the steps 0 .. n_steps - 1: the largest, 2 n_steps + 1, must stay
+    // below 2^23)
+    if (n_steps >= (1 << 22)) return hipErrorInvalidValue;
+    if (!mh_segment_sparse_available(Sp, M.n_nodes, M.batch) || I.X0 == nullptr || I.zcur == nullptr || I.NPz != 1) return hipErrorInvalidValue;
     if (list_all && Sp.n > kSsegList) return hipErrorInvalidValue;
     int cpw = 0, sz = 0;
     sseg_geometry(M.n_nodes, (Sp.n + 63) / 64 * 64, cpw, sz);
-    const bool help = !opt_is(OPT_MH_PRIOR_WAVES, 0);        // (mcd_set_option "MCD_MH_PRIOR_WAVES" = 0: the chain wave evaluates the whole ln prior; tests, timing)
+    const bool help = prior_waves;
     if (cpw == 2 && help) return launch_sseg<2, true>(M, Sp, T, P, I, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, gs_base, summands_kept, Q, sz, list_all, st);
     if (cpw == 2) return launch_sseg<2, false>(M, Sp, T, P, I, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, gs_base, summands_kept, Q, sz, list_all, st);
     if (help) return launch_sseg<1, true>(M, Sp, T, P, I, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, gs_base, summands_kept, Q, sz, list_all, st);

@@ -298,7 +298,7 @@ __global__ __launch_bounds__(256) void k_sparse_quad(SparseDev S, SparseTreeDev 
 }
 
 static size_t sparse_quad_lds(int n, int C) { return sizeof(double) * ((size_t)C * n + 4 * (size_t)C); }
-bool sparse_quad_available(const SparseDev& S, int64_t batch) { return S.q_rc != nullptr && S.n <= 65535 && sparse_quad_lds(S.n, 1) <= 160 * 1024 && batch >= 1; }
+bool sparse_quad_available(const SparseFacts& S, int64_t batch) { return S.quad && S.n <= 65535 && sparse_quad_lds(S.n, 1) <= 160 * 1024 && batch >= 1; }
 
 template <int C, bool TREE>
 static hipError_t launch_quad_C(const SparseDev& S, const SparseTreeDev& T, const double* X, const double* Rt, int64_t ld, const double* tH, const double* rMu,

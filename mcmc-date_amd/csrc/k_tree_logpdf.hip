@@ -194,7 +194,7 @@ hipError_t launch_tree_logpdf_prior_g2(const MvnDev& M, const TreeDev& T, const 
 hipError_t launch_tree_logpdf_prior_g3(const MvnDev& M, const TreeDev& T, const double* H, const double* Rt, int64_t lds, const double* tH,
                                        const double* rMu, int64_t batch, double* ll, double* logjac, const MhDev& J, const PriorDev& JP, hipStream_t st);
 // the sweep serves this launch, and the slices of the ring the prior waves use fit it
-bool tree_logpdf_can_carry_prior(const MvnDev& M, int64_t batch, int n_nodes)
+bool tree_logpdf_can_carry_prior(const MvnFacts& M, int64_t batch, int n_nodes)
 {
     if (batch <= 0 || use_split(M, batch) || use_wide(M, batch)) return false;
     const Geometry g = pick_geometry(batch);

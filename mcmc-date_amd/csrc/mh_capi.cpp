@@ -1,7 +1,7 @@
 // mh_capi.cpp -- C ABI of the lock-step Metropolis-Hastings-Green driver (include/mcmcdate_mvn.h, "mcd_mh_*").
-// Trees of at most 64 nodes: the whole schedule in one launch (k_mh_chain.hip).  Larger trees, two launches per step:
-// [accept the previous step + propose + ln prior] (k_mh.hip) and [batched likelihood + root-branch Jacobian]
-// (k_tree_logpdf.hip), enqueued on one stream; the state stays on the device.  No CPU path.
+// mcd_mh_run plans every run once (plan_run: one of the nine MCD_MH_PATH_* launch structures and every choice its launches depend on),
+// then one runner enqueues its launches on the handle's stream: a whole-schedule kernel (k_mh_chain.hip, k_mh_chain_big.hip), the segment
+// loop (k_mh_segment*.hip) or the two-launch step loop (k_mh.hip + a likelihood launch).  The state stays on the device.  No CPU path.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -133,43 +133,21 @@ int eval_posterior(mcd_mh* m, const double* sc, const double* H, const double* R
 
 }  // namespace
 
-extern "C" {
-
-}  // extern "C"
-
 namespace {
 
-// the part of mcd_mh_create / mcd_mh_create_sparse behind the handles: m->mvn / m->tree (dense) or m->sp / m->sp_tree / m->tree
-// (= &m->tree_shim, sparse) and m->prior are set, `parent` is the host copy of the topology, host_L the host factor (dense) or null
-int mh_create_impl(mcd_mh_t** out, std::unique_ptr<mcd_mh>& m, const mcd_prior_t* prior, int dev_t, int dev_p, const int32_t* parent, const double* host_L,
-                   int n_prop, const int32_t* kind, const int32_t* node, const int32_t* n1, const int32_t* n2, const int32_t* jac_root,
-                   const int32_t* dim, const double* p0, const double* p1, int64_t batch, uint64_t seed)
+// host copies of the topology that the proposal table is checked and classified against
+struct HostTree {
+    int n;
+    const int32_t* parent;
+    std::vector<int32_t> size;                     // nodes of every sub tree
+    std::vector<int32_t> brace_ptr, brace_nodes;   // the prior's braces (their tables live in device memory)
+};
+
+// the proposal table checks: the reference raises `error` for a path to a leaf / an invalid path when the proposal is built
+int check_proposals(const HostTree& t, int n_prop, const int32_t* kind, const int32_t* node, const int32_t* dim, const double* p0, const double* p1)
 {
-    if (dev_t != dev_p) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_create: tree (device %d) and prior (device %d) live on different GPUs", dev_t, dev_p);
-    const int n = m->tree->n_nodes;
-    if (m->prior->n_nodes != n) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_create: tree has %d nodes, prior %d", n, m->prior->n_nodes);
-    {   // tree and prior must describe the same topology: compare the prior's parent array (device) with the tree's
-        std::vector<int32_t> pp(n);
-        MHIP_TRY(hipSetDevice(dev_p));
-        MHIP_TRY(hipMemcpy(pp.data(), m->prior->parent, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-        for (int v = 0; v < n; ++v)
-            if (pp[v] != parent[v]) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_create: tree and prior have different topologies (node %d)", v);
-    }
-    std::vector<int32_t> size(n, 1);
-    for (int v = n - 1; v > 0; --v) size[parent[v]] += size[v];
-    // the braces live in the prior's tables (device memory): a host copy for the checks below
-    const int nbr = m->prior->n_brace;
-    std::vector<int32_t> host_brace_ptr(nbr + 1, 0), host_brace_nodes;
-    if (nbr > 0) {
-        int dev_prior = 0;
-        const mcd::PriorDev* pd = nullptr;
-        (void)mcd_prior_internal_(prior, &pd, &dev_prior);
-        MHIP_TRY(hipSetDevice(dev_prior));
-        MHIP_TRY(hipMemcpy(host_brace_ptr.data(), pd->brace_ptr, sizeof(int32_t) * (nbr + 1), hipMemcpyDeviceToHost));
-        host_brace_nodes.resize(host_brace_ptr[nbr]);
-        MHIP_TRY(hipMemcpy(host_brace_nodes.data(), pd->brace_nodes, sizeof(int32_t) * host_brace_nodes.size(), hipMemcpyDeviceToHost));
-    }
-    // proposal table checks: the reference raises `error` for a path to a leaf / an invalid path when the proposal is built
+    const int n = t.n, n_brace = (int)t.brace_ptr.size() - 1;
+    const std::vector<int32_t>& size = t.size;
     const int root_right = 1 + size[1];
     for (int i = 0; i < n_prop; ++i) {
         const int k = kind[i], v = node[i];
@@ -202,9 +180,9 @@ int mh_create_impl(mcd_mh_t** out, std::unique_ptr<mcd_mh>& m, const mcd_prior_t
                 break;
             case MCD_PROP_SLIDE_BRACE:
             case MCD_PROP_SLIDE_BRACE_CONTRA:
-                if (v < 0 || v >= m->prior->n_brace) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_create: proposal %d: the prior has no brace %d", i, v);
-                for (int j = host_brace_ptr[v]; j < host_brace_ptr[v + 1]; ++j) {
-                    const int x = host_brace_nodes[j];
+                if (v < 0 || v >= n_brace) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_create: proposal %d: the prior has no brace %d", i, v);
+                for (int j = t.brace_ptr[v]; j < t.brace_ptr[v + 1]; ++j) {
+                    const int x = t.brace_nodes[j];
                     if (x == 0) return mfail(MCD_ERR_INVALID_ARG, "slideBracedNodesUltrametric: Braced root node (proposal %d).", i);
                     if (size[x] == 1) return mfail(MCD_ERR_INVALID_ARG, "slideBracedNodesUltrametric: Path of a node leads to a leaf (proposal %d).", i);
                 }
@@ -219,74 +197,108 @@ int mh_create_impl(mcd_mh_t** out, std::unique_ptr<mcd_mh>& m, const mcd_prior_t
             default: return mfail(MCD_ERR_UNSUPPORTED, "mcd_mh_create: proposal %d: unknown kind %d", i, k);
         }
     }
-    // Which proposals move only a few branch distances (k_mh_chain_big.hip evaluates those by columns of L^-1 instead of a sweep):
-    // a distance changes where a node's height, its parent's height or its rate changes -- for the node kinds below the node
-    // itself with its daughters, or its sub tree.  The root's two daughters share distance slot 0.  This is a performance hint
-    // only: the kernel finds the moved distances from the data and is right for any number of them.
-    // (sparse_inc: the same for the two-launch path's incremental evaluation, k_mh_inc.hip, whose list of moved distances is not bounded
-    // by registers: up to kMhIncSlots columns of L^-1 still cost less than a likelihood launch.)
-    std::vector<int32_t> sparse((size_t)n_prop, 0), sparse_inc((size_t)n_prop, 0);
-    const int opt_slots = mcd::opt_get(mcd::OPT_MH_INC_SLOTS);      // (mcd_set_option "MCD_MH_INC_SLOTS", read here)
-    // (where the segment kernel runs the sparse proposals, k_mh_segment.hip, many more: a likelihood launch there also costs the whole
-    // state's way through memory twice; measured at 1025 nodes x 512 chains: 16 -> 22.5, 64 -> 14.2, 128 -> 12.7, 192 -> 12.5 us per lock step)
-    mcd::MhDev probe{};
-    probe.n_nodes = n;
-    probe.batch = batch;
-    const bool seg_capable = m->mvn != nullptr && mcd::mh_segment_available(probe, *m->mvn);
-    // (over a sparse precision matrix, k_mh_segment_sparse.hip: a listed distance costs a row of the matrix, some 15 entries, where the
-    // two launches of a dense proposal cost a full product -- whatever the list holds)
-    const bool sseg_capable = m->sp != nullptr && mcd::mh_segment_sparse_available(probe, *m->sp);
+    return MCD_OK;
+}
+
+// Per proposal: 1 where it moves at most `limit` branch distances, or everywhere (all).  A distance changes where a node's height, its
+// parent's height or its rate changes -- for the node kinds below the node itself with its daughters, or its sub tree.  The root's two
+// daughters share distance slot 0.  This is a performance hint only: the kernels find the moved distances from the data and are right for
+// any number of them.
+std::vector<int32_t> moves_few(const HostTree& t, int limit, bool all, int n_prop, const int32_t* kind, const int32_t* node)
+{
+    std::vector<std::vector<int>> kids((size_t)t.n);
+    for (int v = 1; v < t.n; ++v) kids[(size_t)t.parent[v]].push_back(v);
+    auto slots_of = [&](const std::vector<int>& nodes) {
+        std::vector<int> sl;
+        for (int w : nodes) {
+            if (w == 0) continue;
+            const int key = (t.parent[w] == 0) ? 1 : w;              // both root daughters -> one slot
+            if (std::find(sl.begin(), sl.end(), key) == sl.end()) sl.push_back(key);
+        }
+        return (int)sl.size();
+    };
+    std::vector<int32_t> out((size_t)n_prop, 0);
+    for (int i = 0; i < n_prop; ++i) {
+        const int k = kind[i], v = node[i];
+        std::vector<int> touched;
+        bool known = true;
+        switch (k) {
+            case MCD_PROP_SLIDE_NODE:
+            case MCD_PROP_SLIDE_NODE_CONTRA:
+                touched.push_back(v);
+                for (int c : kids[(size_t)v]) touched.push_back(c);
+                break;
+            case MCD_PROP_SCALE_BRANCH_RATE: touched.push_back(v); break;
+            case MCD_PROP_SCALE_SUBTREE_TIME:
+            case MCD_PROP_SCALE_SUBTREE_RATE:
+            case MCD_PROP_SCALE_SUBTREE_CONTRA:
+                if (t.size[v] > 2 * limit) { known = false; break; }
+                for (int w = v; w < v + t.size[v]; ++w) touched.push_back(w);
+                break;
+            case MCD_PROP_SLIDE_BRACE:
+            case MCD_PROP_SLIDE_BRACE_CONTRA:
+                for (int j = t.brace_ptr[v]; j < t.brace_ptr[v + 1]; ++j) {
+                    touched.push_back(t.brace_nodes[j]);
+                    for (int c : kids[(size_t)t.brace_nodes[j]]) touched.push_back(c);
+                }
+                break;
+            default: known = false; break;                         // scalars, whole-tree scalings, pulley, root slide
+        }
+        out[(size_t)i] = ((known && slots_of(touched) <= limit) || all) ? 1 : 0;
+    }
+    return out;
+}
+
+// the part of mcd_mh_create / mcd_mh_create_sparse behind the handles: m->mvn / m->tree (dense) or m->sp / m->sp_tree / m->tree
+// (= &m->tree_shim, sparse) and m->prior are set, `parent` is the host copy of the topology, host_L the host factor (dense) or null
+int mh_create_impl(mcd_mh_t** out, std::unique_ptr<mcd_mh>& m, const mcd_prior_t* prior, int dev_t, int dev_p, const int32_t* parent, const double* host_L,
+                   int n_prop, const int32_t* kind, const int32_t* node, const int32_t* n1, const int32_t* n2, const int32_t* jac_root,
+                   const int32_t* dim, const double* p0, const double* p1, int64_t batch, uint64_t seed)
+{
+    // the knobs (mcd_set_option) that creation reads; every run reads the others when it starts (plan_run)
+    const int opt_inc_slots = mcd::opt_get(mcd::OPT_MH_INC_SLOTS), opt_sparse_slots = mcd::opt_get(mcd::OPT_MH_SPARSE_SLOTS);
+    const bool per_phase = mcd::opt_is(mcd::OPT_MH_PER_PHASE, 1);
+    if (dev_t != dev_p) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_create: tree (device %d) and prior (device %d) live on different GPUs", dev_t, dev_p);
+    const int n = m->tree->n_nodes;
+    if (m->prior->n_nodes != n) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_create: tree has %d nodes, prior %d", n, m->prior->n_nodes);
+    {   // tree and prior must describe the same topology: compare the prior's parent array (device) with the tree's
+        std::vector<int32_t> pp(n);
+        MHIP_TRY(hipSetDevice(dev_p));
+        MHIP_TRY(hipMemcpy(pp.data(), m->prior->parent, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+        for (int v = 0; v < n; ++v)
+            if (pp[v] != parent[v]) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_create: tree and prior have different topologies (node %d)", v);
+    }
+    HostTree t{n, parent, std::vector<int32_t>(n, 1), {}, {}};
+    for (int v = n - 1; v > 0; --v) t.size[parent[v]] += t.size[v];
+    const int nbr = m->prior->n_brace;
+    t.brace_ptr.assign(nbr + 1, 0);
+    if (nbr > 0) {
+        int dev_prior = 0;
+        const mcd::PriorDev* pd = nullptr;
+        (void)mcd_prior_internal_(prior, &pd, &dev_prior);
+        MHIP_TRY(hipSetDevice(dev_prior));
+        MHIP_TRY(hipMemcpy(t.brace_ptr.data(), pd->brace_ptr, sizeof(int32_t) * (nbr + 1), hipMemcpyDeviceToHost));
+        t.brace_nodes.resize(t.brace_ptr[nbr]);
+        MHIP_TRY(hipMemcpy(t.brace_nodes.data(), pd->brace_nodes, sizeof(int32_t) * t.brace_nodes.size(), hipMemcpyDeviceToHost));
+    }
+    if (int rc = check_proposals(t, n_prop, kind, node, dim, p0, p1)) return rc;
+    // Which proposals move only a few branch distances: the streaming chain kernel (k_mh_chain_big.hip) evaluates those by columns of L^-1
+    // instead of a sweep -- up to 258 nodes its likelihood wave takes the columns four at a time beside the prior: kMhSparseSlots, tuning:
+    // MCD_MH_SPARSE_SLOTS, at most 64 (its list, kMhbList).  The two-launch path's incremental evaluation (k_mh_inc.hip) is not bounded by
+    // registers: up to kMhIncSlots columns of L^-1 still cost less than a likelihood launch.  Where the segment kernel runs the sparse
+    // proposals (k_mh_segment.hip), many more: a likelihood launch there also costs the whole state's way through memory twice; measured at
+    // 1025 nodes x 512 chains: 16 -> 22.5, 64 -> 14.2, 128 -> 12.7, 192 -> 12.5 us per lock step.  Over a sparse precision matrix
+    // (k_mh_segment_sparse.hip) a listed distance costs a row of the matrix, some 15 entries, where the two launches of a dense proposal
+    // cost a full product -- whatever the list holds.  MCD_MH_INC_SLOTS sets the latter three.
+    const bool seg_capable = m->mvn != nullptr && mcd::mh_segment_available(*m->mvn, n, batch);
+    const bool sseg_capable = m->sp != nullptr && mcd::mh_segment_sparse_available(*m->sp, n, batch);
     const int list_cap = sseg_capable ? mcd::mh_segment_sparse_list() : mcd::kMhSegList;
-    const int inc_slots = opt_slots != mcd::MCD_OPT_UNSET ? std::max(1, std::min(list_cap, opt_slots)) : sseg_capable ? list_cap : seg_capable ? mcd::kMhSegSlots : mcd::kMhIncSlots;
+    const int inc_slots = opt_inc_slots != mcd::MCD_OPT_UNSET ? std::max(1, std::min(list_cap, opt_inc_slots)) : sseg_capable ? list_cap : seg_capable ? mcd::kMhSegSlots : mcd::kMhIncSlots;
     // a tree whose distance slots ALL fit the sparse segment kernel's list: every proposal of the cycle can run inside a segment
     m->list_all = sseg_capable && m->sp->n <= list_cap;
-    for (int pass = 0; pass < 2; ++pass) {
-        const int opt_ss = mcd::opt_get(mcd::OPT_MH_SPARSE_SLOTS);      // (the streaming chain kernel's threshold; tuning: mcd_set_option "MCD_MH_SPARSE_SLOTS")
-        // (up to 258 nodes the chain's likelihood wave takes the columns four at a time beside the prior: 48; above, where the chain wave
-        // itself fetches them two at a time -- the sweep-only builds of the larger trees, which otherwise run in segments --: 16)
-        const int big_default = (m->mvn != nullptr && m->mvn->R <= 4) ? mcd::kMhSparseSlots : 16;
-        const int limit = pass ? inc_slots : opt_ss != mcd::MCD_OPT_UNSET ? std::max(1, std::min(64, opt_ss)) : big_default;      // (64: the kernel's list, kMhbList)
-        std::vector<std::vector<int>> kids((size_t)n);
-        for (int v = 1; v < n; ++v) kids[(size_t)parent[v]].push_back(v);
-        auto slots_of = [&](const std::vector<int>& nodes) {
-            std::vector<int> sl;
-            for (int w : nodes) {
-                if (w == 0) continue;
-                const int key = (parent[w] == 0) ? 1 : w;              // both root daughters -> one slot
-                if (std::find(sl.begin(), sl.end(), key) == sl.end()) sl.push_back(key);
-            }
-            return (int)sl.size();
-        };
-        for (int i = 0; i < n_prop; ++i) {
-            const int k = kind[i], v = node[i];
-            std::vector<int> touched;
-            bool known = true;
-            switch (k) {
-                case MCD_PROP_SLIDE_NODE:
-                case MCD_PROP_SLIDE_NODE_CONTRA:
-                    touched.push_back(v);
-                    for (int c : kids[(size_t)v]) touched.push_back(c);
-                    break;
-                case MCD_PROP_SCALE_BRANCH_RATE: touched.push_back(v); break;
-                case MCD_PROP_SCALE_SUBTREE_TIME:
-                case MCD_PROP_SCALE_SUBTREE_RATE:
-                case MCD_PROP_SCALE_SUBTREE_CONTRA:
-                    if (size[v] > 2 * limit) { known = false; break; }
-                    for (int w = v; w < v + size[v]; ++w) touched.push_back(w);
-                    break;
-                case MCD_PROP_SLIDE_BRACE:
-                case MCD_PROP_SLIDE_BRACE_CONTRA:
-                    for (int j = host_brace_ptr[v]; j < host_brace_ptr[v + 1]; ++j) {
-                        touched.push_back(host_brace_nodes[j]);
-                        for (int c : kids[(size_t)host_brace_nodes[j]]) touched.push_back(c);
-                    }
-                    break;
-                default: known = false; break;                         // scalars, whole-tree scalings, pulley, root slide
-            }
-            (pass ? sparse_inc : sparse)[(size_t)i] = ((known && slots_of(touched) <= limit) || (pass && m->list_all)) ? 1 : 0;
-        }
-    }
-    m->sparse_rows = sparse_inc;
+    const int chain_slots = opt_sparse_slots != mcd::MCD_OPT_UNSET ? std::max(1, std::min(64, opt_sparse_slots)) : mcd::kMhSparseSlots;
+    const std::vector<int32_t> sparse = moves_few(t, chain_slots, false, n_prop, kind, node);
+    m->sparse_rows = moves_few(t, inc_slots, m->list_all, n_prop, kind, node);
     m->device = dev_t;
     m->seed = seed;
     for (int i = 0; i < n_prop; ++i) m->rows.push_back(mcd::MhRow{kind[i], node[i], n1[i], n2[i], jac_root[i], p0[i], p1[i]});
@@ -304,7 +316,7 @@ int mh_create_impl(mcd_mh_t** out, std::unique_ptr<mcd_mh>& m, const mcd_prior_t
     D.n_brace = nbr;
     int rc = MCD_OK;
     const size_t B = (size_t)batch, BL = B * (size_t)D.ld, BP = B * (size_t)n_prop, BN = B * (size_t)n;
-    if ((rc = dev_upload(m.get(), &D.size, size.data(), (size_t)n)) || (rc = dev_upload(m.get(), &D.kind, kind, (size_t)n_prop)) ||
+    if ((rc = dev_upload(m.get(), &D.size, t.size.data(), (size_t)n)) || (rc = dev_upload(m.get(), &D.kind, kind, (size_t)n_prop)) ||
         (rc = dev_upload(m.get(), &D.node, node, (size_t)n_prop)) || (rc = dev_upload(m.get(), &D.n1, n1, (size_t)n_prop)) ||
         (rc = dev_upload(m.get(), &D.n2, n2, (size_t)n_prop)) || (rc = dev_upload(m.get(), &D.jac_root, jac_root, (size_t)n_prop)) ||
         (rc = dev_upload(m.get(), &D.dim, dim, (size_t)n_prop)) || (rc = dev_upload(m.get(), &D.p0, p0, (size_t)n_prop)) ||
@@ -322,7 +334,7 @@ int mh_create_impl(mcd_mh_t** out, std::unique_ptr<mcd_mh>& m, const mcd_prior_t
     // trees of at most 64 nodes: the whole schedule runs in one launch with the factor staged in LDS (k_mh_chain.hip).
     // MCD_MH_PER_PHASE=1 (diagnostic) keeps the two-launches-per-step path that larger trees use.
     const int nd = m->mvn ? m->mvn->n : m->sp->n;
-    if (m->mvn && n <= 64 && !mcd::opt_is(mcd::OPT_MH_PER_PHASE, 1) && mcd::mh_chain_lds_bytes(nd, n_prop, 4) + sizeof(double) * mcd::prior_node_tables_doubles(m->prior->n_cal, m->prior->n_con) <= 64 * 1024) {
+    if (m->mvn && n <= 64 && !per_phase && mcd::mh_chain_lds_bytes(nd, n_prop, 4) + sizeof(double) * mcd::prior_node_tables_doubles(m->prior->n_cal, m->prior->n_con) <= 64 * 1024) {
         std::vector<double> Fp((size_t)nd * 64, 0.0);
         for (int i = 0; i < nd; ++i) {
             const double inv = 1.0 / host_L[(size_t)i * nd + i];
@@ -540,6 +552,420 @@ int mcd_mh_mc3_get(const mcd_mh_t* cm, int32_t* rank, int64_t* tried, int64_t* a
     return MCD_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// ---- mcd_mh_run: a plan per run, one runner per family of launch structures ----------------------------------------------------
+
+// the knobs (mcd_set_option) that a run depends on, read once when it starts: MCD_OPT_UNSET or the value
+struct MhOptions {
+    int per_phase, segments, incremental, prior, prior_cache, step_wg, chain_lw, prior_waves, seg_tail, ahead_from, prior_draws;
+};
+
+MhOptions mh_options()
+{
+    using mcd::opt_get;
+    return MhOptions{opt_get(mcd::OPT_MH_PER_PHASE), opt_get(mcd::OPT_MH_SEGMENTS), opt_get(mcd::OPT_MH_INCREMENTAL), opt_get(mcd::OPT_MH_PRIOR),
+                     opt_get(mcd::OPT_MH_PRIOR_CACHE), opt_get(mcd::OPT_MH_STEP_WG), opt_get(mcd::OPT_MH_CHAIN_LW), opt_get(mcd::OPT_MH_PRIOR_WAVES),
+                     opt_get(mcd::OPT_MH_SEG_TAIL), opt_get(mcd::OPT_MH_AHEAD_FROM), opt_get(mcd::OPT_MH_PRIOR_DRAWS)};
+}
+
+// what a plan depends on besides the knobs: the handle's shape and its create-time decisions, as plain facts
+struct MhShape {
+    int n_nodes, n_prop;
+    int64_t batch;
+    bool dense;              // a dense likelihood (mvn), else a sparse one (sp)
+    mcd::MvnFacts mvn;
+    mcd::SparseFacts sp;
+    bool chain_kernel, list_all;
+};
+
+MhShape shape_of(const mcd_mh* m)
+{
+    MhShape s{m->dev.n_nodes, m->dev.n_prop, m->dev.batch, m->mvn != nullptr, {}, {}, m->chain_kernel, m->list_all};
+    if (m->mvn) s.mvn = *m->mvn;
+    else s.sp = *m->sp;
+    return s;
+}
+
+// every decision that the launches of one run depend on
+struct MhPlan {
+    int path = MCD_MH_PATH_NONE;
+    const char* refused = nullptr;   // path NONE: why the run cannot be served
+    bool likelihood_wave = false;    // small-tree kernel: the likelihood by a second wave per chain, beside the prior
+    bool incremental = false;        // streamed chain kernel / per-step paths: sparse proposals by columns of L^-1 on a kept z
+    bool beside = false, use_x = false, step_wg = false, keep = false;   // see plan_run
+    bool inc_dense = false, inc_sparse = false, chunked = false, segments = false, tails = false;
+    bool prior_waves = false, prior_draws = false;   // the segment kernels' prior waves, which also draw the next proposal
+    int ahead_from = 0;              // MhSegPending::ahead_from
+    int flags() const
+    {
+        const bool f[] = {likelihood_wave, incremental, beside, use_x, step_wg, keep, inc_dense, inc_sparse, chunked, segments, tails, prior_waves, prior_draws};
+        int r = 0;
+        for (int i = 0; i < (int)(sizeof f / sizeof f[0]); ++i) r |= (f[i] ? 1 : 0) << i;
+        return r;
+    }
+};
+
+MhPlan plan_run(const MhShape& s, const MhOptions& o)
+{
+    MhPlan p;
+    const bool per_phase = o.per_phase == 1, seg_off = o.segments == 0, inc_off = o.incremental == 0;
+    p.likelihood_wave = o.chain_lw != 0;
+    p.incremental = !inc_off;
+    p.prior_waves = o.prior_waves != 0;
+    p.prior_draws = o.prior_draws != 0 && p.prior_waves;
+    p.ahead_from = o.ahead_from != mcd::MCD_OPT_UNSET ? o.ahead_from : mcd::kSegAheadFrom;
+    if (s.chain_kernel) {                      // trees of at most 64 nodes (mcd_mh_create): the whole schedule in one launch
+        p.path = MCD_MH_PATH_CHAIN_LDS;
+        return p;
+    }
+    // Larger trees at a sampler's batch: the whole schedule in one launch as well, the factor streamed once per step (k_mh_chain_big.hip).
+    // From 259 nodes (R >= 6) the segment path is ahead of it (271 nodes x 512 chains 11.3 -> 9.6 us per lock step, 513 nodes 16.0 -> 9.6):
+    // the factor streamed for every dense proposal costs more there than two launches for the few proposals that move more than 192
+    // distances.
+    const int64_t split_batch = std::min<int64_t>(s.batch, mcd::kSplitMaxBatch);
+    const bool prefer_segments = s.dense && !seg_off && !inc_off && mcd::mh_segment_available(s.mvn, s.n_nodes, s.batch) && mcd::use_split(s.mvn, split_batch);
+    if (s.dense && !per_phase && s.mvn.form != MCD_FORM_MULTIPLY && mcd::mh_chain_big_available(s.mvn, s.n_nodes, s.n_prop, s.batch) && !prefer_segments) {
+        p.path = MCD_MH_PATH_CHAIN_STREAMED;
+        return p;
+    }
+    // two launches per step: [accept step s-1 + propose step s + ln prior] and [likelihood + root-branch Jacobian]
+    if ((size_t)s.n_nodes * 32 > 64 * 1024) {
+        p.refused = "more than 2048 nodes";
+        return p;
+    }
+    // The ln prior of a proposed state depends on the proposal only, like its ln likelihood: where the sweep serves the likelihood launch,
+    // that launch carries the prior as workgroups of a second role (k_tree_logpdf.hip, mh_prior_role.hpp) and the step kernel leaves it out.
+    // (A launch of its own for the prior with four waves per chain was measured for the larger trees: 58.9 -> 56.4 us per lock step at
+    // 1025 nodes, 33.3 -> 35.4 at 513 -- the step kernel's other strided loops weigh more there; not kept.)
+    p.beside = s.dense && !prefer_segments && o.prior != 0 && mcd::tree_logpdf_can_carry_prior(s.mvn, s.batch, s.n_nodes);
+    const bool prior_inline = !p.beside;
+    // Large trees: the workgroup-per-chain step kernel leaves the proposed states' DISTANCES, the likelihood launch takes them as plain
+    // vectors (the row-split kernel's tree staging costs 6 us more at 1023 slots); same arithmetic, same bits.  MCD_MH_STEP_WG = 1 / 0
+    // forces / forbids that step kernel.
+    const int wg_from = !s.dense ? 0 : prefer_segments ? 258 : 320;
+    const bool wg_fits = mcd::mh_step_wg_fits(s.n_nodes);
+    auto wg_for = [&](int min_nodes) { return (o.step_wg != mcd::MCD_OPT_UNSET ? o.step_wg != 0 : (prior_inline && s.n_nodes > min_nodes)) && wg_fits; };
+    p.use_x = wg_for(wg_from) && !p.beside && s.n_nodes > wg_from;
+    if (!s.dense && !p.use_x) {
+        p.refused = "the sparse driver needs the workgroup-per-chain step kernel (MCD_MH_STEP_WG must not be 0)";
+        return p;
+    }
+    p.step_wg = p.use_x || wg_for(320);
+    p.keep = prior_inline && wg_for(wg_from) && o.prior_cache != 0;   // (MCD_MH_PRIOR_CACHE = 0: every summand at every step)
+    // Large trees at a sampler's batch: the likelihood launch only for the proposals that move many distances (k_mh_inc.hip); the others
+    // are evaluated from columns of L^-1 on the kept z.  Over a sparse precision matrix (k_mh_segment_sparse.hip) the incremental form keeps
+    // the quadratic form q itself (MhInc with NPz = 1); it exists only together with the segments.
+    p.inc_dense = s.dense && p.use_x && !inc_off && s.mvn.cols && 64 * s.mvn.R <= 1024 && mcd::use_split(s.mvn, split_batch);
+    p.inc_sparse = !s.dense && p.use_x && !inc_off && !seg_off && mcd::mh_segment_sparse_available(s.sp, s.n_nodes, s.batch) &&
+                   mcd::sparse_quad_available(s.sp, s.batch);
+    p.chunked = p.inc_dense && s.batch > mcd::kSplitMaxBatch;
+    // Trees of 259 .. 1026 nodes: the runs of steps between two dense proposals as ONE launch each, every chain's state in LDS
+    // (k_mh_segment.hip); a dense proposal: its likelihood by the row-split launch, decided by the step kernel or the next segment
+    p.segments = p.inc_sparse || (p.inc_dense && !seg_off && mcd::mh_segment_available(s.mvn, s.n_nodes, s.batch));
+    p.tails = p.keep && o.seg_tail != 0;
+    p.path = p.segments ? (p.inc_sparse ? MCD_MH_PATH_SEGMENTS_SPARSE : MCD_MH_PATH_SEGMENTS)
+             : !s.dense ? MCD_MH_PATH_STEP_WG_SPARSE
+             : p.inc_dense ? MCD_MH_PATH_STEP_WG_INCREMENTAL
+             : p.use_x ? MCD_MH_PATH_STEP_WG_X
+             : p.beside ? MCD_MH_PATH_TWO_LAUNCH_PRIOR_BESIDE : MCD_MH_PATH_TWO_LAUNCH;
+    return p;
+}
+
+// the device buffers of the per-step paths, allocated on first use: the proposed distances (d_X1), the kept summands of the ln prior
+// (d_psum, d_psel), the arrays of the incremental likelihood (MhInc)
+int plan_buffers(mcd_mh* m, const MhPlan& p)
+{
+    mcd::MhDev& D = m->dev;
+    const size_t B = (size_t)D.batch, n_dim = (size_t)(m->mvn ? m->mvn->n : m->sp->n);
+    if (p.use_x && m->d_X1 == nullptr)
+        if (int rc = dev_alloc(m, &m->d_X1, B * n_dim, false)) return rc;
+    if (p.keep && m->d_psum == nullptr) {
+        const size_t NS = (size_t)((D.n_nodes - 1 + 63) / 64) * 64;
+        if (int rc = dev_alloc(m, &m->d_psum, B * 4 * NS, false)) return rc;
+        if (int rc = dev_alloc(m, &m->d_psel, 2 * B, false)) return rc;
+    }
+    D.psum = p.keep ? m->d_psum : nullptr;
+    D.psel = p.keep ? m->d_psel : nullptr;
+    mcd::MhInc& I = m->inc;
+    if (p.inc_sparse && I.X0 == nullptr) {            // zcur / zprop = q of the current states / of the pending dense proposal
+        I.NPz = 1;
+        if (int rc = dev_alloc(m, &I.X0, B * n_dim, false)) return rc;
+        if (int rc = dev_alloc(m, &I.zcur, 2 * B, false)) return rc;
+        I.zprop = I.zcur + B;
+    }
+    if (p.inc_dense && I.X0 == nullptr) {
+        I.NPz = 64 * m->mvn->R;
+        if (int rc = dev_alloc(m, &I.X0, B * n_dim, false)) return rc;
+        if (int rc = dev_alloc(m, &I.zcur, B * (size_t)I.NPz, false)) return rc;
+        if (int rc = dev_alloc(m, &I.zprop, B * (size_t)I.NPz, false)) return rc;
+        if (int rc = dev_alloc(m, &m->d_inc_ll, B, false)) return rc;
+    }
+    return MCD_OK;
+}
+
+const mcd::MhRow kNoRow{0, 0, 0, 0, 0, 1.0, 0.0};
+
+// one run of a plan: the handle, the schedule and what the runners share
+struct MhRun {
+    mcd_mh* m;
+    const MhPlan& p;
+    const int32_t* schedule;
+    int64_t total;                   // steps
+    int32_t S;
+    int accumulate;
+    bool trace;
+    uint64_t step_base;              // the step number of schedule position 0
+    int n_dim;
+    int prior_inline;
+    const mcd::TreeDev* Tx;          // the step kernel's distances (use_x)
+    double* X1;
+    bool inc;
+    int dense_mode;                  // where the z' (q') of a dense proposal is afterwards: zprop (1) or the z tiles (2)
+
+    MhRun(mcd_mh* m_, const MhPlan& p_, const int32_t* schedule_, int64_t total_, int32_t S_, int accumulate_, bool trace_)
+        : m(m_), p(p_), schedule(schedule_), total(total_), S(S_), accumulate(accumulate_), trace(trace_), step_base(m_->step),
+          n_dim(m_->mvn ? m_->mvn->n : m_->sp->n), prior_inline(p_.beside ? 0 : 1), Tx(p_.use_x ? m_->tree : nullptr), X1(p_.use_x ? m_->d_X1 : nullptr),
+          inc(p_.inc_dense || p_.inc_sparse), dense_mode((p_.chunked || p_.inc_sparse) ? 1 : 2) {}
+    double* alpha(int64_t gs) const { return trace ? m->d_trace_alpha + gs * m->dev.batch : nullptr; }
+    int8_t* accept(int64_t gs) const { return trace ? m->d_trace_accept + gs * m->dev.batch : nullptr; }
+
+    // the draws of schedule positions [64 k, 64 k + 64) are computed when position 64 k is about to be proposed
+    int draws_for(int64_t idx) const
+    {
+        if ((idx & 63) == 0) {
+            const int count = (int)((total - idx < 64) ? total - idx : 64);
+            MHIP_TRY(mcd::launch_mh_draws(m->dev, m->d_sched, idx, count, step_base + (uint64_t)idx, m->seed, m->stream));
+        }
+        return MCD_OK;
+    }
+    // ll and z = L^-1 (X - mu) of every chain by full products (the row-split kernel, at most 1024 chains per launch); z to dst
+    // (chain-major) -- or, for a batch of one launch and dst = null, left in that launch's z tiles
+    int z_product(const double* X, double* ll, double* dst) const
+    {
+        const mcd::MhDev& D = m->dev;
+        mcd::MhInc& I = m->inc;
+        if (p.inc_sparse) {                            // the full form in one launch (k_sparse.hip: k_sparse_quad): ll and q (dst)
+            MHIP_TRY(mcd::launch_sparse_quad(*m->sp, nullptr, X, nullptr, n_dim, nullptr, nullptr, D.batch, ll, nullptr, dst, m->stream));
+            return MCD_OK;
+        }
+        for (int64_t c0 = 0; c0 < D.batch; c0 += mcd::kSplitMaxBatch) {
+            const int64_t cnt = std::min<int64_t>(mcd::kSplitMaxBatch, D.batch - c0);
+            MHIP_TRY(mcd::launch_logpdf_split_z(*m->mvn, X + c0 * n_dim, n_dim, cnt, ll + c0, &I.zt, &I.nr, m->stream));
+            if (dst) MHIP_TRY(mcd::launch_mh_inc_take_z(I, dst, c0, cnt, m->stream));
+        }
+        return MCD_OK;
+    }
+    // (dense: the ll of that product is not used -- q is |z'|^2 afresh at every step; sparse: q itself is what is kept, and the chains' ln
+    // likelihood is set to the recomputed value with it, so that the two stay the same number)
+    int refresh_z() const { return z_product(m->inc.X0, p.inc_sparse ? m->dev.post + m->dev.batch : m->d_inc_ll, m->inc.zcur); }
+    // how the likelihood of proposal row q is evaluated: 0 not moved, 1 by columns of L^-1 (rows of the matrix), 2 by a full product
+    int inc_mode(int q) const
+    {
+        if (q < 0) return 0;
+        const mcd::MhRow& r = m->rows[(size_t)q];
+        if (r.kind == MCD_PROP_SCALE_SCALAR && (r.node == 0 || r.node == 1 || r.node == 4)) return 0;
+        return m->sparse_rows[(size_t)q] ? 1 : 2;
+    }
+    // what both per-step runners start with: the first block of draws, X0 and z of the current states
+    int begin() const
+    {
+        if (int rc = draws_for(0)) return rc;
+        if (inc) {
+            m->inc.mode = 0;
+            MHIP_TRY(mcd::launch_mh_inc_init(m->dev, *m->tree, m->inc, n_dim, n_dim, m->stream));
+            if (int rc = refresh_z()) return rc;
+        }
+        return MCD_OK;
+    }
+};
+
+int run_chain(const MhRun& r)
+{
+    mcd_mh* m = r.m;
+    MHIP_TRY(mcd::launch_mh_chain(m->dev, *m->mvn, *m->tree, *m->prior, m->d_Fp, m->d_sched, r.total, r.S, r.accumulate, m->step, m->seed,
+                                  r.alpha(0), r.accept(0), r.p.likelihood_wave, m->stream));
+    m->step += (uint64_t)r.total;
+    if (r.accumulate) m->n_samples += r.total / r.S;
+    return MCD_OK;
+}
+
+int run_streamed(const MhRun& r)
+{
+    mcd_mh* m = r.m;
+    // (launches of at most ~64 k steps, whole iterations each: a second or so of kernel time; what a launch costs -- the chains' state in,
+    // out again -- is some 20 us)
+    const int64_t per_launch = (int64_t)r.S * (65536 / r.S > 0 ? 65536 / r.S : 1);
+    for (int64_t done = 0; done < r.total; done += per_launch) {
+        const int64_t now = (r.total - done < per_launch) ? r.total - done : per_launch;
+        MHIP_TRY(mcd::launch_mh_chain_big(m->dev, *m->mvn, *m->tree, *m->prior, m->d_sched + done, now, r.S, r.accumulate, m->step, m->seed,
+                                          r.alpha(done), r.accept(done), r.p.incremental, m->stream));
+        m->step += (uint64_t)now;
+    }
+    if (r.accumulate) m->n_samples += r.total / r.S;
+    return MCD_OK;
+}
+
+// the segment paths (MCD_MH_PATH_SEGMENTS, _SEGMENTS_SPARSE): every run of steps between two dense proposals in one launch
+int run_segments(const MhRun& r)
+{
+    mcd_mh* m = r.m;
+    const MhPlan& p = r.p;
+    mcd::MhDev& D = m->dev;
+    mcd::MhInc& I = m->inc;
+    const int32_t* schedule = r.schedule;
+    const int64_t total = r.total;
+    if (int rc = r.begin()) return rc;
+    static const mcd::MvnDev no_mvn{};                   // (k_mh_step_wg takes the incremental bookkeeping only with an MvnDev beside it)
+    const mcd::MvnDev* Vinc = m->mvn ? m->mvn : &no_mvn;
+    bool summands_kept = false;                      // MhDev::psum holds the current states' summands
+    int64_t draws_block = 0;                         // (begin: draws_for(0))
+    auto need_draws = [&](int64_t idx) -> int {
+        if ((idx >> 6) != draws_block) {
+            draws_block = idx >> 6;
+            return r.draws_for(idx & ~(int64_t)63);
+        }
+        return MCD_OK;
+    };
+    // a dense proposal followed by a segment is decided by that segment's launch (k_mh_segment.hip: MhSegPending), not by a
+    // launch of the step kernel that would do nothing else
+    mcd::MhSegPending pending{};
+    pending.p_acc = -1;
+    pending.ahead_from = p.ahead_from;
+    pending.prior_draws = p.prior_draws ? 1 : 0;
+    bool have_pending = false;
+    // ... and a dense proposal that follows a segment is PROPOSED by that segment's launch, from the state it holds in LDS
+    // (MhSegPending::p_tail), not by a launch of the step kernel that reads everything back first.  MCD_MH_SEG_TAIL=0: by the step kernel.
+    bool proposed = false;                           // schedule[gs] is already proposed (by the segment before it)
+    int64_t gs = 0;
+    while (gs < total) {
+        if (r.inc_mode(schedule[gs]) != 2) {
+            int64_t e = gs + 1;                      // ... up to the next recomputation of z (every 256 steps)
+            while (e < total && r.inc_mode(schedule[e]) != 2 && (e & 255) != 0) ++e;
+            if (!have_pending) pending.p_acc = -1;
+            pending.p_tail = (p.tails && e < total && r.inc_mode(schedule[e]) == 2) ? schedule[e] : -1;
+            pending.X1_tail = r.X1;
+            proposed = pending.p_tail >= 0;
+            if (p.inc_sparse)
+                MHIP_TRY(mcd::launch_mh_segment_sparse(D, *m->sp, *m->tree, *m->prior, I, m->d_sched + gs, e - gs, r.S, r.accumulate ? 1 : 0,
+                                                       r.step_base + (uint64_t)gs, m->seed, r.alpha(gs), r.accept(gs), gs, summands_kept ? 1 : 0, pending,
+                                                       m->list_all ? 1 : 0, p.prior_waves, m->stream));
+            else
+                MHIP_TRY(mcd::launch_mh_segment(D, *m->mvn, *m->tree, *m->prior, I, m->d_sched + gs, e - gs, r.S, r.accumulate ? 1 : 0,
+                                                r.step_base + (uint64_t)gs, m->seed, r.alpha(gs), r.accept(gs), gs, summands_kept ? 1 : 0, pending,
+                                                p.prior_waves, m->stream));
+            have_pending = false;
+            if (D.psum != nullptr) summands_kept = true;
+            if (r.accumulate) m->n_samples += (e / r.S) - (gs / r.S);      // iterations closed by steps gs .. e - 1
+            m->step += (uint64_t)(e - gs);
+            gs = e;
+            if ((gs & 255) == 0 && gs < total)
+                if (int rc = r.refresh_z()) return rc;
+            continue;
+        }
+        // a dense proposal (and those that follow it directly)
+        if (!proposed) {
+            if (int rc = need_draws(gs)) return rc;
+            I.mode = 0;
+            I.prop_mode = 2;
+            MHIP_TRY(mcd::launch_mh_step(D, *m->prior, -1, 0, schedule[gs], m->rows[schedule[gs]], (int)(gs & 63), m->step, m->seed, 0, nullptr,
+                                         nullptr, r.prior_inline, p.step_wg, r.Tx, r.n_dim, r.X1, r.n_dim, m->stream, &I, Vinc, summands_kept ? 0 : 1));
+            if (D.psum != nullptr) summands_kept = true;
+        }
+        proposed = false;
+        while (true) {
+            const int pa = schedule[gs];
+            if (int rc = r.z_product(r.X1, D.post1 + D.batch, (p.chunked || p.inc_sparse) ? I.zprop : nullptr)) return rc;
+            I.mode = r.dense_mode;
+            const bool closes = ((gs + 1) % r.S) == 0;
+            const bool refresh_now = ((gs + 1) & 255) == 0;
+            const int pn = (gs + 1 < total && r.inc_mode(schedule[gs + 1]) == 2) ? schedule[gs + 1] : -1;
+            if (pn >= 0)
+                if (int rc = need_draws(gs + 1)) return rc;
+            if (pn < 0 && gs + 1 < total && !refresh_now && D.psum != nullptr && summands_kept) {
+                pending.p_acc = pa;
+                pending.jac_root = m->rows[pa].jac_root;
+                pending.accumulate = (r.accumulate && closes) ? 1 : 0;
+                pending.step = m->step;
+                pending.trace_alpha = r.alpha(gs);
+                pending.trace_accept = r.accept(gs);
+                pending.X1 = r.X1;
+                pending.z_in_zprop = p.chunked ? 1 : 0;
+                have_pending = true;
+                m->step += 1;
+                if (r.accumulate && closes) m->n_samples += 1;
+                gs += 1;
+                break;
+            }
+            I.prop_mode = 2;
+            MHIP_TRY(mcd::launch_mh_step(D, *m->prior, pa, m->rows[pa].jac_root, pn, pn >= 0 ? m->rows[pn] : kNoRow, (int)((gs + 1) & 63), m->step,
+                                         m->seed, (r.accumulate && closes) ? 1 : 0, r.alpha(gs), r.accept(gs), r.prior_inline, p.step_wg, r.Tx, r.n_dim, r.X1,
+                                         r.n_dim, m->stream, &I, Vinc, 0));
+            if (refresh_now && gs + 1 < total)
+                if (int rc = r.refresh_z()) return rc;
+            m->step += 1;
+            if (r.accumulate && closes) m->n_samples += 1;
+            gs += 1;
+            if (pn < 0) break;
+        }
+    }
+    return MCD_OK;
+}
+
+// the two-launch step loop (MCD_MH_PATH_TWO_LAUNCH .. _STEP_WG_SPARSE): [accept step s-1 + propose step s] and [the likelihood of step s]
+int run_steps(const MhRun& r)
+{
+    mcd_mh* m = r.m;
+    mcd::MhDev& D = m->dev;
+    mcd::MhInc& I = m->inc;
+    const int32_t* schedule = r.schedule;
+    if (int rc = r.begin()) return rc;
+    I.prop_mode = r.inc ? r.inc_mode(schedule[0]) : 0;
+    MHIP_TRY(mcd::launch_mh_step(D, *m->prior, -1, 0, schedule[0], m->rows[schedule[0]], 0, m->step - 1, m->seed, 0, nullptr, nullptr,
+                                 r.prior_inline, r.p.step_wg, r.Tx, r.n_dim, r.X1, r.n_dim, m->stream, r.inc ? &I : nullptr, m->mvn));
+    for (int64_t gs = 0; gs < r.total; ++gs) {
+        const int pa = schedule[gs];
+        if (r.inc) {
+            I.mode = r.inc_mode(pa);                 // the step kernel evaluated modes 0 and 1 itself
+            if (I.mode == 2) {
+                if (int rc = r.z_product(r.X1, D.post1 + D.batch, r.p.chunked ? I.zprop : nullptr)) return rc;
+                I.mode = r.dense_mode;
+            }
+        } else if (m->sp) {
+            double* scr = nullptr;
+            if (int rc = mcd_sparse_scratch_(m->sp_handle, m->stream, D.batch, &scr)) return rc;
+            MHIP_TRY(mcd::launch_sparse_logpdf(*m->sp, r.X1, r.n_dim, D.batch, D.post1 + D.batch, scr, m->stream));
+        } else if (r.p.use_x)
+            MHIP_TRY(mcd::launch_logpdf(*m->mvn, r.X1, r.n_dim, D.batch, D.post1 + D.batch, m->stream));
+        else if (r.p.beside)
+            MHIP_TRY(mcd::launch_tree_logpdf_with_prior(*m->mvn, *m->tree, D.H1, D.R1, D.ld, D.sc1 + 2 * D.batch, D.sc1 + 3 * D.batch, D.batch,
+                                                        D.post1 + D.batch, D.post1 + 2 * D.batch, D, *m->prior, m->stream));
+        else
+            MHIP_TRY(mcd::launch_tree_logpdf(*m->mvn, *m->tree, D.H1, D.R1, D.ld, D.sc1 + 2 * D.batch, D.sc1 + 3 * D.batch, D.batch,
+                                             D.post1 + D.batch, D.post1 + 2 * D.batch, m->stream));
+        const bool closes = ((gs + 1) % r.S) == 0;
+        const int pn = (gs + 1 < r.total) ? schedule[gs + 1] : -1;
+        if (pn >= 0)
+            if (int rc = r.draws_for(gs + 1)) return rc;
+        const bool refresh_now = r.inc && ((gs + 1) & 255) == 0;
+        I.prop_mode = r.inc ? r.inc_mode(pn) : 0;
+        MHIP_TRY(mcd::launch_mh_step(D, *m->prior, pa, m->rows[pa].jac_root, pn, pn >= 0 ? m->rows[pn] : kNoRow, (int)((gs + 1) & 63), m->step,
+                                     m->seed, (r.accumulate && closes) ? 1 : 0, r.alpha(gs), r.accept(gs), r.prior_inline, r.p.step_wg, r.Tx, r.n_dim,
+                                     r.X1, r.n_dim, m->stream, r.inc ? &I : nullptr, m->mvn));
+        if (refresh_now)                                 // (X0 is exact; z has been updated column by column since the last full product)
+            if (int rc = r.refresh_z()) return rc;
+        m->step += 1;
+        if (r.accumulate && closes) m->n_samples += 1;
+    }
+    return MCD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 int mcd_mh_run(mcd_mh_t* m, const int32_t* schedule, int64_t n_iter, int32_t S, int accumulate, double* trace_alpha,
                int8_t* trace_accept)
 {
@@ -573,288 +999,14 @@ int mcd_mh_run(mcd_mh_t* m, const int32_t* schedule, int64_t n_iter, int32_t S, 
         MHIP_TRY(hipMalloc((void**)&m->d_trace_accept, steps * B));
         m->trace_cap = steps * B;
     }
-    if (m->chain_kernel) {
-        m->last_path = MCD_MH_PATH_CHAIN_LDS;
-        MHIP_TRY(mcd::launch_mh_chain(D, *m->mvn, *m->tree, *m->prior, m->d_Fp, m->d_sched, (int64_t)steps, S, accumulate, m->step, m->seed,
-                                      trace ? m->d_trace_alpha : nullptr, trace ? m->d_trace_accept : nullptr, m->stream));
-        m->step += steps;
-        if (accumulate) m->n_samples += n_iter;
-    }
-    // larger trees at a sampler's batch: the whole schedule in one launch as well, the factor streamed once per step
-    // (k_mh_chain_big.hip).  MCD_MH_PER_PHASE=1 keeps the two-launch path (tests, timing; read per call).
-    const bool per_phase = mcd::opt_is(mcd::OPT_MH_PER_PHASE, 1);
-    const bool seg_off = mcd::opt_is(mcd::OPT_MH_SEGMENTS, 0), inc_off = mcd::opt_is(mcd::OPT_MH_INCREMENTAL, 0);
-    // From 259 nodes (R >= 6) the segment path below is ahead of it (271 nodes x 512 chains 11.3 -> 9.6 us per lock step, 513 nodes
-    // 16.0 -> 9.6): the factor streamed for every dense proposal costs more there than two launches for the few proposals that
-    // move more than 192 distances.  MCD_MH_SEGMENTS=0 / MCD_MH_INCREMENTAL=0 keep the streaming kernel.
-    const bool prefer_segments = m->mvn && !m->chain_kernel && !seg_off && !inc_off &&
-                                 mcd::mh_segment_available(D, *m->mvn) && mcd::use_split(*m->mvn, std::min<int64_t>(D.batch, mcd::kSplitMaxBatch));
-    const bool streaming = m->mvn && !m->chain_kernel && !per_phase && mcd::effective_form(*m->mvn) != MCD_FORM_MULTIPLY &&
-                           mcd::mh_chain_big_available(D, *m->mvn) && !prefer_segments;
-    if (streaming) {
-        m->last_path = MCD_MH_PATH_CHAIN_STREAMED;
-        // (launches of at most ~64 k steps, whole iterations each: a second or so of kernel time; what a launch costs -- the chains'
-        // state in, out again -- is some 20 us)
-        const int64_t per_launch = (int64_t)S * (65536 / S > 0 ? 65536 / S : 1);
-        for (int64_t done = 0; done < (int64_t)steps; done += per_launch) {
-            const int64_t now = ((int64_t)steps - done < per_launch) ? (int64_t)steps - done : per_launch;
-            MHIP_TRY(mcd::launch_mh_chain_big(D, *m->mvn, *m->tree, *m->prior, m->d_sched + done, now, S, accumulate, m->step, m->seed,
-                                              trace ? m->d_trace_alpha + done * B : nullptr, trace ? m->d_trace_accept + done * B : nullptr,
-                                              m->stream));
-            m->step += (uint64_t)now;
-        }
-        if (accumulate) m->n_samples += n_iter;
-    }
-    if (!m->chain_kernel && !streaming) {
-        // two launches per step: [accept step s-1 + propose step s + ln prior] and [likelihood + root-branch Jacobian]
-        const int64_t total = (int64_t)steps;
-        if ((size_t)D.n_nodes * 32 > 64 * 1024) return mfail(MCD_ERR_UNSUPPORTED, "mcd_mh_run: more than 2048 nodes");
-        const mcd::MhRow none{0, 0, 0, 0, 0, 1.0, 0.0};
-        // the draws of schedule positions [64 k, 64 k + 64) are computed when position 64 k is about to be proposed
-        const uint64_t step_base = m->step;                      // the step number of schedule position 0
-        auto draws_for = [&](int64_t idx) -> int {
-            if ((idx & 63) == 0) {
-                const int count = (int)((total - idx < 64) ? total - idx : 64);
-                const hipError_t e = mcd::launch_mh_draws(D, m->d_sched, idx, count, step_base + (uint64_t)idx, m->seed, m->stream);
-                if (e != hipSuccess) return mfail(MCD_ERR_HIP, "launch_mh_draws: %s", hipGetErrorString(e));
-            }
-            return MCD_OK;
-        };
-        if (int rc = draws_for(0)) return rc;
-        // The ln prior of a proposed state depends on the proposal only, like its ln likelihood: where the sweep serves the
-        // likelihood launch, that launch carries the prior as workgroups of a second role (k_tree_logpdf.hip, mh_prior_role.hpp)
-        // and k_mh_step leaves it out; elsewhere (row-split / multiply form) k_mh_step evaluates it as before.  Same functions
-        // on the same numbers either way: the same chains.  MCD_MH_PRIOR=0 keeps it inside the step everywhere (tests, timing).
-        const bool prior_in_step = mcd::opt_is(mcd::OPT_MH_PRIOR, 0);
-        // (A launch of its own for the prior with four waves per chain was measured for the larger trees: 58.9 -> 56.4 us per
-        // lock step at 1025 nodes, 33.3 -> 35.4 at 513 -- the step kernel's other strided loops weigh more there; not kept.)
-        const bool beside = m->mvn && !prefer_segments && !prior_in_step && mcd::tree_logpdf_can_carry_prior(*m->mvn, D.batch, D.n_nodes);
-        const int prior_inline = beside ? 0 : 1;
-        // large trees: the step kernel (a workgroup per chain) leaves the proposed states' DISTANCES, the likelihood launch takes
-        // them as plain vectors (the row-split kernel's tree staging costs 6 us more at 1023 slots); same arithmetic, same bits
-        const int n_dim = m->mvn ? m->mvn->n : m->sp->n;
-        const int wg_from = m->sp ? 0 : prefer_segments ? 258 : 320;   // (the workgroup-per-chain step kernel: the only one that leaves distances)
-        const bool use_x = mcd::mh_step_wg_active(D, prior_inline, wg_from) && !beside && D.n_nodes > wg_from;
-        if (m->sp && !use_x) return mfail(MCD_ERR_UNSUPPORTED, "mcd_mh_run: the sparse driver needs the workgroup-per-chain step kernel (MCD_MH_STEP_WG must not be 0)");
-        if (use_x && m->d_X1 == nullptr) {
-            MHIP_TRY(hipMalloc((void**)&m->d_X1, sizeof(double) * (size_t)D.batch * (size_t)n_dim));
-            m->allocs.push_back(m->d_X1);
-        }
-        // the workgroup-per-chain step kernel keeps the per-node summands of the ln prior between launches (k_mh.hip: psum);
-        // MCD_MH_PRIOR_CACHE=0: every summand at every step
-        {
-            const bool keep = prior_inline && mcd::mh_step_wg_active(D, prior_inline, wg_from) && !mcd::opt_is(mcd::OPT_MH_PRIOR_CACHE, 0);
-            if (keep && m->d_psum == nullptr) {
-                const size_t NS = (size_t)((D.n_nodes - 1 + 63) / 64) * 64;
-                MHIP_TRY(hipMalloc((void**)&m->d_psum, sizeof(double) * (size_t)D.batch * 4 * NS));
-                m->allocs.push_back(m->d_psum);
-                MHIP_TRY(hipMalloc((void**)&m->d_psel, sizeof(int32_t) * 2 * (size_t)D.batch));
-                m->allocs.push_back(m->d_psel);
-            }
-            D.psum = keep ? m->d_psum : nullptr;
-            D.psel = keep ? m->d_psel : nullptr;
-        }
-        m->last_path = use_x ? MCD_MH_PATH_STEP_WG_X : beside ? MCD_MH_PATH_TWO_LAUNCH_PRIOR_BESIDE : MCD_MH_PATH_TWO_LAUNCH;
-        const mcd::TreeDev* Tx = use_x ? m->tree : nullptr;
-        double* X1 = use_x ? m->d_X1 : nullptr;
-        // Large trees at a sampler's batch: the likelihood launch only for the proposals that move many distances (k_mh_inc.hip);
-        // the others are evaluated from columns of L^-1 on the kept z.  MCD_MH_INCREMENTAL=0: the full evaluation at every step.
-        // (batches beyond the row-split kernel's 1024 chains: its z products chunk by chunk, z' of a dense proposal copied to zprop)
-        const bool inc_dense = m->mvn && use_x && !inc_off && m->mvn->Wc != nullptr && 64 * m->mvn->R <= 1024 &&
-                               mcd::use_split(*m->mvn, std::min<int64_t>(D.batch, mcd::kSplitMaxBatch));
-        // Over a sparse precision matrix (k_mh_segment_sparse.hip) the incremental form keeps the quadratic form q itself: MhInc with
-        // NPz = 1 -- zcur / zprop = q of the current states / of the pending dense proposal -- so that k_mh_step_wg's accept half moves
-        // X1 -> X0 and q' -> q like it moves z' -> z.  It exists only together with the segments.
-        const bool inc_sparse = m->sp && use_x && !inc_off && !seg_off && mcd::mh_segment_sparse_available(D, *m->sp) && mcd::sparse_quad_available(*m->sp, D.batch);
-        const bool inc = inc_dense || inc_sparse;
-        const bool chunked = inc_dense && D.batch > mcd::kSplitMaxBatch;
-        const int dense_mode = (chunked || inc_sparse) ? 1 : 2;   // where the z' (q') of a dense proposal is afterwards: zprop or the z tiles
-        static const mcd::MvnDev no_mvn{};                   // (k_mh_step_wg takes the incremental bookkeeping only with an MvnDev beside it)
-        const mcd::MvnDev* Vinc = m->mvn ? m->mvn : &no_mvn;
-        mcd::MhInc& I = m->inc;
-        if (inc_sparse && I.X0 == nullptr) {
-            I.NPz = 1;
-            MHIP_TRY(hipMalloc((void**)&I.X0, sizeof(double) * (size_t)D.batch * (size_t)n_dim));
-            m->allocs.push_back(I.X0);
-            MHIP_TRY(hipMalloc((void**)&I.zcur, sizeof(double) * 2 * (size_t)D.batch));
-            m->allocs.push_back(I.zcur);
-            I.zprop = I.zcur + D.batch;
-        }
-        if (inc_dense && I.X0 == nullptr) {
-            I.NPz = 64 * m->mvn->R;
-            MHIP_TRY(hipMalloc((void**)&I.X0, sizeof(double) * (size_t)D.batch * (size_t)n_dim));
-            m->allocs.push_back(I.X0);
-            MHIP_TRY(hipMalloc((void**)&I.zcur, sizeof(double) * (size_t)D.batch * (size_t)I.NPz));
-            m->allocs.push_back(I.zcur);
-            MHIP_TRY(hipMalloc((void**)&I.zprop, sizeof(double) * (size_t)D.batch * (size_t)I.NPz));
-            m->allocs.push_back(I.zprop);
-            MHIP_TRY(hipMalloc((void**)&m->d_inc_ll, sizeof(double) * (size_t)D.batch));
-            m->allocs.push_back(m->d_inc_ll);
-        }
-        // ll and z = L^-1 (X - mu) of every chain by full products (the row-split kernel, at most 1024 chains per launch); z to dst
-        // (chain-major) -- or, for a batch of one launch and dst = null, left in that launch's z tiles
-        auto z_product = [&](const double* X, double* ll, double* dst) -> int {
-            if (inc_sparse) {                                // the full form in one launch (k_sparse.hip: k_sparse_quad): ll and q (dst)
-                MHIP_TRY(mcd::launch_sparse_quad(*m->sp, nullptr, X, nullptr, n_dim, nullptr, nullptr, D.batch, ll, nullptr, dst, m->stream));
-                return MCD_OK;
-            }
-            for (int64_t c0 = 0; c0 < D.batch; c0 += mcd::kSplitMaxBatch) {
-                const int64_t cnt = std::min<int64_t>(mcd::kSplitMaxBatch, D.batch - c0);
-                MHIP_TRY(mcd::launch_logpdf_split_z(*m->mvn, X + c0 * n_dim, n_dim, cnt, ll + c0, &I.zt, &I.nr, m->stream));
-                if (dst) MHIP_TRY(mcd::launch_mh_inc_take_z(I, dst, c0, cnt, m->stream));
-            }
-            return MCD_OK;
-        };
-        // (dense: the ll of that product is not used -- q is |z'|^2 afresh at every step; sparse: q itself is what is kept, and the chains' ln
-        // likelihood is set to the recomputed value with it, so that the two stay the same number)
-        auto refresh_z = [&]() -> int { return z_product(I.X0, inc_sparse ? D.post + D.batch : m->d_inc_ll, I.zcur); };
-        if (inc) {
-            I.mode = 0;
-            MHIP_TRY(mcd::launch_mh_inc_init(D, *m->tree, I, n_dim, n_dim, m->stream));
-            if (int rc = refresh_z()) return rc;
-        }
-        auto moves_likelihood = [&](int p) { return !(m->rows[p].kind == MCD_PROP_SCALE_SCALAR && (m->rows[p].node == 0 || m->rows[p].node == 1 || m->rows[p].node == 4)); };
-        auto inc_mode = [&](int p) { return p < 0 ? 0 : !moves_likelihood(p) ? 0 : m->sparse_rows[(size_t)p] ? 1 : 2; };
-        // Trees of 259 .. 1026 nodes: the runs of steps between two dense proposals as ONE launch each, every chain's state in LDS from
-        // the run's first step to its last (k_mh_chain_big.hip, SEG); a dense proposal as before: proposed by the step kernel, its
-        // likelihood by the row-split launch, accepted by the step kernel.  MCD_MH_SEGMENTS=0: every step by the two launches.
-        const bool segments = inc_sparse || (inc_dense && !seg_off && mcd::mh_segment_available(D, *m->mvn) && I.NPz == 64 * m->mvn->R);
-        if (segments) {
-            bool summands_kept = false;                      // MhDev::psum holds the current states' summands
-            int64_t draws_block = 0;                         // (draws_for(0) above)
-            auto need_draws = [&](int64_t idx) -> int {
-                if ((idx >> 6) != draws_block) {
-                    draws_block = idx >> 6;
-                    return draws_for(idx & ~(int64_t)63);
-                }
-                return MCD_OK;
-            };
-            // a dense proposal followed by a segment is decided by that segment's launch (k_mh_segment.hip: MhSegPending), not by a
-            // launch of the step kernel that would do nothing else
-            mcd::MhSegPending pending{};
-            pending.p_acc = -1;
-            bool have_pending = false;
-            // ... and a dense proposal that follows a segment is PROPOSED by that segment's launch, from the state it holds in LDS
-            // (MhSegPending::p_tail), not by a launch of the step kernel that reads everything back first.  MCD_MH_SEG_TAIL=0: by the step kernel.
-            const bool tails = D.psum != nullptr && !mcd::opt_is(mcd::OPT_MH_SEG_TAIL, 0);
-            bool proposed = false;                           // schedule[gs] is already proposed (by the segment before it)
-            int64_t gs = 0;
-            while (gs < total) {
-                if (inc_mode(schedule[gs]) != 2) {
-                    int64_t e = gs + 1;                      // ... up to the next recomputation of z (every 256 steps)
-                    while (e < total && inc_mode(schedule[e]) != 2 && (e & 255) != 0) ++e;
-                    if (!have_pending) pending.p_acc = -1;
-                    pending.p_tail = (tails && e < total && inc_mode(schedule[e]) == 2) ? schedule[e] : -1;
-                    pending.X1_tail = X1;
-                    proposed = pending.p_tail >= 0;
-                    if (inc_sparse)
-                        MHIP_TRY(mcd::launch_mh_segment_sparse(D, *m->sp, *m->tree, *m->prior, I, m->d_sched + gs, e - gs, S, accumulate ? 1 : 0,
-                                                               step_base + (uint64_t)gs, m->seed, trace ? m->d_trace_alpha + gs * B : nullptr,
-                                                               trace ? m->d_trace_accept + gs * B : nullptr, gs, summands_kept ? 1 : 0, &pending,
-                                                               m->list_all ? 1 : 0, m->stream));
-                    else
-                        MHIP_TRY(mcd::launch_mh_segment(D, *m->mvn, *m->tree, *m->prior, I, m->d_sched + gs, e - gs, S, accumulate ? 1 : 0, step_base + (uint64_t)gs,
-                                                        m->seed, trace ? m->d_trace_alpha + gs * B : nullptr, trace ? m->d_trace_accept + gs * B : nullptr, gs,
-                                                        summands_kept ? 1 : 0, &pending, m->stream));
-                    have_pending = false;
-                    if (D.psum != nullptr) summands_kept = true;
-                    if (accumulate) m->n_samples += (e / S) - (gs / S);          // iterations closed by steps gs .. e - 1
-                    m->step += (uint64_t)(e - gs);
-                    gs = e;
-                    if ((gs & 255) == 0 && gs < total)
-                        if (int rc = refresh_z()) return rc;
-                    continue;
-                }
-                // a dense proposal (and those that follow it directly)
-                if (!proposed) {
-                    if (int rc = need_draws(gs)) return rc;
-                    I.mode = 0;
-                    I.prop_mode = 2;
-                    MHIP_TRY(mcd::launch_mh_step(D, *m->prior, -1, 0, schedule[gs], m->rows[schedule[gs]], (int)(gs & 63), m->step, m->seed, 0, nullptr,
-                                                 nullptr, prior_inline, Tx, n_dim, X1, n_dim, m->stream, &I, Vinc, summands_kept ? 0 : 1));
-                    if (D.psum != nullptr) summands_kept = true;
-                }
-                proposed = false;
-                while (true) {
-                    const int pa = schedule[gs];
-                    if (int rc = z_product(X1, D.post1 + D.batch, (chunked || inc_sparse) ? I.zprop : nullptr)) return rc;
-                    I.mode = dense_mode;
-                    const bool closes = ((gs + 1) % S) == 0;
-                    const bool refresh_now = ((gs + 1) & 255) == 0;
-                    const int pn = (gs + 1 < total && inc_mode(schedule[gs + 1]) == 2) ? schedule[gs + 1] : -1;
-                    if (pn >= 0)
-                        if (int rc = need_draws(gs + 1)) return rc;
-                    if (pn < 0 && gs + 1 < total && !refresh_now && D.psum != nullptr && summands_kept) {
-                        pending.p_acc = pa;
-                        pending.jac_root = m->rows[pa].jac_root;
-                        pending.accumulate = (accumulate && closes) ? 1 : 0;
-                        pending.step = m->step;
-                        pending.trace_alpha = trace ? m->d_trace_alpha + gs * B : nullptr;
-                        pending.trace_accept = trace ? m->d_trace_accept + gs * B : nullptr;
-                        pending.X1 = X1;
-                        pending.z_in_zprop = chunked ? 1 : 0;
-                        have_pending = true;
-                        m->step += 1;
-                        if (accumulate && closes) m->n_samples += 1;
-                        gs += 1;
-                        break;
-                    }
-                    I.prop_mode = 2;
-                    MHIP_TRY(mcd::launch_mh_step(D, *m->prior, pa, m->rows[pa].jac_root, pn, pn >= 0 ? m->rows[pn] : none, (int)((gs + 1) & 63), m->step,
-                                                 m->seed, (accumulate && closes) ? 1 : 0, trace ? m->d_trace_alpha + gs * B : nullptr,
-                                                 trace ? m->d_trace_accept + gs * B : nullptr, prior_inline, Tx, n_dim, X1, n_dim, m->stream, &I, Vinc, 0));
-                    if (refresh_now && gs + 1 < total)
-                        if (int rc = refresh_z()) return rc;
-                    m->step += 1;
-                    if (accumulate && closes) m->n_samples += 1;
-                    gs += 1;
-                    if (pn < 0) break;
-                }
-            }
-            m->last_path = inc_sparse ? MCD_MH_PATH_SEGMENTS_SPARSE : MCD_MH_PATH_SEGMENTS;
-        } else {
-        I.prop_mode = inc ? inc_mode(schedule[0]) : 0;
-        MHIP_TRY(mcd::launch_mh_step(D, *m->prior, -1, 0, schedule[0], m->rows[schedule[0]], 0, m->step - 1, m->seed, 0, nullptr, nullptr,
-                                     prior_inline, Tx, n_dim, X1, n_dim, m->stream, inc ? &I : nullptr, m->mvn));
-        for (int64_t gs = 0; gs < total; ++gs) {
-            const int pa = schedule[gs];
-            if (inc) {
-                I.mode = inc_mode(pa);                       // the step kernel evaluated modes 0 and 1 itself
-                if (I.mode == 2) {
-                    if (int rc = z_product(X1, D.post1 + D.batch, chunked ? I.zprop : nullptr)) return rc;
-                    I.mode = dense_mode;
-                }
-            } else if (m->sp) {
-                double* scr = nullptr;
-                if (int rc = mcd_sparse_scratch_(m->sp_handle, m->stream, D.batch, &scr)) return rc;
-                MHIP_TRY(mcd::launch_sparse_logpdf(*m->sp, X1, n_dim, D.batch, D.post1 + D.batch, scr, m->stream));
-            } else if (use_x)
-                MHIP_TRY(mcd::launch_logpdf(*m->mvn, X1, n_dim, D.batch, D.post1 + D.batch, m->stream));
-            else if (beside)
-                MHIP_TRY(mcd::launch_tree_logpdf_with_prior(*m->mvn, *m->tree, D.H1, D.R1, D.ld, D.sc1 + 2 * D.batch, D.sc1 + 3 * D.batch, D.batch,
-                                                            D.post1 + D.batch, D.post1 + 2 * D.batch, D, *m->prior, m->stream));
-            else
-                MHIP_TRY(mcd::launch_tree_logpdf(*m->mvn, *m->tree, D.H1, D.R1, D.ld, D.sc1 + 2 * D.batch, D.sc1 + 3 * D.batch, D.batch,
-                                                 D.post1 + D.batch, D.post1 + 2 * D.batch, m->stream));
-            const bool closes = ((gs + 1) % S) == 0;
-            const int pn = (gs + 1 < total) ? schedule[gs + 1] : -1;
-            if (pn >= 0)
-                if (int rc = draws_for(gs + 1)) return rc;
-            const bool refresh_now = inc && ((gs + 1) & 255) == 0;
-            I.prop_mode = inc ? inc_mode(pn) : 0;
-            MHIP_TRY(mcd::launch_mh_step(D, *m->prior, pa, m->rows[pa].jac_root, pn, pn >= 0 ? m->rows[pn] : none, (int)((gs + 1) & 63), m->step,
-                                         m->seed, (accumulate && closes) ? 1 : 0, trace ? m->d_trace_alpha + gs * B : nullptr,
-                                         trace ? m->d_trace_accept + gs * B : nullptr, prior_inline, Tx, n_dim, X1, n_dim, m->stream,
-                                         inc ? &I : nullptr, m->mvn));
-            if (refresh_now)                                 // (X0 is exact; z has been updated column by column since the last full product)
-                if (int rc = refresh_z()) return rc;
-            m->step += 1;
-            if (accumulate && closes) m->n_samples += 1;
-        }
-        if (inc) m->last_path = MCD_MH_PATH_STEP_WG_INCREMENTAL;
-        if (m->sp) m->last_path = MCD_MH_PATH_STEP_WG_SPARSE;
-        }
-    }
+    const MhPlan p = plan_run(shape_of(m), mh_options());
+    if (p.path == MCD_MH_PATH_NONE) return mfail(MCD_ERR_UNSUPPORTED, "mcd_mh_run: %s", p.refused);
+    if (p.path != MCD_MH_PATH_CHAIN_LDS && p.path != MCD_MH_PATH_CHAIN_STREAMED)
+        if (int rc = plan_buffers(m, p)) return rc;
+    m->last_path = p.path;
+    const MhRun r(m, p, schedule, (int64_t)steps, S, accumulate, trace);
+    const int rc = p.path == MCD_MH_PATH_CHAIN_LDS ? run_chain(r) : p.path == MCD_MH_PATH_CHAIN_STREAMED ? run_streamed(r) : p.segments ? run_segments(r) : run_steps(r);
+    if (rc) return rc;
     m->last_lds = mcd::last_dynamic_lds();
     if (trace_alpha) MHIP_TRY(hipMemcpyAsync(trace_alpha, m->d_trace_alpha, sizeof(double) * steps * B, hipMemcpyDeviceToHost, m->stream));
     if (trace_accept) MHIP_TRY(hipMemcpyAsync(trace_accept, m->d_trace_accept, steps * B, hipMemcpyDeviceToHost, m->stream));
@@ -932,6 +1084,23 @@ int mcd_mh_get_age_sums(const mcd_mh_t* cm, double* age_sum, double* age_sq, int
     if (age_sq) MHIP_TRY(hipMemcpy(age_sq, D.age_sq, sizeof(double) * BN, hipMemcpyDeviceToHost));
     if (n_samples) *n_samples = cm->n_samples;
     return MCD_OK;
+}
+
+// Test hook (tests/test_host.py; no device): the plan of a run under the knobs as they stand, for a handle of these facts -- R > 0: a dense
+// likelihood of dimension n in R register blocks, split = 1 where its row-split tables exist, form = the form in force (MCD_FORM_*); R = 0:
+// a sparse one of dimension n; the other tables exist, as mcd_tree_create / mcd_sparse_tree_create build them -- and these create-time
+// decisions.  Returns the path (MCD_MH_PATH_*; 0: refused) | MhPlan::flags() << 4.
+int mcd_mh_plan_selftest_(int n_nodes, int n_prop, int64_t batch, int R, int n, int split, int form, int chain_kernel, int list_all)
+{
+    MhShape s{n_nodes, n_prop, batch, R > 0, {}, {}, chain_kernel != 0, list_all != 0};
+    s.mvn.n = s.sp.n = n;
+    s.mvn.R = R;
+    s.mvn.form = form;
+    s.mvn.split = split != 0;
+    s.mvn.wide = s.mvn.cols = true;
+    s.sp.rows = s.sp.quad = true;
+    const MhPlan p = plan_run(s, mh_options());
+    return p.path | p.flags() << 4;
 }
 
 int mcd_mh_reset_age_sums(mcd_mh_t* m)

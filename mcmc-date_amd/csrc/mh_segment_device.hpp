@@ -114,7 +114,6 @@ struct SegHelpWords {
 };
 static_assert(sizeof(SegHelpWords) == 128, "sixteen doubles of LDS");
 constexpr int kSegHelpDoubles = 16;
-constexpr int kSegAheadFrom = 200;                         // (MhSegPending::ahead_from; measured: profiles/r04_segment_ahead.txt)
 
 // LDS of one chain's CHAIN wave and the constants of its likelihood: set up by the kernel, read by seg_chain_wave
 struct SegChainCtx {

@@ -22,9 +22,16 @@ struct MvnDev {
     const double* Wt;       // W = L^-1 as 16 x 4 MFMA operand tiles (host_factor.h: pack_w_tiles), for k_wide.hip
     const double* Wtb;      // the tiles of W^T for the gradient's second product (k_wide_grad.hip)
     const double* Wc;       // W = L^-1 column by column, [N][NP] (column j = NP doubles, zero above row j and in the padding): the
-                            // incremental evaluation of sparse proposals in k_mh_chain_big.hip; NULL for R > 4
+                            // incremental evaluation of sparse proposals (k_mh_chain_big.hip, k_mh_inc.hip, k_mh_segment.hip)
     const struct SplitHost* split;   // HOST pointer (never dereferenced on the device): schedules + scratch of the row-split form (k_split.hip)
     const int* form;        // HOST pointer: this handle's form override (MCD_FORM_*; 0 = the process default), mcd_mvn_set_form
+};
+// What the launch choices read of a dense handle: plain facts, so that the Metropolis-Hastings planner (mh_capi.cpp) also runs without a device
+struct MvnFacts {
+    int n, R, form;            // form: the one in force (effective_form)
+    bool split, wide, cols;    // the row-split tables (split), the multiply form's tiles (Wt), the columns of W (Wc) exist
+    MvnFacts() = default;
+    MvnFacts(const MvnDev& M);   // (k_logpdf.hip)
 };
 
 // Row-split multiply form (k_split.hip).  One tile stream per (handle, G): the row blocks of W = L^-1 dealt to G row groups of
@@ -147,6 +154,13 @@ struct SparseDev {
     const int32_t* ell_more;   // [n]
 };
 constexpr int kSparseEllW = 16;
+// What the launch choices read of a sparse handle: plain facts, so that the Metropolis-Hastings planner (mh_capi.cpp) also runs without a device
+struct SparseFacts {
+    int n;
+    bool rows, quad;           // the symmetric part's rows (s_rowptr) / the one-launch form's entry stream (q_rc) exist
+    SparseFacts() = default;
+    SparseFacts(const SparseDev& S) : n(S.n), rows(S.s_rowptr != nullptr), quad(S.q_rc != nullptr) {}
+};
 struct SparseTreeDev {
     int n_nodes, root_right;
     const int32_t* slot_node;     // [n] distance slot -> node (getBranches . sumFirstTwo order)
@@ -163,7 +177,7 @@ hipError_t launch_sparse_tree_logpdf(const SparseDev& S, const SparseTreeDev& T,
 // ONE launch, no scratch: a workgroup stages the dx of one or two chains in LDS and walks the flat entry stream (k_sparse.hip: k_sparse_quad);
 // T != null: tree states (X = heights, Rt = rates, ld = their row stride; logjac may be null), else X = plain vectors; ll and qout
 // (the quadratic form dx^T P dx itself; what the Metropolis-Hastings driver keeps per chain) may each be null
-bool sparse_quad_available(const SparseDev& S, int64_t batch);
+bool sparse_quad_available(const SparseFacts& S, int64_t batch);
 hipError_t launch_sparse_quad(const SparseDev& S, const SparseTreeDev* T, const double* X, const double* Rt, int64_t ld, const double* tH,
                               const double* rMu, int64_t batch, double* ll, double* logjac, double* qout, hipStream_t st);
 
@@ -202,20 +216,21 @@ struct MhSegPending {          // a dense proposal that is still to be decided w
     // launch of k_mh_step_wg would do after reading everything back: H1 / R1 / sc1 / post1 / pcomp1 / lnqj / the summands / its distances)
     int p_tail;                // its row of the proposal table, -1 = none
     double* X1_tail;           // [batch][n] its distances
-    int ahead_from;            // trees from this many nodes: the chain wave draws the next step's proposal while the step in flight is evaluated
+    int ahead_from;            // trees from this many nodes (default kSegAheadFrom): the chain wave draws the next step's proposal while the step in flight is evaluated
     int prior_draws;           // the clock prior wave draws the next step's proposal (segment kernels with prior waves; mh_segment_device.hpp: SegSpec)
 };
-bool mh_segment_available(const MhDev& M, const MvnDev& V);
+constexpr int kSegAheadFrom = 200;   // (MhSegPending::ahead_from; measured: profiles/r04_segment_ahead.txt)
+bool mh_segment_available(const MvnFacts& V, int n_nodes, int64_t batch);
 // the same over a sparse precision matrix (k_mh_segment_sparse.hip); I: X0 = current distances [batch][n], zcur / zprop = the quadratic
 // forms q [batch] of the current states / of the pending dense proposal (NPz = 1)
-bool mh_segment_sparse_available(const MhDev& M, const SparseDev& Sp);
+bool mh_segment_sparse_available(const SparseFacts& Sp, int n_nodes, int64_t batch);
 int mh_segment_sparse_list();      // moved distances of one proposal at most
 hipError_t launch_mh_segment_sparse(const MhDev& M, const SparseDev& Sp, const TreeDev& T, const PriorDev& P, const MhInc& I, const int32_t* sched,
                                     int64_t n_steps, int32_t S, int accumulate, uint64_t step0, uint64_t seed, double* trace_alpha, int8_t* trace_accept,
-                                    int64_t gs_base, int summands_kept, const MhSegPending* pending, int list_all, hipStream_t st);
+                                    int64_t gs_base, int summands_kept, const MhSegPending& pending, int list_all, bool prior_waves, hipStream_t st);
 hipError_t launch_mh_segment(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const MhInc& I, const int32_t* sched,
                              int64_t n_steps, int32_t S, int accumulate, uint64_t step0, uint64_t seed, double* trace_alpha, int8_t* trace_accept,
-                             int64_t gs_base, int summands_kept, const MhSegPending* pending, hipStream_t st);
+                             int64_t gs_base, int summands_kept, const MhSegPending& pending, bool prior_waves, hipStream_t st);
 hipError_t launch_mh_inc_init(const MhDev& M, const TreeDev& T, const MhInc& I, int n_dim, int64_t ldx, hipStream_t st);   // X0 from the current states
 hipError_t launch_mh_inc_take_z(const MhInc& I, double* dst, int64_t b0, int64_t count, hipStream_t st);                 // dst[b0 ..] <- zt of `count` chains
 
@@ -273,7 +288,7 @@ constexpr size_t kSplitCounters = kSplitMaxBatch / 16;
 SplitHost* split_host_create(int n, const double* W_rowmajor, hipError_t* err);   // W = L^-1; tile streams on the current device + scratch pool
 void split_host_destroy(SplitHost* s);
 hipError_t split_release_stream(SplitHost* s, hipStream_t st);   // the stream's eager scratch set back to the pool (mcd_mvn_release_stream)
-bool use_split(const MvnDev& M, int64_t batch);
+bool use_split(const MvnFacts& M, int64_t batch);
 hipError_t launch_logpdf_split(const MvnDev& M, const double* X, int64_t ldx, int64_t batch, double* ll, hipStream_t st);
 hipError_t launch_tree_logpdf_split(const MvnDev& M, const TreeDev& T, const double* H, const double* Rt, int64_t lds, const double* tH,
                                     const double* rMu, int64_t batch, double* ll, double* logjac, hipStream_t st);
@@ -288,7 +303,7 @@ hipError_t prepare_wide_grad();
 hipError_t prepare_wide_grad_mc();
 bool use_wide_grad(const MvnDev& M, int64_t batch);
 int wide_chain_tiles(int64_t batch);
-bool use_wide(const MvnDev& M, int64_t batch);
+bool use_wide(const MvnFacts& M, int64_t batch);
 int set_logpdf_form(int form);
 hipError_t launch_logpdf(const MvnDev& M, const double* X, int64_t ldx, int64_t batch, double* ll, hipStream_t st);
 hipError_t launch_grad(const MvnDev& M, const double* X, int64_t ldx, int64_t batch, double* ll, double* G, int64_t ldg,
@@ -322,18 +337,18 @@ struct MhRow {
 // accept the pending step of proposal p_acc (< 0: none) and propose proposal p_prop (< 0: none) with the ln prior of its proposed state
 hipError_t launch_mh_step(const MhDev& M, const PriorDev& P, int p_acc, int jac_root_acc, int p_prop, const MhRow& row_prop, int draw_slot,
                           uint64_t step_acc, uint64_t seed, int accumulate_now, double* trace_alpha, int8_t* trace_accept, int prior_inline,
-                          const TreeDev* T, int n_dim, double* X1, int64_t ldx, hipStream_t st, const MhInc* inc = nullptr, const MvnDev* V = nullptr,
+                          bool wg, const TreeDev* T, int n_dim, double* X1, int64_t ldx, hipStream_t st, const MhInc* inc = nullptr, const MvnDev* V = nullptr,
                           int summands_init = -1);   // 1: MhDev::psum does not hold the current states' summands yet (-1: when nothing is pending)
-// true: launch_mh_step takes the workgroup-per-chain kernel, which can also leave the proposed states' distances in X1 [batch][ldx]
-// (T, n_dim, X1 given) for a plain-vector likelihood launch
-bool mh_step_wg_active(const MhDev& M, int prior_inline, int min_nodes = 320);   // (default: trees of more than min_nodes nodes)
+// wg: the workgroup-per-chain kernel, which can also leave the proposed states' distances in X1 [batch][ldx] (T, n_dim, X1 given) for a
+// plain-vector likelihood launch; it exists for the trees where mh_step_wg_fits(n_nodes)
+bool mh_step_wg_fits(int n_nodes);
 hipError_t launch_mh_tune(const MhDev& M, hipStream_t st);
 hipError_t launch_mc3_swap(const Mc3Dev& C, const double* lnpost, int world, int64_t per_rank, int n_swaps, uint64_t seed, uint64_t phase,
                            double* beta_local, int64_t chain0, int64_t batch, hipStream_t st);
 // ln prior of the proposed states from pflags / pcomp (what launch_mh_step leaves when asked not to evaluate it itself) as extra
 // workgroups of the sweep's tree-likelihood launch (k_tree_logpdf.hip): the ln prior and the ln likelihood of a proposal depend
 // on nothing but the proposal
-bool tree_logpdf_can_carry_prior(const MvnDev& M, int64_t batch, int n_nodes);
+bool tree_logpdf_can_carry_prior(const MvnFacts& M, int64_t batch, int n_nodes);
 hipError_t launch_tree_logpdf_with_prior(const MvnDev& M, const TreeDev& T, const double* H, const double* Rt, int64_t lds, const double* tH,
                                          const double* rMu, int64_t batch, double* ll, double* logjac, const MhDev& J, const PriorDev& JP,
                                          hipStream_t st);
@@ -341,15 +356,17 @@ hipError_t launch_tree_logpdf_with_prior(const MvnDev& M, const TreeDev& T, cons
 hipError_t launch_mh_draws(const MhDev& M, const int32_t* sched, int64_t idx0, int count, uint64_t step0, uint64_t seed, hipStream_t st);
 // whole schedule in one launch for trees of 65 .. 320 nodes at up to 1024 chains (k_mh_chain_big.hip): two chains per workgroup,
 // the factor streamed through the sweep's LDS ring once per step
-bool mh_chain_big_available(const MhDev& M, const MvnDev& V);
+bool mh_chain_big_available(const MvnFacts& V, int n_nodes, int n_prop, int64_t batch);
+// incremental: the proposals that move few distances by columns of L^-1 on a kept z (else every one through the full sweep)
 hipError_t launch_mh_chain_big(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const int32_t* sched, int64_t n_steps,
                                int32_t S, int accumulate, uint64_t step0, uint64_t seed, double* trace_alpha, int8_t* trace_accept,
-                               hipStream_t st);
-// whole schedule in one launch (k_mh_chain.hip); needs n_nodes <= 64 and mh_chain_lds_bytes(...) <= 64 KB
+                               bool incremental, hipStream_t st);
+// whole schedule in one launch (k_mh_chain.hip); needs n_nodes <= 64 and mh_chain_lds_bytes(...) <= 64 KB; likelihood_wave: below 1024
+// chains a second wave per chain evaluates the likelihood beside the prior (else one wave per chain, the same bits)
 size_t mh_chain_lds_bytes(int n, int n_prop, int wpb);
 hipError_t launch_mh_chain(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const double* Fp,
                            const int32_t* sched, int64_t n_steps, int32_t S, int accumulate, uint64_t step0, uint64_t seed,
-                           double* trace_alpha, int8_t* trace_accept, hipStream_t st);
+                           double* trace_alpha, int8_t* trace_accept, bool likelihood_wave, hipStream_t st);
 
 }  // namespace mcd
 

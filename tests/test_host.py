@@ -380,3 +380,103 @@ def test_mc3_swap_host_keeps_a_permutation_per_group():
     r2 = rank.copy()
     SM.mc3_swap_host(r2, np.full(40, np.nan), ladder, 4, 9, 99)                                  # NaN posteriors: no swap
     assert np.array_equal(r2, rank)
+
+
+# (dimension, chains, sparse likelihood, knobs, proposals, path): the launch structure (mcd_mh_last_path) that a run of bench.py's synthetic
+# tree of that dimension takes, recorded on the GPU with the library before its run planner was split out of mcd_mh_run (0: the run is
+# refused); the knobs are set before the handle is created
+MH_PLAN_CASES = [
+    (61, 512, False, {}, 224, 1),
+    (61, 2048, False, {}, 224, 1),
+    (61, 512, False, {'MCD_MH_PER_PHASE': 1}, 224, 3),
+    (61, 512, False, {'MCD_MH_PER_PHASE': 1, 'MCD_MH_PRIOR': 0}, 224, 4),
+    (61, 512, False, {'MCD_MH_CHAIN_LW': 0}, 224, 1),
+    (61, 2048, False, {'MCD_MH_PER_PHASE': 1}, 224, 3),
+    (127, 512, False, {}, 456, 2),
+    (127, 512, False, {'MCD_MH_PER_PHASE': 1, 'MCD_MH_STEP_WG': 1}, 456, 3),
+    (255, 512, False, {}, 904, 2),
+    (255, 1024, False, {}, 904, 2),
+    (255, 1025, False, {}, 904, 3),
+    (255, 2048, False, {}, 904, 4),
+    (255, 512, False, {'MCD_MH_PER_PHASE': 1}, 904, 3),
+    (255, 512, False, {'MCD_MH_PER_PHASE': 1, 'MCD_MH_STEP_WG': 1}, 904, 3),
+    (255, 512, False, {'MCD_MH_PER_PHASE': 1, 'MCD_MH_PRIOR': 0}, 904, 4),
+    (255, 512, False, {'MCD_MH_INCREMENTAL': 0}, 904, 2),
+    (255, 512, False, {'MCD_MH_SEGMENTS': 0}, 904, 2),
+    (255, 64, False, {}, 904, 2),
+    (257, 512, False, {}, 911, 8),
+    (277, 33, False, {}, 981, 8),
+    (277, 512, False, {}, 981, 8),
+    (297, 512, False, {}, 1051, 8),
+    (317, 64, False, {}, 1121, 8),
+    (317, 1024, False, {}, 1121, 8),
+    (317, 1025, False, {}, 1121, 8),
+    (319, 512, False, {}, 1128, 8),
+    (317, 512, False, {'MCD_MH_SEGMENTS': 0}, 1121, 4),
+    (317, 512, False, {'MCD_MH_STEP_WG': 1}, 1121, 8),
+    (381, 512, False, {}, 1345, 8),
+    (511, 512, False, {}, 1800, 8),
+    (511, 512, False, {'MCD_MH_SEGMENTS': 0}, 1800, 6),
+    (1023, 512, False, {}, 3592, 8),
+    (1023, 1024, False, {}, 3592, 8),
+    (1023, 1025, False, {}, 3592, 8),
+    (1023, 2048, False, {}, 3592, 8),
+    (1023, 512, False, {'MCD_MH_SEGMENTS': 0}, 3592, 6),
+    (1023, 512, False, {'MCD_MH_INCREMENTAL': 0}, 3592, 5),
+    (1023, 512, False, {'MCD_MH_STEP_WG': 0}, 3592, 4),
+    (1023, 512, False, {'MCD_MH_STEP_WG': 1}, 3592, 8),
+    (1023, 512, False, {'MCD_MH_PRIOR': 0}, 3592, 8),
+    (1023, 512, False, {'MCD_MH_PRIOR_CACHE': 0}, 3592, 8),
+    (1023, 2048, False, {'MCD_MH_SEGMENTS': 0}, 3592, 6),
+    (1023, 2048, False, {'MCD_MH_INCREMENTAL': 0}, 3592, 5),
+    (61, 512, True, {}, 224, 9),
+    (255, 512, True, {}, 904, 9),
+    (1023, 512, True, {}, 3592, 9),
+    (1023, 2048, True, {}, 3592, 9),
+    (2011, 512, True, {}, 7050, 9),
+    (1023, 512, True, {'MCD_MH_SEGMENTS': 0}, 3592, 7),
+    (1023, 512, True, {'MCD_MH_INCREMENTAL': 0}, 3592, 7),
+    (1023, 512, True, {'MCD_MH_STEP_WG': 0}, 3592, 0),
+    (61, 512, True, {'MCD_MH_SEGMENTS': 0}, 224, 7),
+]
+# MhPlan::flags() (mh_capi.cpp), from bit 4 of the hook's result
+PLAN_FLAGS = ["likelihood_wave", "incremental", "beside", "use_x", "step_wg", "keep", "inc_dense", "inc_sparse", "chunked", "segments", "tails",
+              "prior_waves", "prior_draws"]
+
+
+def test_mh_run_plan_table(knobs):
+    """The run planner of mcd_mh_run is host code: for the shape of a handle and the knobs it chooses one of the nine launch structures
+    and every decision the launches depend on.  mcd_mh_plan_selftest_ plans from plain facts, no device: each case must take the path the
+    GPU recorded, and the flags must agree with it."""
+    L = C.CDLL(M._capi.LIB_PATH)
+    f = L.mcd_mh_plan_selftest_
+    f.restype = C.c_int
+    f.argtypes = [C.c_int, C.c_int, C.c_int64] + [C.c_int] * 6
+    paths = set()
+    for dim, B, sparse, opts, n_prop, want in MH_PLAN_CASES:
+        for k, v in opts.items():
+            knobs.setenv(k, v)
+        n_nodes = dim + 2
+        R = 0 if sparse else next(r for r in (1, 2, 3, 4, 6, 8, 12, 16) if 64 * r >= dim)
+        chain_kernel = not sparse and n_nodes <= 64 and opts.get("MCD_MH_PER_PHASE") != 1
+        res = f(n_nodes, n_prop, B, R, dim, int(dim > 128), 0, int(chain_kernel), int(sparse and dim <= 254))
+        for k in opts:
+            knobs.delenv(k)
+        path, fl = res & 15, {name for i, name in enumerate(PLAN_FLAGS) if res >> (4 + i) & 1}
+        case = (dim, B, sparse, opts, sorted(fl))
+        assert path == want, case
+        paths.add(path)
+        assert ("prior_waves" in fl) == (opts.get("MCD_MH_PRIOR_WAVES") != 0) and ("incremental" in fl) == (opts.get("MCD_MH_INCREMENTAL") != 0), case
+        assert ("likelihood_wave" in fl) == (opts.get("MCD_MH_CHAIN_LW") != 0), case
+        if path in (1, 2, 0):
+            assert not fl & {"beside", "use_x", "step_wg", "keep", "segments"}, case
+            continue
+        assert ("segments" in fl) == (path in (8, 9)) and ("beside" in fl) == (path == 3), case
+        assert ("use_x" in fl) == (path >= 5) and ("inc_sparse" in fl) == (path == 9), case
+        assert ("inc_dense" in fl) == (path in (6, 8)) and ("chunked" in fl) == ("inc_dense" in fl and B > 1024), case
+        assert ("use_x" not in fl) or "step_wg" in fl, case
+        assert ("keep" in fl) == ("step_wg" in fl and "beside" not in fl and opts.get("MCD_MH_PRIOR_CACHE") != 0), case
+        assert ("tails" in fl) == ("keep" in fl), case
+        if opts.get("MCD_MH_STEP_WG") == 0:
+            assert "step_wg" not in fl, case
+    assert paths == set(range(10))
