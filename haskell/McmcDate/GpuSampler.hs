@@ -19,6 +19,9 @@
 --     (:440-441) in blocks of the monitor period (2, :288-417): @mcd_mh_run@ per block, @mcd_mh_tune@ per tuning period,
 --     @mcd_mh_get_state@ per block -> the chains' states as values of 'I', handed to the caller's monitor action (the reference's
 --     'Definitions.monitor' executes on an 'I'); @mcd_mh_get_age_sums@ at the end for the node-age summary of @scripts/analyze@;
+--   * 'runRecorded' is the same loop without the cut at every monitor period: the device keeps the samples while a chunk of
+--     iterations runs in ONE @mcd_mh_run@ (@mcd_mh_record_begin@ / @_fetch@ / @_end@), and the monitor action is called from the
+--     fetched samples, one @mcd_mh_record_fetch@ per chunk instead of one @mcd_mh_get_state@ per two iterations;
 --   * 'runMc3Gpu' is @mc3 (MC3Settings (NChains 4) (SwapPeriod 2) (NSwaps 3))@ (app/Main.hs:476-478): @mcd_mh_mc3_init@, per swap
 --     period @mcd_mh_run@ + @mcd_mh_mc3_swap@, the monitors read the chains whose temperature rank is 0 (@mcd_mh_mc3_get@).
 --
@@ -34,6 +37,7 @@ module McmcDate.GpuSampler
     GpuSampler,
     withGpuSampler,
     runMetropolisHastingsGreenGpu,
+    runRecorded,
     runMc3Gpu,
     nodeAgeSummary,
   )
@@ -119,6 +123,20 @@ foreign import ccall unsafe "mcd_mh_mc3_swap"
 
 foreign import ccall unsafe "mcd_mh_mc3_get"
   c_mh_mc3_get :: Ptr McdMh -> Ptr Int32 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> IO CInt
+
+-- the sample recorder: thinned samples kept on the device while mcd_mh_run runs (what 'runRecorded' drains)
+foreign import ccall unsafe "mcd_mh_record_begin"
+  c_mh_record_begin :: Ptr McdMh -> Int32 -> Int64 -> IO CInt
+
+foreign import ccall unsafe "mcd_mh_record_count"
+  c_mh_record_count :: Ptr McdMh -> Ptr Int64 -> IO CInt
+
+foreign import ccall unsafe "mcd_mh_record_fetch"
+  c_mh_record_fetch ::
+    Ptr McdMh -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+
+foreign import ccall unsafe "mcd_mh_record_end"
+  c_mh_record_end :: Ptr McdMh -> IO CInt
 
 check :: String -> CInt -> IO ()
 check _ 0 = pure ()
@@ -328,27 +346,26 @@ getStates s = do
   scv <- VS.freeze sc
   hv <- VS.freeze hh
   rv <- VS.freeze rr
-  let at k i = realToFrac (scv VS.! (k * b + i)) :: Double
-      slice v i = map realToFrac (VS.toList (VS.slice (i * nn) nn v)) :: [Double]
-      relabelH x ls = HeightTree (relabel (getHeightTree (x ^. timeTree)) ls)
-      relabelR x ls = LengthTree (relabel (getLengthTree (x ^. rateTree)) ls)
-      x0 = gsTemplate s
-  pure
-    [ x0
-        & timeBirthRate .~ at 0 i
-        & timeDeathRate .~ at 1 i
-        & timeHeight .~ at 2 i
-        & rateMean .~ at 3 i
-        & rateVariance .~ at 4 i
-        & timeTree .~ relabelH x0 (slice hv i)
-        & rateTree .~ relabelR x0 (slice rv i)
-      | i <- [0 .. b - 1]
-    ]
+  pure [pourState s (\k -> realToFrac (scv VS.! (k * b + i))) (VS.slice (i * nn) nn hv) (VS.slice (i * nn) nn rv) | i <- [0 .. b - 1]]
+
+-- one state as a value of 'I': the five scalars (birth, death, tH, rMu, rVar) by index, heights and rates in pre-order
+pourState :: GpuSampler -> (Int -> Double) -> VS.Vector CDouble -> VS.Vector CDouble -> I
+pourState s at hs rs =
+  x0
+    & timeBirthRate .~ at 0
+    & timeDeathRate .~ at 1
+    & timeHeight .~ at 2
+    & rateMean .~ at 3
+    & rateVariance .~ at 4
+    & timeTree .~ HeightTree (relabel (getHeightTree (x0 ^. timeTree)) (list hs))
+    & rateTree .~ LengthTree (relabel (getLengthTree (x0 ^. rateTree)) (list rs))
   where
+    x0 = gsTemplate s
+    list v = map realToFrac (VS.toList v) :: [Double]
     -- new branch labels in pre-order (the order of 'T.branches')
     relabel t ls = case T.setBranches ls t of
       Just t' -> t'
-      Nothing -> error "getStates: wrong number of branch labels."
+      Nothing -> error "pourState: wrong number of branch labels."
 
 -- one block of iterations through the shuffled cycle; accumulate: add the node ages to the running sums after every iteration
 runBlock :: StatefulGen g IO => GpuSampler -> g -> Int -> Bool -> IO ()
@@ -384,6 +401,54 @@ runMetropolisHastingsGreenGpu s g burnInPeriods iterations period onSample = do
           i <- VSM.read it 0
           when (k == period) (getStates s >>= onSample i)
           go (left - k)
+
+-- | 'runMetropolisHastingsGreenGpu' with the samples kept on the device (the recorder of include/mcmcdate_mvn.h): every tuning period
+-- and the iterations run in calls of up to @chunk@ iterations instead of @period@, and the monitor action is called from what
+-- @mcd_mh_record_fetch@ returns after each call -- the same iteration numbers as long as every tuning period is a multiple of
+-- @period@ (the reference's are all even, its period is 2: the old loop restarts its blocks at every tuning period and skips a short
+-- last block, the recorder samples on global multiples of @period@) and, the rounding of the incremental likelihood apart
+-- (every call restarts it from a full product), the same states.  The recorder counts iterations from its begin, which is the start
+-- of the run here, so the iteration numbers are the loop's own.
+runRecorded :: StatefulGen g IO => GpuSampler -> g -> [Int] -> Int -> Int -> Int -> (Int -> [I] -> IO ()) -> IO ()
+runRecorded s g burnInPeriods iterations period chunk onSample = do
+  getStates s >>= onSample 0
+  let cap = (chunk + period - 1) `div` period -- what one call can add at most
+  check "mcd_mh_record_begin" =<< c_mh_record_begin (gsHandle s) (fromIntegral period) (fromIntegral cap)
+  forM_ burnInPeriods $ \p -> do
+    chunks cap p False
+    check "mcd_mh_tune" =<< c_mh_tune (gsHandle s)
+  check "mcd_mh_reset_age_sums" =<< c_mh_reset_age_sums (gsHandle s)
+  chunks cap iterations True
+  check "mcd_mh_record_end" =<< c_mh_record_end (gsHandle s)
+  where
+    b = gsChains s
+    nn = gsNodes s
+    chunks cap n acc = go n
+      where
+        go left = when (left > 0) $ do
+          let k = min chunk left
+          runBlock s g k acc
+          drain cap
+          go (left - k)
+    drain cap = do
+      its <- VSM.new cap
+      sc <- VSM.new (cap * b * 5)
+      hh <- VSM.new (cap * b * nn)
+      rr <- VSM.new (cap * b * nn)
+      n <- alloca $ \pn -> do
+        VSM.unsafeWith its $ \pi' -> VSM.unsafeWith sc $ \ps -> VSM.unsafeWith hh $ \ph -> VSM.unsafeWith rr $ \pr ->
+          check "mcd_mh_record_fetch" =<< c_mh_record_fetch (gsHandle s) (fromIntegral cap) pn pi' ps ph pr nullPtr nullPtr
+        fromIntegral <$> peek pn
+      iv <- VS.freeze its
+      scv <- VS.freeze sc
+      hv <- VS.freeze hh
+      rv <- VS.freeze rr
+      forM_ [0 .. n - 1] $ \k ->
+        onSample
+          (fromIntegral (iv VS.! k))
+          [ pourState s (\f -> realToFrac (scv VS.! ((k * b + i) * 5 + f))) (VS.slice ((k * b + i) * nn) nn hv) (VS.slice ((k * b + i) * nn) nn rv)
+            | i <- [0 .. b - 1]
+          ]
 
 -- | @mc3 (MC3Settings (NChains nChains) (SwapPeriod swapPeriod) (NSwaps nSwaps))@ (app/Main.hs:476-478) over the same driver: the
 -- global set of chains is cut into groups of @nChains@ consecutive chains with the ladder of reciprocal temperatures @betas@ (head = 1);

@@ -430,6 +430,35 @@ int mcd_mh_mc3_get(const mcd_mh_t* m, int32_t* rank, int64_t* tried, int64_t* ac
 /* age_sum / age_sq: [batch][n_nodes] running sums over *n_samples accumulated iterations; reset with the call below. */
 int mcd_mh_get_age_sums(const mcd_mh_t* m, double* age_sum, double* age_sq, int64_t* n_samples);
 int mcd_mh_reset_age_sums(mcd_mh_t* m);
+/*
+ * The sample recorder: thinned samples of every chain kept ON THE DEVICE while mcd_mh_run runs.  Replaces: the `monitor` of
+ * app/Definitions.hs:288-417 (`mcmc`'s MonitorFile with period 2 everywhere) as the source of the states that the monitor files and
+ * scripts/analyze read -- without cutting the run into calls of one monitor period with a state read-back after each.
+ *   mcd_mh_record_begin   a ring of capacity_samples slots on the handle's device; the iteration count starts at 0.  period >= 1,
+ *                         capacity_samples >= 1; one recorder per handle (a second begin without end is refused).
+ *   mcd_mh_run            while a recorder is active: the state of every chain at the END of every iteration whose number is a multiple of
+ *                         period is stored as one sample, by the kernels of whichever launch structure the run takes (all of
+ *                         MCD_MH_PATH_*).  Iterations count from mcd_mh_record_begin over consecutive calls, so calls of any lengths give
+ *                         the samples of one long call.  A call whose samples do not fit the free slots returns MCD_ERR_INVALID_ARG before
+ *                         anything is launched (the message names both numbers) and leaves the handle as it was.  The chains themselves do
+ *                         not change: states, posteriors, traces, counters and age sums are the same bits with and without a recorder.
+ *                         This host-side check is the contract.  On the device sample number k = iteration / period goes to slot
+ *                         (k - 1) mod capacity, so no store can leave the ring; were the host's count ever wrong, the newest sample
+ *                         would overwrite the oldest unfetched one (not be dropped).  If a call fails after it has launched
+ *                         (MCD_ERR_HIP), the recorder's count no longer matches the chains: end the recorder.
+ *   mcd_mh_record_count   samples waiting to be fetched.
+ *   mcd_mh_record_fetch   waits for the handle's stream, copies the oldest *n_out = min(waiting, max_samples) samples to the host,
+ *                         sample-major, and frees their slots: iteration[n], scalars[n][batch][5] (birth, death, tH, rMu, rVar),
+ *                         heights[n][batch][n_nodes], rates[n][batch][n_nodes], post[n][batch][3] (ln prior, ln likelihood, ln
+ *                         jacobianRootBranch of the accepted state), beta[n][batch] (the reciprocal temperature the chain had: which chains
+ *                         were cold under MC3).  Any of the arrays may be NULL.
+ *   mcd_mh_record_end     frees the ring.  mcd_mh_set_state leaves an active recorder and its count alone; mcd_mh_destroy frees it.
+ */
+int mcd_mh_record_begin(mcd_mh_t* m, int32_t period, int64_t capacity_samples);
+int mcd_mh_record_count(const mcd_mh_t* m, int64_t* n_samples);
+int mcd_mh_record_fetch(mcd_mh_t* m, int64_t max_samples, int64_t* n_out, int64_t* iteration, double* scalars, double* heights, double* rates,
+                        double* post, double* beta);
+int mcd_mh_record_end(mcd_mh_t* m);
 
 /* ------------------------------------------------------------------------------------------------
  * The sparse form: the precision matrix as it is, in CSR on the device, no densification; N up to MCD_MAX_SPARSE_DIM.

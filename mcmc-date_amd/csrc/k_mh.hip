@@ -124,6 +124,13 @@ __global__ __launch_bounds__(256) void k_mh_step(MhDev M, PriorDev P, int p_acc,
             M.age_sq[b * n + w] += a * a;
         }
     }
+    if (M.rec.base != nullptr) {                          // the sample recorder (mh_device.hpp; MhRec::iter0 = the iteration this step closes)
+        if (double* rec = mh_rec_at(M, M.rec.iter0, b)) {
+            mh_rec_nodes(rec, M.ld, n, lane, 64, Hc, Rc);
+            const double* ps = ok ? M.post1 : M.post;     // (M.post itself is being written by other lanes)
+            if (lane == 0) mh_rec_tail(rec, M.ld, sc, ps[b], ps[B + b], ps[2 * B + b], M.beta[b]);
+        }
+    }
     if (p_prop < 0) return;
     __builtin_amdgcn_wave_barrier();
     MHS_T(2);
@@ -405,6 +412,19 @@ __global__ __launch_bounds__(64 * MHW, 2) void k_mh_step_wg(MhDev M, PriorDev P,
                     M.age_sum[b * n + w] = s1[k] + a;
                     M.age_sq[b * n + w] = s2[k] + a * a;
                 }
+            }
+        }
+        if (M.rec.base != nullptr) {                       // the sample recorder (mh_device.hpp; MhRec::iter0 = the iteration this step closes)
+            if (double* rec = mh_rec_at(M, M.rec.iter0, b)) {
+#pragma unroll
+                for (int k = 0; k < KM; ++k) {
+                    const int w = tid + NT * k;
+                    if (w < n) {
+                        rec[w] = hv[k];
+                        rec[M.ld + w] = rv[k];
+                    }
+                }
+                if (tid == 0) mh_rec_tail(rec, M.ld, sc, ok ? po1[0] : po[0], ok ? po1[1] : po[1], ok ? po1[2] : po[2], be);
             }
         }
     }
@@ -711,6 +731,35 @@ __global__ __launch_bounds__(256) void k_mh_tune(MhDev M)
     }
     M.acc[i] = 0;
     M.tried[i] = 0;
+}
+
+// mcd_mh_record_fetch: the records of the recorder's ring (MhRec, mvn_kernels.h: per chain heights, rates, then the nine scalars) as the
+// sample-major arrays the host takes; one workgroup per (sample, chain), threads = nodes
+__global__ __launch_bounds__(256) void k_mh_rec_unpack(MhDev M, MhRec R, int64_t first, double* __restrict__ scalars, double* __restrict__ heights,
+                                                       double* __restrict__ rates, double* __restrict__ post, double* __restrict__ beta)
+{
+    const int64_t i = (int64_t)blockIdx.x / M.batch, b = (int64_t)blockIdx.x - i * M.batch;
+    const int64_t slot = (first + i) % R.capacity;
+    const double* rec = R.base + (slot * M.batch + b) * mh_rec_stride(M.ld);
+    const int64_t o = i * M.batch + b;
+    const int n = M.n_nodes, tid = threadIdx.x;
+    for (int w = tid; w < n; w += 256) {
+        if (heights) heights[o * n + w] = rec[w];
+        if (rates) rates[o * n + w] = rec[M.ld + w];
+    }
+    const double* t = rec + 2 * M.ld;
+    if (scalars && tid < 5) scalars[o * 5 + tid] = t[tid];
+    if (post && tid < 3) post[o * 3 + tid] = t[5 + tid];
+    if (beta && tid == 0) beta[o] = t[8];
+}
+
+hipError_t launch_mh_rec_unpack(const MhDev& M, const MhRec& R, int64_t first, int64_t count, double* scalars, double* heights, double* rates,
+                                double* post, double* beta, hipStream_t st)
+{
+    if (count <= 0) return hipSuccess;
+    if (R.base == nullptr || count * M.batch > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_mh_rec_unpack, dim3((unsigned)(count * M.batch)), dim3(256), 0, st, M, R, first, scalars, heights, rates, post, beta);
+    return hipGetLastError();
 }
 
 hipError_t launch_mh_draws(const MhDev& M, const int32_t* sched, int64_t idx0, int count, uint64_t step0, uint64_t seed, hipStream_t st)

@@ -936,6 +936,12 @@ __global__ __launch_bounds__(256, 1) void k_mh_chain_big(MhDev M, MvnDev V, Tree
                 M.age_sq[b * nn + w] += a * a;
             }
         }
+        if (M.rec.base != nullptr && valid) {                // the sample recorder (mh_device.hpp)
+            if (double* rec = mh_rec_step(M, gs, S, b)) {
+                mh_rec_nodes(rec, M.ld, nn, lane, 64, Hc, Rc);
+                if (lane == 0) mh_rec_tail(rec, M.ld, sc, lp, ll, lj, beta);
+            }
+        }
         p = __builtin_amdgcn_readfirstlane(p_next);
         p_next = p_next2;
         row = mh_row_scalar(row_next);

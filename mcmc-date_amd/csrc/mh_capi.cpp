@@ -80,10 +80,19 @@ struct mcd_mh {
     // Metropolis-coupled MCMC (mcd_mh_mc3_*): temperature ranks of all GLOBAL chains, ladder, counters; phase = swap phases done
     mcd::Mc3Dev mc3{};
     uint64_t mc3_seed = 0, mc3_phase = 0;
+    // the sample recorder (mcd_mh_record_*): a ring of rec_cap slots (mcd::MhRec), the staging buffer of the fetch (rec_stage_cap samples);
+    // rec_iter = iterations since begin, so rec_iter / rec_period samples were taken, rec_fetched of them handed out
+    double* d_rec = nullptr;
+    double* d_rec_stage = nullptr;
+    int64_t rec_cap = 0, rec_stage_cap = 0, rec_iter = 0, rec_fetched = 0;
+    int32_t rec_period = 0;
+    int64_t rec_filled() const { return rec_iter / rec_period - rec_fetched; }
 
     ~mcd_mh()
     {
         (void)hipSetDevice(device);
+        if (d_rec) (void)hipFree(d_rec);
+        if (d_rec_stage) (void)hipFree(d_rec_stage);
         for (void* p : allocs) (void)hipFree(p);
         if (d_sched) (void)hipFree(d_sched);
         if (d_trace_alpha) (void)hipFree(d_trace_alpha);
@@ -724,11 +733,26 @@ struct MhRun {
     double* X1;
     bool inc;
     int dense_mode;                  // where the z' (q') of a dense proposal is afterwards: zprop (1) or the z tiles (2)
+    mcd::MhRec rec;                  // the sample recorder as it stands when the call starts (base null: off)
 
     MhRun(mcd_mh* m_, const MhPlan& p_, const int32_t* schedule_, int64_t total_, int32_t S_, int accumulate_, bool trace_)
         : m(m_), p(p_), schedule(schedule_), total(total_), S(S_), accumulate(accumulate_), trace(trace_), step_base(m_->step),
           n_dim(m_->mvn ? m_->mvn->n : m_->sp->n), prior_inline(p_.beside ? 0 : 1), Tx(p_.use_x ? m_->tree : nullptr), X1(p_.use_x ? m_->d_X1 : nullptr),
-          inc(p_.inc_dense || p_.inc_sparse), dense_mode((p_.chunked || p_.inc_sparse) ? 1 : 2) {}
+          inc(p_.inc_dense || p_.inc_sparse), dense_mode((p_.chunked || p_.inc_sparse) ? 1 : 2),
+          rec(mcd::MhRec{m_->d_rec, m_->rec_iter, m_->rec_cap, m_->rec_period}) {}
+    // what the next launch sees of the recorder (MhDev::rec): a whole-schedule or segment launch whose step 0 is `steps_before` steps (whole
+    // iterations) into the call; a step launch that decides schedule position gs (gs < 0: decides nothing); nothing
+    void rec_launch(int64_t steps_before) const
+    {
+        m->dev.rec = rec;
+        m->dev.rec.iter0 += steps_before / S;
+    }
+    void rec_step(int64_t gs) const
+    {
+        m->dev.rec = rec;
+        if (gs < 0 || (gs + 1) % S != 0) m->dev.rec.base = nullptr;
+        else m->dev.rec.iter0 += (gs + 1) / S;
+    }
     double* alpha(int64_t gs) const { return trace ? m->d_trace_alpha + gs * m->dev.batch : nullptr; }
     int8_t* accept(int64_t gs) const { return trace ? m->d_trace_accept + gs * m->dev.batch : nullptr; }
 
@@ -785,6 +809,7 @@ struct MhRun {
 int run_chain(const MhRun& r)
 {
     mcd_mh* m = r.m;
+    r.rec_launch(0);
     MHIP_TRY(mcd::launch_mh_chain(m->dev, *m->mvn, *m->tree, *m->prior, m->d_Fp, m->d_sched, r.total, r.S, r.accumulate, m->step, m->seed,
                                   r.alpha(0), r.accept(0), r.p.likelihood_wave, m->stream));
     m->step += (uint64_t)r.total;
@@ -800,6 +825,7 @@ int run_streamed(const MhRun& r)
     const int64_t per_launch = (int64_t)r.S * (65536 / r.S > 0 ? 65536 / r.S : 1);
     for (int64_t done = 0; done < r.total; done += per_launch) {
         const int64_t now = (r.total - done < per_launch) ? r.total - done : per_launch;
+        r.rec_launch(done);
         MHIP_TRY(mcd::launch_mh_chain_big(m->dev, *m->mvn, *m->tree, *m->prior, m->d_sched + done, now, r.S, r.accumulate, m->step, m->seed,
                                           r.alpha(done), r.accept(done), r.p.incremental, m->stream));
         m->step += (uint64_t)now;
@@ -848,6 +874,7 @@ int run_segments(const MhRun& r)
             pending.p_tail = (p.tails && e < total && r.inc_mode(schedule[e]) == 2) ? schedule[e] : -1;
             pending.X1_tail = r.X1;
             proposed = pending.p_tail >= 0;
+            r.rec_launch(0);                         // (the segment kernels count from the call's first step: gs_base + their own)
             if (p.inc_sparse)
                 MHIP_TRY(mcd::launch_mh_segment_sparse(D, *m->sp, *m->tree, *m->prior, I, m->d_sched + gs, e - gs, r.S, r.accumulate ? 1 : 0,
                                                        r.step_base + (uint64_t)gs, m->seed, r.alpha(gs), r.accept(gs), gs, summands_kept ? 1 : 0, pending,
@@ -870,6 +897,7 @@ int run_segments(const MhRun& r)
             if (int rc = need_draws(gs)) return rc;
             I.mode = 0;
             I.prop_mode = 2;
+            r.rec_step(-1);
             MHIP_TRY(mcd::launch_mh_step(D, *m->prior, -1, 0, schedule[gs], m->rows[schedule[gs]], (int)(gs & 63), m->step, m->seed, 0, nullptr,
                                          nullptr, r.prior_inline, p.step_wg, r.Tx, r.n_dim, r.X1, r.n_dim, m->stream, &I, Vinc, summands_kept ? 0 : 1));
             if (D.psum != nullptr) summands_kept = true;
@@ -900,6 +928,7 @@ int run_segments(const MhRun& r)
                 break;
             }
             I.prop_mode = 2;
+            r.rec_step(gs);
             MHIP_TRY(mcd::launch_mh_step(D, *m->prior, pa, m->rows[pa].jac_root, pn, pn >= 0 ? m->rows[pn] : kNoRow, (int)((gs + 1) & 63), m->step,
                                          m->seed, (r.accumulate && closes) ? 1 : 0, r.alpha(gs), r.accept(gs), r.prior_inline, p.step_wg, r.Tx, r.n_dim, r.X1,
                                          r.n_dim, m->stream, &I, Vinc, 0));
@@ -923,6 +952,7 @@ int run_steps(const MhRun& r)
     const int32_t* schedule = r.schedule;
     if (int rc = r.begin()) return rc;
     I.prop_mode = r.inc ? r.inc_mode(schedule[0]) : 0;
+    r.rec_step(-1);
     MHIP_TRY(mcd::launch_mh_step(D, *m->prior, -1, 0, schedule[0], m->rows[schedule[0]], 0, m->step - 1, m->seed, 0, nullptr, nullptr,
                                  r.prior_inline, r.p.step_wg, r.Tx, r.n_dim, r.X1, r.n_dim, m->stream, r.inc ? &I : nullptr, m->mvn));
     for (int64_t gs = 0; gs < r.total; ++gs) {
@@ -951,6 +981,7 @@ int run_steps(const MhRun& r)
             if (int rc = r.draws_for(gs + 1)) return rc;
         const bool refresh_now = r.inc && ((gs + 1) & 255) == 0;
         I.prop_mode = r.inc ? r.inc_mode(pn) : 0;
+        r.rec_step(gs);
         MHIP_TRY(mcd::launch_mh_step(D, *m->prior, pa, m->rows[pa].jac_root, pn, pn >= 0 ? m->rows[pn] : kNoRow, (int)((gs + 1) & 63), m->step,
                                      m->seed, (r.accumulate && closes) ? 1 : 0, r.alpha(gs), r.accept(gs), r.prior_inline, r.p.step_wg, r.Tx, r.n_dim,
                                      r.X1, r.n_dim, m->stream, r.inc ? &I : nullptr, m->mvn));
@@ -978,6 +1009,12 @@ int mcd_mh_run(mcd_mh_t* m, const int32_t* schedule, int64_t n_iter, int32_t S, 
     const size_t steps = (size_t)n_iter * (size_t)S;
     for (size_t i = 0; i < steps; ++i)
         if (schedule[i] < 0 || schedule[i] >= D.n_prop) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_run: schedule[%zu] = %d is not a proposal row", i, schedule[i]);
+    if (m->d_rec) {                                  // an active recorder: the samples of this call must fit, or nothing is launched
+        const int64_t adds = (m->rec_iter + n_iter) / m->rec_period - m->rec_iter / m->rec_period, free_slots = m->rec_cap - m->rec_filled();
+        if (adds > free_slots)
+            return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_run: the call would record %lld samples, the recorder has %lld free slots (mcd_mh_record_fetch frees them)",
+                         (long long)adds, (long long)free_slots);
+    }
     MHIP_TRY(hipSetDevice(m->device));
     if (steps > m->sched_cap) {
         if (m->d_sched) (void)hipFree(m->d_sched);
@@ -1006,7 +1043,9 @@ int mcd_mh_run(mcd_mh_t* m, const int32_t* schedule, int64_t n_iter, int32_t S, 
     m->last_path = p.path;
     const MhRun r(m, p, schedule, (int64_t)steps, S, accumulate, trace);
     const int rc = p.path == MCD_MH_PATH_CHAIN_LDS ? run_chain(r) : p.path == MCD_MH_PATH_CHAIN_STREAMED ? run_streamed(r) : p.segments ? run_segments(r) : run_steps(r);
+    m->dev.rec = mcd::MhRec{};
     if (rc) return rc;
+    if (m->d_rec) m->rec_iter += n_iter;
     m->last_lds = mcd::last_dynamic_lds();
     if (trace_alpha) MHIP_TRY(hipMemcpyAsync(trace_alpha, m->d_trace_alpha, sizeof(double) * steps * B, hipMemcpyDeviceToHost, m->stream));
     if (trace_accept) MHIP_TRY(hipMemcpyAsync(trace_accept, m->d_trace_accept, steps * B, hipMemcpyDeviceToHost, m->stream));
@@ -1083,6 +1122,98 @@ int mcd_mh_get_age_sums(const mcd_mh_t* cm, double* age_sum, double* age_sq, int
     if (age_sum) MHIP_TRY(hipMemcpy(age_sum, D.age_sum, sizeof(double) * BN, hipMemcpyDeviceToHost));
     if (age_sq) MHIP_TRY(hipMemcpy(age_sq, D.age_sq, sizeof(double) * BN, hipMemcpyDeviceToHost));
     if (n_samples) *n_samples = cm->n_samples;
+    return MCD_OK;
+}
+
+// ---- the sample recorder: thinned samples of every chain kept on the device while mcd_mh_run runs (mcd::MhRec, mvn_kernels.h) -------
+int mcd_mh_record_begin(mcd_mh_t* m, int32_t period, int64_t capacity_samples)
+{
+    if (!m) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_begin: NULL handle");
+    if (m->d_rec) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_begin: a recorder is active already (mcd_mh_record_end first)");
+    if (period < 1) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_begin: period must be >= 1 (got %d)", (int)period);
+    if (capacity_samples < 1) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_begin: capacity must be >= 1 sample (got %lld)", (long long)capacity_samples);
+    const mcd::MhDev& D = m->dev;
+    const int64_t per_sample = D.batch * mcd::mh_rec_stride(D.ld);                 // doubles of one slot
+    if (capacity_samples > ((int64_t)1 << 50) / per_sample)
+        return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_begin: %lld samples of %lld bytes each", (long long)capacity_samples, (long long)per_sample * 8);
+    // the fetch unpacks into a staging buffer of at most 64 MiB (at least one sample) and copies from there, piece by piece
+    const int64_t out_sample = D.batch * (2 * (int64_t)D.n_nodes + 9);
+    const int64_t stage = std::max<int64_t>(1, std::min<int64_t>(capacity_samples, ((int64_t)8 << 20) / out_sample));
+    MHIP_TRY(hipSetDevice(m->device));
+    double *ring = nullptr, *st = nullptr;
+    hipError_t e = hipMalloc((void**)&ring, sizeof(double) * (size_t)(per_sample * capacity_samples));
+    if (e == hipSuccess) e = hipMalloc((void**)&st, sizeof(double) * (size_t)(out_sample * stage));
+    if (e == hipSuccess) e = hipMemsetAsync(ring, 0, sizeof(double) * (size_t)(per_sample * capacity_samples), m->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
+    if (e != hipSuccess) {
+        if (ring) (void)hipFree(ring);
+        if (st) (void)hipFree(st);
+        return mfail(MCD_ERR_HIP, "mcd_mh_record_begin: %lld samples of %lld bytes each: %s", (long long)capacity_samples, (long long)per_sample * 8, hipGetErrorString(e));
+    }
+    m->d_rec = ring;
+    m->d_rec_stage = st;
+    m->rec_cap = capacity_samples;
+    m->rec_stage_cap = stage;
+    m->rec_period = period;
+    m->rec_iter = 0;
+    m->rec_fetched = 0;
+    return MCD_OK;
+}
+
+int mcd_mh_record_count(const mcd_mh_t* m, int64_t* n_samples)
+{
+    if (!m || !n_samples) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_count: NULL argument");
+    if (!m->d_rec) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_count: no recorder is active (mcd_mh_record_begin first)");
+    *n_samples = m->rec_filled();
+    return MCD_OK;
+}
+
+int mcd_mh_record_fetch(mcd_mh_t* m, int64_t max_samples, int64_t* n_out, int64_t* iteration, double* scalars, double* heights, double* rates,
+                        double* post, double* beta)
+{
+    if (!m || !n_out) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_fetch: NULL argument");
+    *n_out = 0;
+    if (!m->d_rec) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_fetch: no recorder is active (mcd_mh_record_begin first)");
+    if (max_samples < 0) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_fetch: max_samples < 0");
+    const mcd::MhDev& D = m->dev;
+    const int64_t n = std::min(m->rec_filled(), max_samples), B = D.batch, nn = D.n_nodes;
+    const mcd::MhRec R{m->d_rec, 0, m->rec_cap, m->rec_period};
+    MHIP_TRY(hipSetDevice(m->device));
+    for (int64_t done = 0; done < n; done += m->rec_stage_cap) {
+        const int64_t cnt = std::min(m->rec_stage_cap, n - done);
+        double* s_sc = m->d_rec_stage;                       // the staging buffer's five arrays for `cnt` samples
+        double* s_H = s_sc + cnt * B * 5;
+        double* s_R = s_H + cnt * B * nn;
+        double* s_post = s_R + cnt * B * nn;
+        double* s_beta = s_post + cnt * B * 3;
+        MHIP_TRY(mcd::launch_mh_rec_unpack(D, R, m->rec_fetched + done, cnt, scalars ? s_sc : nullptr, heights ? s_H : nullptr, rates ? s_R : nullptr,
+                                           post ? s_post : nullptr, beta ? s_beta : nullptr, m->stream));
+        const size_t c = sizeof(double) * (size_t)(cnt * B), o = (size_t)(done * B);
+        if (scalars) MHIP_TRY(hipMemcpyAsync(scalars + o * 5, s_sc, c * 5, hipMemcpyDeviceToHost, m->stream));
+        if (heights) MHIP_TRY(hipMemcpyAsync(heights + o * (size_t)nn, s_H, c * (size_t)nn, hipMemcpyDeviceToHost, m->stream));
+        if (rates) MHIP_TRY(hipMemcpyAsync(rates + o * (size_t)nn, s_R, c * (size_t)nn, hipMemcpyDeviceToHost, m->stream));
+        if (post) MHIP_TRY(hipMemcpyAsync(post + o * 3, s_post, c * 3, hipMemcpyDeviceToHost, m->stream));
+        if (beta) MHIP_TRY(hipMemcpyAsync(beta + o, s_beta, c, hipMemcpyDeviceToHost, m->stream));
+        MHIP_TRY(hipStreamSynchronize(m->stream));           // (the next piece reuses the staging buffer)
+    }
+    if (iteration)
+        for (int64_t i = 0; i < n; ++i) iteration[i] = (m->rec_fetched + 1 + i) * m->rec_period;
+    m->rec_fetched += n;
+    *n_out = n;
+    return MCD_OK;
+}
+
+int mcd_mh_record_end(mcd_mh_t* m)
+{
+    if (!m) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_end: NULL handle");
+    if (!m->d_rec) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_end: no recorder is active (mcd_mh_record_begin first)");
+    MHIP_TRY(hipSetDevice(m->device));
+    MHIP_TRY(hipStreamSynchronize(m->stream));
+    (void)hipFree(m->d_rec);
+    (void)hipFree(m->d_rec_stage);
+    m->d_rec = m->d_rec_stage = nullptr;
+    m->rec_cap = m->rec_stage_cap = m->rec_iter = m->rec_fetched = 0;
+    m->rec_period = 0;
     return MCD_OK;
 }
 

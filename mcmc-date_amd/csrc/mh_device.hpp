@@ -600,6 +600,42 @@ __device__ __forceinline__ double mh_propose_wave(const MhDev& M, const PropRow&
     return lnqj;
 }
 
+// ---- the sample recorder (MhRec, mvn_kernels.h): all of it wave-uniform, and behind `M.rec.base != nullptr` at every site
+// chain b's record of the sample taken at the end of iteration `it`; null where `it` is not a positive multiple of the period
+__device__ __forceinline__ double* mh_rec_at(const MhDev& M, int64_t it, int64_t b)
+{
+    const int64_t k = it / M.rec.period;
+    if (k < 1 || k * M.rec.period != it) return nullptr;
+    const int64_t slot = (k - 1) % M.rec.capacity;           // a ring; also the clamp: no store leaves the buffer
+    return M.rec.base + (slot * M.batch + b) * mh_rec_stride(M.ld);
+}
+// ... for step G of a launch whose steps count from an iteration boundary (S steps per iteration, MhRec::iter0 iterations before step 0):
+// null unless the step closes a recorded iteration
+__device__ __forceinline__ double* mh_rec_step(const MhDev& M, int64_t G, int32_t S, int64_t b)
+{
+    if (M.rec.base == nullptr || (G + 1) % S != 0) return nullptr;
+    return mh_rec_at(M, M.rec.iter0 + (G + 1) / S, b);
+}
+// heights and rates, threads = nodes (thread t of nt takes the nodes t, t + nt, ...): contiguous stores
+__device__ __forceinline__ void mh_rec_nodes(double* rec, int64_t ld, int n, int t, int nt, const double* H, const double* R)
+{
+    for (int w = t; w < n; w += nt) {
+        rec[w] = H[w];
+        rec[ld + w] = R[w];
+    }
+}
+// the scalars, the posterior triple and the temperature: one lane
+__device__ __forceinline__ void mh_rec_tail(double* rec, int64_t ld, const double (&sc)[5], double lp, double ll, double lj, double beta)
+{
+    double* t = rec + 2 * ld;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) t[i] = sc[i];
+    t[5] = lp;
+    t[6] = ll;
+    t[7] = lj;
+    t[8] = beta;
+}
+
 __device__ __forceinline__ double mh_optimal_rate(int dim)
 {
     return (dim == 1) ? 0.44 : (dim == 2) ? 0.352 : (dim == 3) ? 0.316 : (dim == 4) ? 0.279 : (dim == 5) ? 0.275 : 0.234;

@@ -516,6 +516,12 @@ __device__ __forceinline__ void seg_chain_wave(const MhDev& M, const PriorDev& P
             M.age_sq[b * nn + w] += a * a;
         }
     }
+    if (Q.p_acc >= 0 && M.rec.base != nullptr && valid) {    // ... the sample recorder (mh_device.hpp): the pending step is step gs_base - 1
+        if (double* rec = mh_rec_step(M, gs_base - 1, S, b)) {
+            mh_rec_nodes(rec, M.ld, nn, lane, 64, Hc, Rc);
+            if (lane == 0) mh_rec_tail(rec, M.ld, sc, lp, ll, lj, beta);
+        }
+    }
     // The nodes a proposal writes (PropApply: up to three pre-order ranges, five single nodes, the braced nodes with their
     // daughters): f(w) for each of them, lanes in parallel (a node may come twice).  Between steps the proposed arrays equal the
     // current ones, so a step applies, commits or takes back its proposal on these nodes only.
@@ -849,6 +855,12 @@ __device__ __forceinline__ void seg_chain_wave(const MhDev& M, const PriorDev& P
                         const double a = sc[2] * Hc[w];
                         M.age_sum[b * nn + w] += a;
                         M.age_sq[b * nn + w] += a * a;
+                    }
+                }
+                if (M.rec.base != nullptr && valid) {        // the sample recorder (mh_device.hpp)
+                    if (double* rec = mh_rec_step(M, gs_base + gs, S, b)) {
+                        mh_rec_nodes(rec, M.ld, nn, lane, 64, Hc, Rc);
+                        if (lane == 0) mh_rec_tail(rec, M.ld, sc, lp, ll, lj, beta);
                     }
                 }
             }

@@ -157,6 +157,7 @@ struct mcd_mvn {
 
 struct mcd_tree {
     const mcd_mvn* mvn = nullptr;
+    int device = 0;                // the likelihood handle's (kept here: the handle may be destroyed before its trees)
     int n_nodes = 0;
     mcd::TreeDev dev{};
     int32_t *d_parent = nullptr, *d_slot = nullptr, *d_cptr = nullptr, *d_cidx = nullptr;
@@ -164,7 +165,7 @@ struct mcd_tree {
 
     ~mcd_tree()
     {
-        if (mvn) (void)hipSetDevice(mvn->device);
+        (void)hipSetDevice(device);
         if (d_parent) (void)hipFree(d_parent);
         if (d_slot) (void)hipFree(d_slot);
         if (d_cptr) (void)hipFree(d_cptr);
@@ -476,6 +477,7 @@ int mcd_tree_create(mcd_tree_t** out, const mcd_mvn_t* h, int n_nodes, const int
     }
     std::unique_ptr<mcd_tree> t(new mcd_tree());
     t->mvn = h;
+    t->device = h->device;
     t->n_nodes = n_nodes;
     t->parent.assign(parent, parent + n_nodes);
     HIP_TRY(hipSetDevice(h->device));

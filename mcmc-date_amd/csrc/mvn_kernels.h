@@ -87,6 +87,21 @@ __host__ __device__ inline size_t prior_node_tables_doubles(int n_cal, int n_con
     return 4 * (size_t)n_cal + (size_t)n_con + (3 * (size_t)n_cal + 2 * (size_t)n_con + 1) / 2;
 }
 
+// Sample recorder of the Metropolis-Hastings driver (mcd_mh_record_*): while base is not null, the wave that holds a chain's accepted state
+// at the end of an iteration whose number is a multiple of `period` stores it as one sample.  Iterations count from mcd_mh_record_begin;
+// sample number k = iteration / period (1, 2, ...) goes to slot (k - 1) % capacity of a ring of `capacity` slots -- the modulo is also the
+// clamp: whatever the host counted, no store leaves the buffer.  A slot is [batch] records of mh_rec_stride(ld) doubles, one per chain:
+// heights [ld], rates [ld], then birth, death, tH, rMu, rVar, ln prior, ln likelihood, ln jacobianRootBranch, beta and seven doubles of
+// padding -- so that the lanes of a wave, one node each, store 512 contiguous bytes per 64 nodes.
+struct MhRec {
+    double* base;        // null: off
+    int64_t iter0;       // whole-schedule and segment kernels: iterations counted before step 0 of what the launch calls gs (gs_base + gs in
+                         // a segment); step kernels: the number of the iteration that the launch's accept half closes
+    int64_t capacity;    // slots
+    int32_t period;
+};
+__host__ __device__ inline int64_t mh_rec_stride(int64_t ld) { return 2 * ld + 16; }
+
 // Lock-step Metropolis-Hastings workspace of one batch of chains (k_mh.hip); all pointers are device memory.
 struct MhDev {
     int n_nodes, n_prop;
@@ -117,6 +132,7 @@ struct MhDev {
     // the blocks the pending proposal wrote (the bits of pflags); null: not kept
     double* psum;
     int32_t* psel;
+    MhRec rec;                 // the sample recorder as it stands for ONE launch (mh_capi.cpp sets it before every launch of a run); base null: off
 };
 constexpr int kMhSparseSlots = 48;      // (257 nodes x 512 chains, us per lock step: 8 -> 8.96, 32 -> 8.35 before the likelihood wave; with it 24 -> 7.70, 32 -> 7.52, 48 -> 7.44, 64 -> 7.44)
 constexpr int kMhIncSlots = 32;       // the same bound for the two-launch path's incremental evaluation (k_mh_inc.hip; MCD_MH_INC_SLOTS)
@@ -343,6 +359,10 @@ hipError_t launch_mh_step(const MhDev& M, const PriorDev& P, int p_acc, int jac_
 // plain-vector likelihood launch; it exists for the trees where mh_step_wg_fits(n_nodes)
 bool mh_step_wg_fits(int n_nodes);
 hipError_t launch_mh_tune(const MhDev& M, hipStream_t st);
+// `count` samples of the recorder's ring from slot `first` on, into the sample-major arrays that mcd_mh_record_fetch hands out (device
+// staging; any may be null): scalars [count][batch][5], heights / rates [count][batch][n_nodes], post [count][batch][3], beta [count][batch]
+hipError_t launch_mh_rec_unpack(const MhDev& M, const MhRec& R, int64_t first, int64_t count, double* scalars, double* heights, double* rates,
+                                double* post, double* beta, hipStream_t st);
 hipError_t launch_mc3_swap(const Mc3Dev& C, const double* lnpost, int world, int64_t per_rank, int n_swaps, uint64_t seed, uint64_t phase,
                            double* beta_local, int64_t chain0, int64_t batch, hipStream_t st);
 // ln prior of the proposed states from pflags / pcomp (what launch_mh_step leaves when asked not to evaluate it itself) as extra

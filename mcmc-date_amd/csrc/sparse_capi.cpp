@@ -58,12 +58,13 @@ struct mcd_sparse {
 
 struct mcd_sparse_tree {
     const mcd_sparse* sp = nullptr;
+    int device = 0;                // the sparse handle's (kept here: the handle may be destroyed before its trees)
     mcd::SparseTreeDev dev{};
     std::vector<int32_t> parent;   // host copy (the Metropolis-Hastings driver checks its proposal table against the topology)
     int32_t* d_slot = nullptr;
     ~mcd_sparse_tree()
     {
-        if (sp) (void)hipSetDevice(sp->device);
+        (void)hipSetDevice(device);
         if (d_slot) (void)hipFree(d_slot);
     }
 };
@@ -384,6 +385,7 @@ int mcd_sparse_tree_create(mcd_sparse_tree_t** out, const mcd_sparse_t* h, int n
     for (size_t i = 0; i < n; ++i) slot[n + i] = parent[slot[i]];
     std::unique_ptr<mcd_sparse_tree> t(new mcd_sparse_tree());
     t->sp = h;
+    t->device = h->device;
     t->parent.assign(parent, parent + n_nodes);
     SHIP_TRY(hipSetDevice(h->device));
     SHIP_TRY(hipMalloc((void**)&t->d_slot, sizeof(int32_t) * slot.size()));

@@ -9,7 +9,8 @@ Host-side mirror of
     samples, per node the mean, the maximum-likelihood variance, minimum, maximum and the 95 % interval taken from
     the sorted ages as slice(floor(0.025 l), floor(0.95 l)).
 
-The states come from the device sampler (`Sampler.state()` every `period` iterations); nothing here computes a
+The states come from the device sampler -- `record`: kept on the device while it runs (mcd_mh_record_*) and fetched once per
+chunk of iterations; `collect`: `Sampler.state()` after every run of `period` iterations --; nothing here computes a
 likelihood or a prior on the host -- the prior blocks are evaluated by the device prior (`PriorFunction.logprior`).
 """
 from __future__ import annotations
@@ -38,6 +39,8 @@ class Trace:
     rate_mean: np.ndarray
     rate_variance: np.ndarray
     rates: np.ndarray
+    post: Optional[np.ndarray] = None    # [n_samples, B, 3] ln prior, ln likelihood, ln jacobianRootBranch (`record` only)
+    beta: Optional[np.ndarray] = None    # [n_samples, B] reciprocal temperature of the chain when the sample was taken (`record` only)
 
     def ages(self) -> np.ndarray:
         """Absolute node ages tH * h_v, [n_samples, B, n_nodes] (getTimeTreeNodeHeight, app/Definitions.hs:300-304)."""
@@ -66,15 +69,55 @@ def collect(sampler, n_iter: int, period: int = PERIOD, accumulate: bool = False
     return Trace(np.asarray(its, np.int64), *st)
 
 
+def record(sampler, n_iter: int, period: int = PERIOD, accumulate: bool = False, chunk: int = 256) -> Trace:
+    """`collect` without cutting the run into pieces of one monitor period: the sampler's recorder keeps the samples on the device
+    while `chunk` iterations run in one call, and they are fetched once per chunk.  The same samples at the same iterations as
+    `collect` (the chains do not depend on how a run is cut, up to the rounding of the incremental likelihood, which every call
+    restarts from a full product), with the posterior terms and the temperatures beside them."""
+    if n_iter < 0 or period < 1 or chunk < 1:
+        raise ValueError("record: need n_iter >= 0, period >= 1, chunk >= 1")
+    base = sampler.iterations_done
+    parts: List[tuple] = []
+    sampler.record_begin(period, (chunk + period - 1) // period)      # (what one chunk can add at most)
+    try:
+        done = 0
+        while done < n_iter:
+            k = min(chunk, n_iter - done)
+            sampler.run(k, accumulate=accumulate, chunk=k)
+            done += k
+            parts.append(sampler.record_fetch())
+    finally:
+        sampler.record_end()
+    if not parts or sum(len(p[0]) for p in parts) == 0:
+        e = np.empty((0,))
+        return Trace(np.empty(0, np.int64), e, e, e, e, e, e, e, e, e)
+    it, sc, H, R, post, beta = (np.concatenate([p[i] for p in parts]) for i in range(6))
+    return Trace(base + it, sc[..., 0], sc[..., 1], sc[..., 2], H, sc[..., 3], sc[..., 4], R, post, beta)
+
+
+def prior_components(prior, trace: Trace, piece: int = 1 << 16) -> np.ndarray:
+    """The three prior blocks (node priors, birth-death, clock) of ALL samples of all chains, [n_samples, B, 3], by batched
+    evaluations of the device prior over samples x chains (at most `piece` states per call) instead of one per sample and chain."""
+    n, B = trace.heights.shape[:2]
+    flat = StateBatch(trace.heights.reshape(n * B, -1), trace.rates.reshape(n * B, -1), trace.time_height.reshape(-1), trace.rate_mean.reshape(-1),
+                      trace.time_birth_rate.reshape(-1), trace.time_death_rate.reshape(-1), trace.rate_variance.reshape(-1))
+    out = np.empty((n * B, 3))
+    for lo in range(0, n * B, piece):
+        hi = min(n * B, lo + piece)
+        out[lo:hi] = prior.logprior(flat.slice(lo, hi), want_components=True)[1]
+    return out.reshape(n, B, 3)
+
+
 # ---- monitor files ---------------------------------------------------------------------------------------------------
 def _fmt(x: float) -> str:
     return repr(float(x))
 
 
 def write_monitor_files(prefix: str, trace: Trace, chain: int, topo: Topology, calibrations: Sequence = (), constraints: Sequence = (),
-                        braces: Sequence = (), prior=None) -> List[str]:
+                        braces: Sequence = (), prior=None, components: Optional[np.ndarray] = None) -> List[str]:
     """Write <prefix>.params.monitor, .timetree.monitor, .ratetree.monitor (and .prior.monitor when the device prior
-    `prior` is given) for one chain.  Returns the file names."""
+    `prior` is given, or its blocks `components` = prior_components(prior, trace), which saves the evaluation per sample) for
+    one chain.  Returns the file names."""
     files = []
     ages = trace.ages()[:, chain, :]
     names = (["TimeBirthRate", "TimeDeathRate", "TimeHeight", "RateMean", "RateVariance"]
@@ -102,7 +145,14 @@ def write_monitor_files(prefix: str, trace: Trace, chain: int, topo: Topology, c
                     lengths = trace.rates[k, chain]
                 f.write(f"{int(it)}\t{to_newick(topo, lengths)}\n")
         files.append(fn)
-    if prior is not None:
+    if components is not None:
+        fn = prefix + ".prior.monitor"
+        with open(fn, "w") as f:
+            f.write("Iteration\tPriorCsKsBs\tPriorBirthDeath\tPriorRelaxedMolecularClock\n")
+            for k, it in enumerate(trace.iteration):
+                f.write("\t".join([str(int(it))] + [_fmt(x) for x in components[k, chain]]) + "\n")
+        files.append(fn)
+    elif prior is not None:
         fn = prefix + ".prior.monitor"
         with open(fn, "w") as f:
             f.write("Iteration\tPriorCsKsBs\tPriorBirthDeath\tPriorRelaxedMolecularClock\n")

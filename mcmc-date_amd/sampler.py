@@ -344,6 +344,38 @@ class Sampler:
     def reset_age_sums(self):
         _capi.check(_capi.lib().mcd_mh_reset_age_sums(self._h))
 
+    # -- the sample recorder (mcd_mh_record_*) ------------------------------------------------------------------------------
+    def record_begin(self, period: int = 2, capacity: int = 128):
+        """Keep the state of every chain at the end of every `period`-th iteration (counted from this call) on the device, in a
+        ring of `capacity` samples; a run whose samples would not fit is refused before it starts (drain with record_fetch)."""
+        _capi.check(_capi.lib().mcd_mh_record_begin(self._h, int(period), int(capacity)))
+
+    def record_count(self) -> int:
+        """Samples waiting to be fetched."""
+        n = C.c_int64(0)
+        _capi.check(_capi.lib().mcd_mh_record_count(self._h, C.byref(n)))
+        return int(n.value)
+
+    def record_fetch(self, max_samples: Optional[int] = None):
+        """The oldest waiting samples (all of them, or at most max_samples), whose slots are free afterwards:
+        (iteration [n] counted from record_begin, scalars [n, B, 5] = birth, death, tH, rMu, rVar, heights [n, B, n_nodes],
+        rates [n, B, n_nodes], post [n, B, 3] = ln prior, ln likelihood, ln jacobianRootBranch, beta [n, B])."""
+        B, nn = self.batch, self.topo.n_nodes
+        n = self.record_count()
+        if max_samples is not None:
+            n = min(n, int(max_samples))
+        it = np.empty(n, np.int64)
+        sc, H, R, post, beta = np.empty((n, B, 5)), np.empty((n, B, nn)), np.empty((n, B, nn)), np.empty((n, B, 3)), np.empty((n, B))
+        got = C.c_int64(0)
+        _capi.check(_capi.lib().mcd_mh_record_fetch(self._h, n, C.byref(got), it.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                    *[a.ctypes.data_as(_dp) for a in (sc, H, R, post, beta)]))
+        if got.value != n:
+            raise RuntimeError(f"record_fetch: asked for {n} samples, got {got.value}")
+        return it, sc, H, R, post, beta
+
+    def record_end(self):
+        _capi.check(_capi.lib().mcd_mh_record_end(self._h))
+
     def node_age_summary(self):
         """Posterior mean and variance of every node age pooled over chains and accumulated iterations, plus the
         standard error of the mean estimated from the spread of the per-chain means."""

@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """MH proposal-steps per second of the lock-step driver (mcd_mh_*) on a golden dataset, next to the CPU twin
 (oracle/mh_oracle.c, OpenMP over chains).  BASELINE.json configs[1]: tests/12-leaves-variable-rate, 64 chains.
-One JSON line per chain count.  Usage: python tools/bench_mh.py [--name 12-leaves-variable-rate] [--chains 64,4096]"""
+One JSON line per chain count.  Usage: python tools/bench_mh.py [--name 12-leaves-variable-rate] [--chains 64,4096]
+  --synthetic N_LEAVES[:sparse]   a synthetic tree instead (tools/bench_mh_large.py's problem; no CPU twin), the whole shuffled cycle
+  --record PERIOD                 the same timed run three ways: unmonitored, with the device recorder at that period drained per chunk of
+                                  256 iterations (the drain inside the timed region; monitor.record), and cut into calls of PERIOD iterations
+                                  with a state read-back after each (monitor.collect)
+  --repeat N                      the timed region N times (every value is printed; gpu_steps_per_s and gpu_us_per_lockstep are then the
+                                  median of the N runs -- with the default N = 1 the one timed run, as before)"""
 import argparse
 import json
 import os
@@ -21,8 +27,61 @@ def main():
     ap.add_argument("--chains", default="64,4096")
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--cpu-iters", type=int, default=20)
+    ap.add_argument("--synthetic", default=None)
+    ap.add_argument("--record", type=int, default=0)
+    ap.add_argument("--repeat", type=int, default=1)
     args = ap.parse_args()
     import mcmc_date_amd as M
+
+    def timed(f):
+        t0 = time.perf_counter()
+        f()
+        return time.perf_counter() - t0
+
+    def figures(smp, S, B, n_nodes, dataset):
+        """the timed runs of one sampler: unmonitored, and with --record the recorded and the chopped loop beside it"""
+        out = {"dataset": dataset, "chains": B, "n_nodes": n_nodes, "steps_per_iteration": S, "iterations": args.iters, "path": smp.last_path()}
+        per_step = lambda dt: 1e6 * dt / (S * args.iters)
+        out["gpu_us_per_lockstep_runs"] = [per_step(timed(lambda: smp.run(args.iters))) for _ in range(args.repeat)]
+        if args.record > 0:
+            from mcmc_date_amd import monitor
+
+            rec = [timed(lambda: monitor.record(smp, args.iters, period=args.record, chunk=256)) for _ in range(args.repeat)]
+            cut = [timed(lambda: monitor.collect(smp, args.iters, period=args.record)) for _ in range(args.repeat)]
+            out.update({"record_period": args.record, "recorded_us_per_lockstep_runs": [per_step(x) for x in rec],
+                        "chopped_us_per_lockstep_runs": [per_step(x) for x in cut],
+                        "unmonitored_us_per_iteration": float(np.median(out["gpu_us_per_lockstep_runs"])) * S,
+                        "recorded_us_per_iteration": 1e6 * float(np.median(rec)) / args.iters,
+                        "chopped_us_per_iteration": 1e6 * float(np.median(cut)) / args.iters})
+        return out
+
+    if args.synthetic:
+        from mcmc_date_amd import synthetic as SY
+
+        n_leaves, _, form = args.synthetic.partition(":")
+        topo = SY.random_topology(int(n_leaves), seed=3)
+        n = topo.n_nodes - 2
+        if form == "sparse":
+            _, assoc = SY.banded_precision(n, seed=3)
+            lik = M.SparseLikelihood(M.Sparse(np.random.default_rng(3).uniform(0.01, 0.2, n), assoc, 0.0)).bind_tree(topo)
+        else:
+            mu, sigma = SY.random_spd_problem(n, seed=3)
+            lik = M.MvnLikelihood.from_covariance(mu, sigma).bind_tree(topo)
+        pf = M.PriorFunction(1.0, "UncorrelatedGamma", [], [], [], topo)
+        ps, _ = M.proposals(topo, [], calibrations_available=True)
+        S = sum(p.weight for p in ps)
+        for B in [int(x) for x in args.chains.split(",")]:
+            s0 = SY.random_states(topo, B, seed=4)
+            s0.time_birth_rate = np.full(B, 1.0); s0.time_death_rate = np.full(B, 0.8); s0.rate_variance = np.full(B, 0.3)
+            smp = M.Sampler(lik, pf, ps, B, seed=13)
+            smp.set_state(s0)
+            smp.run(2)
+            smp.autotune()
+            smp.run(1)
+            r = figures(smp, S, B, topo.n_nodes, f"synthetic {n_leaves} leaves, {form or 'dense'}")
+            r["gpu_us_per_lockstep"] = float(np.median(r["gpu_us_per_lockstep_runs"]))
+            print(json.dumps({"metric": "MH lock step (us), synthetic tree", **r}), flush=True)
+        return
     import oracle as O
     from test_gpu_mh import setup
 
@@ -32,9 +91,8 @@ def main():
         S = sum(p.weight for p in ps)
         smp.run(20)
         smp.autotune()
-        t0 = time.perf_counter()
-        smp.run(args.iters)
-        dt = time.perf_counter() - t0
+        extra = figures(smp, S, B, topo.n_nodes, args.name)
+        dt = float(np.median(extra["gpu_us_per_lockstep_runs"])) * 1e-6 * S * args.iters
         rng = np.random.default_rng(0)
         twin.run(M.cycle_schedule(ps, 2, rng))
         t1 = time.perf_counter()
@@ -42,7 +100,8 @@ def main():
         dc = time.perf_counter() - t1
         print(json.dumps({"metric": "MH proposal steps/sec (chains x steps)", "dataset": args.name, "chains": B, "n_nodes": topo.n_nodes,
                           "steps_per_iteration": S, "gpu_steps_per_s": B * S * args.iters / dt, "gpu_us_per_lockstep": 1e6 * dt / (S * args.iters),
-                          "cpu_twin_steps_per_s": B * S * args.cpu_iters / dc, "cpu_threads": os.cpu_count()}), flush=True)
+                          "cpu_twin_steps_per_s": B * S * args.cpu_iters / dc, "cpu_threads": os.cpu_count(),
+                          **{k: v for k, v in extra.items() if k.endswith("_runs") or "record" in k or k.endswith("_per_iteration") or k == "path"}}), flush=True)
 
 
 if __name__ == "__main__":
