@@ -22,6 +22,8 @@
 --   * 'runRecorded' is the same loop without the cut at every monitor period: the device keeps the samples while a chunk of
 --     iterations runs in ONE @mcd_mh_run@ (@mcd_mh_record_begin@ / @_fetch@ / @_end@), and the monitor action is called from the
 --     fetched samples, one @mcd_mh_record_fetch@ per chunk instead of one @mcd_mh_get_state@ per two iterations;
+--   * 'recordSummary' asks the device for the node-age summary, split R-hat and effective sample size of the samples the recorder
+--     holds (@mcd_mh_record_summary@) instead of fetching them;
 --   * 'runMc3Gpu' is @mc3 (MC3Settings (NChains 4) (SwapPeriod 2) (NSwaps 3))@ (app/Main.hs:476-478): @mcd_mh_mc3_init@, per swap
 --     period @mcd_mh_run@ + @mcd_mh_mc3_swap@, the monitors read the chains whose temperature rank is 0 (@mcd_mh_mc3_get@).
 --
@@ -38,6 +40,7 @@ module McmcDate.GpuSampler
     withGpuSampler,
     runMetropolisHastingsGreenGpu,
     runRecorded,
+    recordSummary,
     runMc3Gpu,
     nodeAgeSummary,
   )
@@ -137,6 +140,13 @@ foreign import ccall unsafe "mcd_mh_record_fetch"
 
 foreign import ccall unsafe "mcd_mh_record_end"
   c_mh_record_end :: Ptr McdMh -> IO CInt
+
+foreign import ccall unsafe "mcd_mh_record_quantities"
+  c_mh_record_quantities :: Ptr McdMh -> Ptr Int64 -> IO CInt
+
+-- (safe: several passes over the whole ring)
+foreign import ccall safe "mcd_mh_record_summary"
+  c_mh_record_summary :: Ptr McdMh -> Int64 -> Int64 -> Int32 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> IO CInt
 
 check :: String -> CInt -> IO ()
 check _ 0 = pure ()
@@ -449,6 +459,27 @@ runRecorded s g burnInPeriods iterations period chunk onSample = do
           [ pourState s (\f -> realToFrac (scv VS.! ((k * b + i) * 5 + f))) (VS.slice ((k * b + i) * nn) nn hv) (VS.slice ((k * b + i) * nn) nn rv)
             | i <- [0 .. b - 1]
           ]
+
+-- | Posterior summaries and convergence diagnostics of the samples waiting in the recorder, computed on the device where they lie
+-- (@mcd_mh_record_summary@; call it between @mcd_mh_record_begin@ and @_end@, e.g. from a variant of 'runRecorded' that fetches
+-- nothing): the samples @[skip, skip + n)@ (all after @skip@ when @n < 0@), the lag cap @maxLag@ of the effective sample size (odd, at
+-- most 255 and half the window less one; 0: none).  Returns the number of samples used and, per quantity -- ages @tH * h_v@ per node,
+-- rates per node, birth, death, tH, rMu, rVar, ln prior, ln likelihood, ln jacobianRootBranch, ln posterior -- the nine columns mean,
+-- maximum-likelihood variance, minimum, maximum, the two order statistics of the 95 % interval of
+-- @scripts/trees-monitor-summary-ultrametric@, split R-hat, effective sample size, last lag of Geyer's sum.
+recordSummary :: GpuSampler -> Int -> Int -> Int -> IO (Int, [[Double]])
+recordSummary s skip n maxLag = do
+  q <- alloca $ \pq -> do
+    check "mcd_mh_record_quantities" =<< c_mh_record_quantities (gsHandle s) pq
+    fromIntegral <$> peek pq
+  out <- VSM.new (q * 9)
+  used <- alloca $ \pn -> do
+    VSM.unsafeWith out $ \po ->
+      check "mcd_mh_record_summary"
+        =<< c_mh_record_summary (gsHandle s) (fromIntegral skip) (fromIntegral n) (fromIntegral maxLag) pn po nullPtr
+    fromIntegral <$> peek pn
+  v <- VS.freeze out
+  pure (used, [[realToFrac (v VS.! (i * 9 + j)) | j <- [0 .. 8]] | i <- [0 .. q - 1]])
 
 -- | @mc3 (MC3Settings (NChains nChains) (SwapPeriod swapPeriod) (NSwaps nSwaps))@ (app/Main.hs:476-478) over the same driver: the
 -- global set of chains is cut into groups of @nChains@ consecutive chains with the ladder of reciprocal temperatures @betas@ (head = 1);

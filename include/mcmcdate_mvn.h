@@ -459,6 +459,45 @@ int mcd_mh_record_count(const mcd_mh_t* m, int64_t* n_samples);
 int mcd_mh_record_fetch(mcd_mh_t* m, int64_t max_samples, int64_t* n_out, int64_t* iteration, double* scalars, double* heights, double* rates,
                         double* post, double* beta);
 int mcd_mh_record_end(mcd_mh_t* m);
+/*
+ * Posterior summaries and convergence diagnostics of a trace, computed on the device (k_summary.hip).  Replaces: the node-age summary of
+ * scripts/trees-monitor-summary-ultrametric:149-175 (mean, maximum-likelihood variance, minimum, maximum and the 95 % interval per node)
+ * without fetching a sample, and what the reference leaves to Tracer on its one chain: split R-hat and the effective sample size over
+ * the lock-step chains.  A trace is n samples x batch chains x q quantities; with l = n batch pooled values, per quantity (pooled[q][9]):
+ *   0 mean, 1 variance (/ l; two passes, never sum x^2 - (sum x)^2 / l), 2 minimum, 3 maximum,
+ *   4, 5  sorted[i] and sorted[i + m - 1], i = floor(0.025 l), m = floor(0.95 l): EXACT, elements of the input (radix select),
+ *   6 split R-hat: the oldest sample is dropped if n is odd, every chain is halved into M = 2 batch sequences of n_h = n / 2 samples;
+ *     W = mean of their unbiased variances, Bv = n_h x unbiased variance of their means, var+ = (n_h - 1) / n_h W + Bv / n_h,
+ *     rhat = sqrt(var+ / W),
+ *   7 effective sample size on the same sequences: gamma_{m,t} = 1 / n_h sum_i (x_i - mean_m)(x_{i+t} - mean_m),
+ *     rho_t = 1 - (W - mean_m gamma_{m,t}) / var+, P_k = rho_{2k} + rho_{2k+1}; tau = -1 + 2 sum_k min(P_k, P_{k-1}) while P_k > 0 and
+ *     2 k + 1 <= max_lag; tau = max(tau, 1 / log10(M n_h)); ess = M n_h / tau,
+ *   8 the last lag that entered that sum (-1: none); equal to max_lag: the cap ended the sum, not Geyer's rule.
+ * per_chain[batch][q][4] (may be NULL): mean, unbiased variance (/ (n - 1)), minimum, maximum of every chain.
+ * max_lag: odd, 1 .. min(MCD_SUMMARY_MAX_LAG, n_h - 1); 0: no effective sample size (7 and 8 are NaN).  n batch must lie in [2, 2^32).
+ * A constant sequence or chain has the variance 0 exactly, whatever the rounding of its mean.
+ * A quantity with W = 0 or var+ = 0 (a leaf's age, the root's height) or n_h < 2 has rhat = ess = last lag = NaN.  A NaN anywhere in a
+ * quantity makes every output of that quantity NaN and touches no other quantity; +-inf are ordered as numbers; which of -0.0 and +0.0
+ * is the smaller is unspecified.  No floating-point atomics and a fixed order of every sum: two calls on the same data return the same bits.
+ *   mcd_trace_summary         a plain array X[n][batch][ldq], ldq >= q, on the host (copied) or on device device_id (read in place).
+ *   mcd_mh_record_quantities  q = 2 n_nodes + 9 of the call below, in the order: ages tH h_v [n_nodes] (one fp64 multiply), rates
+ *                             [n_nodes], birth, death, tH, rMu, rVar, ln prior, ln likelihood, ln jacobianRootBranch,
+ *                             ln posterior = (ln prior + ln likelihood) + ln jacobianRootBranch.
+ *   mcd_mh_record_summary     waits for the handle's stream and summarises the waiting samples [skip, skip + n_samples) of the recorder
+ *                             (n_samples < 0: all after skip; *n_used = their number), read in the ring where they lie -- also where the
+ *                             window wraps around its end.  Frees no slot and changes nothing that a later mcd_mh_record_fetch,
+ *                             mcd_mh_run or mcd_mh_get_* can see.  Refused before any launch, the handle untouched: no active recorder,
+ *                             skip at or beyond the waiting count, a window past it, a bad max_lag (MCD_ERR_INVALID_ARG); MC3 initialised
+ *                             on the handle or a temperature other than 1 (MCD_ERR_UNSUPPORTED: under MC3 the temperatures wander
+ *                             between the chains, so a chain is not a cold sequence; pooling the cold samples by the recorded beta is
+ *                             left for later).
+ */
+#define MCD_SUMMARY_COLS 9
+#define MCD_SUMMARY_MAX_LAG 255 /* four waves of 64 lags each share one sliding window of 256 + 32 rows in LDS */
+int mcd_trace_summary(int64_t n, int64_t batch, int64_t q, int64_t ldq, const double* X, int on_device, int device_id, int32_t max_lag,
+                      double* pooled, double* per_chain);
+int mcd_mh_record_quantities(const mcd_mh_t* m, int64_t* q);
+int mcd_mh_record_summary(mcd_mh_t* m, int64_t skip, int64_t n_samples, int32_t max_lag, int64_t* n_used, double* pooled, double* per_chain);
 
 /* ------------------------------------------------------------------------------------------------
  * The sparse form: the precision matrix as it is, in CSR on the device, no densification; N up to MCD_MAX_SPARSE_DIM.

@@ -19,6 +19,8 @@ MCD_ERR_HIP = -3
 MCD_ERR_ROOT_NOT_BIFURCATING = -4
 MCD_ERR_NO_DEVICE = -5
 MCD_ERR_UNSUPPORTED = -6
+MCD_SUMMARY_COLS = 9
+MCD_SUMMARY_MAX_LAG = 255
 MCD_MAT_SIGMA = 0
 MCD_MAT_SIGMA_INV = 1
 
@@ -108,6 +110,9 @@ SYMBOLS = {
     "mcd_mh_record_count": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "mcd_mh_record_fetch": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _dp, _dp, _dp, _dp, _dp]),
     "mcd_mh_record_end": (C.c_int, [_vp]),
+    "mcd_trace_summary": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, C.c_int, C.c_int, C.c_int32, _dp, _dp]),
+    "mcd_mh_record_quantities": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    "mcd_mh_record_summary": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64), _dp, _dp]),
 }
 
 

@@ -15,7 +15,10 @@
 #include "../../include/mcmcdate_mvn.h"
 #include "mvn_kernels.h"
 #include "options.h"
+#include "summary_device.hpp"
 
+int mcd_summary_check_(const char* who, int64_t n, int64_t batch, int64_t q, int32_t max_lag);                       // summary_capi.cpp
+int mcd_summary_run_(const mcd::SumSrc& S, int32_t max_lag, hipStream_t st, double* pooled, double* per_chain);
 extern "C" int mcd_set_last_error_(int code, const char* msg);   // mvn_capi.cpp
 struct mcd_sparse;
 struct mcd_sparse_tree;
@@ -1214,6 +1217,54 @@ int mcd_mh_record_end(mcd_mh_t* m)
     m->d_rec = m->d_rec_stage = nullptr;
     m->rec_cap = m->rec_stage_cap = m->rec_iter = m->rec_fetched = 0;
     m->rec_period = 0;
+    return MCD_OK;
+}
+
+// ---- summaries of the waiting samples, read in the ring (k_summary.hip) -------------------------------------------------------------------
+int mcd_mh_record_quantities(const mcd_mh_t* m, int64_t* q)
+{
+    if (!m || !q) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_quantities: NULL argument");
+    *q = 2 * (int64_t)m->dev.n_nodes + 9;
+    return MCD_OK;
+}
+
+int mcd_mh_record_summary(mcd_mh_t* m, int64_t skip, int64_t n_samples, int32_t max_lag, int64_t* n_used, double* pooled, double* per_chain)
+{
+    if (!m || !pooled) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_summary: NULL argument");
+    if (n_used) *n_used = 0;
+    if (!m->d_rec) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_summary: no recorder is active (mcd_mh_record_begin first)");
+    const mcd::MhDev& D = m->dev;
+    const int64_t waiting = m->rec_filled();
+    if (skip < 0 || skip >= waiting)
+        return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_summary: skip = %lld, %lld samples are waiting", (long long)skip, (long long)waiting);
+    const int64_t n = n_samples < 0 ? waiting - skip : n_samples;
+    if (n < 1 || n > waiting - skip)
+        return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_summary: the window [%lld, %lld) ends past the %lld waiting samples", (long long)skip,
+                     (long long)(skip + n), (long long)waiting);
+    const int64_t Q = 2 * (int64_t)D.n_nodes + 9;
+    if (int rc = mcd_summary_check_("mcd_mh_record_summary", n, D.batch, Q, max_lag)) return rc;
+    if (m->mc3.n_chains != 0)
+        return mfail(MCD_ERR_UNSUPPORTED, "mcd_mh_record_summary: Metropolis-coupled MCMC is initialised on this handle: its temperatures wander between the chains, so a chain is not a cold sequence");
+    MHIP_TRY(hipSetDevice(m->device));
+    MHIP_TRY(hipStreamSynchronize(m->stream));
+    std::vector<double> beta((size_t)D.batch);
+    MHIP_TRY(hipMemcpy(beta.data(), D.beta, sizeof(double) * beta.size(), hipMemcpyDeviceToHost));
+    for (int64_t b = 0; b < D.batch; ++b)
+        if (beta[(size_t)b] != 1.0)
+            return mfail(MCD_ERR_UNSUPPORTED, "mcd_mh_record_summary: chain %lld has the reciprocal temperature %g: only cold chains (1) are summarised", (long long)b, beta[(size_t)b]);
+    mcd::SumSrc S{};
+    S.base = m->d_rec;
+    S.n = n;
+    S.B = D.batch;
+    S.Q = Q;
+    S.ring = 1;
+    S.n_nodes = D.n_nodes;
+    S.first = (m->rec_fetched + skip) % m->rec_cap;            // sample number k (1, 2, ...) lies in slot (k - 1) mod capacity
+    S.cap = m->rec_cap;
+    S.stride = mcd::mh_rec_stride(D.ld);
+    S.ld = D.ld;
+    if (int rc = mcd_summary_run_(S, max_lag, m->stream, pooled, per_chain)) return rc;
+    if (n_used) *n_used = n;
     return MCD_OK;
 }
 

@@ -1,0 +1,182 @@
+"""Posterior summaries and convergence diagnostics of a trace x[n samples, B chains, Q quantities].
+
+Two things live here:
+  * a plain-numpy restatement of the definitions of include/mcmcdate_mvn.h (mcd_trace_summary) -- `split_rhat`, `ess`, `summary` --: the host
+    mirror of csrc/k_summary.hip and the reference of its tests;
+  * `trace_summary`: the same numbers from the device kernels, through the C ABI.
+
+Definitions, with l = n B pooled values per quantity:
+  mean, variance (maximum likelihood, / l), minimum, maximum, and the two order statistics of monitor.summarize_node_ages,
+  sorted[i] and sorted[i + m - 1] with i = floor(0.025 l), m = floor(0.95 l);
+  split R-hat (Gelman et al., BDA3 11.4; Vehtari et al. 2021): the oldest sample is dropped if n is odd, every chain is halved into
+  M = 2 B sequences of n_h = n // 2 samples; W = mean of their unbiased variances, Bv = n_h x unbiased variance of their means,
+  var+ = (n_h - 1) / n_h W + Bv / n_h, rhat = sqrt(var+ / W);
+  effective sample size on the same sequences: gamma_{m,t} = 1 / n_h sum_i (x_i - mean_m)(x_{i+t} - mean_m),
+  rho_t = 1 - (W - mean_m gamma_{m,t}) / var+, P_k = rho_{2k} + rho_{2k+1}; tau = -1 + 2 sum_k min(P_k, P_{k-1}) while P_k > 0 and
+  2 k + 1 <= max_lag (Geyer's initial monotone sequence); tau = max(tau, 1 / log10(M n_h)); ess = M n_h / tau.
+A constant sequence has the variance 0 exactly.  W = 0, var+ = 0 or n_h < 2: rhat = ess = NaN.  A NaN anywhere in a quantity makes every output of that quantity NaN.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+
+from . import _capi
+
+COLUMNS = ("mean", "variance", "minimum", "maximum", "ci_lower", "ci_upper", "rhat", "ess", "last_lag")
+
+
+def _split(x: np.ndarray) -> np.ndarray:
+    """[n, B, ...] -> the split sequences [n_h, 2 B, ...]; sequence 2 b + h is half h of chain b."""
+    n = x.shape[0]
+    nh = n // 2
+    x = x[n - 2 * nh:]
+    halves = np.stack([x[:nh], x[nh:]], axis=2)                       # [n_h, B, 2, ...]
+    return halves.reshape((nh, 2 * x.shape[1]) + x.shape[2:])
+
+
+def _var(x: np.ndarray, ddof: int) -> np.ndarray:
+    """Variance along axis 0; a constant sequence has the variance 0 exactly, whatever the rounding of its mean."""
+    return np.where(x.max(axis=0) == x.min(axis=0), 0.0, x.var(axis=0, ddof=ddof))
+
+
+def _w_varp(seq: np.ndarray):
+    nh = seq.shape[0]
+    means = seq.mean(axis=0)
+    w = _var(seq, 1).mean(axis=0)
+    bv = nh * means.var(axis=0, ddof=1)
+    return means, w, (nh - 1) / nh * w + bv / nh
+
+
+def _degenerate(w, varp):
+    return ~np.isfinite(w) | ~np.isfinite(varp) | (w == 0) | (varp == 0)
+
+
+def split_rhat(x: np.ndarray) -> np.ndarray:
+    """x [n, B] or [n, B, Q] -> rhat (scalar array or [Q])."""
+    x = np.asarray(x, dtype=np.float64)
+    shape = x.shape[2:]
+    if x.shape[0] // 2 < 2:
+        return np.full(shape, np.nan)
+    with np.errstate(all="ignore"):
+        _, w, varp = _w_varp(_split(x))
+        r = np.sqrt(varp / w)
+    return np.where(_degenerate(w, varp), np.nan, r)
+
+
+def ess(x: np.ndarray, max_lag: int, details: bool = False):
+    """x [n, B] or [n, B, Q] -> ess; details: (ess, last lag that entered the sum (-1: none), smallest |P_k| examined)."""
+    x = np.asarray(x, dtype=np.float64)
+    flat = x.reshape(x.shape[0], x.shape[1], -1)
+    Q = flat.shape[2]
+    nh = flat.shape[0] // 2
+    out, last, pmin = np.full(Q, np.nan), np.full(Q, np.nan), np.full(Q, np.inf)
+    if max_lag % 2 != 1 or not 1 <= max_lag <= nh - 1:
+        raise ValueError("ess: max_lag must be odd and 1 <= max_lag <= n // 2 - 1")
+    seq = _split(flat)
+    M = seq.shape[1]
+    with np.errstate(all="ignore"):
+        means, w, varp = _w_varp(seq)
+        c = seq - means
+        g = np.stack([(c[:nh - t] * c[t:]).sum(axis=0).mean(axis=0) / nh for t in range(max_lag + 1)])     # [lags, Q]
+        rho = 1.0 - (w - g) / varp
+    bad = _degenerate(w, varp)
+    for q in range(Q):
+        if bad[q]:
+            continue
+        tau, prev, lag = -1.0, math.inf, -1.0
+        k = 0
+        while 2 * k + 1 <= max_lag:
+            p = rho[2 * k, q] + rho[2 * k + 1, q]
+            pmin[q] = min(pmin[q], abs(p))
+            if not p > 0:
+                break
+            p = min(p, prev)
+            tau += 2.0 * p
+            prev = p
+            lag = 2.0 * k + 1
+            k += 1
+        tau = max(tau, 1.0 / math.log10(M * nh))
+        out[q] = M * nh / tau
+        last[q] = lag
+    shape = x.shape[2:]
+    if details:
+        return out.reshape(shape), last.reshape(shape), pmin.reshape(shape)
+    return out.reshape(shape)
+
+
+@dataclass
+class Summary:
+    """pooled [Q, 9] in the order of COLUMNS; per_chain [B, Q, 4] = mean, unbiased variance, minimum, maximum (or None);
+    min_abs_p [Q]: the smallest |P_k| the effective sample size examined (host mirror only: how close a stop of Geyer's rule was)."""
+    pooled: np.ndarray
+    per_chain: Optional[np.ndarray] = None
+    min_abs_p: Optional[np.ndarray] = None
+
+    def __getattr__(self, name):
+        if name in COLUMNS:
+            return self.pooled[..., COLUMNS.index(name)]
+        raise AttributeError(name)
+
+
+def summary(x: np.ndarray, max_lag: int = 0, per_chain: bool = True) -> Summary:
+    """The host restatement of mcd_trace_summary on x [n, B, Q]."""
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim != 3:
+        raise ValueError("summary: expected [n, B, Q]")
+    n, B, Q = x.shape
+    l = n * B
+    i_ci, n_ci = int(math.floor(l * 0.025)), int(math.floor(l * 0.95))
+    if n_ci < 1:
+        raise ValueError("summary: too few samples for the 95 % interval")
+    pooled = np.full((Q, len(COLUMNS)), np.nan)
+    flat = x.reshape(l, Q)
+    nan = np.isnan(flat).any(axis=0)
+    with np.errstate(all="ignore"):
+        srt = np.sort(flat, axis=0)
+        pooled[:, 0] = flat.mean(axis=0)
+        pooled[:, 1] = flat.var(axis=0)
+        pooled[:, 2], pooled[:, 3], pooled[:, 4], pooled[:, 5] = srt[0], srt[-1], srt[i_ci], srt[i_ci + n_ci - 1]
+        pooled[:, 6] = split_rhat(x)
+        pmin = np.full(Q, np.inf)
+        if max_lag and n // 2 >= 2:
+            pooled[:, 7], pooled[:, 8], pmin = ess(x, max_lag, details=True)
+        pc = None
+        if per_chain:
+            pc = np.stack([x.mean(axis=0), _var(x, 1) if n > 1 else np.full((B, Q), np.nan), x.min(axis=0), x.max(axis=0)], axis=2)
+            pc[:, nan, :] = np.nan
+    pooled[nan, :] = np.nan
+    return Summary(pooled, pc, pmin)
+
+
+def trace_summary(X, max_lag: int = 0, device=True, per_chain: bool = True, q: Optional[int] = None) -> Summary:
+    """mcd_trace_summary on X [n, B, ldq]: a numpy array (copied to device 0, or to device `device` if that is an int) or a torch
+    tensor on a GPU (read in place).  q: the quantities summarised (default: all ldq of them).  There is no host path: `device` False
+    is refused -- the host restatement is `summary`."""
+    if device is False:
+        raise ValueError("trace_summary: the kernels run on the device; diagnostics.summary is the host restatement")
+    on_device = hasattr(X, "data_ptr")
+    if on_device:
+        if not X.is_cuda or not X.is_contiguous() or str(X.dtype) != "torch.float64" or X.dim() != 3:
+            raise ValueError("trace_summary: expected a contiguous float64 GPU tensor [n, B, ldq]")
+        ptr, dev = C.c_void_p(X.data_ptr()), X.device.index or 0
+        import torch
+
+        torch.cuda.current_stream(X.device).synchronize()
+    else:
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        if X.ndim != 3:
+            raise ValueError("trace_summary: expected [n, B, ldq]")
+        ptr, dev = C.c_void_p(X.ctypes.data), 0 if device is True else int(device)
+    n, B, ldq = (int(s) for s in X.shape)
+    Q = ldq if q is None else int(q)
+    pooled = np.empty((max(Q, 0), len(COLUMNS)))
+    pc = np.empty((B, max(Q, 0), 4)) if per_chain else None
+    dp = C.POINTER(C.c_double)
+    _capi.check(_capi.lib().mcd_trace_summary(n, B, Q, ldq, ptr, int(on_device), dev, int(max_lag), pooled.ctypes.data_as(dp),
+                                              pc.ctypes.data_as(dp) if per_chain else None))
+    return Summary(pooled, pc)

@@ -376,6 +376,23 @@ class Sampler:
     def record_end(self):
         _capi.check(_capi.lib().mcd_mh_record_end(self._h))
 
+    def record_summary(self, skip: int = 0, n: Optional[int] = None, max_lag: int = 255, per_chain: bool = False) -> "RecordSummary":
+        """Posterior summaries and convergence diagnostics of the waiting samples [skip, skip + n) (n None: all after skip), computed on the
+        device from the ring where they lie (mcd_mh_record_summary): nothing is fetched and no slot is freed.  max_lag: the lag cap of the
+        effective sample size, lowered to what the window allows (odd, at most n // 2 - 1; 0 when the window is shorter than 4 samples)."""
+        Q = C.c_int64(0)
+        _capi.check(_capi.lib().mcd_mh_record_quantities(self._h, C.byref(Q)))
+        Q = int(Q.value)
+        count = self.record_count() - int(skip) if n is None else int(n)
+        lag = min(int(max_lag), max(count, 0) // 2 - 1)
+        lag = max(0, lag if lag % 2 == 1 else lag - 1)
+        pooled = np.empty((Q, _capi.MCD_SUMMARY_COLS))
+        pc = np.empty((self.batch, Q, 4)) if per_chain else None
+        used = C.c_int64(0)
+        _capi.check(_capi.lib().mcd_mh_record_summary(self._h, int(skip), -1 if n is None else int(n), lag, C.byref(used), pooled.ctypes.data_as(_dp),
+                                                      pc.ctypes.data_as(_dp) if per_chain else None))
+        return RecordSummary(pooled, self.topo.n_nodes, int(used.value), lag, pc)
+
     def node_age_summary(self):
         """Posterior mean and variance of every node age pooled over chains and accumulated iterations, plus the
         standard error of the mean estimated from the spread of the per-chain means."""
@@ -387,6 +404,40 @@ class Sampler:
         var = q.sum(axis=0) / (n * self.batch) - mean * mean
         sem = per_chain.std(axis=0, ddof=1) / math.sqrt(self.batch) if self.batch > 1 else np.full_like(mean, np.nan)
         return mean, var, sem
+
+
+@dataclass
+class RecordSummary:
+    """What Sampler.record_summary returns: pooled [2 n_nodes + 9, 9] with the columns of diagnostics.COLUMNS (mean, variance, minimum,
+    maximum, ci_lower, ci_upper, rhat, ess, last_lag) and the quantities in the order ages, rates, the five scalars, ln prior, ln
+    likelihood, ln jacobianRootBranch, ln posterior; per_chain [B, Q, 4] = mean, unbiased variance, minimum, maximum, or None."""
+    pooled: np.ndarray
+    n_nodes: int
+    n_samples: int
+    max_lag: int
+    per_chain: Optional[np.ndarray] = None
+
+    SCALARS = ("time_birth_rate", "time_death_rate", "time_height", "rate_mean", "rate_variance")
+    POST = ("ln_prior", "ln_likelihood", "ln_jacobian_root_branch", "ln_posterior")
+
+    @property
+    def ages(self) -> np.ndarray:
+        """[n_nodes, 9]: the absolute node ages tH * h_v."""
+        return self.pooled[:self.n_nodes]
+
+    @property
+    def rates(self) -> np.ndarray:
+        return self.pooled[self.n_nodes:2 * self.n_nodes]
+
+    @property
+    def scalars(self) -> np.ndarray:
+        """[5, 9]: birth, death, tH, rMu, rVar."""
+        return self.pooled[2 * self.n_nodes:2 * self.n_nodes + 5]
+
+    @property
+    def post(self) -> np.ndarray:
+        """[4, 9]: ln prior, ln likelihood, ln jacobianRootBranch, ln posterior."""
+        return self.pooled[2 * self.n_nodes + 5:]
 
 
 # ---- Metropolis-coupled MCMC -- `mc3 (MC3Settings (NChains 4) (SwapPeriod 2) (NSwaps 3))`, app/Main.hs:476-478 -----------

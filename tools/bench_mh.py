@@ -6,6 +6,10 @@ One JSON line per chain count.  Usage: python tools/bench_mh.py [--name 12-leave
   --record PERIOD                 the same timed run three ways: unmonitored, with the device recorder at that period drained per chunk of
                                   256 iterations (the drain inside the timed region; monitor.record), and cut into calls of PERIOD iterations
                                   with a state read-back after each (monitor.collect)
+  --summary WINDOW                after the timed runs, WINDOW samples are recorded (period 1, a short random schedule) and the node-age summary
+                                  of that window is taken two ways on the same samples, each timed: (b) Sampler.record_summary, on the device
+                                  in the ring (all quantities, with rhat and ess, lag cap 255); (a) record_fetch of the window +
+                                  monitor.summarize_node_ages on the host (ages only).  (b) runs first: the fetch frees the slots.
   --repeat N                      the timed region N times (every value is printed; gpu_steps_per_s and gpu_us_per_lockstep are then the
                                   median of the N runs -- with the default N = 1 the one timed run, as before)"""
 import argparse
@@ -30,6 +34,7 @@ def main():
     ap.add_argument("--synthetic", default=None)
     ap.add_argument("--record", type=int, default=0)
     ap.add_argument("--repeat", type=int, default=1)
+    ap.add_argument("--summary", type=int, default=0)
     args = ap.parse_args()
     import mcmc_date_amd as M
 
@@ -53,6 +58,26 @@ def main():
                         "unmonitored_us_per_iteration": float(np.median(out["gpu_us_per_lockstep_runs"])) * S,
                         "recorded_us_per_iteration": 1e6 * float(np.median(rec)) / args.iters,
                         "chopped_us_per_iteration": 1e6 * float(np.median(cut)) / args.iters})
+        if args.summary > 0:
+            from mcmc_date_amd import monitor
+
+            window = args.summary
+            sched = np.random.default_rng(5).integers(0, len(smp.table), size=(window, 8)).astype(np.int32)   # 8 steps per sample: the run is not what is timed
+            smp.record_begin(1, window)
+            smp.run_schedule(sched)
+            smp.record_summary(max_lag=1)                                            # (first call: code object load)
+            got = []
+            t_dev = [timed(lambda: got.append(smp.record_summary(max_lag=255))) for _ in range(max(args.repeat, 1))]
+            fetched = []
+            t_fetch = timed(lambda: fetched.append(smp.record_fetch()))
+            it, sc, H = fetched[0][:3]
+            host = []
+            t_host = timed(lambda: host.append(monitor.summarize_node_ages((sc[:, :, 2][:, :, None] * H).reshape(-1, n_nodes), burn_in=0.0)))
+            smp.record_end()
+            same = bool(np.array_equal(got[-1].ages[:, 2:6], np.stack([host[0].minimum, host[0].maximum, host[0].ci_lower, host[0].ci_upper], axis=1)))
+            out.update({"summary_window_samples": window, "summary_window_bytes": int(window * B * (2 * n_nodes + 9) * 8),
+                        "summary_max_lag": got[-1].max_lag, "device_summary_s_runs": t_dev, "host_fetch_s": t_fetch, "host_summarize_s": t_host,
+                        "host_total_s": t_fetch + t_host, "device_summary_s": float(np.median(t_dev)), "order_statistics_equal": same})
         return out
 
     if args.synthetic:
@@ -101,7 +126,7 @@ def main():
         print(json.dumps({"metric": "MH proposal steps/sec (chains x steps)", "dataset": args.name, "chains": B, "n_nodes": topo.n_nodes,
                           "steps_per_iteration": S, "gpu_steps_per_s": B * S * args.iters / dt, "gpu_us_per_lockstep": 1e6 * dt / (S * args.iters),
                           "cpu_twin_steps_per_s": B * S * args.cpu_iters / dc, "cpu_threads": os.cpu_count(),
-                          **{k: v for k, v in extra.items() if k.endswith("_runs") or "record" in k or k.endswith("_per_iteration") or k == "path"}}), flush=True)
+                          **{k: v for k, v in extra.items() if k.endswith("_runs") or "record" in k or "summary" in k or k.startswith("host_") or k.startswith("order_") or k.endswith("_per_iteration") or k == "path"}}), flush=True)
 
 
 if __name__ == "__main__":
