@@ -92,7 +92,8 @@ const char* mcd_last_error(void);
  * "MCD_SPLIT_SCATTER", "MCD_SPLIT_NOROT", "MCD_SPLIT_PROBE", "MCD_GEOM", "MCD_WIDE_CT", "MCD_SPARSE_QUAD", "MCD_MH_PRIOR_WAVES", "MCD_LOADERS",
  * "MCD_MH_SEG_TAIL" (0: a dense proposal after a segment is proposed by the step kernel), "MCD_MH_AHEAD_FROM" (nodes from which a segment's chain
  * wave draws the next proposal ahead of the decision), "MCD_MH_PRIOR_DRAWS" (0: no prior wave draws the next proposal's rejected branch),
- * "MCD_FSTREAM" (the column sweep's forward factor stream at 129 .. 256 dimensions: 0 = padded, 1 = compact, 2 = compact by LDS-DMA); value = a decimal integer, NULL or ""
+ * "MCD_FSTREAM" (the column sweep's forward factor stream at 129 .. 256 dimensions: 0 = padded, 1 = compact, 2 = compact by LDS-DMA),
+ * "MCD_SPARSE_GRAD_CHAINS" (1 | 2: chains per workgroup of mcd_sparse_tree_grad_batch; the same bits); value = a decimal integer, NULL or ""
  * = back to the default.  What each knob does is said where it acts (mcd_mh_run, the forms above).  The environment variables of the same
  * names are read ONCE, when the library is loaded, as initial values -- never afterwards.  No knob changes a result beyond rounding.
  */
@@ -226,6 +227,7 @@ int mcd_prior_logprior_batch(const mcd_prior_t* p, const double* birth, const do
  * g_rates[.][0] = 0).  Outside the support (ln prior = -inf or NaN) every gradient entry of that chain is NaN.  In the
  * near-critical regime of the birth-death prior (|birth - death| < 1e-6, BirthDeath.hs:117-118) the gradient is the one
  * of the exact formulas at the edge of that regime (relative deviation O(1e-6) from the first-order value's derivative).
+ * Trees of up to 2048 nodes (MCD_ERR_UNSUPPORTED beyond: the kernel keeps 7 n_nodes + 2 doubles in LDS).
  */
 int mcd_prior_grad_batch(const mcd_prior_t* p, const double* birth, const double* death, const double* tH,
                          const double* heights, const double* rMu, const double* rVar, const double* rates,
@@ -511,8 +513,9 @@ int mcd_mh_record_summary(mcd_mh_t* m, int64_t skip, int64_t n_samples, int32_t 
  * no positive-definiteness check: the reference evaluates the form with whatever the .data file holds).  Batches are chain-major
  * like everywhere; trees as in mcd_tree_create.  Up to 4096 chains the log-density is ONE launch (a workgroup stages the dx of one or two
  * chains in LDS and walks the flat stream of the matrix's entries; for an exactly symmetric matrix the upper triangle only), beyond that
- * three launches with lanes = chains; the two agree to rounding.  (mcd_mvn_create with a densified matrix remains the route to the gradient
- * of tree states and to the NUTS driver, N <= MCD_MAX_DIM; the Metropolis-Hastings driver takes the sparse handle: mcd_mh_create_sparse.)
+ * three launches with lanes = chains; the two agree to rounding.  Both samplers take the sparse handle as it is, for trees of 3 .. 2048
+ * nodes: the Metropolis-Hastings driver by mcd_mh_create_sparse, the leapfrog / NUTS driver by mcd_hmc_create_sparse over
+ * mcd_sparse_tree_grad_batch (nothing is densified; mcd_mvn_create with a densified matrix, N <= MCD_MAX_DIM, is no longer needed for either).
  * mcd_sparse_release_stream: a host that makes short-lived streams calls it before destroying one (the gradient's and the large batches'
  * scratch buffer of that stream is freed; like mcd_mvn_release_stream).
  */
@@ -534,6 +537,21 @@ int mcd_sparse_tree_create(mcd_sparse_tree_t** out, const mcd_sparse_t* h, int n
 void mcd_sparse_tree_destroy(mcd_sparse_tree_t* t);
 int mcd_sparse_tree_loglik_batch(const mcd_sparse_tree_t* t, const double* heights, const double* rates, int64_t ld_state, const double* tH,
                                  const double* rMu, int64_t batch, int on_device, void* stream, double* ll, double* log_jac);
+/* State -> ln likelihood and its gradient with respect to the state over the sparse precision matrix: arguments and semantics of
+ * mcd_tree_grad_batch (g_heights / g_rates [batch][ld_state], every node; g_rates[.][0] = 0), with y = 1/2 (P + P^T) dx in place of the
+ * factor sweep.  ONE launch, no scratch buffer, a workgroup per one or two chains (csrc/k_sparse_grad.hip); every sum in an order that the
+ * matrix and the tree fix: a chain's outputs are the same bits whatever the batch, the chains per workgroup (mcd_set_option
+ * "MCD_SPARSE_GRAD_CHAINS" = 1 | 2) and the kind of pointers.  A chain whose ln likelihood is NaN has NaN in every gradient entry; no
+ * other chain is touched.  Trees of 3 .. 2048 nodes (MCD_ERR_UNSUPPORTED beyond).  Device pointers: an output may be its own input array
+ * (g_heights = heights, g_rates = rates), not the other one. */
+int mcd_sparse_tree_grad_batch(const mcd_sparse_tree_t* t, const double* heights, const double* rates, int64_t ld_state, const double* tH,
+                               const double* rMu, int64_t batch, int on_device, void* stream, double* ll, double* g_heights, double* g_rates,
+                               double* g_tH, double* g_rMu);
+/* The leapfrog / NUTS driver (mcd_hmc_*, above) over that likelihood: an ordinary mcd_hmc_t -- every mcd_hmc_* entry point works on it
+ * unchanged; a leapfrog step and a NUTS round are still the two gradient launches + one (the prior gradient, mcd_sparse_tree_grad_batch's
+ * launch, k_hmc / k_nuts).  Trees of 3 .. 2048 nodes, the range of mcd_mh_create_sparse (MCD_ERR_UNSUPPORTED beyond); tree and prior on
+ * the same device with the same node count (MCD_ERR_INVALID_ARG otherwise); they must outlive the driver. */
+int mcd_hmc_create_sparse(mcd_hmc_t** out, const mcd_sparse_tree_t* tree, const mcd_prior_t* prior, int calibrations_available, int64_t batch);
 
 /* ------------------------------------------------------------------------------------------------
  * Multi-GPU.  Chains are independent: every rank (one process per GPU) holds the operands and evaluates its own

@@ -69,6 +69,8 @@ SYMBOLS = {
     "mcd_sparse_tree_create": (C.c_int, [C.POINTER(_vp), _vp, C.c_int, _ip]),
     "mcd_sparse_tree_destroy": (None, [_vp]),
     "mcd_sparse_tree_loglik_batch": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp]),
+    "mcd_sparse_tree_grad_batch": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcd_hmc_create_sparse": (C.c_int, [C.POINTER(_vp), _vp, _vp, C.c_int, C.c_int64]),
     "mcd_hmc_create": (C.c_int, [C.POINTER(_vp), _vp, _vp, C.c_int, C.c_int64]),
     "mcd_hmc_destroy": (None, [_vp]),
     "mcd_hmc_dim": (C.c_int, [_vp]),

@@ -1,6 +1,6 @@
 // hmc_capi.cpp -- C ABI of the device leapfrog (include/mcmcdate_mvn.h, "mcd_hmc_*").  The state of `batch` chains, their
 // momenta and gradients stay on the device; one leapfrog step = kick, drift (k_hmc.hip), prior gradient (k_prior_grad.hip),
-// likelihood gradient (k_tree_grad.hip).  No CPU path.
+// likelihood gradient (k_tree_grad.hip, or k_sparse_grad.hip over a sparse precision matrix: mcd_hmc_create_sparse).  No CPU path.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -38,6 +38,9 @@ struct mcd_hmc {
     int device = 0;
     const mcd::MvnDev* mvn = nullptr;
     const mcd::TreeDev* tree = nullptr;
+    // a likelihood over a SPARSE precision matrix instead (mcd_hmc_create_sparse): mvn and tree stay null
+    const mcd::SparseDev* sp = nullptr;
+    const mcd::SparseTreeDev* sp_tree = nullptr;
     const mcd::PriorDev* prior = nullptr;
     mcd::HmcDev dev{};
     double *d_eps = nullptr, *d_dir = nullptr, *d_inv_mass = nullptr;
@@ -74,30 +77,19 @@ int eval_gradients(mcd_hmc* m)
     const int64_t B = D.batch;
     HHIP_TRY(mcd::launch_prior_grad(*m->prior, D.sc, D.sc + B, D.sc + 2 * B, D.H, D.sc + 3 * B, D.sc + 4 * B, D.R, D.ld, B, D.lp, D.gp_sc,
                                     D.gp_sc + B, D.gp_sc + 2 * B, D.gp_H, D.gp_sc + 3 * B, D.gp_sc + 4 * B, D.gp_R, m->stream));
-    HHIP_TRY(mcd::launch_tree_grad(*m->mvn, *m->tree, D.H, D.R, D.ld, D.sc + 2 * B, D.sc + 3 * B, B, D.ll, D.gl_H, D.gl_R, D.gl_tH, D.gl_rMu,
-                                   m->stream));
+    if (m->sp)
+        HHIP_TRY(mcd::launch_sparse_tree_grad(*m->sp, *m->sp_tree, D.H, D.R, D.ld, D.sc + 2 * B, D.sc + 3 * B, B, D.ll, D.gl_H, D.gl_R, D.gl_tH,
+                                              D.gl_rMu, m->stream));
+    else
+        HHIP_TRY(mcd::launch_tree_grad(*m->mvn, *m->tree, D.H, D.R, D.ld, D.sc + 2 * B, D.sc + 3 * B, B, D.ll, D.gl_H, D.gl_R, D.gl_tH, D.gl_rMu,
+                                       m->stream));
     return MCD_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int mcd_hmc_create(mcd_hmc_t** out, const mcd_tree_t* tree, const mcd_prior_t* prior, int calibrations_available, int64_t batch)
+// the part of mcd_hmc_create / mcd_hmc_create_sparse behind the handles: the likelihood and the prior of `m` are set, `parent` is the host
+// copy of the topology of n nodes
+int hmc_build(std::unique_ptr<mcd_hmc>& m, int n, int root_right, const int32_t* parent, int calibrations_available, int64_t batch, mcd_hmc_t** out)
 {
-    if (!out) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_create: out is NULL");
-    *out = nullptr;
-    if (!tree || !prior) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_create: NULL tree or prior handle");
-    if (batch <= 0) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_create: batch must be positive");
-    std::unique_ptr<mcd_hmc> m(new mcd_hmc());
-    int dev_t = 0, dev_p = 0;
-    const int32_t* parent = nullptr;
-    const double* host_L = nullptr;
-    if (mcd_tree_internal_(tree, &m->mvn, &m->tree, &dev_t, &parent, &host_L) || mcd_prior_internal_(prior, &m->prior, &dev_p))
-        return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_create: invalid handle");
-    if (dev_t != dev_p) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_create: tree and prior live on different GPUs");
-    const int n = m->tree->n_nodes;
-    if (m->prior->n_nodes != n) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_create: tree has %d nodes, prior %d", n, m->prior->n_nodes);
     // getMask (app/Hamiltonian.hs:33-47) in fold order of the state record, then toVector's reverse order (:49-53)
     std::vector<char> leaf(n, 1);
     for (int v = 1; v < n; ++v) leaf[parent[v]] = 0;
@@ -116,13 +108,12 @@ int mcd_hmc_create(mcd_hmc_t** out, const mcd_tree_t* tree, const mcd_prior_t* p
     for (int v = 1; v < n; ++v) push(6, v);       // the stem of the rate tree is masked
     std::vector<int32_t> rf(field.rbegin(), field.rend()), ri(index.rbegin(), index.rend());
     const int dim = (int)rf.size();
-    m->device = dev_t;
     HHIP_TRY(hipSetDevice(m->device));
     HHIP_TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
     mcd::HmcDev& D = m->dev;
     D.n_nodes = n;
     D.dim = dim;
-    D.root_right = m->tree->root_right;
+    D.root_right = root_right;
     D.batch = batch;
     D.ld = (n + 7) / 8 * 8;
     const size_t B = (size_t)batch, BL = B * (size_t)D.ld, BD = B * (size_t)dim;
@@ -145,6 +136,53 @@ int mcd_hmc_create(mcd_hmc_t** out, const mcd_tree_t* tree, const mcd_prior_t* p
     D.inv_mass = m->d_inv_mass;
     *out = m.release();
     return MCD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mcd_hmc_create(mcd_hmc_t** out, const mcd_tree_t* tree, const mcd_prior_t* prior, int calibrations_available, int64_t batch)
+{
+    if (!out) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_create: out is NULL");
+    *out = nullptr;
+    if (!tree || !prior) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_create: NULL tree or prior handle");
+    if (batch <= 0) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_create: batch must be positive");
+    std::unique_ptr<mcd_hmc> m(new mcd_hmc());
+    int dev_t = 0, dev_p = 0;
+    const int32_t* parent = nullptr;
+    const double* host_L = nullptr;
+    if (mcd_tree_internal_(tree, &m->mvn, &m->tree, &dev_t, &parent, &host_L) || mcd_prior_internal_(prior, &m->prior, &dev_p))
+        return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_create: invalid handle");
+    if (dev_t != dev_p) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_create: tree and prior live on different GPUs");
+    const int n = m->tree->n_nodes;
+    if (m->prior->n_nodes != n) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_create: tree has %d nodes, prior %d", n, m->prior->n_nodes);
+    m->device = dev_t;
+    return hmc_build(m, n, m->tree->root_right, parent, calibrations_available, batch, out);
+}
+
+// The same driver over a likelihood whose precision matrix stays sparse on the device (mcd_sparse_tree_create): the likelihood gradient is
+// k_sparse_grad.hip's one launch, everything else is shared.
+int mcd_hmc_create_sparse(mcd_hmc_t** out, const mcd_sparse_tree_t* tree, const mcd_prior_t* prior, int calibrations_available, int64_t batch)
+{
+    if (!out) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_create_sparse: out is NULL");
+    *out = nullptr;
+    if (!tree || !prior) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_create_sparse: NULL tree or prior handle");
+    if (batch <= 0 || batch > 0x7fffffffLL) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_create_sparse: batch must be in [1, 2^31)");
+    std::unique_ptr<mcd_hmc> m(new mcd_hmc());
+    int dev_t = 0, dev_p = 0;
+    const int32_t* parent = nullptr;
+    if (mcd_sparse_tree_grad_internal_(tree, &m->sp, &m->sp_tree, &dev_t, &parent) || mcd_prior_internal_(prior, &m->prior, &dev_p))
+        return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_create_sparse: invalid handle");
+    const int n = m->sp_tree->n_nodes;
+    if (n < 3 || n > mcd::kSparseGradMaxNodes || n > mcd::kPriorGradMaxNodes)
+        return hfail(MCD_ERR_UNSUPPORTED, "mcd_hmc_create_sparse: %d nodes (the sparse driver serves trees of 3 .. %d nodes)", n, mcd::kSparseGradMaxNodes);
+    if (!mcd::sparse_tree_grad_available(mcd::SparseFacts(*m->sp), n))
+        return hfail(MCD_ERR_UNSUPPORTED, "mcd_hmc_create_sparse: the handle has no rows of the symmetric part");
+    if (dev_t != dev_p) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_create_sparse: tree and prior live on different GPUs");
+    if (m->prior->n_nodes != n) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_create_sparse: tree has %d nodes, prior %d", n, m->prior->n_nodes);
+    m->device = dev_t;
+    return hmc_build(m, n, m->sp_tree->root_right, parent, calibrations_available, batch, out);
 }
 
 void mcd_hmc_destroy(mcd_hmc_t* m) { delete m; }

@@ -168,6 +168,11 @@ struct SparseDev {
     const double* ell_val;     // [n][kSparseEllW]
     const double* ell_mu;      // [n][kSparseEllW]
     const int32_t* ell_more;   // [n]
+    // ... and the records' columns and values once more SLICE-MAJOR, [kSparseEllW][n_pad] (n_pad = n rounded up to 64; padding as above): a
+    // thread per row makes the k-th load of a wave's 64 rows one coalesced line (k_sparse_grad.hip)
+    int n_pad;
+    const int32_t* ellT_col;   // [kSparseEllW][n_pad]
+    const double* ellT_val;    // [kSparseEllW][n_pad]
 };
 constexpr int kSparseEllW = 16;
 // What the launch choices read of a sparse handle: plain facts, so that the Metropolis-Hastings planner (mh_capi.cpp) also runs without a device
@@ -181,6 +186,8 @@ struct SparseTreeDev {
     int n_nodes, root_right;
     const int32_t* slot_node;     // [n] distance slot -> node (getBranches . sumFirstTwo order)
     const int32_t* slot_parent;   // [n] that node's parent
+    const int32_t* child_ptr;     // [n_nodes + 1] CSR children, as TreeDev's
+    const int32_t* child_idx;     // [n_nodes - 1]
 };
 constexpr int kSparseMaxDim = 8192;
 // scratch: sparse_scratch_doubles(n, batch, gradient?) doubles of device memory that live until the launches have run
@@ -196,6 +203,13 @@ hipError_t launch_sparse_tree_logpdf(const SparseDev& S, const SparseTreeDev& T,
 bool sparse_quad_available(const SparseFacts& S, int64_t batch);
 hipError_t launch_sparse_quad(const SparseDev& S, const SparseTreeDev* T, const double* X, const double* Rt, int64_t ld, const double* tH,
                               const double* rMu, int64_t batch, double* ll, double* logjac, double* qout, hipStream_t st);
+// tree state -> ll and its gradient wrt the state over the symmetric part's rows, ONE launch, no scratch (k_sparse_grad.hip): outputs as
+// launch_tree_grad's; trees of 3 .. kSparseGradMaxNodes nodes (the range of mcd_mh_create_sparse).  gH may be H and gR may be Rt; an output must
+// not be the OTHER input array
+constexpr int kSparseGradMaxNodes = 2048;
+bool sparse_tree_grad_available(const SparseFacts& S, int n_nodes);
+hipError_t launch_sparse_tree_grad(const SparseDev& S, const SparseTreeDev& T, const double* H, const double* Rt, int64_t ld, const double* tH,
+                                   const double* rMu, int64_t batch, double* ll, double* gH, double* gR, double* gtH, double* grMu, hipStream_t st);
 
 // Metropolis-coupled MCMC (k_mc3.hip): the temperature rank of every GLOBAL chain, the ladder of reciprocal temperatures and the
 // swap counters per rung; all pointers are device memory.
@@ -335,6 +349,8 @@ hipError_t launch_prior(const PriorDev& P, const double* birth, const double* de
                         const double* rMu, const double* rVar, const double* Rt, int64_t lds, int64_t batch, double* lp,
                         double* comp, hipStream_t st);
 
+// trees up to kPriorGradMaxNodes nodes (7 n_nodes + 2 doubles of LDS per workgroup: above 64 KiB the launcher opts in once per device)
+constexpr int kPriorGradMaxNodes = 2048;
 hipError_t launch_prior_grad(const PriorDev& P, const double* birth, const double* death, const double* tH, const double* H,
                              const double* rMu, const double* rVar, const double* Rt, int64_t lds, int64_t batch, double* lp,
                              double* g_birth, double* g_death, double* g_tH, double* g_H, double* g_rMu, double* g_rVar, double* g_R,
@@ -393,6 +409,9 @@ hipError_t launch_mh_chain(const MhDev& M, const MvnDev& V, const TreeDev& T, co
 // handle internals shared between the translation units of the C ABI (mvn_capi.cpp, prior_capi.cpp, mh_capi.cpp)
 struct mcd_tree;
 struct mcd_prior;
+struct mcd_sparse_tree;
+int mcd_sparse_tree_grad_internal_(const mcd_sparse_tree* t, const mcd::SparseDev** dev, const mcd::SparseTreeDev** tree, int* device,
+                                   const int32_t** host_parent);   // sparse_capi.cpp
 int mcd_tree_internal_(const mcd_tree* t, const mcd::MvnDev** mvn, const mcd::TreeDev** tree, int* device, const int32_t** host_parent,
                        const double** host_L);
 int mcd_prior_internal_(const mcd_prior* p, const mcd::PriorDev** prior, int* device);

@@ -32,6 +32,7 @@ enum Option {
     OPT_MH_PRIOR_DRAWS,     // 0: the next step's proposal is not drawn by a prior wave (the chain wave draws ahead itself from MCD_MH_AHEAD_FROM nodes; A/B, tests)
     OPT_FSTREAM,            // the column sweep's forward factor stream at 129 .. 256 dimensions: 0 = padded (Ft), register-staged; 1 = compact (Fc),
                             // register-staged; 2 = compact, LDS-DMA (A/B, tests; fc_layout.hpp, mvn_device.hpp)
+    OPT_SPARSE_GRAD_CHAINS, // 1 | 2: chains per workgroup of the sparse tree gradient (k_sparse_grad.hip; default: 2 from 512 chains; the same bits)
     OPT_COUNT
 };
 constexpr int MCD_OPT_UNSET = -2147483647 - 1;

@@ -247,7 +247,9 @@ int mcd_prior_grad_batch(const mcd_prior_t* cp, const double* birth, const doubl
     if (!birth || !death || !tH || !heights || !rMu || !rVar || !rates || !lp || !g_birth || !g_death || !g_tH || !g_heights || !g_rMu ||
         !g_rVar || !g_rates)
         return pfail(MCD_ERR_INVALID_ARG, "mcd_prior_grad_batch: NULL data pointer");
-    if ((size_t)p->n_nodes * 16 > 64 * 1024) return pfail(MCD_ERR_UNSUPPORTED, "mcd_prior_grad_batch: more than 4096 nodes");
+    if (p->n_nodes > mcd::kPriorGradMaxNodes)
+        return pfail(MCD_ERR_UNSUPPORTED, "mcd_prior_grad_batch: %d nodes (the prior gradient serves trees of up to %d nodes)", p->n_nodes,
+                     mcd::kPriorGradMaxNodes);
     PHIP_TRY(hipSetDevice(p->device));
     if (on_device) {
         PHIP_TRY(mcd::launch_prior_grad(p->dev, birth, death, tH, heights, rMu, rVar, rates, ld_state, batch, lp, g_birth, g_death, g_tH,

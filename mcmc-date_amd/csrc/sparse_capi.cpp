@@ -137,6 +137,17 @@ int mcd_sparse_tree_internal_(const mcd_sparse_tree* t, const mcd_sparse** sp, c
     *host_parent = t->parent.data();
     return MCD_OK;
 }
+// for the leapfrog / NUTS driver (hmc_capi.cpp)
+int mcd_sparse_tree_grad_internal_(const mcd_sparse_tree* t, const mcd::SparseDev** dev, const mcd::SparseTreeDev** tree, int* device,
+                                   const int32_t** host_parent)
+{
+    if (!t || !t->sp) return MCD_ERR_INVALID_ARG;
+    *dev = &t->sp->dev;
+    *tree = &t->dev;
+    *device = t->sp->device;
+    *host_parent = t->parent.data();
+    return MCD_OK;
+}
 int mcd_sparse_scratch_(const mcd_sparse* h, hipStream_t st, int64_t batch, double** out)
 {
     return scratch_for(h, st, mcd::sparse_scratch_doubles(h->n, batch, false), out);
@@ -266,6 +277,17 @@ int mcd_sparse_create(mcd_sparse_t** out, int n, const double* mu, int64_t nnz, 
             if ((rc = upload(h.get(), &h->dev.ell_col, ec.data(), ec.size())) || (rc = upload(h.get(), &h->dev.ell_val, ev.data(), ev.size())) ||
                 (rc = upload(h.get(), &h->dev.ell_mu, eu.data(), eu.size())) || (rc = upload(h.get(), &h->dev.ell_more, em.data(), em.size())))
                 return rc;
+            // the same records slice-major (SparseDev::ellT_*: the sparse tree gradient, a thread per row)
+            const int np = (n + 63) / 64 * 64;
+            std::vector<int32_t> tc((size_t)W * np);
+            std::vector<double> tv((size_t)W * np, 0.0);
+            for (int u = 0; u < W; ++u)
+                for (int i = 0; i < np; ++i) {
+                    tc[(size_t)u * np + i] = i < n ? ec[(size_t)i * W + u] : 0;
+                    tv[(size_t)u * np + i] = i < n ? ev[(size_t)i * W + u] : 0.0;
+                }
+            h->dev.n_pad = np;
+            if ((rc = upload(h.get(), &h->dev.ellT_col, tc.data(), tc.size())) || (rc = upload(h.get(), &h->dev.ellT_val, tv.data(), tv.size()))) return rc;
         }
         // the flat entry stream of the one-launch form: (row | column << 16, value); a symmetric matrix as its upper triangle with the
         // off-diagonal values doubled
@@ -383,6 +405,16 @@ int mcd_sparse_tree_create(mcd_sparse_tree_t** out, const mcd_sparse_t* h, int n
     const size_t n = slot.size();
     slot.resize(2 * n);
     for (size_t i = 0; i < n; ++i) slot[n + i] = parent[slot[i]];
+    // CSR children behind them, as mcd_tree_create builds them (the gradient's gather of the heights' chain rule)
+    std::vector<int32_t> cptr((size_t)n_nodes + 1, 0), cidx((size_t)n_nodes - 1);
+    for (int v = 1; v < n_nodes; ++v) cptr[(size_t)parent[v] + 1]++;
+    for (int v = 0; v < n_nodes; ++v) cptr[(size_t)v + 1] += cptr[(size_t)v];
+    {
+        std::vector<int32_t> fill(cptr.begin(), cptr.end() - 1);
+        for (int v = 1; v < n_nodes; ++v) cidx[(size_t)fill[(size_t)parent[v]]++] = v;   // ascending ids = left to right
+    }
+    slot.insert(slot.end(), cptr.begin(), cptr.end());
+    slot.insert(slot.end(), cidx.begin(), cidx.end());
     std::unique_ptr<mcd_sparse_tree> t(new mcd_sparse_tree());
     t->sp = h;
     t->device = h->device;
@@ -394,6 +426,8 @@ int mcd_sparse_tree_create(mcd_sparse_tree_t** out, const mcd_sparse_t* h, int n
     t->dev.root_right = r;
     t->dev.slot_node = t->d_slot;
     t->dev.slot_parent = t->d_slot + n;
+    t->dev.child_ptr = t->d_slot + 2 * n;
+    t->dev.child_idx = t->d_slot + 2 * n + (size_t)n_nodes + 1;
     *out = t.release();
     return MCD_OK;
 }
@@ -431,6 +465,54 @@ int mcd_sparse_tree_loglik_batch(const mcd_sparse_tree_t* t, const double* heigh
     SHIP_TRY(mcd::launch_sparse_tree_logpdf(h->dev, t->dev, dH, dR, nn, dsc, dsc + B, batch, dsc + 2 * B, dsc + 3 * B, sc, s.st));
     SHIP_TRY(hipMemcpyAsync(ll, dsc + 2 * B, sizeof(double) * B, hipMemcpyDeviceToHost, s.st));
     if (log_jac) SHIP_TRY(hipMemcpyAsync(log_jac, dsc + 3 * B, sizeof(double) * B, hipMemcpyDeviceToHost, s.st));
+    SHIP_TRY(hipStreamSynchronize(s.st));
+    return MCD_OK;
+}
+
+int mcd_sparse_tree_grad_batch(const mcd_sparse_tree_t* t, const double* heights, const double* rates, int64_t ld_state, const double* tH,
+                               const double* rMu, int64_t batch, int on_device, void* stream, double* ll, double* g_heights, double* g_rates,
+                               double* g_tH, double* g_rMu)
+{
+    if (!t) return sfail(MCD_ERR_INVALID_ARG, "mcd_sparse_tree_grad_batch: NULL handle");
+    const int nn = t->dev.n_nodes;
+    if (batch < 0 || ld_state < nn) return sfail(MCD_ERR_INVALID_ARG, "mcd_sparse_tree_grad_batch: need batch >= 0 and ld_state >= n_nodes");
+    const mcd_sparse* h = t->sp;
+    if (nn > mcd::kSparseGradMaxNodes)
+        return sfail(MCD_ERR_UNSUPPORTED, "mcd_sparse_tree_grad_batch: %d nodes (the sparse tree gradient serves trees of 3 .. %d nodes)", nn,
+                     mcd::kSparseGradMaxNodes);
+    if (!mcd::sparse_tree_grad_available(mcd::SparseFacts(h->dev), nn))
+        return sfail(MCD_ERR_UNSUPPORTED, "mcd_sparse_tree_grad_batch: the handle has no rows of the symmetric part");
+    if (batch == 0) return MCD_OK;
+    if (!heights || !rates || !tH || !rMu || !ll || !g_heights || !g_rates || !g_tH || !g_rMu)
+        return sfail(MCD_ERR_INVALID_ARG, "mcd_sparse_tree_grad_batch: NULL data pointer");
+    if (batch > 0x7fffffffLL) return sfail(MCD_ERR_INVALID_ARG, "mcd_sparse_tree_grad_batch: batch must be below 2^31");
+    SHIP_TRY(hipSetDevice(h->device));
+    if (on_device) {
+        if ((const double*)g_heights == rates || (const double*)g_rates == heights)
+            return sfail(MCD_ERR_INVALID_ARG, "mcd_sparse_tree_grad_batch: an output may be its own input, not the other input array");
+        SHIP_TRY(mcd::launch_sparse_tree_grad(h->dev, t->dev, heights, rates, ld_state, tH, rMu, batch, ll, g_heights, g_rates, g_tH, g_rMu,
+                                              (hipStream_t)stream));
+        return MCD_OK;
+    }
+    Scratch s;
+    SHIP_TRY(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
+    const size_t BN = (size_t)batch * nn, B = (size_t)batch;
+    double* dH = s.alloc(BN);
+    double* dR = s.alloc(BN);
+    double* dgH = s.alloc(BN);
+    double* dgR = s.alloc(BN);
+    double* dsc = s.alloc(5 * B);                            // tH, rMu | ll, g_tH, g_rMu
+    if (!dH || !dR || !dgH || !dgR || !dsc) return sfail(MCD_ERR_HIP, "mcd_sparse_tree_grad_batch: out of device memory");
+    SHIP_TRY(hipMemcpy2DAsync(dH, sizeof(double) * nn, heights, sizeof(double) * ld_state, sizeof(double) * nn, B, hipMemcpyHostToDevice, s.st));
+    SHIP_TRY(hipMemcpy2DAsync(dR, sizeof(double) * nn, rates, sizeof(double) * ld_state, sizeof(double) * nn, B, hipMemcpyHostToDevice, s.st));
+    SHIP_TRY(hipMemcpyAsync(dsc, tH, sizeof(double) * B, hipMemcpyHostToDevice, s.st));
+    SHIP_TRY(hipMemcpyAsync(dsc + B, rMu, sizeof(double) * B, hipMemcpyHostToDevice, s.st));
+    SHIP_TRY(mcd::launch_sparse_tree_grad(h->dev, t->dev, dH, dR, nn, dsc, dsc + B, batch, dsc + 2 * B, dgH, dgR, dsc + 3 * B, dsc + 4 * B, s.st));
+    SHIP_TRY(hipMemcpyAsync(ll, dsc + 2 * B, sizeof(double) * B, hipMemcpyDeviceToHost, s.st));
+    SHIP_TRY(hipMemcpyAsync(g_tH, dsc + 3 * B, sizeof(double) * B, hipMemcpyDeviceToHost, s.st));
+    SHIP_TRY(hipMemcpyAsync(g_rMu, dsc + 4 * B, sizeof(double) * B, hipMemcpyDeviceToHost, s.st));
+    SHIP_TRY(hipMemcpy2DAsync(g_heights, sizeof(double) * ld_state, dgH, sizeof(double) * nn, sizeof(double) * nn, B, hipMemcpyDeviceToHost, s.st));
+    SHIP_TRY(hipMemcpy2DAsync(g_rates, sizeof(double) * ld_state, dgR, sizeof(double) * nn, sizeof(double) * nn, B, hipMemcpyDeviceToHost, s.st));
     SHIP_TRY(hipStreamSynchronize(s.st));
     return MCD_OK;
 }

@@ -25,7 +25,7 @@ from typing import Optional
 import numpy as np
 
 from . import _capi
-from .likelihood import TreeLikelihood
+from .likelihood import SparseTreeLikelihood, TreeLikelihood
 from .prior import PriorFunction
 from .state import StateBatch
 
@@ -37,14 +37,16 @@ def _p(a):
 
 
 class Leapfrog:
-    """B chains on one GPU.  `tree_lik` and `prior` must live on the same device and outlive this object."""
+    """B chains on one GPU.  `tree_lik` (a TreeLikelihood, or a SparseTreeLikelihood: the precision matrix stays sparse on the device,
+    mcd_hmc_create_sparse, trees of up to 2048 nodes) and `prior` must live on the same device and outlive this object."""
 
-    def __init__(self, tree_lik: TreeLikelihood, prior: PriorFunction, calibrations_available: bool, batch: int):
+    def __init__(self, tree_lik: "TreeLikelihood | SparseTreeLikelihood", prior: PriorFunction, calibrations_available: bool, batch: int):
         self.topo = tree_lik.topo
         self.batch = int(batch)
         self._keep = (tree_lik, prior)
         self._h = C.c_void_p()
-        _capi.check(_capi.lib().mcd_hmc_create(C.byref(self._h), tree_lik._t, prior._p, int(bool(calibrations_available)), self.batch))
+        create = _capi.lib().mcd_hmc_create_sparse if isinstance(tree_lik, SparseTreeLikelihood) else _capi.lib().mcd_hmc_create
+        _capi.check(create(C.byref(self._h), tree_lik._t, prior._p, int(bool(calibrations_available)), self.batch))
         self.dim = int(_capi.lib().mcd_hmc_dim(self._h))
 
     def close(self):

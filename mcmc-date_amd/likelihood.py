@@ -416,7 +416,8 @@ class SparseLikelihood:
     """`likelihoodFunction (Sparse mu sigmaInvSparse logDetSigma)` (app/Probability.hs:279, 178-184) with the precision matrix kept
     sparse on the device (csrc/k_sparse.hip, mcd_sparse_*): the reference's route for trees with thousands of branches.  Takes the
     `Sparse` record of a `.data` file (read_data_file) or of `prepare`.  logpdf / grad on raw vectors, bind_tree(topo).loglik on
-    states.  `MvnLikelihood(Sparse ...)` densifies instead (N <= 1024) and is what the samplers and the tree gradient use."""
+    states, bind_tree(topo).grad for the gradient of states (trees of up to 2048 nodes); `Sampler` and `hmc.Leapfrog` take the bound tree
+    as it is.  `MvnLikelihood(Sparse ...)` densifies instead (N <= 1024)."""
 
     def __init__(self, lhd: Sparse, device: int = 0):
         if not isinstance(lhd, Sparse):
@@ -536,6 +537,42 @@ class SparseTreeLikelihood:
         _capi.check(L.mcd_sparse_tree_loglik_batch(self._t, _ptr(H), _ptr(R), nn, _ptr(tH), _ptr(rMu), B, 0, None, _ptr(ll),
                                                    _ptr(lj) if want_jacobian else None))
         return ll, lj
+
+    def grad(self, states: StateBatch):
+        """(ll, g_heights[batch, n_nodes], g_rates[batch, n_nodes], g_time_height[batch], g_rate_mean[batch]), as TreeLikelihood.grad: one
+        launch over the sparse matrix (mcd_sparse_tree_grad_batch, csrc/k_sparse_grad.hip), trees of up to 2048 nodes."""
+        H, R, tH, rMu = states.heights, states.rates, states.time_height, states.rate_mean
+        L = _capi.lib()
+        nn = self.topo.n_nodes
+        if _is_torch(H):
+            import torch
+
+            dev = self.sp.device
+            for t, nm in ((H, "heights"), (R, "rates"), (tH, "time_height"), (rMu, "rate_mean")):
+                _check_cuda(t, dev, nm)
+            B = H.shape[0]
+            ll = torch.empty(B, dtype=torch.float64, device=H.device)
+            gH = torch.empty_like(H)
+            gR = torch.empty_like(R)
+            gt = torch.empty_like(tH)
+            gm = torch.empty_like(rMu)
+            if gH.stride(0) != H.stride(0) or gR.stride(0) != H.stride(0) or R.stride(0) != H.stride(0):
+                raise ValueError("grad: heights and rates must share one row stride")
+            _capi.check(L.mcd_sparse_tree_grad_batch(self._t, _ptr(H), _ptr(R), H.stride(0), _ptr(tH), _ptr(rMu), B, 1, _stream_ptr(dev),
+                                                     _ptr(ll), _ptr(gH), _ptr(gR), _ptr(gt), _ptr(gm)))
+            return ll, gH, gR, gt, gm
+        H, R, tH, rMu = (_host(a) for a in (H, R, tH, rMu))
+        B = H.shape[0]
+        if H.shape != (B, nn) or R.shape != (B, nn) or tH.shape != (B,) or rMu.shape != (B,):
+            raise ValueError("grad: inconsistent state shapes")
+        ll = np.empty(B)
+        gH = np.empty_like(H)
+        gR = np.empty_like(R)
+        gt = np.empty(B)
+        gm = np.empty(B)
+        _capi.check(L.mcd_sparse_tree_grad_batch(self._t, _ptr(H), _ptr(R), nn, _ptr(tH), _ptr(rMu), B, 0, None, _ptr(ll), _ptr(gH), _ptr(gR),
+                                                 _ptr(gt), _ptr(gm)))
+        return ll, gH, gR, gt, gm
 
 
 # ----------------------------------------------------------------------------------------------
