@@ -43,6 +43,13 @@ module McmcDate.GpuSampler
     recordSummary,
     runMc3Gpu,
     nodeAgeSummary,
+    -- the NUTS driver's recorder, raw (the handle comes from 'McmcDate.Gpu')
+    c_hmc_record_begin,
+    c_hmc_record_count,
+    c_hmc_record_fetch,
+    c_hmc_record_end,
+    c_hmc_record_quantities,
+    c_hmc_record_summary,
   )
 where
 
@@ -58,7 +65,7 @@ import Foreign
 import Foreign.C.String
 import Foreign.C.Types
 import Mcmc.Tree (HeightTree (..), LengthTree (..), getHeightTree, getLengthTree)
-import McmcDate.Gpu (McdMh, McdPrior, McdSparseTree, McdTree)
+import McmcDate.Gpu (McdHmc, McdMh, McdPrior, McdSparseTree, McdTree)
 import State (I, IG (..), rateMean, rateTree, rateVariance, timeBirthRate, timeDeathRate, timeHeight, timeTree)
 import System.Random.Stateful (StatefulGen, uniformRM)
 
@@ -147,6 +154,29 @@ foreign import ccall unsafe "mcd_mh_record_quantities"
 -- (safe: several passes over the whole ring)
 foreign import ccall safe "mcd_mh_record_summary"
   c_mh_record_summary :: Ptr McdMh -> Int64 -> Int64 -> Int32 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> IO CInt
+
+-- the same recorder on the NUTS driver (runs with @--hamiltonian@; the handle is 'McmcDate.Gpu.McdHmc'): every transition through
+-- @mcd_hmc_nuts@ / @_nuts_run@ / @_nuts_warmup@ counts, a sample carries the transition's diagnostics (depth, leapfrog steps, acceptance
+-- statistic, diverged, step size, -H at the start) where a Metropolis-Hastings sample carries its temperature
+foreign import ccall unsafe "mcd_hmc_record_begin"
+  c_hmc_record_begin :: Ptr McdHmc -> Int32 -> Int64 -> IO CInt
+
+foreign import ccall unsafe "mcd_hmc_record_count"
+  c_hmc_record_count :: Ptr McdHmc -> Ptr Int64 -> IO CInt
+
+foreign import ccall unsafe "mcd_hmc_record_fetch"
+  c_hmc_record_fetch ::
+    Ptr McdHmc -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+
+foreign import ccall unsafe "mcd_hmc_record_end"
+  c_hmc_record_end :: Ptr McdHmc -> IO CInt
+
+foreign import ccall unsafe "mcd_hmc_record_quantities"
+  c_hmc_record_quantities :: Ptr McdHmc -> Ptr Int64 -> IO CInt
+
+-- (safe: several passes over the whole ring)
+foreign import ccall safe "mcd_hmc_record_summary"
+  c_hmc_record_summary :: Ptr McdHmc -> Int64 -> Int64 -> Int32 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
 
 check :: String -> CInt -> IO ()
 check _ 0 = pure ()

@@ -284,6 +284,46 @@ int mcd_hmc_nuts_run(mcd_hmc_t* m, int n_transitions, int adapt, double* eps, co
  * first_transition + (windows + 1) window - 1 of the random streams.  eps, inv_mass: in = starting values, out = tuned. */
 int mcd_hmc_nuts_warmup(mcd_hmc_t* m, int windows, int window, double* eps, double* inv_mass, double delta, int max_depth, uint64_t seed,
                         int64_t chain_offset, uint64_t first_transition, double* mean_alpha);
+/*
+ * The sample recorder of the NUTS driver: thinned samples of every chain AND the diagnostics of the transitions behind them kept ON THE
+ * DEVICE while mcd_hmc_nuts / _nuts_run / _nuts_warmup run.  Replaces: the `monitor` of app/Definitions.hs:288-417 (`mcmc`'s MonitorFile
+ * with period 2 everywhere) for runs with `--hamiltonian`, as the source of the states that the monitor files and scripts/analyze read --
+ * without one mcd_hmc_nuts call and one mcd_hmc_get_state per transition -- and what `mcmc` prints of its NUTS proposal.  The contracts are
+ * those of mcd_mh_record_* (below) point for point; the ring holds the same records, read by the same kernels.
+ *   mcd_hmc_record_begin   a ring of capacity_samples slots on the handle's device; the transition count starts at 0.  period >= 1,
+ *                          capacity_samples >= 1; one recorder per handle (a second begin without end is refused).
+ *   mcd_hmc_nuts*          while a recorder is active every transition counts, through whichever of the three entry points, so calls of
+ *                          any lengths give the samples of one long call; after every transition whose number is a multiple of period
+ *                          the state of every chain is stored as one sample (k_hmc_record.hip).  A call whose samples do not fit the
+ *                          free slots returns MCD_ERR_INVALID_ARG before anything is launched (the message names both numbers) and leaves
+ *                          the handle as it was: _nuts_run and _nuts_warmup count their transitions up front, mcd_hmc_nuts is refused when
+ *                          its transition would be sampled and the ring is full.  The chains do not change: end state, alpha, depth, the
+ *                          tuned eps, the masses and q_mean / q_var are the same bits with and without a recorder.  On the device sample
+ *                          number k goes to slot (k - 1) mod capacity, so no store can leave the ring.  If a call fails after it has
+ *                          launched (MCD_ERR_HIP), the recorder's count no longer matches the chains: end the recorder.
+ *   mcd_hmc_record_count   samples waiting to be fetched.
+ *   mcd_hmc_record_fetch   waits for the handle's stream, copies the oldest *n_out = min(waiting, max_samples) samples to the host,
+ *                          sample-major, and frees their slots: transition[n] (counted from begin), scalars[n][batch][5] (birth, death,
+ *                          tH, rMu, rVar), heights / rates[n][batch][n_nodes], post[n][batch][3] (ln prior, ln likelihood, ln
+ *                          jacobianRootBranch of the accepted state; their sum is mcd_hmc_get_position's value re-evaluated),
+ *                          nuts[n][batch][6]: tree depth, leapfrog steps, acceptance statistic (the alpha of mcd_hmc_nuts), diverged (1: a
+ *                          leaf failed the Delta_max test or left the support), the step size used, -H at the start of the transition.
+ *                          Any of the arrays may be NULL.
+ *   mcd_hmc_record_end     frees the ring.  mcd_hmc_set_state leaves an active recorder and its count alone; mcd_hmc_destroy frees it.
+ *   mcd_hmc_record_quantities / mcd_hmc_record_summary   as mcd_mh_record_quantities / mcd_mh_record_summary (same quantities, same order,
+ *                          same columns, same refusals before any launch, the same bits on every call, no slot freed); nuts_stats
+ *                          [batch][4] (may be NULL): per chain over the window divergent transitions, mean tree depth, maximum tree
+ *                          depth, leapfrog steps.
+ * Dense and sparse handles alike.
+ */
+int mcd_hmc_record_begin(mcd_hmc_t* m, int32_t period, int64_t capacity_samples);
+int mcd_hmc_record_count(const mcd_hmc_t* m, int64_t* n_samples);
+int mcd_hmc_record_fetch(mcd_hmc_t* m, int64_t max_samples, int64_t* n_out, int64_t* transition, double* scalars, double* heights, double* rates,
+                         double* post, double* nuts);
+int mcd_hmc_record_end(mcd_hmc_t* m);
+int mcd_hmc_record_quantities(const mcd_hmc_t* m, int64_t* q);
+int mcd_hmc_record_summary(mcd_hmc_t* m, int64_t skip, int64_t n_samples, int32_t max_lag, int64_t* n_used, double* pooled, double* per_chain,
+                           double* nuts_stats);
 /* One leapfrog step from ARBITRARY phase points (what a NUTS tree needs: it extends either end of a trajectory):
  * q, p, grad [batch][dim] in/out (host), value [batch] out (ln target at the new point, may be NULL).  have_grad = 0:
  * the gradient at q is evaluated first (grad is output only).  The handle's own state becomes the new point. */

@@ -3,6 +3,7 @@
 // likelihood gradient (k_tree_grad.hip, or k_sparse_grad.hip over a sparse precision matrix: mcd_hmc_create_sparse).  No CPU path.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -11,7 +12,10 @@
 
 #include "../../include/mcmcdate_mvn.h"
 #include "mvn_kernels.h"
+#include "summary_device.hpp"
 
+int mcd_summary_check_(const char* who, int64_t n, int64_t batch, int64_t q, int32_t max_lag);                       // summary_capi.cpp
+int mcd_summary_run_(const mcd::SumSrc& S, int32_t max_lag, hipStream_t st, double* pooled, double* per_chain);
 extern "C" int mcd_set_last_error_(int code, const char* msg);   // mvn_capi.cpp
 
 namespace {
@@ -46,14 +50,24 @@ struct mcd_hmc {
     double *d_eps = nullptr, *d_dir = nullptr, *d_inv_mass = nullptr;
     mcd::NutsDev nuts{};           // allocated by the first NUTS transition (mcd_hmc_nuts)
     int* d_active = nullptr;
+    double *d_s1 = nullptr, *d_s2 = nullptr;   // [dim] position moments of one mcd_hmc_nuts_run (k_hmc_moments)
     bool have_state = false;
     hipStream_t stream = nullptr;
     std::vector<void*> allocs;
+    // the sample recorder (mcd_hmc_record_*): a ring of rec_cap slots (mcd::MhRec), the staging buffer of the fetch (rec_stage_cap samples);
+    // rec_iter = transitions since begin, so rec_iter / rec_period samples were taken, rec_fetched of them handed out
+    double* d_rec = nullptr;
+    double* d_rec_stage = nullptr;
+    int64_t rec_cap = 0, rec_stage_cap = 0, rec_iter = 0, rec_fetched = 0;
+    int32_t rec_period = 0;
+    int64_t rec_filled() const { return rec_iter / rec_period - rec_fetched; }
 
     ~mcd_hmc()
     {
         (void)hipSetDevice(device);
         for (void* p : allocs) (void)hipFree(p);
+        if (d_rec) (void)hipFree(d_rec);
+        if (d_rec_stage) (void)hipFree(d_rec_stage);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -333,10 +347,22 @@ int nuts_alloc(mcd_hmc* m)
     double** pb[] = {&N.lpc, &N.lpn, &N.log_u, &N.joint0, &N.alpha};
     for (double** p : pb)
         if ((rc = halloc(m, p, B))) return rc;
-    int** pi[] = {&N.j, &N.v, &N.i, &N.n, &N.n1, &N.s1, &N.done, &N.n_alpha, &N.depth, &N.leaf};
+    int** pi[] = {&N.j, &N.v, &N.i, &N.n, &N.n1, &N.s1, &N.done, &N.n_alpha, &N.depth, &N.leaf, &N.diverged};
     for (int** p : pi)
         if ((rc = halloc(m, p, B))) return rc;
+    if ((rc = halloc(m, &m->d_s1, (size_t)D.dim)) || (rc = halloc(m, &m->d_s2, (size_t)D.dim))) return rc;
     return halloc(m, &m->d_active, 1);
+}
+
+// The recorder's host-side check, the contract of mcd_hmc_record_*: `n` more transitions must fit the free slots; nothing is launched otherwise
+int rec_room(const mcd_hmc* m, const char* who, int64_t n)
+{
+    if (!m->d_rec) return MCD_OK;
+    const int64_t adds = (m->rec_iter + n) / m->rec_period - m->rec_iter / m->rec_period, free_slots = m->rec_cap - m->rec_filled();
+    if (adds > free_slots)
+        return hfail(MCD_ERR_INVALID_ARG, "%s: the call would record %lld samples, the recorder has %lld free slots (mcd_hmc_record_fetch frees them)", who,
+                     (long long)adds, (long long)free_slots);
+    return MCD_OK;
 }
 
 // one transition for every chain; eps and inv_mass already on the device
@@ -361,6 +387,12 @@ int nuts_transition(mcd_hmc* m, int max_depth, uint64_t seed, int64_t chain0, ui
     // half kick reads those raw outputs: evaluate them at the accepted point so that every entry point may follow a transition.
     if (int rc = eval_gradients(m)) return rc;
     HHIP_TRY(mcd::launch_hmc_collect(D, m->stream));
+    // the sample recorder: D.lp / D.ll are the accepted point's now, D.eps the step sizes the transition used
+    if (m->d_rec) {
+        m->rec_iter += 1;
+        if (m->rec_iter % m->rec_period == 0)
+            HHIP_TRY(mcd::launch_hmc_record(D, m->nuts, mcd::MhRec{m->d_rec, 0, m->rec_cap, m->rec_period}, m->rec_iter / m->rec_period, m->stream));
+    }
     return MCD_OK;
 }
 
@@ -380,6 +412,7 @@ int mcd_hmc_nuts(mcd_hmc_t* m, const double* eps, const double* inv_mass, int ma
         if (!(inv_mass[k] > 0) || !std::isfinite(inv_mass[k])) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts: inverse masses must be positive");
     for (size_t b = 0; b < B; ++b)
         if (!(eps[b] > 0) || !std::isfinite(eps[b])) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts: step sizes must be positive");
+    if (int rc = rec_room(m, "mcd_hmc_nuts", 1)) return rc;
     HHIP_TRY(hipSetDevice(m->device));
     if (int rc = nuts_alloc(m)) return rc;
     HHIP_TRY(hipMemcpyAsync(m->d_eps, eps, sizeof(double) * B, hipMemcpyHostToDevice, m->stream));
@@ -404,13 +437,17 @@ int mcd_hmc_nuts_run(mcd_hmc_t* m, int n_transitions, int adapt, double* eps, co
     if (!m || !eps || !inv_mass) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_run: NULL argument");
     if (n_transitions < 0) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_run: negative number of transitions");
     if (adapt && !(delta > 0 && delta < 1)) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_run: delta must be in (0, 1)");
+    if (int rc = rec_room(m, "mcd_hmc_nuts_run", n_transitions)) return rc;
     const mcd::HmcDev& D = m->dev;
     const size_t B = (size_t)D.batch, dim = (size_t)D.dim;
     // dual averaging of ln eps per chain: Hoffman & Gelman (2014), Algorithm 6 (gamma = 0.05, t0 = 10, kappa = 0.75)
     const double gamma = 0.05, t0 = 10.0, kappa = 0.75;
     std::vector<double> mu(B), h_bar(B, 0.0), log_eps_bar(B, 0.0), cur(eps, eps + B), alpha(B), asum(B, 0.0);
     for (size_t b = 0; b < B; ++b) mu[b] = std::log(10.0 * eps[b]);
-    std::vector<double> q(q_mean || q_var ? B * dim : 0), s1(dim, 0.0), s2(dim, 0.0);
+    // the position moments are summed on the device after every transition (k_hmc_moments: the order of the host loop this replaces,
+    // chains in order inside a transition, transitions in order) and read once at the end
+    const bool moments = q_mean || q_var;
+    std::vector<double> s1(dim, 0.0), s2(dim, 0.0);
     for (int t = 1; t <= n_transitions; ++t) {
         if (int rc = mcd_hmc_nuts(m, cur.data(), inv_mass, max_depth, seed, chain_offset, first_transition + (uint64_t)(t - 1), alpha.data(), nullptr))
             return rc;
@@ -424,22 +461,25 @@ int mcd_hmc_nuts_run(mcd_hmc_t* m, int n_transitions, int adapt, double* eps, co
                 cur[b] = std::exp(log_eps);
             }
         }
-        if (!q.empty()) {
-            HHIP_TRY(hipMemcpy(q.data(), D.q, sizeof(double) * B * dim, hipMemcpyDeviceToHost));
-            for (size_t b = 0; b < B; ++b)
-                for (size_t k = 0; k < dim; ++k) {
-                    const double x = q[b * dim + k];
-                    s1[k] += x;
-                    s2[k] += x * x;
-                }
+        if (moments) {
+            if (t == 1) {                                        // (the first transition has allocated them)
+                HHIP_TRY(hipMemsetAsync(m->d_s1, 0, sizeof(double) * dim, m->stream));
+                HHIP_TRY(hipMemsetAsync(m->d_s2, 0, sizeof(double) * dim, m->stream));
+            }
+            HHIP_TRY(mcd::launch_hmc_moments(D, m->d_s1, m->d_s2, m->stream));
         }
+    }
+    if (moments && n_transitions > 0) {
+        HHIP_TRY(hipMemcpyAsync(s1.data(), m->d_s1, sizeof(double) * dim, hipMemcpyDeviceToHost, m->stream));
+        HHIP_TRY(hipMemcpyAsync(s2.data(), m->d_s2, sizeof(double) * dim, hipMemcpyDeviceToHost, m->stream));
+        HHIP_TRY(hipStreamSynchronize(m->stream));
     }
     for (size_t b = 0; b < B; ++b) {
         if (adapt && n_transitions > 0) eps[b] = std::exp(log_eps_bar[b]);
         if (mean_alpha) mean_alpha[b] = n_transitions > 0 ? asum[b] / n_transitions : 0.0;
     }
     const double cnt = (double)B * (double)(n_transitions > 0 ? n_transitions : 1);
-    for (size_t k = 0; k < dim && !q.empty(); ++k) {
+    for (size_t k = 0; k < dim && moments; ++k) {
         const double mean = s1[k] / cnt;
         if (q_mean) q_mean[k] = mean;
         if (q_var) q_var[k] = s2[k] / cnt - mean * mean;          // pooled over chains and transitions (what mass tuning uses)
@@ -456,6 +496,7 @@ int mcd_hmc_nuts_warmup(mcd_hmc_t* m, int windows, int window, double* eps, doub
 {
     if (!m || !eps || !inv_mass) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_warmup: NULL argument");
     if (windows < 0 || window < 1) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_warmup: need windows >= 0 and window >= 1");
+    if (int rc = rec_room(m, "mcd_hmc_nuts_warmup", ((int64_t)windows + 1) * (int64_t)window)) return rc;
     const size_t B = (size_t)m->dev.batch, dim = (size_t)m->dev.dim;
     std::vector<double> qv(dim), alpha(B);
     uint64_t t = first_transition;
@@ -470,6 +511,150 @@ int mcd_hmc_nuts_warmup(mcd_hmc_t* m, int windows, int window, double* eps, doub
     }
     if (int rc = mcd_hmc_nuts_run(m, window, 1, eps, inv_mass, delta, max_depth, seed, chain_offset, t, alpha.data(), nullptr, nullptr)) return rc;
     if (mean_alpha) std::copy(alpha.begin(), alpha.end(), mean_alpha);
+    return MCD_OK;
+}
+
+// ---- the sample recorder: thinned samples and the transitions' diagnostics kept on the device (k_hmc_record.hip) -----------------------
+int mcd_hmc_record_begin(mcd_hmc_t* m, int32_t period, int64_t capacity_samples)
+{
+    if (!m) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_begin: NULL handle");
+    if (m->d_rec) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_begin: a recorder is active already (mcd_hmc_record_end first)");
+    if (period < 1) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_begin: period must be >= 1 (got %d)", (int)period);
+    if (capacity_samples < 1) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_begin: capacity must be >= 1 sample (got %lld)", (long long)capacity_samples);
+    const mcd::HmcDev& D = m->dev;
+    const int64_t per_sample = D.batch * mcd::mh_rec_stride(D.ld);                 // doubles of one slot
+    if (capacity_samples > ((int64_t)1 << 50) / per_sample)
+        return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_begin: %lld samples of %lld bytes each", (long long)capacity_samples, (long long)per_sample * 8);
+    // the fetch unpacks into a staging buffer of at most 64 MiB (at least one sample) and copies from there, piece by piece
+    const int64_t out_sample = D.batch * (2 * (int64_t)D.n_nodes + 8 + mcd::kHmcRecDiag);
+    const int64_t stage = std::max<int64_t>(1, std::min<int64_t>(capacity_samples, ((int64_t)8 << 20) / out_sample));
+    HHIP_TRY(hipSetDevice(m->device));
+    double *ring = nullptr, *st = nullptr;
+    hipError_t e = hipMalloc((void**)&ring, sizeof(double) * (size_t)(per_sample * capacity_samples));
+    if (e == hipSuccess) e = hipMalloc((void**)&st, sizeof(double) * (size_t)(out_sample * stage));
+    if (e == hipSuccess) e = hipMemsetAsync(ring, 0, sizeof(double) * (size_t)(per_sample * capacity_samples), m->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
+    if (e != hipSuccess) {
+        if (ring) (void)hipFree(ring);
+        if (st) (void)hipFree(st);
+        return hfail(MCD_ERR_HIP, "mcd_hmc_record_begin: %lld samples of %lld bytes each: %s", (long long)capacity_samples, (long long)per_sample * 8, hipGetErrorString(e));
+    }
+    m->d_rec = ring;
+    m->d_rec_stage = st;
+    m->rec_cap = capacity_samples;
+    m->rec_stage_cap = stage;
+    m->rec_period = period;
+    m->rec_iter = 0;
+    m->rec_fetched = 0;
+    return MCD_OK;
+}
+
+int mcd_hmc_record_count(const mcd_hmc_t* m, int64_t* n_samples)
+{
+    if (!m || !n_samples) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_count: NULL argument");
+    if (!m->d_rec) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_count: no recorder is active (mcd_hmc_record_begin first)");
+    *n_samples = m->rec_filled();
+    return MCD_OK;
+}
+
+int mcd_hmc_record_fetch(mcd_hmc_t* m, int64_t max_samples, int64_t* n_out, int64_t* transition, double* scalars, double* heights, double* rates,
+                         double* post, double* nuts)
+{
+    if (!m || !n_out) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_fetch: NULL argument");
+    *n_out = 0;
+    if (!m->d_rec) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_fetch: no recorder is active (mcd_hmc_record_begin first)");
+    if (max_samples < 0) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_fetch: max_samples < 0");
+    const mcd::HmcDev& D = m->dev;
+    const int64_t n = std::min(m->rec_filled(), max_samples), B = D.batch, nn = D.n_nodes, nd = mcd::kHmcRecDiag;
+    const mcd::MhRec R{m->d_rec, 0, m->rec_cap, m->rec_period};
+    const mcd::MhRecDims dims{D.batch, D.ld, D.n_nodes};
+    HHIP_TRY(hipSetDevice(m->device));
+    for (int64_t done = 0; done < n; done += m->rec_stage_cap) {
+        const int64_t cnt = std::min(m->rec_stage_cap, n - done);
+        double* s_sc = m->d_rec_stage;                       // the staging buffer's five arrays for `cnt` samples
+        double* s_H = s_sc + cnt * B * 5;
+        double* s_R = s_H + cnt * B * nn;
+        double* s_post = s_R + cnt * B * nn;
+        double* s_nuts = s_post + cnt * B * 3;
+        HHIP_TRY(mcd::launch_mh_rec_unpack(dims, R, m->rec_fetched + done, cnt, scalars ? s_sc : nullptr, heights ? s_H : nullptr, rates ? s_R : nullptr,
+                                           post ? s_post : nullptr, nullptr, nuts ? s_nuts : nullptr, m->stream));
+        const size_t c = sizeof(double) * (size_t)(cnt * B), o = (size_t)(done * B);
+        if (scalars) HHIP_TRY(hipMemcpyAsync(scalars + o * 5, s_sc, c * 5, hipMemcpyDeviceToHost, m->stream));
+        if (heights) HHIP_TRY(hipMemcpyAsync(heights + o * (size_t)nn, s_H, c * (size_t)nn, hipMemcpyDeviceToHost, m->stream));
+        if (rates) HHIP_TRY(hipMemcpyAsync(rates + o * (size_t)nn, s_R, c * (size_t)nn, hipMemcpyDeviceToHost, m->stream));
+        if (post) HHIP_TRY(hipMemcpyAsync(post + o * 3, s_post, c * 3, hipMemcpyDeviceToHost, m->stream));
+        if (nuts) HHIP_TRY(hipMemcpyAsync(nuts + o * (size_t)nd, s_nuts, c * (size_t)nd, hipMemcpyDeviceToHost, m->stream));
+        HHIP_TRY(hipStreamSynchronize(m->stream));           // (the next piece reuses the staging buffer)
+    }
+    if (transition)
+        for (int64_t i = 0; i < n; ++i) transition[i] = (m->rec_fetched + 1 + i) * m->rec_period;
+    m->rec_fetched += n;
+    *n_out = n;
+    return MCD_OK;
+}
+
+int mcd_hmc_record_end(mcd_hmc_t* m)
+{
+    if (!m) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_end: NULL handle");
+    if (!m->d_rec) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_end: no recorder is active (mcd_hmc_record_begin first)");
+    HHIP_TRY(hipSetDevice(m->device));
+    HHIP_TRY(hipStreamSynchronize(m->stream));
+    (void)hipFree(m->d_rec);
+    (void)hipFree(m->d_rec_stage);
+    m->d_rec = m->d_rec_stage = nullptr;
+    m->rec_cap = m->rec_stage_cap = m->rec_iter = m->rec_fetched = 0;
+    m->rec_period = 0;
+    return MCD_OK;
+}
+
+int mcd_hmc_record_quantities(const mcd_hmc_t* m, int64_t* q)
+{
+    if (!m || !q) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_quantities: NULL argument");
+    *q = 2 * (int64_t)m->dev.n_nodes + 9;
+    return MCD_OK;
+}
+
+int mcd_hmc_record_summary(mcd_hmc_t* m, int64_t skip, int64_t n_samples, int32_t max_lag, int64_t* n_used, double* pooled, double* per_chain,
+                           double* nuts_stats)
+{
+    if (!m || !pooled) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_summary: NULL argument");
+    if (n_used) *n_used = 0;
+    if (!m->d_rec) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_summary: no recorder is active (mcd_hmc_record_begin first)");
+    const mcd::HmcDev& D = m->dev;
+    const int64_t waiting = m->rec_filled();
+    if (skip < 0 || skip >= waiting)
+        return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_summary: skip = %lld, %lld samples are waiting", (long long)skip, (long long)waiting);
+    const int64_t n = n_samples < 0 ? waiting - skip : n_samples;
+    if (n < 1 || n > waiting - skip)
+        return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_summary: the window [%lld, %lld) ends past the %lld waiting samples", (long long)skip,
+                     (long long)(skip + n), (long long)waiting);
+    const int64_t Q = 2 * (int64_t)D.n_nodes + 9;
+    if (int rc = mcd_summary_check_("mcd_hmc_record_summary", n, D.batch, Q, max_lag)) return rc;
+    HHIP_TRY(hipSetDevice(m->device));
+    HHIP_TRY(hipStreamSynchronize(m->stream));
+    mcd::SumSrc S{};
+    S.base = m->d_rec;
+    S.n = n;
+    S.B = D.batch;
+    S.Q = Q;
+    S.ring = 1;
+    S.n_nodes = D.n_nodes;
+    S.first = (m->rec_fetched + skip) % m->rec_cap;            // sample number k (1, 2, ...) lies in slot (k - 1) mod capacity
+    S.cap = m->rec_cap;
+    S.stride = mcd::mh_rec_stride(D.ld);
+    S.ld = D.ld;
+    if (int rc = mcd_summary_run_(S, max_lag, m->stream, pooled, per_chain)) return rc;
+    if (nuts_stats) {
+        double* d_stats = nullptr;
+        HHIP_TRY(hipMalloc((void**)&d_stats, sizeof(double) * 4 * (size_t)D.batch));
+        hipError_t e = mcd::launch_hmc_record_stats(mcd::MhRecDims{D.batch, D.ld, D.n_nodes}, mcd::MhRec{m->d_rec, 0, m->rec_cap, m->rec_period}, S.first, n,
+                                                    d_stats, m->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(nuts_stats, d_stats, sizeof(double) * 4 * (size_t)D.batch, hipMemcpyDeviceToHost, m->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
+        (void)hipFree(d_stats);
+        if (e != hipSuccess) return hfail(MCD_ERR_HIP, "mcd_hmc_record_summary: diagnostics: %s", hipGetErrorString(e));
+    }
+    if (n_used) *n_used = n;
     return MCD_OK;
 }
 

@@ -733,10 +733,11 @@ __global__ __launch_bounds__(256) void k_mh_tune(MhDev M)
     M.tried[i] = 0;
 }
 
-// mcd_mh_record_fetch: the records of the recorder's ring (MhRec, mvn_kernels.h: per chain heights, rates, then the nine scalars) as the
-// sample-major arrays the host takes; one workgroup per (sample, chain), threads = nodes
-__global__ __launch_bounds__(256) void k_mh_rec_unpack(MhDev M, MhRec R, int64_t first, double* __restrict__ scalars, double* __restrict__ heights,
-                                                       double* __restrict__ rates, double* __restrict__ post, double* __restrict__ beta)
+// mcd_mh_record_fetch / mcd_hmc_record_fetch: the records of a recorder's ring (MhRec, mvn_kernels.h: per chain heights, rates, then the nine
+// scalars and the doubles behind them) as the sample-major arrays the host takes; one workgroup per (sample, chain), threads = nodes
+__global__ __launch_bounds__(256) void k_mh_rec_unpack(MhRecDims M, MhRec R, int64_t first, double* __restrict__ scalars, double* __restrict__ heights,
+                                                       double* __restrict__ rates, double* __restrict__ post, double* __restrict__ beta,
+                                                       double* __restrict__ diag)
 {
     const int64_t i = (int64_t)blockIdx.x / M.batch, b = (int64_t)blockIdx.x - i * M.batch;
     const int64_t slot = (first + i) % R.capacity;
@@ -751,14 +752,15 @@ __global__ __launch_bounds__(256) void k_mh_rec_unpack(MhDev M, MhRec R, int64_t
     if (scalars && tid < 5) scalars[o * 5 + tid] = t[tid];
     if (post && tid < 3) post[o * 3 + tid] = t[5 + tid];
     if (beta && tid == 0) beta[o] = t[8];
+    if (diag && tid < kHmcRecDiag) diag[o * kHmcRecDiag + tid] = t[9 + tid];
 }
 
-hipError_t launch_mh_rec_unpack(const MhDev& M, const MhRec& R, int64_t first, int64_t count, double* scalars, double* heights, double* rates,
-                                double* post, double* beta, hipStream_t st)
+hipError_t launch_mh_rec_unpack(const MhRecDims& M, const MhRec& R, int64_t first, int64_t count, double* scalars, double* heights, double* rates,
+                                double* post, double* beta, double* diag, hipStream_t st)
 {
     if (count <= 0) return hipSuccess;
     if (R.base == nullptr || count * M.batch > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_mh_rec_unpack, dim3((unsigned)(count * M.batch)), dim3(256), 0, st, M, R, first, scalars, heights, rates, post, beta);
+    hipLaunchKernelGGL(k_mh_rec_unpack, dim3((unsigned)(count * M.batch)), dim3(256), 0, st, M, R, first, scalars, heights, rates, post, beta, diag);
     return hipGetLastError();
 }
 

@@ -168,6 +168,7 @@ __global__ __launch_bounds__(256) void k_nuts_begin(HmcDev D, NutsDev N, uint64_
         N.leaf[b] = 0;
         N.depth[b] = 0;
         N.done[b] = 0;
+        N.diverged[b] = 0;
     }
     __syncthreads();
     nuts_launch_leaf(D, N, b, v);
@@ -214,6 +215,7 @@ __global__ __launch_bounds__(256) void k_nuts_step(HmcDev D, NutsDev N, uint64_t
     const bool sl = log_u < NUTS_DELTA_MAX + joint;
     int n1 = N.n1[b] + (nl ? 1 : 0);
     bool s1 = N.s1[b] != 0 && sl;
+    if (!sl && threadIdx.x == 0) N.diverged[b] = 1;                 // what the sample recorder reports (k_hmc_record.hip)
     const int leaf = N.leaf[b];
     if (nl) {                                                       // reservoir over the admissible leaves of the sub tree
         double ua, ub;

@@ -1189,8 +1189,9 @@ int mcd_mh_record_fetch(mcd_mh_t* m, int64_t max_samples, int64_t* n_out, int64_
         double* s_R = s_H + cnt * B * nn;
         double* s_post = s_R + cnt * B * nn;
         double* s_beta = s_post + cnt * B * 3;
-        MHIP_TRY(mcd::launch_mh_rec_unpack(D, R, m->rec_fetched + done, cnt, scalars ? s_sc : nullptr, heights ? s_H : nullptr, rates ? s_R : nullptr,
-                                           post ? s_post : nullptr, beta ? s_beta : nullptr, m->stream));
+        MHIP_TRY(mcd::launch_mh_rec_unpack(mcd::MhRecDims{D.batch, D.ld, D.n_nodes}, R, m->rec_fetched + done, cnt, scalars ? s_sc : nullptr,
+                                           heights ? s_H : nullptr, rates ? s_R : nullptr, post ? s_post : nullptr, beta ? s_beta : nullptr, nullptr,
+                                           m->stream));
         const size_t c = sizeof(double) * (size_t)(cnt * B), o = (size_t)(done * B);
         if (scalars) MHIP_TRY(hipMemcpyAsync(scalars + o * 5, s_sc, c * 5, hipMemcpyDeviceToHost, m->stream));
         if (heights) MHIP_TRY(hipMemcpyAsync(heights + o * (size_t)nn, s_H, c * (size_t)nn, hipMemcpyDeviceToHost, m->stream));

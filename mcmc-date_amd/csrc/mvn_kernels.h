@@ -101,6 +101,11 @@ struct MhRec {
     int32_t period;
 };
 __host__ __device__ inline int64_t mh_rec_stride(int64_t ld) { return 2 * ld + 16; }
+// what the ring's readers need of the driver that filled it (the Metropolis-Hastings driver's MhDev, the NUTS driver's HmcDev)
+struct MhRecDims {
+    int64_t batch, ld;
+    int n_nodes;
+};
 
 // Lock-step Metropolis-Hastings workspace of one batch of chains (k_mh.hip); all pointers are device memory.
 struct MhDev {
@@ -285,11 +290,22 @@ struct NutsDev {
     double *sq, *sp;                        // [batch][max_depth][dim] first leaf (position, momentum) of the open sub tree of 2^k leaves
     double *log_u, *joint0, *alpha;         // [batch] slice variable, -H at the start, sum of min(1, exp(H0 - H)) over the leaves
     int *j, *v, *i, *n, *n1, *s1, *done, *n_alpha, *depth, *leaf;   // [batch] doubling, direction, leaf index, counts, flags
+    int* diverged;                          // [batch] 1: a leaf of this transition failed log_u < NUTS_DELTA_MAX + joint
 };
 hipError_t launch_nuts_begin(const HmcDev& D, const NutsDev& N, uint64_t seed, int64_t chain0, uint64_t transition, hipStream_t st);
 hipError_t launch_nuts_step(const HmcDev& D, const NutsDev& N, uint64_t seed, int64_t chain0, uint64_t transition, int max_depth, int* active,
                             hipStream_t st);
 hipError_t launch_nuts_end(const HmcDev& D, const NutsDev& N, hipStream_t st);
+// The NUTS driver's sample recorder (k_hmc_record.hip; mcd_hmc_record_*): the state the handle holds after a transition as sample number
+// `sample` (1, 2, ...) of the ring R -- the MhRec slot layout, slot (sample - 1) % capacity, beta = 1; the seven doubles that are padding in
+// a Metropolis-Hastings record carry the transition's diagnostics: tree depth, leapfrog steps, acceptance statistic alpha / max(n_alpha, 1),
+// diverged flag, the step size used, joint0 (-H at the start of the transition), 0.  D.lp / D.ll must be the accepted point's.
+constexpr int kHmcRecDiag = 6;        // diagnostics handed out per (sample, chain): the first six of those seven
+hipError_t launch_hmc_record(const HmcDev& D, const NutsDev& N, const MhRec& R, int64_t sample, hipStream_t st);
+// per chain over the `count` samples from slot `first` on: divergent transitions, mean depth, maximum depth, leapfrog steps; stats [batch][4]
+hipError_t launch_hmc_record_stats(const MhRecDims& S, const MhRec& R, int64_t first, int64_t count, double* stats, hipStream_t st);
+// s1[k] += sum_b q[b][k], s2[k] += sum_b q[b][k]^2 in the order b = 0, 1, ... (what mcd_hmc_nuts_run adds per transition); s1, s2 [dim]
+hipError_t launch_hmc_moments(const HmcDev& D, double* s1, double* s2, hipStream_t st);
 
 int padded_blocks(int n);          // supported R for dimension n, or -1
 int sweep_chunk_columns(int R);    // columns per register buffer (ncols granularity)
@@ -376,9 +392,10 @@ hipError_t launch_mh_step(const MhDev& M, const PriorDev& P, int p_acc, int jac_
 bool mh_step_wg_fits(int n_nodes);
 hipError_t launch_mh_tune(const MhDev& M, hipStream_t st);
 // `count` samples of the recorder's ring from slot `first` on, into the sample-major arrays that mcd_mh_record_fetch hands out (device
-// staging; any may be null): scalars [count][batch][5], heights / rates [count][batch][n_nodes], post [count][batch][3], beta [count][batch]
-hipError_t launch_mh_rec_unpack(const MhDev& M, const MhRec& R, int64_t first, int64_t count, double* scalars, double* heights, double* rates,
-                                double* post, double* beta, hipStream_t st);
+// staging; any may be null): scalars [count][batch][5], heights / rates [count][batch][n_nodes], post [count][batch][3], beta [count][batch],
+// diag [count][batch][kHmcRecDiag] (the doubles behind beta: padding in the Metropolis-Hastings driver's records, mcd_hmc_record_*'s diagnostics)
+hipError_t launch_mh_rec_unpack(const MhRecDims& S, const MhRec& R, int64_t first, int64_t count, double* scalars, double* heights, double* rates,
+                                double* post, double* beta, double* diag, hipStream_t st);
 hipError_t launch_mc3_swap(const Mc3Dev& C, const double* lnpost, int world, int64_t per_rank, int n_swaps, uint64_t seed, uint64_t phase,
                            double* beta_local, int64_t chain0, int64_t batch, hipStream_t st);
 // ln prior of the proposed states from pflags / pcomp (what launch_mh_step leaves when asked not to evaluate it itself) as extra

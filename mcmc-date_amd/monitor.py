@@ -10,7 +10,8 @@ Host-side mirror of
     the sorted ages as slice(floor(0.025 l), floor(0.95 l)).
 
 The states come from the device sampler -- `record`: kept on the device while it runs (mcd_mh_record_*) and fetched once per
-chunk of iterations; `collect`: `Sampler.state()` after every run of `period` iterations --; nothing here computes a
+chunk of iterations (`record_nuts`: the same for the NUTS driver, mcd_hmc_record_*); `collect`: `Sampler.state()` after every run of
+`period` iterations --; nothing here computes a
 likelihood or a prior on the host -- the prior blocks are evaluated by the device prior (`PriorFunction.logprior`).
 """
 from __future__ import annotations
@@ -41,6 +42,7 @@ class Trace:
     rates: np.ndarray
     post: Optional[np.ndarray] = None    # [n_samples, B, 3] ln prior, ln likelihood, ln jacobianRootBranch (`record` only)
     beta: Optional[np.ndarray] = None    # [n_samples, B] reciprocal temperature of the chain when the sample was taken (`record` only)
+    nuts: Optional[np.ndarray] = None    # [n_samples, B, 6] hmc.Leapfrog.NUTS_FIELDS of the transition behind the sample (`record_nuts` only)
 
     def ages(self) -> np.ndarray:
         """Absolute node ages tH * h_v, [n_samples, B, n_nodes] (getTimeTreeNodeHeight, app/Definitions.hs:300-304)."""
@@ -93,6 +95,34 @@ def record(sampler, n_iter: int, period: int = PERIOD, accumulate: bool = False,
         return Trace(np.empty(0, np.int64), e, e, e, e, e, e, e, e, e)
     it, sc, H, R, post, beta = (np.concatenate([p[i] for p in parts]) for i in range(6))
     return Trace(base + it, sc[..., 0], sc[..., 1], sc[..., 2], H, sc[..., 3], sc[..., 4], R, post, beta)
+
+
+def record_nuts(lf, n_transitions: int, eps, inv_mass, period: int = PERIOD, chunk: int = 256, max_depth: int = 8, seed: int = 0,
+                first_transition: int = 0, chain_offset: int = 0) -> Trace:
+    """`record` for the NUTS driver (hmc.Leapfrog; runs with `--hamiltonian`): n_transitions transitions at fixed step sizes and masses in
+    calls of up to `chunk` transitions (Leapfrog.nuts_run), the recorder keeping every `period`-th state on the device with the
+    transition's diagnostics (Trace.nuts), one fetch per chunk.  `iteration` counts the transitions of the random streams
+    (first_transition + ...), so a trace continues where the last one ended.  The trace feeds write_monitor_files as any other; for a
+    summary without a fetch call summarize_recorded(lf) between lf.record_begin and lf.record_end instead."""
+    if n_transitions < 0 or period < 1 or chunk < 1:
+        raise ValueError("record_nuts: need n_transitions >= 0, period >= 1, chunk >= 1")
+    parts: List[tuple] = []
+    lf.record_begin(period, (chunk + period - 1) // period)           # (what one chunk can add at most)
+    try:
+        done = 0
+        while done < n_transitions:
+            k = min(chunk, n_transitions - done)
+            lf.nuts_run(k, eps, inv_mass, adapt=False, max_depth=max_depth, seed=seed, first_transition=first_transition + done,
+                        chain_offset=chain_offset)
+            done += k
+            parts.append(lf.record_fetch())
+    finally:
+        lf.record_end()
+    if not parts or sum(len(p[0]) for p in parts) == 0:
+        e = np.empty((0,))
+        return Trace(np.empty(0, np.int64), e, e, e, e, e, e, e, e, None, e)
+    it, sc, H, R, post, nuts = (np.concatenate([p[i] for p in parts]) for i in range(6))
+    return Trace(first_transition + it, sc[..., 0], sc[..., 1], sc[..., 2], H, sc[..., 3], sc[..., 4], R, post, None, nuts)
 
 
 def prior_components(prior, trace: Trace, piece: int = 1 << 16) -> np.ndarray:
@@ -213,7 +243,8 @@ def summarize_node_ages(ages: np.ndarray, burn_in: float = 0.25, names: Optional
 def summarize_recorded(sampler, burn_in: float = 0.25, names: Optional[Sequence[str]] = None, max_lag: int = 255) -> AgeSummary:
     """`summarize_node_ages` of the pooled ages of the samples waiting in the sampler's recorder, after dropping the oldest
     round(waiting * burn_in) of them -- computed on the device where the samples lie (Sampler.record_summary): nothing is fetched and the
-    samples stay where they are.  Also gives the split R-hat and the effective sample size of every node's age over the chains."""
+    samples stay where they are.  Also gives the split R-hat and the effective sample size of every node's age over the chains.
+    `sampler`: a Sampler or an hmc.Leapfrog with an active recorder (both have record_count / record_summary)."""
     waiting = sampler.record_count()
     skip = int(round(waiting * burn_in))
     if skip >= waiting:

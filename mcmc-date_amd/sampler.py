@@ -416,6 +416,7 @@ class RecordSummary:
     n_samples: int
     max_lag: int
     per_chain: Optional[np.ndarray] = None
+    nuts_stats: Optional[np.ndarray] = None    # [B, 4] hmc.Leapfrog.NUTS_STATS of the window (Leapfrog.record_summary only)
 
     SCALARS = ("time_birth_rate", "time_death_rate", "time_height", "rate_mean", "rate_variance")
     POST = ("ln_prior", "ln_likelihood", "ln_jacobian_root_branch", "ln_posterior")

@@ -1,0 +1,125 @@
+#!/usr/bin/env python
+"""Device NUTS (mcd_hmc_nuts*) with and without its sample recorder: transitions per second of the SAME run -- same start states, step
+sizes, masses and random streams -- three ways:
+  unrecorded   one mcd_hmc_nuts_run of --transitions transitions, nothing kept;
+  recorded     the same with the device recorder at --record PERIOD, drained once per chunk of 256 transitions, the drain inside the timed
+               region (monitor.record_nuts);
+  cut          one mcd_hmc_nuts per transition with a state read-back after each (mcd_hmc_get_state): what a caller who wants every sample
+               had to do before the recorder (the read-back does not depend on PERIOD: a caller cannot know the state without it).
+  --name NAME            a committed input (dense likelihood), Metropolis-Hastings burn-in for the start states
+  --synthetic N_LEAVES   a random tree over a banded sparse precision matrix around the states' own distances (2 N_LEAVES - 1 nodes)
+One JSON line per run; *_runs hold every repeat, the headline figures are their medians."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import mcmc_date_amd as M  # noqa: E402
+from mcmc_date_amd import monitor  # noqa: E402
+
+
+def golden_problem(name, B):
+    fx = dict(np.load(os.path.join(ROOT, "tests", "golden", name + ".npz")))
+    topo = M.Topology(fx["parent"])
+    cal = [M.Calibration(f"c{i}", int(r[0]), r[2] if r[1] else None, r[3], r[5] if r[4] else None, r[6]) for i, r in enumerate(fx["cal"])]
+    con = [M.Constraint(f"k{i}", int(r[0]), int(r[1]), r[2]) for i, r in enumerate(fx["con"])]
+    br = [M.Brace(f"b{i}", [int(n) for n in fx["brace_nodes"][fx["brace_ptr"][i]:fx["brace_ptr"][i + 1]]], float(s)) for i, s in enumerate(fx["brace_sd"])]
+    ht = float(fx["prior_ht"])
+    pf = M.PriorFunction(ht, "UncorrelatedGamma", cal, con, br, topo)
+    lik = M.MvnLikelihood(M.Full(fx["mu"], fx["sigma_inv"], float(fx["logdet"]))).bind_tree(topo)
+    ps, _ = M.proposals(topo, br, calibrations_available=len(cal) > 0)
+    smp = M.Sampler(lik, pf, ps, B, seed=3)
+    x0 = M.init_with(topo, fx["mean_lengths"])
+    if cal:
+        x0.time_height = ht
+    smp.set_initial_state(x0)
+    smp.burn_in(fast=[10, 10, 20, 40], slow=[100, 100])
+    lf = M.Leapfrog(lik, pf, len(cal) > 0, B)
+    lf.set_state(smp.state())
+    q0 = lf.position()[0]
+    inv_mass = np.maximum((0.1 * np.abs(q0)).mean(axis=0) ** 2, 1e-12)
+    eps, _, _, _ = lf.nuts_run(40, 0.05, inv_mass, adapt=True, max_depth=5, seed=1)
+    return topo, lf, eps, inv_mass, "dense"
+
+
+def synthetic_problem(n_leaves, B):
+    import oracle as O
+    from mcmc_date_amd import synthetic as S
+
+    topo = S.random_topology(n_leaves, seed=5)
+    n = topo.n_nodes - 2
+    _, assoc = S.banded_precision(n, seed=5)
+    st0 = S.random_states(topo, 1, seed=7)
+    mu = O.distances(topo.parent, st0.heights[0], st0.rates[0], st0.time_height[0], st0.rate_mean[0])
+    lik = M.SparseLikelihood(M.Sparse(mu, assoc, 0.0)).bind_tree(topo)
+    pf = M.PriorFunction(1.0, "UncorrelatedGamma", [], [], [], topo)
+    st = S.random_states(topo, B, seed=7, jitter=0.002)
+    rng = np.random.default_rng(12)
+    full = M.StateBatch(st.heights, st.rates, st.time_height, st.rate_mean, np.exp(0.1 * rng.standard_normal(B)), np.exp(0.1 * rng.standard_normal(B)),
+                        0.5 + 0.2 * rng.random(B))
+    lf = M.Leapfrog(lik, pf, False, B)
+    lf.set_state(full)
+    q0, _, g0 = lf.position()
+    # masses from the positions' own scales, step sizes from the gradient in those scales (tests/test_gpu_sparse_hmc.py)
+    inv_mass = np.maximum((0.1 * np.abs(q0)).mean(axis=0) ** 2, 1e-60)
+    eps = 1e-2 / np.maximum(1.0, (np.abs(g0) * np.sqrt(inv_mass)).max(axis=1))
+    return topo, lf, eps, inv_mass, "sparse"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--name", default="24-leaves-braces")
+    ap.add_argument("--synthetic", type=int, default=0)
+    ap.add_argument("--chains", type=int, default=128)
+    ap.add_argument("--transitions", type=int, default=60)
+    ap.add_argument("--max-depth", type=int, default=5)
+    ap.add_argument("--record", type=int, default=1)
+    ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=5)
+    args = ap.parse_args()
+    B, T = args.chains, args.transitions
+    topo, lf, eps, inv_mass, form = synthetic_problem(args.synthetic, B) if args.synthetic else golden_problem(args.name, B)
+    start = lf.state()
+    kw = dict(max_depth=args.max_depth, seed=args.seed)
+
+    def timed(fn):
+        lf.set_state(start)
+        t0 = time.perf_counter()
+        fn()
+        return time.perf_counter() - t0
+
+    def cut():
+        for t in range(T):
+            lf.nuts(eps, inv_mass, transition=t, **kw)
+            lf.state()
+
+    timed(lambda: lf.nuts_run(2, eps, inv_mass, adapt=False, **kw))                     # (code objects, allocations)
+    runs = {"unrecorded": [], "recorded": [], "cut": []}
+    ends = {}
+    for _ in range(max(1, args.repeat)):
+        runs["unrecorded"].append(timed(lambda: lf.nuts_run(T, eps, inv_mass, adapt=False, **kw)))
+        ends["unrecorded"] = lf.state()
+        runs["recorded"].append(timed(lambda: monitor.record_nuts(lf, T, eps, inv_mass, period=args.record, chunk=256, **kw)))
+        ends["recorded"] = lf.state()
+        runs["cut"].append(timed(cut))
+        ends["cut"] = lf.state()
+    same = all(np.array_equal(ends["unrecorded"].heights, ends[k].heights) and np.array_equal(ends["unrecorded"].rates, ends[k].rates) for k in ends)
+    rate = {k: T / float(np.median(v)) for k, v in runs.items()}
+    spread = {k: (max(v) - min(v)) / float(np.median(v)) for k, v in runs.items()}
+    print(json.dumps({"metric": "NUTS transitions/s (all chains in lock step)", "dataset": f"synthetic {args.synthetic} leaves" if args.synthetic else args.name,
+                      "likelihood": form, "n_nodes": topo.n_nodes, "chains": B, "transitions": T, "max_depth": args.max_depth, "record_period": args.record,
+                      "unrecorded_transitions_per_s": rate["unrecorded"], "recorded_transitions_per_s": rate["recorded"],
+                      "cut_transitions_per_s": rate["cut"], "recorded_over_cut": rate["recorded"] / rate["cut"],
+                      "recorded_over_unrecorded": rate["recorded"] / rate["unrecorded"], "same_end_state": bool(same),
+                      "relative_spread": spread, **{k + "_s_runs": v for k, v in runs.items()}}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
