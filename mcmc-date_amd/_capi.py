@@ -165,6 +165,16 @@ def lib():
     return _lib
 
 
+def record_ring_selftest(period: int, cap: int, it: int, fetched: int, n: int, skip: int):
+    """Test hook mcd_record_ring_selftest_ (csrc/recorder.cpp; outside the header, no device, no handle): (samples that n more iterations add,
+    free slots, waiting samples, slot of waiting sample `skip`) of a ring in this state, by the counts every mcd_*_record_* call uses."""
+    f = lib().mcd_record_ring_selftest_
+    f.restype, f.argtypes = C.c_int, [C.c_int32] + [C.c_int64] * 5 + [C.POINTER(C.c_int64)]
+    out = (C.c_int64 * 4)()
+    check(f(period, cap, it, fetched, n, skip, out))
+    return tuple(out)
+
+
 def set_option(name: str, value=None):
     """A test / tuning knob of the library (include/mcmcdate_mvn.h: mcd_set_option): value = an integer (or its string), None = back to the
     default.  The names are the environment variables of rounds 1-3 ("MCD_MH_SEGMENTS", "MCD_SPLIT", ...); the environment itself is read

@@ -12,10 +12,10 @@
 
 #include "../../include/mcmcdate_mvn.h"
 #include "mvn_kernels.h"
+#include "recorder.hpp"
 #include "summary_device.hpp"
 
-int mcd_summary_check_(const char* who, int64_t n, int64_t batch, int64_t q, int32_t max_lag);                       // summary_capi.cpp
-int mcd_summary_run_(const mcd::SumSrc& S, int32_t max_lag, hipStream_t st, double* pooled, double* per_chain);
+int mcd_summary_run_(const mcd::SumSrc& S, int32_t max_lag, hipStream_t st, double* pooled, double* per_chain);   // summary_capi.cpp
 extern "C" int mcd_set_last_error_(int code, const char* msg);   // mvn_capi.cpp
 
 namespace {
@@ -54,20 +54,13 @@ struct mcd_hmc {
     bool have_state = false;
     hipStream_t stream = nullptr;
     std::vector<void*> allocs;
-    // the sample recorder (mcd_hmc_record_*): a ring of rec_cap slots (mcd::MhRec), the staging buffer of the fetch (rec_stage_cap samples);
-    // rec_iter = transitions since begin, so rec_iter / rec_period samples were taken, rec_fetched of them handed out
-    double* d_rec = nullptr;
-    double* d_rec_stage = nullptr;
-    int64_t rec_cap = 0, rec_stage_cap = 0, rec_iter = 0, rec_fetched = 0;
-    int32_t rec_period = 0;
-    int64_t rec_filled() const { return rec_iter / rec_period - rec_fetched; }
+    mcd::Recorder rec{"mcd_hmc_record"};       // the sample recorder (mcd_hmc_record_*, recorder.cpp): it counts transitions
+    mcd::RecOn rec_on() const { return {device, stream, mcd::MhRecDims{dev.batch, dev.ld, dev.n_nodes}}; }
 
     ~mcd_hmc()
     {
         (void)hipSetDevice(device);
         for (void* p : allocs) (void)hipFree(p);
-        if (d_rec) (void)hipFree(d_rec);
-        if (d_rec_stage) (void)hipFree(d_rec_stage);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -354,17 +347,6 @@ int nuts_alloc(mcd_hmc* m)
     return halloc(m, &m->d_active, 1);
 }
 
-// The recorder's host-side check, the contract of mcd_hmc_record_*: `n` more transitions must fit the free slots; nothing is launched otherwise
-int rec_room(const mcd_hmc* m, const char* who, int64_t n)
-{
-    if (!m->d_rec) return MCD_OK;
-    const int64_t adds = (m->rec_iter + n) / m->rec_period - m->rec_iter / m->rec_period, free_slots = m->rec_cap - m->rec_filled();
-    if (adds > free_slots)
-        return hfail(MCD_ERR_INVALID_ARG, "%s: the call would record %lld samples, the recorder has %lld free slots (mcd_hmc_record_fetch frees them)", who,
-                     (long long)adds, (long long)free_slots);
-    return MCD_OK;
-}
-
 // one transition for every chain; eps and inv_mass already on the device
 int nuts_transition(mcd_hmc* m, int max_depth, uint64_t seed, int64_t chain0, uint64_t transition)
 {
@@ -388,11 +370,7 @@ int nuts_transition(mcd_hmc* m, int max_depth, uint64_t seed, int64_t chain0, ui
     if (int rc = eval_gradients(m)) return rc;
     HHIP_TRY(mcd::launch_hmc_collect(D, m->stream));
     // the sample recorder: D.lp / D.ll are the accepted point's now, D.eps the step sizes the transition used
-    if (m->d_rec) {
-        m->rec_iter += 1;
-        if (m->rec_iter % m->rec_period == 0)
-            HHIP_TRY(mcd::launch_hmc_record(D, m->nuts, mcd::MhRec{m->d_rec, 0, m->rec_cap, m->rec_period}, m->rec_iter / m->rec_period, m->stream));
-    }
+    if (m->rec.step()) HHIP_TRY(mcd::launch_hmc_record(D, m->nuts, m->rec.view(), m->rec.counts().taken(), m->stream));
     return MCD_OK;
 }
 
@@ -412,7 +390,7 @@ int mcd_hmc_nuts(mcd_hmc_t* m, const double* eps, const double* inv_mass, int ma
         if (!(inv_mass[k] > 0) || !std::isfinite(inv_mass[k])) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts: inverse masses must be positive");
     for (size_t b = 0; b < B; ++b)
         if (!(eps[b] > 0) || !std::isfinite(eps[b])) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts: step sizes must be positive");
-    if (int rc = rec_room(m, "mcd_hmc_nuts", 1)) return rc;
+    if (int rc = m->rec.room("mcd_hmc_nuts", 1)) return rc;
     HHIP_TRY(hipSetDevice(m->device));
     if (int rc = nuts_alloc(m)) return rc;
     HHIP_TRY(hipMemcpyAsync(m->d_eps, eps, sizeof(double) * B, hipMemcpyHostToDevice, m->stream));
@@ -437,7 +415,7 @@ int mcd_hmc_nuts_run(mcd_hmc_t* m, int n_transitions, int adapt, double* eps, co
     if (!m || !eps || !inv_mass) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_run: NULL argument");
     if (n_transitions < 0) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_run: negative number of transitions");
     if (adapt && !(delta > 0 && delta < 1)) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_run: delta must be in (0, 1)");
-    if (int rc = rec_room(m, "mcd_hmc_nuts_run", n_transitions)) return rc;
+    if (int rc = m->rec.room("mcd_hmc_nuts_run", n_transitions)) return rc;
     const mcd::HmcDev& D = m->dev;
     const size_t B = (size_t)D.batch, dim = (size_t)D.dim;
     // dual averaging of ln eps per chain: Hoffman & Gelman (2014), Algorithm 6 (gamma = 0.05, t0 = 10, kappa = 0.75)
@@ -496,7 +474,7 @@ int mcd_hmc_nuts_warmup(mcd_hmc_t* m, int windows, int window, double* eps, doub
 {
     if (!m || !eps || !inv_mass) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_warmup: NULL argument");
     if (windows < 0 || window < 1) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_warmup: need windows >= 0 and window >= 1");
-    if (int rc = rec_room(m, "mcd_hmc_nuts_warmup", ((int64_t)windows + 1) * (int64_t)window)) return rc;
+    if (int rc = m->rec.room("mcd_hmc_nuts_warmup", ((int64_t)windows + 1) * (int64_t)window)) return rc;
     const size_t B = (size_t)m->dev.batch, dim = (size_t)m->dev.dim;
     std::vector<double> qv(dim), alpha(B);
     uint64_t t = first_transition;
@@ -514,97 +492,27 @@ int mcd_hmc_nuts_warmup(mcd_hmc_t* m, int windows, int window, double* eps, doub
     return MCD_OK;
 }
 
-// ---- the sample recorder: thinned samples and the transitions' diagnostics kept on the device (k_hmc_record.hip) -----------------------
+// ---- the sample recorder: thinned samples and the transitions' diagnostics kept on the device (k_hmc_record.hip; host side: recorder.cpp) ----
 int mcd_hmc_record_begin(mcd_hmc_t* m, int32_t period, int64_t capacity_samples)
 {
-    if (!m) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_begin: NULL handle");
-    if (m->d_rec) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_begin: a recorder is active already (mcd_hmc_record_end first)");
-    if (period < 1) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_begin: period must be >= 1 (got %d)", (int)period);
-    if (capacity_samples < 1) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_begin: capacity must be >= 1 sample (got %lld)", (long long)capacity_samples);
-    const mcd::HmcDev& D = m->dev;
-    const int64_t per_sample = D.batch * mcd::mh_rec_stride(D.ld);                 // doubles of one slot
-    if (capacity_samples > ((int64_t)1 << 50) / per_sample)
-        return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_begin: %lld samples of %lld bytes each", (long long)capacity_samples, (long long)per_sample * 8);
-    // the fetch unpacks into a staging buffer of at most 64 MiB (at least one sample) and copies from there, piece by piece
-    const int64_t out_sample = D.batch * (2 * (int64_t)D.n_nodes + 8 + mcd::kHmcRecDiag);
-    const int64_t stage = std::max<int64_t>(1, std::min<int64_t>(capacity_samples, ((int64_t)8 << 20) / out_sample));
-    HHIP_TRY(hipSetDevice(m->device));
-    double *ring = nullptr, *st = nullptr;
-    hipError_t e = hipMalloc((void**)&ring, sizeof(double) * (size_t)(per_sample * capacity_samples));
-    if (e == hipSuccess) e = hipMalloc((void**)&st, sizeof(double) * (size_t)(out_sample * stage));
-    if (e == hipSuccess) e = hipMemsetAsync(ring, 0, sizeof(double) * (size_t)(per_sample * capacity_samples), m->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-    if (e != hipSuccess) {
-        if (ring) (void)hipFree(ring);
-        if (st) (void)hipFree(st);
-        return hfail(MCD_ERR_HIP, "mcd_hmc_record_begin: %lld samples of %lld bytes each: %s", (long long)capacity_samples, (long long)per_sample * 8, hipGetErrorString(e));
-    }
-    m->d_rec = ring;
-    m->d_rec_stage = st;
-    m->rec_cap = capacity_samples;
-    m->rec_stage_cap = stage;
-    m->rec_period = period;
-    m->rec_iter = 0;
-    m->rec_fetched = 0;
-    return MCD_OK;
+    return m ? m->rec.begin("mcd_hmc_record_begin", m->rec_on(), period, capacity_samples, mcd::kHmcRecDiag) : hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_begin: NULL handle");
 }
 
 int mcd_hmc_record_count(const mcd_hmc_t* m, int64_t* n_samples)
 {
-    if (!m || !n_samples) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_count: NULL argument");
-    if (!m->d_rec) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_count: no recorder is active (mcd_hmc_record_begin first)");
-    *n_samples = m->rec_filled();
-    return MCD_OK;
+    return m && n_samples ? m->rec.count("mcd_hmc_record_count", n_samples) : hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_count: NULL argument");
 }
 
 int mcd_hmc_record_fetch(mcd_hmc_t* m, int64_t max_samples, int64_t* n_out, int64_t* transition, double* scalars, double* heights, double* rates,
                          double* post, double* nuts)
 {
     if (!m || !n_out) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_fetch: NULL argument");
-    *n_out = 0;
-    if (!m->d_rec) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_fetch: no recorder is active (mcd_hmc_record_begin first)");
-    if (max_samples < 0) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_fetch: max_samples < 0");
-    const mcd::HmcDev& D = m->dev;
-    const int64_t n = std::min(m->rec_filled(), max_samples), B = D.batch, nn = D.n_nodes, nd = mcd::kHmcRecDiag;
-    const mcd::MhRec R{m->d_rec, 0, m->rec_cap, m->rec_period};
-    const mcd::MhRecDims dims{D.batch, D.ld, D.n_nodes};
-    HHIP_TRY(hipSetDevice(m->device));
-    for (int64_t done = 0; done < n; done += m->rec_stage_cap) {
-        const int64_t cnt = std::min(m->rec_stage_cap, n - done);
-        double* s_sc = m->d_rec_stage;                       // the staging buffer's five arrays for `cnt` samples
-        double* s_H = s_sc + cnt * B * 5;
-        double* s_R = s_H + cnt * B * nn;
-        double* s_post = s_R + cnt * B * nn;
-        double* s_nuts = s_post + cnt * B * 3;
-        HHIP_TRY(mcd::launch_mh_rec_unpack(dims, R, m->rec_fetched + done, cnt, scalars ? s_sc : nullptr, heights ? s_H : nullptr, rates ? s_R : nullptr,
-                                           post ? s_post : nullptr, nullptr, nuts ? s_nuts : nullptr, m->stream));
-        const size_t c = sizeof(double) * (size_t)(cnt * B), o = (size_t)(done * B);
-        if (scalars) HHIP_TRY(hipMemcpyAsync(scalars + o * 5, s_sc, c * 5, hipMemcpyDeviceToHost, m->stream));
-        if (heights) HHIP_TRY(hipMemcpyAsync(heights + o * (size_t)nn, s_H, c * (size_t)nn, hipMemcpyDeviceToHost, m->stream));
-        if (rates) HHIP_TRY(hipMemcpyAsync(rates + o * (size_t)nn, s_R, c * (size_t)nn, hipMemcpyDeviceToHost, m->stream));
-        if (post) HHIP_TRY(hipMemcpyAsync(post + o * 3, s_post, c * 3, hipMemcpyDeviceToHost, m->stream));
-        if (nuts) HHIP_TRY(hipMemcpyAsync(nuts + o * (size_t)nd, s_nuts, c * (size_t)nd, hipMemcpyDeviceToHost, m->stream));
-        HHIP_TRY(hipStreamSynchronize(m->stream));           // (the next piece reuses the staging buffer)
-    }
-    if (transition)
-        for (int64_t i = 0; i < n; ++i) transition[i] = (m->rec_fetched + 1 + i) * m->rec_period;
-    m->rec_fetched += n;
-    *n_out = n;
-    return MCD_OK;
+    return m->rec.fetch("mcd_hmc_record_fetch", m->rec_on(), max_samples, n_out, transition, scalars, heights, rates, post, nullptr, nuts);
 }
 
 int mcd_hmc_record_end(mcd_hmc_t* m)
 {
-    if (!m) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_end: NULL handle");
-    if (!m->d_rec) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_end: no recorder is active (mcd_hmc_record_begin first)");
-    HHIP_TRY(hipSetDevice(m->device));
-    HHIP_TRY(hipStreamSynchronize(m->stream));
-    (void)hipFree(m->d_rec);
-    (void)hipFree(m->d_rec_stage);
-    m->d_rec = m->d_rec_stage = nullptr;
-    m->rec_cap = m->rec_stage_cap = m->rec_iter = m->rec_fetched = 0;
-    m->rec_period = 0;
-    return MCD_OK;
+    return m ? m->rec.end("mcd_hmc_record_end", m->rec_on()) : hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_end: NULL handle");
 }
 
 int mcd_hmc_record_quantities(const mcd_hmc_t* m, int64_t* q)
@@ -619,36 +527,17 @@ int mcd_hmc_record_summary(mcd_hmc_t* m, int64_t skip, int64_t n_samples, int32_
 {
     if (!m || !pooled) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_summary: NULL argument");
     if (n_used) *n_used = 0;
-    if (!m->d_rec) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_summary: no recorder is active (mcd_hmc_record_begin first)");
     const mcd::HmcDev& D = m->dev;
-    const int64_t waiting = m->rec_filled();
-    if (skip < 0 || skip >= waiting)
-        return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_summary: skip = %lld, %lld samples are waiting", (long long)skip, (long long)waiting);
-    const int64_t n = n_samples < 0 ? waiting - skip : n_samples;
-    if (n < 1 || n > waiting - skip)
-        return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_record_summary: the window [%lld, %lld) ends past the %lld waiting samples", (long long)skip,
-                     (long long)(skip + n), (long long)waiting);
-    const int64_t Q = 2 * (int64_t)D.n_nodes + 9;
-    if (int rc = mcd_summary_check_("mcd_hmc_record_summary", n, D.batch, Q, max_lag)) return rc;
+    mcd::SumSrc S{};
+    int64_t n = 0;
+    if (int rc = m->rec.window("mcd_hmc_record_summary", m->rec_on(), skip, n_samples, max_lag, &S, &n)) return rc;
     HHIP_TRY(hipSetDevice(m->device));
     HHIP_TRY(hipStreamSynchronize(m->stream));
-    mcd::SumSrc S{};
-    S.base = m->d_rec;
-    S.n = n;
-    S.B = D.batch;
-    S.Q = Q;
-    S.ring = 1;
-    S.n_nodes = D.n_nodes;
-    S.first = (m->rec_fetched + skip) % m->rec_cap;            // sample number k (1, 2, ...) lies in slot (k - 1) mod capacity
-    S.cap = m->rec_cap;
-    S.stride = mcd::mh_rec_stride(D.ld);
-    S.ld = D.ld;
     if (int rc = mcd_summary_run_(S, max_lag, m->stream, pooled, per_chain)) return rc;
     if (nuts_stats) {
         double* d_stats = nullptr;
         HHIP_TRY(hipMalloc((void**)&d_stats, sizeof(double) * 4 * (size_t)D.batch));
-        hipError_t e = mcd::launch_hmc_record_stats(mcd::MhRecDims{D.batch, D.ld, D.n_nodes}, mcd::MhRec{m->d_rec, 0, m->rec_cap, m->rec_period}, S.first, n,
-                                                    d_stats, m->stream);
+        hipError_t e = mcd::launch_hmc_record_stats(m->rec_on().dims, m->rec.view(), S.first, n, d_stats, m->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(nuts_stats, d_stats, sizeof(double) * 4 * (size_t)D.batch, hipMemcpyDeviceToHost, m->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
         (void)hipFree(d_stats);

@@ -15,10 +15,10 @@
 #include "../../include/mcmcdate_mvn.h"
 #include "mvn_kernels.h"
 #include "options.h"
+#include "recorder.hpp"
 #include "summary_device.hpp"
 
-int mcd_summary_check_(const char* who, int64_t n, int64_t batch, int64_t q, int32_t max_lag);                       // summary_capi.cpp
-int mcd_summary_run_(const mcd::SumSrc& S, int32_t max_lag, hipStream_t st, double* pooled, double* per_chain);
+int mcd_summary_run_(const mcd::SumSrc& S, int32_t max_lag, hipStream_t st, double* pooled, double* per_chain);   // summary_capi.cpp
 extern "C" int mcd_set_last_error_(int code, const char* msg);   // mvn_capi.cpp
 struct mcd_sparse;
 struct mcd_sparse_tree;
@@ -83,19 +83,12 @@ struct mcd_mh {
     // Metropolis-coupled MCMC (mcd_mh_mc3_*): temperature ranks of all GLOBAL chains, ladder, counters; phase = swap phases done
     mcd::Mc3Dev mc3{};
     uint64_t mc3_seed = 0, mc3_phase = 0;
-    // the sample recorder (mcd_mh_record_*): a ring of rec_cap slots (mcd::MhRec), the staging buffer of the fetch (rec_stage_cap samples);
-    // rec_iter = iterations since begin, so rec_iter / rec_period samples were taken, rec_fetched of them handed out
-    double* d_rec = nullptr;
-    double* d_rec_stage = nullptr;
-    int64_t rec_cap = 0, rec_stage_cap = 0, rec_iter = 0, rec_fetched = 0;
-    int32_t rec_period = 0;
-    int64_t rec_filled() const { return rec_iter / rec_period - rec_fetched; }
+    mcd::Recorder rec{"mcd_mh_record"};       // the sample recorder (mcd_mh_record_*, recorder.cpp): it counts iterations
+    mcd::RecOn rec_on() const { return {device, stream, mcd::MhRecDims{dev.batch, dev.ld, dev.n_nodes}}; }
 
     ~mcd_mh()
     {
         (void)hipSetDevice(device);
-        if (d_rec) (void)hipFree(d_rec);
-        if (d_rec_stage) (void)hipFree(d_rec_stage);
         for (void* p : allocs) (void)hipFree(p);
         if (d_sched) (void)hipFree(d_sched);
         if (d_trace_alpha) (void)hipFree(d_trace_alpha);
@@ -742,7 +735,7 @@ struct MhRun {
         : m(m_), p(p_), schedule(schedule_), total(total_), S(S_), accumulate(accumulate_), trace(trace_), step_base(m_->step),
           n_dim(m_->mvn ? m_->mvn->n : m_->sp->n), prior_inline(p_.beside ? 0 : 1), Tx(p_.use_x ? m_->tree : nullptr), X1(p_.use_x ? m_->d_X1 : nullptr),
           inc(p_.inc_dense || p_.inc_sparse), dense_mode((p_.chunked || p_.inc_sparse) ? 1 : 2),
-          rec(mcd::MhRec{m_->d_rec, m_->rec_iter, m_->rec_cap, m_->rec_period}) {}
+          rec(m_->rec.view(m_->rec.counts().iter)) {}
     // what the next launch sees of the recorder (MhDev::rec): a whole-schedule or segment launch whose step 0 is `steps_before` steps (whole
     // iterations) into the call; a step launch that decides schedule position gs (gs < 0: decides nothing); nothing
     void rec_launch(int64_t steps_before) const
@@ -1012,12 +1005,7 @@ int mcd_mh_run(mcd_mh_t* m, const int32_t* schedule, int64_t n_iter, int32_t S, 
     const size_t steps = (size_t)n_iter * (size_t)S;
     for (size_t i = 0; i < steps; ++i)
         if (schedule[i] < 0 || schedule[i] >= D.n_prop) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_run: schedule[%zu] = %d is not a proposal row", i, schedule[i]);
-    if (m->d_rec) {                                  // an active recorder: the samples of this call must fit, or nothing is launched
-        const int64_t adds = (m->rec_iter + n_iter) / m->rec_period - m->rec_iter / m->rec_period, free_slots = m->rec_cap - m->rec_filled();
-        if (adds > free_slots)
-            return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_run: the call would record %lld samples, the recorder has %lld free slots (mcd_mh_record_fetch frees them)",
-                         (long long)adds, (long long)free_slots);
-    }
+    if (int rc = m->rec.room("mcd_mh_run", n_iter)) return rc;   // an active recorder: the samples of this call must fit, or nothing is launched
     MHIP_TRY(hipSetDevice(m->device));
     if (steps > m->sched_cap) {
         if (m->d_sched) (void)hipFree(m->d_sched);
@@ -1048,7 +1036,7 @@ int mcd_mh_run(mcd_mh_t* m, const int32_t* schedule, int64_t n_iter, int32_t S, 
     const int rc = p.path == MCD_MH_PATH_CHAIN_LDS ? run_chain(r) : p.path == MCD_MH_PATH_CHAIN_STREAMED ? run_streamed(r) : p.segments ? run_segments(r) : run_steps(r);
     m->dev.rec = mcd::MhRec{};
     if (rc) return rc;
-    if (m->d_rec) m->rec_iter += n_iter;
+    m->rec.advance(n_iter);
     m->last_lds = mcd::last_dynamic_lds();
     if (trace_alpha) MHIP_TRY(hipMemcpyAsync(trace_alpha, m->d_trace_alpha, sizeof(double) * steps * B, hipMemcpyDeviceToHost, m->stream));
     if (trace_accept) MHIP_TRY(hipMemcpyAsync(trace_accept, m->d_trace_accept, steps * B, hipMemcpyDeviceToHost, m->stream));
@@ -1131,94 +1119,24 @@ int mcd_mh_get_age_sums(const mcd_mh_t* cm, double* age_sum, double* age_sq, int
 // ---- the sample recorder: thinned samples of every chain kept on the device while mcd_mh_run runs (mcd::MhRec, mvn_kernels.h) -------
 int mcd_mh_record_begin(mcd_mh_t* m, int32_t period, int64_t capacity_samples)
 {
-    if (!m) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_begin: NULL handle");
-    if (m->d_rec) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_begin: a recorder is active already (mcd_mh_record_end first)");
-    if (period < 1) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_begin: period must be >= 1 (got %d)", (int)period);
-    if (capacity_samples < 1) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_begin: capacity must be >= 1 sample (got %lld)", (long long)capacity_samples);
-    const mcd::MhDev& D = m->dev;
-    const int64_t per_sample = D.batch * mcd::mh_rec_stride(D.ld);                 // doubles of one slot
-    if (capacity_samples > ((int64_t)1 << 50) / per_sample)
-        return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_begin: %lld samples of %lld bytes each", (long long)capacity_samples, (long long)per_sample * 8);
-    // the fetch unpacks into a staging buffer of at most 64 MiB (at least one sample) and copies from there, piece by piece
-    const int64_t out_sample = D.batch * (2 * (int64_t)D.n_nodes + 9);
-    const int64_t stage = std::max<int64_t>(1, std::min<int64_t>(capacity_samples, ((int64_t)8 << 20) / out_sample));
-    MHIP_TRY(hipSetDevice(m->device));
-    double *ring = nullptr, *st = nullptr;
-    hipError_t e = hipMalloc((void**)&ring, sizeof(double) * (size_t)(per_sample * capacity_samples));
-    if (e == hipSuccess) e = hipMalloc((void**)&st, sizeof(double) * (size_t)(out_sample * stage));
-    if (e == hipSuccess) e = hipMemsetAsync(ring, 0, sizeof(double) * (size_t)(per_sample * capacity_samples), m->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-    if (e != hipSuccess) {
-        if (ring) (void)hipFree(ring);
-        if (st) (void)hipFree(st);
-        return mfail(MCD_ERR_HIP, "mcd_mh_record_begin: %lld samples of %lld bytes each: %s", (long long)capacity_samples, (long long)per_sample * 8, hipGetErrorString(e));
-    }
-    m->d_rec = ring;
-    m->d_rec_stage = st;
-    m->rec_cap = capacity_samples;
-    m->rec_stage_cap = stage;
-    m->rec_period = period;
-    m->rec_iter = 0;
-    m->rec_fetched = 0;
-    return MCD_OK;
+    return m ? m->rec.begin("mcd_mh_record_begin", m->rec_on(), period, capacity_samples, 1) : mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_begin: NULL handle");
 }
 
 int mcd_mh_record_count(const mcd_mh_t* m, int64_t* n_samples)
 {
-    if (!m || !n_samples) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_count: NULL argument");
-    if (!m->d_rec) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_count: no recorder is active (mcd_mh_record_begin first)");
-    *n_samples = m->rec_filled();
-    return MCD_OK;
+    return m && n_samples ? m->rec.count("mcd_mh_record_count", n_samples) : mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_count: NULL argument");
 }
 
 int mcd_mh_record_fetch(mcd_mh_t* m, int64_t max_samples, int64_t* n_out, int64_t* iteration, double* scalars, double* heights, double* rates,
                         double* post, double* beta)
 {
     if (!m || !n_out) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_fetch: NULL argument");
-    *n_out = 0;
-    if (!m->d_rec) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_fetch: no recorder is active (mcd_mh_record_begin first)");
-    if (max_samples < 0) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_fetch: max_samples < 0");
-    const mcd::MhDev& D = m->dev;
-    const int64_t n = std::min(m->rec_filled(), max_samples), B = D.batch, nn = D.n_nodes;
-    const mcd::MhRec R{m->d_rec, 0, m->rec_cap, m->rec_period};
-    MHIP_TRY(hipSetDevice(m->device));
-    for (int64_t done = 0; done < n; done += m->rec_stage_cap) {
-        const int64_t cnt = std::min(m->rec_stage_cap, n - done);
-        double* s_sc = m->d_rec_stage;                       // the staging buffer's five arrays for `cnt` samples
-        double* s_H = s_sc + cnt * B * 5;
-        double* s_R = s_H + cnt * B * nn;
-        double* s_post = s_R + cnt * B * nn;
-        double* s_beta = s_post + cnt * B * 3;
-        MHIP_TRY(mcd::launch_mh_rec_unpack(mcd::MhRecDims{D.batch, D.ld, D.n_nodes}, R, m->rec_fetched + done, cnt, scalars ? s_sc : nullptr,
-                                           heights ? s_H : nullptr, rates ? s_R : nullptr, post ? s_post : nullptr, beta ? s_beta : nullptr, nullptr,
-                                           m->stream));
-        const size_t c = sizeof(double) * (size_t)(cnt * B), o = (size_t)(done * B);
-        if (scalars) MHIP_TRY(hipMemcpyAsync(scalars + o * 5, s_sc, c * 5, hipMemcpyDeviceToHost, m->stream));
-        if (heights) MHIP_TRY(hipMemcpyAsync(heights + o * (size_t)nn, s_H, c * (size_t)nn, hipMemcpyDeviceToHost, m->stream));
-        if (rates) MHIP_TRY(hipMemcpyAsync(rates + o * (size_t)nn, s_R, c * (size_t)nn, hipMemcpyDeviceToHost, m->stream));
-        if (post) MHIP_TRY(hipMemcpyAsync(post + o * 3, s_post, c * 3, hipMemcpyDeviceToHost, m->stream));
-        if (beta) MHIP_TRY(hipMemcpyAsync(beta + o, s_beta, c, hipMemcpyDeviceToHost, m->stream));
-        MHIP_TRY(hipStreamSynchronize(m->stream));           // (the next piece reuses the staging buffer)
-    }
-    if (iteration)
-        for (int64_t i = 0; i < n; ++i) iteration[i] = (m->rec_fetched + 1 + i) * m->rec_period;
-    m->rec_fetched += n;
-    *n_out = n;
-    return MCD_OK;
+    return m->rec.fetch("mcd_mh_record_fetch", m->rec_on(), max_samples, n_out, iteration, scalars, heights, rates, post, beta, nullptr);
 }
 
 int mcd_mh_record_end(mcd_mh_t* m)
 {
-    if (!m) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_end: NULL handle");
-    if (!m->d_rec) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_end: no recorder is active (mcd_mh_record_begin first)");
-    MHIP_TRY(hipSetDevice(m->device));
-    MHIP_TRY(hipStreamSynchronize(m->stream));
-    (void)hipFree(m->d_rec);
-    (void)hipFree(m->d_rec_stage);
-    m->d_rec = m->d_rec_stage = nullptr;
-    m->rec_cap = m->rec_stage_cap = m->rec_iter = m->rec_fetched = 0;
-    m->rec_period = 0;
-    return MCD_OK;
+    return m ? m->rec.end("mcd_mh_record_end", m->rec_on()) : mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_end: NULL handle");
 }
 
 // ---- summaries of the waiting samples, read in the ring (k_summary.hip) -------------------------------------------------------------------
@@ -1233,17 +1151,10 @@ int mcd_mh_record_summary(mcd_mh_t* m, int64_t skip, int64_t n_samples, int32_t 
 {
     if (!m || !pooled) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_summary: NULL argument");
     if (n_used) *n_used = 0;
-    if (!m->d_rec) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_summary: no recorder is active (mcd_mh_record_begin first)");
     const mcd::MhDev& D = m->dev;
-    const int64_t waiting = m->rec_filled();
-    if (skip < 0 || skip >= waiting)
-        return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_summary: skip = %lld, %lld samples are waiting", (long long)skip, (long long)waiting);
-    const int64_t n = n_samples < 0 ? waiting - skip : n_samples;
-    if (n < 1 || n > waiting - skip)
-        return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_record_summary: the window [%lld, %lld) ends past the %lld waiting samples", (long long)skip,
-                     (long long)(skip + n), (long long)waiting);
-    const int64_t Q = 2 * (int64_t)D.n_nodes + 9;
-    if (int rc = mcd_summary_check_("mcd_mh_record_summary", n, D.batch, Q, max_lag)) return rc;
+    mcd::SumSrc S{};
+    int64_t n = 0;
+    if (int rc = m->rec.window("mcd_mh_record_summary", m->rec_on(), skip, n_samples, max_lag, &S, &n)) return rc;
     if (m->mc3.n_chains != 0)
         return mfail(MCD_ERR_UNSUPPORTED, "mcd_mh_record_summary: Metropolis-coupled MCMC is initialised on this handle: its temperatures wander between the chains, so a chain is not a cold sequence");
     MHIP_TRY(hipSetDevice(m->device));
@@ -1253,17 +1164,6 @@ int mcd_mh_record_summary(mcd_mh_t* m, int64_t skip, int64_t n_samples, int32_t 
     for (int64_t b = 0; b < D.batch; ++b)
         if (beta[(size_t)b] != 1.0)
             return mfail(MCD_ERR_UNSUPPORTED, "mcd_mh_record_summary: chain %lld has the reciprocal temperature %g: only cold chains (1) are summarised", (long long)b, beta[(size_t)b]);
-    mcd::SumSrc S{};
-    S.base = m->d_rec;
-    S.n = n;
-    S.B = D.batch;
-    S.Q = Q;
-    S.ring = 1;
-    S.n_nodes = D.n_nodes;
-    S.first = (m->rec_fetched + skip) % m->rec_cap;            // sample number k (1, 2, ...) lies in slot (k - 1) mod capacity
-    S.cap = m->rec_cap;
-    S.stride = mcd::mh_rec_stride(D.ld);
-    S.ld = D.ld;
     if (int rc = mcd_summary_run_(S, max_lag, m->stream, pooled, per_chain)) return rc;
     if (n_used) *n_used = n;
     return MCD_OK;

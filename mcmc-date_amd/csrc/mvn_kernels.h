@@ -87,7 +87,7 @@ __host__ __device__ inline size_t prior_node_tables_doubles(int n_cal, int n_con
     return 4 * (size_t)n_cal + (size_t)n_con + (3 * (size_t)n_cal + 2 * (size_t)n_con + 1) / 2;
 }
 
-// Sample recorder of the Metropolis-Hastings driver (mcd_mh_record_*): while base is not null, the wave that holds a chain's accepted state
+// Sample recorder of the Metropolis-Hastings driver (mcd_mh_record_*; the host side, shared with the NUTS driver: recorder.cpp): while base is not null, the wave that holds a chain's accepted state
 // at the end of an iteration whose number is a multiple of `period` stores it as one sample.  Iterations count from mcd_mh_record_begin;
 // sample number k = iteration / period (1, 2, ...) goes to slot (k - 1) % capacity of a ring of `capacity` slots -- the modulo is also the
 // clamp: whatever the host counted, no store leaves the buffer.  A slot is [batch] records of mh_rec_stride(ld) doubles, one per chain:
@@ -101,7 +101,7 @@ struct MhRec {
     int32_t period;
 };
 __host__ __device__ inline int64_t mh_rec_stride(int64_t ld) { return 2 * ld + 16; }
-// what the ring's readers need of the driver that filled it (the Metropolis-Hastings driver's MhDev, the NUTS driver's HmcDev)
+// what the ring's readers need of the driver that filled it (the Metropolis-Hastings driver's MhDev, the NUTS driver's HmcDev): recorder.cpp
 struct MhRecDims {
     int64_t batch, ld;
     int n_nodes;

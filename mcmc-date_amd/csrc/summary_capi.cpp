@@ -1,5 +1,5 @@
 // summary_capi.cpp -- C ABI of the posterior summaries and convergence diagnostics of a trace (include/mcmcdate_mvn.h: mcd_trace_summary;
-// mcd_summary_run_ is what mcd_mh_record_summary, mh_capi.cpp, runs on the recorder's ring).  Kernels: k_summary.hip.  No CPU path.
+// mcd_summary_run_ is what mcd_*_record_summary run on the window of the ring that recorder.cpp checked).  Kernels: k_summary.hip.  No CPU path.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>

@@ -27,6 +27,7 @@ import numpy as np
 from . import _capi
 from .likelihood import SparseTreeLikelihood, TreeLikelihood
 from .prior import PriorFunction
+from .recorder import RecorderCalls
 from .state import StateBatch
 
 _dp = C.POINTER(C.c_double)
@@ -36,7 +37,7 @@ def _p(a):
     return a.ctypes.data_as(_dp)
 
 
-class Leapfrog:
+class Leapfrog(RecorderCalls):
     """B chains on one GPU.  `tree_lik` (a TreeLikelihood, or a SparseTreeLikelihood: the precision matrix stays sparse on the device,
     mcd_hmc_create_sparse, trees of up to 2048 nodes) and `prior` must live on the same device and outlive this object."""
 
@@ -133,18 +134,13 @@ class Leapfrog:
     # -- the sample recorder (mcd_hmc_record_*) ------------------------------------------------------------------------------
     NUTS_FIELDS = ("depth", "leapfrog_steps", "alpha", "diverged", "eps", "joint0")
     NUTS_STATS = ("divergent", "mean_depth", "max_depth", "leapfrog_steps")
+    _REC_API, _REC_TAIL = "mcd_hmc_record", (len(NUTS_FIELDS),)
 
     def record_begin(self, period: int = 1, capacity: int = 128):
         """Keep the state of every chain and the diagnostics of the transition after every `period`-th NUTS transition (counted from
         this call, through nuts / nuts_run / nuts_warmup alike) on the device, in a ring of `capacity` samples; a call whose samples
         would not fit is refused before it starts (drain with record_fetch)."""
-        _capi.check(_capi.lib().mcd_hmc_record_begin(self._h, int(period), int(capacity)))
-
-    def record_count(self) -> int:
-        """Samples waiting to be fetched."""
-        n = C.c_int64(0)
-        _capi.check(_capi.lib().mcd_hmc_record_count(self._h, C.byref(n)))
-        return int(n.value)
+        super().record_begin(period, capacity)
 
     def record_fetch(self, max_samples: Optional[int] = None):
         """The oldest waiting samples (all of them, or at most max_samples), whose slots are free afterwards -- the arrays of
@@ -152,21 +148,7 @@ class Leapfrog:
         (transition [n] counted from record_begin, scalars [n, B, 5] = birth, death, tH, rMu, rVar, heights [n, B, n_nodes],
         rates [n, B, n_nodes], post [n, B, 3] = ln prior, ln likelihood, ln jacobianRootBranch, nuts [n, B, 6] = NUTS_FIELDS: tree
         depth, leapfrog steps, acceptance statistic, diverged (0 / 1), the step size used, -H at the start of the transition)."""
-        B, nn = self.batch, self.topo.n_nodes
-        n = self.record_count()
-        if max_samples is not None:
-            n = min(n, int(max_samples))
-        it = np.empty(n, np.int64)
-        sc, H, R, post, nuts = np.empty((n, B, 5)), np.empty((n, B, nn)), np.empty((n, B, nn)), np.empty((n, B, 3)), np.empty((n, B, 6))
-        got = C.c_int64(0)
-        _capi.check(_capi.lib().mcd_hmc_record_fetch(self._h, n, C.byref(got), it.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                     *[_p(a) for a in (sc, H, R, post, nuts)]))
-        if got.value != n:
-            raise RuntimeError(f"record_fetch: asked for {n} samples, got {got.value}")
-        return it, sc, H, R, post, nuts
-
-    def record_end(self):
-        _capi.check(_capi.lib().mcd_hmc_record_end(self._h))
+        return self._record_fetch(max_samples)
 
     def record_summary(self, skip: int = 0, n: Optional[int] = None, max_lag: int = 255, per_chain: bool = False):
         """Sampler.record_summary on this driver's recorder (mcd_hmc_record_summary: computed on the device from the ring, nothing is
@@ -174,21 +156,9 @@ class Leapfrog:
         transitions, mean and maximum tree depth, leapfrog steps -- of the window."""
         from .sampler import RecordSummary
 
-        Q = C.c_int64(0)
-        _capi.check(_capi.lib().mcd_hmc_record_quantities(self._h, C.byref(Q)))
-        Q = int(Q.value)
-        count = self.record_count() - int(skip) if n is None else int(n)
-        lag = min(int(max_lag), max(count, 0) // 2 - 1)
-        lag = max(0, lag if lag % 2 == 1 else lag - 1)
-        pooled = np.empty((Q, _capi.MCD_SUMMARY_COLS))
-        pc = np.empty((self.batch, Q, 4)) if per_chain else None
         stats = np.empty((self.batch, 4))
-        used = C.c_int64(0)
-        _capi.check(_capi.lib().mcd_hmc_record_summary(self._h, int(skip), -1 if n is None else int(n), lag, C.byref(used), _p(pooled),
-                                                       _p(pc) if per_chain else None, _p(stats)))
-        out = RecordSummary(pooled, self.topo.n_nodes, int(used.value), lag, pc)
-        out.nuts_stats = stats
-        return out
+        pooled, used, lag, pc = self._record_summary(skip, n, max_lag, per_chain, stats)
+        return RecordSummary(pooled, self.topo.n_nodes, used, lag, pc, stats)
 
     def step_from(self, q, p, grad, eps, inv_mass, direction=None, have_grad=True):
         """One leapfrog step from the given phase points (all [B, dim]); returns (q', p', grad', ln target')."""

@@ -71,6 +71,26 @@ def collect(sampler, n_iter: int, period: int = PERIOD, accumulate: bool = False
     return Trace(np.asarray(its, np.int64), *st)
 
 
+def _record_chunks(driver, total: int, period: int, chunk: int, run):
+    """The loop of `record` and `record_nuts`: the driver's recorder holds what one chunk can add at most; run(k, done) advances the driver
+    by the next k of `total` steps (`done` are behind it), one fetch per chunk.  Returns the six arrays of the fetches, concatenated, or
+    None when nothing was recorded."""
+    parts: List[tuple] = []
+    driver.record_begin(period, (chunk + period - 1) // period)
+    try:
+        done = 0
+        while done < total:
+            k = min(chunk, total - done)
+            run(k, done)
+            done += k
+            parts.append(driver.record_fetch())
+    finally:
+        driver.record_end()
+    if sum(len(p[0]) for p in parts) == 0:
+        return None
+    return tuple(np.concatenate([p[i] for p in parts]) for i in range(6))
+
+
 def record(sampler, n_iter: int, period: int = PERIOD, accumulate: bool = False, chunk: int = 256) -> Trace:
     """`collect` without cutting the run into pieces of one monitor period: the sampler's recorder keeps the samples on the device
     while `chunk` iterations run in one call, and they are fetched once per chunk.  The same samples at the same iterations as
@@ -79,21 +99,11 @@ def record(sampler, n_iter: int, period: int = PERIOD, accumulate: bool = False,
     if n_iter < 0 or period < 1 or chunk < 1:
         raise ValueError("record: need n_iter >= 0, period >= 1, chunk >= 1")
     base = sampler.iterations_done
-    parts: List[tuple] = []
-    sampler.record_begin(period, (chunk + period - 1) // period)      # (what one chunk can add at most)
-    try:
-        done = 0
-        while done < n_iter:
-            k = min(chunk, n_iter - done)
-            sampler.run(k, accumulate=accumulate, chunk=k)
-            done += k
-            parts.append(sampler.record_fetch())
-    finally:
-        sampler.record_end()
-    if not parts or sum(len(p[0]) for p in parts) == 0:
+    got = _record_chunks(sampler, n_iter, period, chunk, lambda k, done: sampler.run(k, accumulate=accumulate, chunk=k))
+    if got is None:
         e = np.empty((0,))
         return Trace(np.empty(0, np.int64), e, e, e, e, e, e, e, e, e)
-    it, sc, H, R, post, beta = (np.concatenate([p[i] for p in parts]) for i in range(6))
+    it, sc, H, R, post, beta = got
     return Trace(base + it, sc[..., 0], sc[..., 1], sc[..., 2], H, sc[..., 3], sc[..., 4], R, post, beta)
 
 
@@ -106,22 +116,13 @@ def record_nuts(lf, n_transitions: int, eps, inv_mass, period: int = PERIOD, chu
     summary without a fetch call summarize_recorded(lf) between lf.record_begin and lf.record_end instead."""
     if n_transitions < 0 or period < 1 or chunk < 1:
         raise ValueError("record_nuts: need n_transitions >= 0, period >= 1, chunk >= 1")
-    parts: List[tuple] = []
-    lf.record_begin(period, (chunk + period - 1) // period)           # (what one chunk can add at most)
-    try:
-        done = 0
-        while done < n_transitions:
-            k = min(chunk, n_transitions - done)
-            lf.nuts_run(k, eps, inv_mass, adapt=False, max_depth=max_depth, seed=seed, first_transition=first_transition + done,
-                        chain_offset=chain_offset)
-            done += k
-            parts.append(lf.record_fetch())
-    finally:
-        lf.record_end()
-    if not parts or sum(len(p[0]) for p in parts) == 0:
+    got = _record_chunks(lf, n_transitions, period, chunk,
+                         lambda k, done: lf.nuts_run(k, eps, inv_mass, adapt=False, max_depth=max_depth, seed=seed,
+                                                     first_transition=first_transition + done, chain_offset=chain_offset))
+    if got is None:
         e = np.empty((0,))
         return Trace(np.empty(0, np.int64), e, e, e, e, e, e, e, e, None, e)
-    it, sc, H, R, post, nuts = (np.concatenate([p[i] for p in parts]) for i in range(6))
+    it, sc, H, R, post, nuts = got
     return Trace(first_transition + it, sc[..., 0], sc[..., 1], sc[..., 2], H, sc[..., 3], sc[..., 4], R, post, None, nuts)
 
 

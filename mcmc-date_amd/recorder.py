@@ -1,0 +1,54 @@
+"""The sample recorder's calls, shared by `Sampler` (mcd_mh_record_*) and `hmc.Leapfrog` (mcd_hmc_record_*): the drivers differ in the symbol
+prefix and in the last array of a fetch.  The library is looked up through `_capi.lib()` at every call."""
+import ctypes as C
+
+import numpy as np
+
+from . import _capi
+from ._capi import _dp
+
+
+class RecorderCalls:
+    """Mixin of a driver with `_h`, `batch`, `topo`, _REC_API (the symbol prefix) and _REC_TAIL (shape of the fetch's last array behind [n, B])."""
+
+    def _rec(self, op):
+        return getattr(_capi.lib(), f"{self._REC_API}_{op}")
+
+    def record_begin(self, period, capacity=128):
+        _capi.check(self._rec("begin")(self._h, int(period), int(capacity)))
+
+    def record_count(self) -> int:
+        """Samples waiting to be fetched."""
+        n = C.c_int64(0)
+        _capi.check(self._rec("count")(self._h, C.byref(n)))
+        return int(n.value)
+
+    def record_end(self):
+        _capi.check(self._rec("end")(self._h))
+
+    def _record_fetch(self, max_samples):
+        """(index [n], scalars [n, B, 5], heights, rates [n, B, n_nodes], post [n, B, 3], the last array [n, B, *_REC_TAIL])."""
+        B, nn = self.batch, self.topo.n_nodes
+        n = self.record_count() if max_samples is None else min(self.record_count(), int(max_samples))
+        it = np.empty(n, np.int64)
+        out = [np.empty((n, B) + s) for s in ((5,), (nn,), (nn,), (3,), self._REC_TAIL)]
+        got = C.c_int64(0)
+        _capi.check(self._rec("fetch")(self._h, n, C.byref(got), it.ctypes.data_as(C.POINTER(C.c_int64)), *[a.ctypes.data_as(_dp) for a in out]))
+        if got.value != n:
+            raise RuntimeError(f"record_fetch: asked for {n} samples, got {got.value}")
+        return (it, *out)
+
+    def _record_summary(self, skip, n, max_lag, per_chain, *extra):
+        """(pooled, samples used, lag cap in force, per_chain or None); `extra`: the arrays the driver's call takes behind per_chain."""
+        Q = C.c_int64(0)
+        _capi.check(self._rec("quantities")(self._h, C.byref(Q)))
+        Q = int(Q.value)
+        count = self.record_count() - int(skip) if n is None else int(n)
+        lag = min(int(max_lag), max(count, 0) // 2 - 1)
+        lag = max(0, lag if lag % 2 == 1 else lag - 1)
+        pooled = np.empty((Q, _capi.MCD_SUMMARY_COLS))
+        pc = np.empty((self.batch, Q, 4)) if per_chain else None
+        used = C.c_int64(0)
+        _capi.check(self._rec("summary")(self._h, int(skip), -1 if n is None else int(n), lag, C.byref(used), pooled.ctypes.data_as(_dp),
+                                         pc.ctypes.data_as(_dp) if per_chain else None, *[a.ctypes.data_as(_dp) for a in extra]))
+        return pooled, int(used.value), lag, pc

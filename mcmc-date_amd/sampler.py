@@ -23,6 +23,7 @@ import numpy as np
 from . import _capi
 from .likelihood import TreeLikelihood
 from .prior import PriorFunction
+from .recorder import RecorderCalls
 from .state import State, StateBatch
 from .tree import Topology
 
@@ -203,7 +204,7 @@ _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
 
 
-class Sampler:
+class Sampler(RecorderCalls):
     """B chains on one GPU.  `tree_lik` and `prior` must live on the same device and outlive the sampler."""
 
     def __init__(self, tree_lik: TreeLikelihood, prior: PriorFunction, table: Sequence[Proposal], batch: int, seed: int,
@@ -345,53 +346,25 @@ class Sampler:
         _capi.check(_capi.lib().mcd_mh_reset_age_sums(self._h))
 
     # -- the sample recorder (mcd_mh_record_*) ------------------------------------------------------------------------------
+    _REC_API, _REC_TAIL = "mcd_mh_record", ()        # (the last array of a fetch: beta [n, B])
+
     def record_begin(self, period: int = 2, capacity: int = 128):
         """Keep the state of every chain at the end of every `period`-th iteration (counted from this call) on the device, in a
         ring of `capacity` samples; a run whose samples would not fit is refused before it starts (drain with record_fetch)."""
-        _capi.check(_capi.lib().mcd_mh_record_begin(self._h, int(period), int(capacity)))
-
-    def record_count(self) -> int:
-        """Samples waiting to be fetched."""
-        n = C.c_int64(0)
-        _capi.check(_capi.lib().mcd_mh_record_count(self._h, C.byref(n)))
-        return int(n.value)
+        super().record_begin(period, capacity)
 
     def record_fetch(self, max_samples: Optional[int] = None):
         """The oldest waiting samples (all of them, or at most max_samples), whose slots are free afterwards:
         (iteration [n] counted from record_begin, scalars [n, B, 5] = birth, death, tH, rMu, rVar, heights [n, B, n_nodes],
         rates [n, B, n_nodes], post [n, B, 3] = ln prior, ln likelihood, ln jacobianRootBranch, beta [n, B])."""
-        B, nn = self.batch, self.topo.n_nodes
-        n = self.record_count()
-        if max_samples is not None:
-            n = min(n, int(max_samples))
-        it = np.empty(n, np.int64)
-        sc, H, R, post, beta = np.empty((n, B, 5)), np.empty((n, B, nn)), np.empty((n, B, nn)), np.empty((n, B, 3)), np.empty((n, B))
-        got = C.c_int64(0)
-        _capi.check(_capi.lib().mcd_mh_record_fetch(self._h, n, C.byref(got), it.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                    *[a.ctypes.data_as(_dp) for a in (sc, H, R, post, beta)]))
-        if got.value != n:
-            raise RuntimeError(f"record_fetch: asked for {n} samples, got {got.value}")
-        return it, sc, H, R, post, beta
-
-    def record_end(self):
-        _capi.check(_capi.lib().mcd_mh_record_end(self._h))
+        return self._record_fetch(max_samples)
 
     def record_summary(self, skip: int = 0, n: Optional[int] = None, max_lag: int = 255, per_chain: bool = False) -> "RecordSummary":
         """Posterior summaries and convergence diagnostics of the waiting samples [skip, skip + n) (n None: all after skip), computed on the
         device from the ring where they lie (mcd_mh_record_summary): nothing is fetched and no slot is freed.  max_lag: the lag cap of the
         effective sample size, lowered to what the window allows (odd, at most n // 2 - 1; 0 when the window is shorter than 4 samples)."""
-        Q = C.c_int64(0)
-        _capi.check(_capi.lib().mcd_mh_record_quantities(self._h, C.byref(Q)))
-        Q = int(Q.value)
-        count = self.record_count() - int(skip) if n is None else int(n)
-        lag = min(int(max_lag), max(count, 0) // 2 - 1)
-        lag = max(0, lag if lag % 2 == 1 else lag - 1)
-        pooled = np.empty((Q, _capi.MCD_SUMMARY_COLS))
-        pc = np.empty((self.batch, Q, 4)) if per_chain else None
-        used = C.c_int64(0)
-        _capi.check(_capi.lib().mcd_mh_record_summary(self._h, int(skip), -1 if n is None else int(n), lag, C.byref(used), pooled.ctypes.data_as(_dp),
-                                                      pc.ctypes.data_as(_dp) if per_chain else None))
-        return RecordSummary(pooled, self.topo.n_nodes, int(used.value), lag, pc)
+        pooled, used, lag, pc = self._record_summary(skip, n, max_lag, per_chain)
+        return RecordSummary(pooled, self.topo.n_nodes, used, lag, pc)
 
     def node_age_summary(self):
         """Posterior mean and variance of every node age pooled over chains and accumulated iterations, plus the

@@ -214,9 +214,11 @@ def test_record_nuts_ends_the_recorder_when_a_run_fails():
 
 
 def test_ring_arithmetic():
-    """hmc_capi.cpp's counts: after `it` transitions it // period samples were taken, sample k lies in slot (k - 1) % capacity; a call of n
-    transitions adds (it + n) // period - it // period; the window [skip, skip + m) of the waiting samples starts at slot
-    (fetched + skip) % capacity.  Played against a list for every small ring: no waiting sample is ever overwritten by an accepted call."""
+    """The recorder's counts (csrc/recorder.cpp: one implementation behind mcd_mh_record_* and mcd_hmc_record_*): after `it` transitions
+    it // period samples were taken, sample k lies in slot (k - 1) % capacity; a call of n transitions adds (it + n) // period - it // period;
+    the window [skip, skip + m) of the waiting samples starts at slot (fetched + skip) % capacity.  Played against a list for every small
+    ring: no waiting sample is ever overwritten by an accepted call.  At every step the library's own counts (mcd_record_ring_selftest_,
+    computed by the struct every recorder call uses) must be the numbers of this model."""
     for period in (1, 2, 3):
         for cap in (1, 2, 4, 5):
             ring, it, fetched, taken = [None] * cap, 0, 0, 0
@@ -224,6 +226,7 @@ def test_ring_arithmetic():
             for _ in range(60):
                 n = int(rng.integers(0, 2 * cap * period + 1))
                 adds, free = (it + n) // period - it // period, cap - (it // period - fetched)
+                assert _capi.record_ring_selftest(period, cap, it, fetched, n, 0) == (adds, free, it // period - fetched, fetched % cap)
                 if adds <= free:
                     for _ in range(n):
                         it += 1
@@ -239,6 +242,7 @@ def test_ring_arithmetic():
                     skip = int(rng.integers(0, waiting))
                     m = int(rng.integers(1, waiting - skip + 1))
                     first = (fetched + skip) % cap
+                    assert _capi.record_ring_selftest(period, cap, it, fetched, 0, skip) == (0, cap - waiting, waiting, first)
                     assert [ring[(first + i) % cap] for i in range(m)] == list(range(fetched + skip + 1, fetched + skip + m + 1))
                 k = int(rng.integers(0, waiting + 1))
                 for i in range(k):
