@@ -531,8 +531,27 @@ int mcd_mh_record_end(mcd_mh_t* m);
  *                             mcd_mh_run or mcd_mh_get_* can see.  Refused before any launch, the handle untouched: no active recorder,
  *                             skip at or beyond the waiting count, a window past it, a bad max_lag (MCD_ERR_INVALID_ARG); MC3 initialised
  *                             on the handle or a temperature other than 1 (MCD_ERR_UNSUPPORTED: under MC3 the temperatures wander
- *                             between the chains, so a chain is not a cold sequence; pooling the cold samples by the recorded beta is
- *                             left for later).
+ *                             between the chains, so a chain is not a cold sequence; mcd_mh_record_summary_mc3 below follows a
+ *                             temperature through the swaps).
+ *   mcd_mh_record_summary_mc3 the same summary of a handle with mcd_mh_mc3_init done, over the RUNG-`rung` SEQUENCES of its G = batch /
+ *                             n_chains groups: at every recorded sample exactly one chain of a group ran at ladder[rung] (the recorded
+ *                             beta equals it bit for bit), and the sequence is, sample by sample, the record of that chain (k_mc3_summary.hip
+ *                             gathers it out of the ring; rung 0 is the cold sequence, what the reference's monitors report).  Columns and
+ *                             statistics as above with "chain" read as "a group's rung sequence": pooled[q][9] over l = n G values, split
+ *                             R-hat and effective sample size over 2 G half sequences, per_group[G][q][4] (may be NULL).  Optional outputs:
+ *                             holder[n][G], the local chain (0 .. n_chains - 1) that carried the rung; visits[batch][n_chains], the samples
+ *                             of the window every chain spent at each rung; round_trips[batch], its completed passages cold -> hottest ->
+ *                             cold (armed at rung 0, marked at rung n_chains - 1, counted at the next return to rung 0) -- whether the
+ *                             ladder mixes, which the swap counters of mcd_mh_mc3_get do not show.  The contract is
+ *                             mcd_mh_record_summary's: waits for the stream, reads the window where it lies, frees no slot, changes nothing
+ *                             a later call can see, the same bits on every call; the gathered trace is allocated for the call (an
+ *                             allocation failure: MCD_ERR_HIP with the byte count).  Refused before any launch, the handle untouched and
+ *                             *n_used = 0: what mcd_mh_record_summary refuses as MCD_ERR_INVALID_ARG, with n G in the place of n batch;
+ *                             MC3 not initialised; rung outside 0 .. n_chains - 1 (MCD_ERR_INVALID_ARG); a handle whose chains are not
+ *                             whole groups, first chain or batch no multiple of n_chains (MCD_ERR_UNSUPPORTED).  A window in which some
+ *                             sample of some group does not have exactly one chain at the rung -- recorded before mcd_mh_mc3_init or after
+ *                             a mcd_mh_set_temperatures -- is found by the gather: MCD_ERR_INVALID_ARG, the message names one such sample,
+ *                             its group and the count, and no output other than *n_used is written.
  */
 #define MCD_SUMMARY_COLS 9
 #define MCD_SUMMARY_MAX_LAG 255 /* four waves of 64 lags each share one sliding window of 256 + 32 rows in LDS */
@@ -540,6 +559,8 @@ int mcd_trace_summary(int64_t n, int64_t batch, int64_t q, int64_t ldq, const do
                       double* pooled, double* per_chain);
 int mcd_mh_record_quantities(const mcd_mh_t* m, int64_t* q);
 int mcd_mh_record_summary(mcd_mh_t* m, int64_t skip, int64_t n_samples, int32_t max_lag, int64_t* n_used, double* pooled, double* per_chain);
+int mcd_mh_record_summary_mc3(mcd_mh_t* m, int rung, int64_t skip, int64_t n_samples, int32_t max_lag, int64_t* n_used, double* pooled,
+                              double* per_group, int32_t* holder, int64_t* visits, int64_t* round_trips);
 
 /* ------------------------------------------------------------------------------------------------
  * The sparse form: the precision matrix as it is, in CSR on the device, no densification; N up to MCD_MAX_SPARSE_DIM.

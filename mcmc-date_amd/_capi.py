@@ -115,6 +115,8 @@ SYMBOLS = {
     "mcd_trace_summary": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, C.c_int, C.c_int, C.c_int32, _dp, _dp]),
     "mcd_mh_record_quantities": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "mcd_mh_record_summary": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64), _dp, _dp]),
+    "mcd_mh_record_summary_mc3": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64), _dp, _dp, _ip,
+                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mcd_hmc_record_begin": (C.c_int, [_vp, C.c_int32, C.c_int64]),
     "mcd_hmc_record_count": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "mcd_hmc_record_fetch": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _dp, _dp, _dp, _dp, _dp]),

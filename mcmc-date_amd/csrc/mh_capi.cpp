@@ -19,6 +19,7 @@
 #include "summary_device.hpp"
 
 int mcd_summary_run_(const mcd::SumSrc& S, int32_t max_lag, hipStream_t st, double* pooled, double* per_chain);   // summary_capi.cpp
+int mcd_summary_check_(const char* who, int64_t n, int64_t batch, int64_t q, int32_t max_lag);
 extern "C" int mcd_set_last_error_(int code, const char* msg);   // mvn_capi.cpp
 struct mcd_sparse;
 struct mcd_sparse_tree;
@@ -1165,6 +1166,64 @@ int mcd_mh_record_summary(mcd_mh_t* m, int64_t skip, int64_t n_samples, int32_t 
         if (beta[(size_t)b] != 1.0)
             return mfail(MCD_ERR_UNSUPPORTED, "mcd_mh_record_summary: chain %lld has the reciprocal temperature %g: only cold chains (1) are summarised", (long long)b, beta[(size_t)b]);
     if (int rc = mcd_summary_run_(S, max_lag, m->stream, pooled, per_chain)) return rc;
+    if (n_used) *n_used = n;
+    return MCD_OK;
+}
+
+// ... under MC3: the rung's sequence of every group is gathered out of the ring into a plain trace (k_mc3_summary.hip), which then goes
+// through the same summary.  Everything the call allocates lives in one block that `Scratch` frees on every way out.
+int mcd_mh_record_summary_mc3(mcd_mh_t* m, int rung, int64_t skip, int64_t n_samples, int32_t max_lag, int64_t* n_used, double* pooled,
+                              double* per_group, int32_t* holder, int64_t* visits, int64_t* round_trips)
+{
+    const char* who = "mcd_mh_record_summary_mc3";
+    if (!m || !pooled) return mfail(MCD_ERR_INVALID_ARG, "%s: NULL argument", who);
+    if (n_used) *n_used = 0;
+    const mcd::MhDev& D = m->dev;
+    mcd::SumSrc R{};
+    int64_t n = 0;
+    if (int rc = m->rec.window(who, m->rec_on(), skip, n_samples, max_lag, &R, &n)) return rc;
+    const int C = m->mc3.n_chains;
+    if (C == 0) return mfail(MCD_ERR_INVALID_ARG, "%s: Metropolis-coupled MCMC is not initialised on this handle (mcd_mh_mc3_init first)", who);
+    if (rung < 0 || rung >= C) return mfail(MCD_ERR_INVALID_ARG, "%s: rung %d, the ladder has the rungs 0 .. %d", who, rung, C - 1);
+    if (D.chain0 % C != 0 || D.batch % C != 0)
+        return mfail(MCD_ERR_UNSUPPORTED, "%s: the handle's chains [%lld, %lld) are not whole groups of %d chains: a group's rung can lie on another handle", who,
+                     (long long)D.chain0, (long long)(D.chain0 + D.batch), C);
+    const int64_t G = D.batch / C, Q = R.Q, ldq = 8 * ((Q + 7) / 8);
+    if (int rc = mcd_summary_check_(who, n, G, Q, max_lag)) return rc;
+    const bool flow = visits || round_trips;
+    // one block: the trace [n][G][ldq] doubles, visits [batch][C] and round_trips [batch] int64, the error word, holder [n][G] int32
+    const size_t n_trace = (size_t)(n * G * ldq), n_flow = flow ? (size_t)(D.batch * (C + 1)) : 0, n_hold = (size_t)(n * G);
+    const size_t bytes = 8 * (n_trace + n_flow + 1) + 4 * n_hold;
+    struct Scratch {
+        void* p = nullptr;
+        ~Scratch() { if (p) (void)hipFree(p); }
+    } buf;
+    MHIP_TRY(hipSetDevice(m->device));
+    if (hipError_t e = hipMalloc(&buf.p, bytes)) return mfail(MCD_ERR_HIP, "%s: %zu bytes for the gathered trace: %s", who, bytes, hipGetErrorString(e));
+    double* d_trace = (double*)buf.p;
+    int64_t* d_visits = (int64_t*)(d_trace + n_trace);
+    int64_t* d_trips = d_visits + (flow ? D.batch * C : 0);
+    unsigned long long* d_err = (unsigned long long*)(d_visits + n_flow);
+    int32_t* d_holder = (int32_t*)(d_err + 1);
+    const mcd::Mc3Win W{R.base, n, D.batch, R.first, R.cap, R.stride, R.ld, R.n_nodes, C, m->mc3.ladder};
+    unsigned long long err = 0;
+    MHIP_TRY(hipMemsetAsync(d_err, 0, sizeof err, m->stream));
+    MHIP_TRY(mcd::launch_mc3_gather(W, rung, Q, ldq, d_trace, d_holder, d_err, m->stream));
+    if (flow) MHIP_TRY(mcd::launch_mc3_flow(W, d_visits, d_trips, m->stream));
+    MHIP_TRY(hipMemcpyAsync(&err, d_err, sizeof err, hipMemcpyDeviceToHost, m->stream));
+    MHIP_TRY(hipStreamSynchronize(m->stream));
+    if (err != 0) {
+        const int64_t p = (int64_t)(err >> 8 & 0xffffffffull);
+        return mfail(MCD_ERR_INVALID_ARG, "%s: sample %lld of group %lld has %d chains at rung %d: the window holds samples recorded before mcd_mh_mc3_init or after a mcd_mh_set_temperatures",
+                     who, (long long)(p / G), (long long)(p % G), (int)(err & 0xff), rung);
+    }
+    // base, n, B, Q, ldq, then the ring's fields: a plain trace
+    const mcd::SumSrc S{d_trace, n, G, Q, ldq, 0, 0, 0, 0, 0, 0};
+    if (int rc = mcd_summary_run_(S, max_lag, m->stream, pooled, per_group)) return rc;
+    if (holder) MHIP_TRY(hipMemcpyAsync(holder, d_holder, sizeof(int32_t) * n_hold, hipMemcpyDeviceToHost, m->stream));
+    if (visits) MHIP_TRY(hipMemcpyAsync(visits, d_visits, sizeof(int64_t) * (size_t)(D.batch * C), hipMemcpyDeviceToHost, m->stream));
+    if (round_trips) MHIP_TRY(hipMemcpyAsync(round_trips, d_trips, sizeof(int64_t) * (size_t)D.batch, hipMemcpyDeviceToHost, m->stream));
+    MHIP_TRY(hipStreamSynchronize(m->stream));
     if (n_used) *n_used = n;
     return MCD_OK;
 }

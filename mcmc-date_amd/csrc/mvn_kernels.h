@@ -398,6 +398,21 @@ hipError_t launch_mh_rec_unpack(const MhRecDims& S, const MhRec& R, int64_t firs
                                 double* post, double* beta, double* diag, hipStream_t st);
 hipError_t launch_mc3_swap(const Mc3Dev& C, const double* lnpost, int world, int64_t per_rank, int n_swaps, uint64_t seed, uint64_t phase,
                            double* beta_local, int64_t chain0, int64_t batch, hipStream_t st);
+// A window of the recorder's ring under MC3 (k_mc3_summary.hip): sample k is slot (first + k) % cap, a slot [batch] records of `stride`
+// doubles (MhRec), the handle's chains being batch / n_chains whole groups of n_chains consecutive chains with the ladder [n_chains].
+struct Mc3Win {
+    const double* ring;
+    int64_t n, batch, first, cap, stride, ld;
+    int32_t n_nodes, n_chains;
+    const double* ladder;
+};
+// The rung-`rung` sequence of every group as a plain trace [n][G][ldq], G = batch / n_chains, Q <= ldq quantities in the order of
+// mcd_mh_record_quantities, and holder [n][G] (the local chain that carried the rung).  A (sample, group) without exactly one chain at the
+// rung writes nothing of its row and sets *err (zeroed by the caller) to 1 << 63 | (k G + g) << 8 | count.
+hipError_t launch_mc3_gather(const Mc3Win& W, int rung, int64_t Q, int64_t ldq, double* trace, int32_t* holder, unsigned long long* err,
+                             hipStream_t st);
+// visits [batch][n_chains]: samples of the window each chain spent at each rung; round_trips [batch]: its completed cold -> hottest -> cold passages
+hipError_t launch_mc3_flow(const Mc3Win& W, int64_t* visits, int64_t* round_trips, hipStream_t st);
 // ln prior of the proposed states from pflags / pcomp (what launch_mh_step leaves when asked not to evaluate it itself) as extra
 // workgroups of the sweep's tree-likelihood launch (k_tree_logpdf.hip): the ln prior and the ln likelihood of a proposal depend
 // on nothing but the proposal

@@ -1,9 +1,11 @@
 """Posterior summaries and convergence diagnostics of a trace x[n samples, B chains, Q quantities].
 
-Two things live here:
+Three things live here:
   * a plain-numpy restatement of the definitions of include/mcmcdate_mvn.h (mcd_trace_summary) -- `split_rhat`, `ess`, `summary` --: the host
     mirror of csrc/k_summary.hip and the reference of its tests;
-  * `trace_summary`: the same numbers from the device kernels, through the C ABI.
+  * `trace_summary`: the same numbers from the device kernels, through the C ABI;
+  * `rung_trace`, `replica_flow`: under Metropolis-coupled MCMC, the sequence of one temperature through the swaps and how the chains travel
+    over the ladder -- the restatement of csrc/k_mc3_summary.hip (Sampler.record_summary_mc3).
 
 Definitions, with l = n B pooled values per quantity:
   mean, variance (maximum likelihood, / l), minimum, maximum, and the two order statistics of monitor.summarize_node_ages,
@@ -21,7 +23,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 from dataclasses import dataclass
-from typing import Optional
+from typing import Optional, Sequence
 
 import numpy as np
 
@@ -151,6 +153,53 @@ def summary(x: np.ndarray, max_lag: int = 0, per_chain: bool = True) -> Summary:
             pc[:, nan, :] = np.nan
     pooled[nan, :] = np.nan
     return Summary(pooled, pc, pmin)
+
+
+def rung_trace(x: np.ndarray, beta: np.ndarray, value: float, n_chains: int):
+    """Follow one temperature through the swaps of Metropolis-coupled MCMC -- the numpy restatement of csrc/k_mc3_summary.hip: k_mc3_gather.
+    x [n, B, Q] and beta [n, B] (the reciprocal temperature every chain ran with, as record_fetch returns it); the B chains are B // n_chains
+    groups of n_chains consecutive chains.  Returns (trace [n, B // n_chains, Q], holder [n, B // n_chains] int32): sample by sample the
+    row of the one chain of each group whose beta EQUALS `value` (a rung of the ladder: the swap phase stores the ladder's doubles, so
+    equality is exact), and that chain's index in its group.  ValueError where a (sample, group) does not have exactly one such chain."""
+    x, beta = np.asarray(x, dtype=np.float64), np.asarray(beta, dtype=np.float64)
+    C = int(n_chains)
+    if x.ndim != 3 or beta.shape != x.shape[:2] or C < 1 or x.shape[1] % C != 0:
+        raise ValueError("rung_trace: expected x [n, B, Q], beta [n, B] and B a multiple of n_chains")
+    n, B, Q = x.shape
+    G = B // C
+    hit = beta.reshape(n, G, C) == value
+    count = hit.sum(axis=2)
+    if np.any(count != 1):
+        k, g = (int(v) for v in np.argwhere(count != 1)[0])
+        raise ValueError(f"rung_trace: sample {k} of group {g} has {int(count[k, g])} chains at beta = {value!r}")
+    holder = hit.argmax(axis=2).astype(np.int32)
+    trace = np.take_along_axis(x.reshape(n, G, C, Q), holder[:, :, None, None].astype(np.int64), axis=2)[:, :, 0, :]
+    return np.ascontiguousarray(trace), holder
+
+
+def replica_flow(beta: np.ndarray, ladder: Sequence[float]):
+    """How the chains travel over the temperature ladder (csrc/k_mc3_summary.hip: k_mc3_flow, restated): beta [n, B] as for rung_trace,
+    ladder [C] strictly decreasing from 1.  Returns (visits [B, C] int64: the samples each chain spent at each rung, a beta mapped to its
+    rung by equality; round_trips [B] int64: completed passages cold -> hottest -> cold -- armed at rung 0, marked at rung C - 1, counted at
+    the next return to rung 0).  A beta that is not on the ladder counts nowhere."""
+    beta, ladder = np.asarray(beta, dtype=np.float64), np.asarray(ladder, dtype=np.float64)
+    if beta.ndim != 2 or ladder.ndim != 1 or len(ladder) < 2:
+        raise ValueError("replica_flow: expected beta [n, B] and a ladder of at least two rungs")
+    n, B = beta.shape
+    C = len(ladder)
+    on = beta[:, :, None] == ladder[None, None, :]                       # [n, B, C]
+    visits = on.sum(axis=0).astype(np.int64)
+    rung = np.where(on.any(axis=2), on.argmax(axis=2), -1)
+    trips = np.zeros(B, np.int64)
+    for b in range(B):
+        state = 0                                                        # 0 idle, 1 armed at the cold rung, 2 has reached the hottest
+        for r in rung[:, b]:
+            if r == 0:
+                trips[b] += state == 2
+                state = 1
+            elif r == C - 1 and state == 1:
+                state = 2
+    return visits, trips
 
 
 def trace_summary(X, max_lag: int = 0, device=True, per_chain: bool = True, q: Optional[int] = None) -> Summary:

@@ -241,16 +241,22 @@ def summarize_node_ages(ages: np.ndarray, burn_in: float = 0.25, names: Optional
     return AgeSummary(np.arange(n), list(names) if names is not None else [""] * n, mean, var, srt[0], srt[-1], srt[i_ci], srt[i_ci + n_ci - 1])
 
 
-def summarize_recorded(sampler, burn_in: float = 0.25, names: Optional[Sequence[str]] = None, max_lag: int = 255) -> AgeSummary:
+def summarize_recorded(sampler, burn_in: float = 0.25, names: Optional[Sequence[str]] = None, max_lag: int = 255,
+                       rung: Optional[int] = None) -> AgeSummary:
     """`summarize_node_ages` of the pooled ages of the samples waiting in the sampler's recorder, after dropping the oldest
     round(waiting * burn_in) of them -- computed on the device where the samples lie (Sampler.record_summary): nothing is fetched and the
     samples stay where they are.  Also gives the split R-hat and the effective sample size of every node's age over the chains.
-    `sampler`: a Sampler or an hmc.Leapfrog with an active recorder (both have record_count / record_summary)."""
+    `sampler`: a Sampler or an hmc.Leapfrog with an active recorder (both have record_count / record_summary).
+    rung: for a Sampler under Metropolis-coupled MCMC, the rung of the ladder whose sequences are pooled (0: the cold ones, what the
+    reference's monitors report; Sampler.record_summary_mc3) -- the chains themselves change temperature and are refused."""
     waiting = sampler.record_count()
     skip = int(round(waiting * burn_in))
     if skip >= waiting:
         raise ValueError("summarize_recorded: no samples left after burn-in")
-    a = sampler.record_summary(skip=skip, max_lag=max_lag).ages
+    if rung is None:
+        a = sampler.record_summary(skip=skip, max_lag=max_lag).ages
+    else:
+        a = sampler.record_summary_mc3(rung=rung, skip=skip, max_lag=max_lag).ages
     n = a.shape[0]
     return AgeSummary(np.arange(n), list(names) if names is not None else [""] * n, a[:, 0].copy(), a[:, 1].copy(), a[:, 2].copy(), a[:, 3].copy(),
                       a[:, 4].copy(), a[:, 5].copy(), a[:, 6].copy(), a[:, 7].copy())

@@ -366,6 +366,37 @@ class Sampler(RecorderCalls):
         pooled, used, lag, pc = self._record_summary(skip, n, max_lag, per_chain)
         return RecordSummary(pooled, self.topo.n_nodes, used, lag, pc)
 
+    def record_summary_mc3(self, rung: int = 0, skip: int = 0, n: Optional[int] = None, max_lag: int = 255, per_group: bool = False,
+                           flow: bool = False) -> "RecordSummary":
+        """record_summary under Metropolis-coupled MCMC (an `MC3` over this sampler; mcd_mh_record_summary_mc3): the waiting samples
+        [skip, skip + n) of the RUNG-`rung` sequence of every group of chains -- sample by sample the chain that ran at ladder[rung], followed
+        through the swaps on the device (csrc/k_mc3_summary.hip); rung 0 is the cold sequence.  The statistics are record_summary's with a
+        group's sequence in the place of a chain: `per_chain` [G, Q, 4] holds the per-group block (per_group True), `holder` [n, G] the chain
+        of each group that carried the rung; flow True adds `visits` [B, n_chains] (samples each chain spent at each rung) and `round_trips`
+        [B] (its completed cold -> hottest -> cold passages)."""
+        # the groups' size: what the MC3 over this sampler set.  Without one the library refuses the call; the arrays then have the largest
+        # shapes any ladder could ask for (groups of 2, 16 rungs), so that nothing depends on that refusal
+        known = getattr(self, "_mc3_chains", 0)
+        C_ = known or 16
+        B, G = self.batch, self.batch // (known or 2)
+        Q = 2 * self.topo.n_nodes + 9
+        count = max(self.record_count() - int(skip) if n is None else int(n), 0)
+        lag = min(int(max_lag), count // 2 - 1)
+        lag = max(0, lag if lag % 2 == 1 else lag - 1)
+        pooled = np.empty((Q, _capi.MCD_SUMMARY_COLS))
+        pg = np.empty((G, Q, 4)) if per_group else None
+        holder = np.empty((count, G), np.int32)
+        visits, trips = (np.empty((B, C_), np.int64), np.empty(B, np.int64)) if flow else (None, None)
+        used = C.c_int64(0)
+        lp = C.POINTER(C.c_int64)
+        _capi.check(_capi.lib().mcd_mh_record_summary_mc3(self._h, int(rung), int(skip), -1 if n is None else int(n), lag, C.byref(used),
+                                                          pooled.ctypes.data_as(_dp), pg.ctypes.data_as(_dp) if per_group else None,
+                                                          holder.ctypes.data_as(_ip), visits.ctypes.data_as(lp) if flow else None,
+                                                          trips.ctypes.data_as(lp) if flow else None))
+        if not known or used.value != count:
+            raise RuntimeError("record_summary_mc3: the handle's MC3 was not set up by sampler.MC3, or the recorder moved during the call")
+        return RecordSummary(pooled, self.topo.n_nodes, int(used.value), lag, pg, None, holder, visits, trips)
+
     def node_age_summary(self):
         """Posterior mean and variance of every node age pooled over chains and accumulated iterations, plus the
         standard error of the mean estimated from the spread of the per-chain means."""
@@ -390,6 +421,10 @@ class RecordSummary:
     max_lag: int
     per_chain: Optional[np.ndarray] = None
     nuts_stats: Optional[np.ndarray] = None    # [B, 4] hmc.Leapfrog.NUTS_STATS of the window (Leapfrog.record_summary only)
+    # Sampler.record_summary_mc3 only (per_chain is then per GROUP of chains, [G, Q, 4]):
+    holder: Optional[np.ndarray] = None        # [n_samples, G] int32: the chain of each group that carried the summarised rung
+    visits: Optional[np.ndarray] = None        # [B, n_chains] int64: samples of the window each chain spent at each rung (flow=True)
+    round_trips: Optional[np.ndarray] = None   # [B] int64: completed cold -> hottest -> cold passages of each chain (flow=True)
 
     SCALARS = ("time_birth_rate", "time_death_rate", "time_height", "rate_mean", "rate_variance")
     POST = ("ln_prior", "ln_likelihood", "ln_jacobian_root_branch", "ln_posterior")
@@ -514,6 +549,7 @@ class MC3:
         self.device = isinstance(backend, Sampler)
         if self.device:
             _capi.check(_capi.lib().mcd_mh_mc3_init(backend._h, self.n, self.ladder.ctypes.data_as(_dp), self.total, C.c_uint64(self.seed)))
+            backend._mc3_chains = self.n                               # (Sampler.record_summary_mc3 sizes its arrays by it)
         else:
             self._rank = (np.arange(self.total) % self.n).astype(np.int32)
             self._tried = np.zeros(n_chains - 1, np.int64)
@@ -545,6 +581,13 @@ class MC3:
     def cold(self) -> np.ndarray:
         """Local indices of this backend's chains that are cold right now."""
         return np.nonzero(self.rank[self.lo:self.lo + self.backend.batch] == 0)[0]
+
+    def record_summary(self, **kw) -> "RecordSummary":
+        """Sampler.record_summary_mc3 on the backend's recorder: summaries and convergence diagnostics of one rung's sequences (rung=0: the
+        cold ones) and, with flow=True, how the chains travelled over the ladder.  Device backends only: the ring lives on the device."""
+        if not self.device:
+            raise ValueError("MC3.record_summary: the backend is not a Sampler (no device recorder)")
+        return self.backend.record_summary_mc3(**kw)
 
     def swap(self):
         """One swap phase."""
