@@ -6,22 +6,28 @@
 
 namespace mcd {
 
+// The leading arguments are what the first memory instructions of either role need, scalars and pointers only: gfx950 preloads
+// them into SGPRs at wave launch (-mllvm -amdgpu-kernarg-preload-count, Makefile), so the loads of x and the first LDS-DMA of the
+// factor do not wait for a scalar load from a cold kernarg segment first.  14 dwords fit beside the kernarg pointer in the 16 user
+// SGPRs: F (the stream FS reads, fwd_stream_ptr) .. ncols.  ll, c and logdet are used by finish_ll only and arrive the ordinary way.
 template <int R, int BT, int CW, int LW, int FS>
-__global__ void __launch_bounds__(64 * (CW + LW)) k_logpdf(MvnDev M, const double* __restrict__ X, int64_t ldx,
-                                                           int64_t batch, double* __restrict__ ll)
+__global__ void __launch_bounds__(64 * (CW + LW)) k_logpdf(const double* __restrict__ F, const double* __restrict__ mu,
+                                                           const double* __restrict__ invdiag, const double* __restrict__ X, int64_t ldx,
+                                                           int64_t batch, int n, int ncols, double* __restrict__ ll, double c, double logdet)
 {
     MCD_KERNEL_HEAD_FS(FS)
     MCD_ACC_DECL
     MCD_T(0);
     if (wave >= CW) {                                      // loader role
         const int lw = wave - CW;
-        fwd_loader_role<R, LW, FS>(M, ring, lw, lane, ncols MCD_ACC_ARGS);
+        fwd_loader_role<R, LW, FS>(F, ring, lw, lane, ncols MCD_ACC_ARGS);
         MCD_T(3);
         MCD_ACC_FLUSH(5);
         return;
     }
+    const MvnView M(mu, invdiag, n, c, logdet);
     double d[R][BT];
-    load_rawx<R, BT>(d, M, X, ldx, b0, batch, lane);
+    load_rawx<R, BT, FS == 2>(d, M, X, ldx, b0, batch, lane);
     MCD_T(1);
     lds_barrier();
     MCD_T(2);
@@ -32,28 +38,24 @@ __global__ void __launch_bounds__(64 * (CW + LW)) k_logpdf(MvnDev M, const doubl
     MCD_ACC_FLUSH(5);
 }
 
-template <int R, int BT, int CW, int LW>
-static void launch_geom(const MvnDev& M, const double* X, int64_t ldx, int64_t batch, double* ll, hipStream_t st)
+template <int R, int BT, int CW, int LW, int FS>
+static void launch_fs(const MvnDev& M, const double* X, int64_t ldx, int64_t batch, double* ll, hipStream_t st)
 {
     const int64_t per_wg = (int64_t)CW * BT;
     const unsigned grid = (unsigned)((batch + per_wg - 1) / per_wg);
-    switch (fwd_stream<R>(CW)) {
-    case 1:
-        if constexpr (fwd_stream_compact(R)) {
-            hipLaunchKernelGGL((k_logpdf<R, BT, CW, LW, 1>), dim3(grid), dim3(64 * (CW + LW)), 0, st, M, X, ldx, batch, ll);
-            return;
-        }
-        break;
-    case 2:
-        if constexpr (fwd_stream_compact(R)) {
-            hipLaunchKernelGGL((k_logpdf<R, BT, CW, LW, 2>), dim3(grid), dim3(64 * (CW + LW)), 0, st, M, X, ldx, batch, ll);
-            return;
-        }
-        break;
-    default:
-        break;
+    hipLaunchKernelGGL((k_logpdf<R, BT, CW, LW, FS>), dim3(grid), dim3(64 * (CW + LW)), 0, st, fwd_stream_ptr(M, FS), M.mu, M.invdiag, X, ldx,
+                       batch, M.n, M.ncols, ll, M.c, M.logdet);
+}
+
+template <int R, int BT, int CW, int LW>
+static void launch_geom(const MvnDev& M, const double* X, int64_t ldx, int64_t batch, double* ll, hipStream_t st)
+{
+    if constexpr (fwd_stream_compact(R)) {
+        const int fs = fwd_stream<R>(CW);
+        if (fs == 1) return launch_fs<R, BT, CW, LW, 1>(M, X, ldx, batch, ll, st);
+        if (fs == 2) return launch_fs<R, BT, CW, LW, 2>(M, X, ldx, batch, ll, st);
     }
-    hipLaunchKernelGGL((k_logpdf<R, BT, CW, LW, 0>), dim3(grid), dim3(64 * (CW + LW)), 0, st, M, X, ldx, batch, ll);
+    launch_fs<R, BT, CW, LW, 0>(M, X, ldx, batch, ll, st);
 }
 
 template <int R>

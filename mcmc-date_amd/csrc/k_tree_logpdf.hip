@@ -19,12 +19,18 @@ struct MhPriorJob {
 };
 struct NoJob {};
 
+// The leading arguments are scalars and pointers only, in the order the likelihood role's first memory instructions need them, as
+// far as the preloaded SGPRs reach (k_logpdf.hip): the factor stream for the loaders, the chain's state rows and the node count for
+// the compute waves, then the slot tables, mu and 1/diag.  The prior variant reads J.n_wgs before it knows a wave's role, by a
+// scalar load as before.  F: the stream FS reads (fwd_stream_ptr).
 template <int R, int BT, int CW, int LW, bool PRIOR, int FS>
-__global__ void __launch_bounds__(64 * (CW + LW)) k_tree_logpdf(MvnDev M, TreeDev T, const double* __restrict__ H,
-                                                                const double* __restrict__ Rt, int64_t lds,
-                                                                const double* __restrict__ tH,
-                                                                const double* __restrict__ rMu, int64_t batch,
-                                                                double* __restrict__ ll, double* __restrict__ logjac,
+__global__ void __launch_bounds__(64 * (CW + LW)) k_tree_logpdf(const double* __restrict__ F, const double* __restrict__ H,
+                                                                const double* __restrict__ Rt, int64_t lds, int64_t batch, int n_nodes,
+                                                                int root_right, const int32_t* __restrict__ slot_node,
+                                                                const int32_t* __restrict__ slot_parent, const double* __restrict__ mu,
+                                                                const double* __restrict__ invdiag, const double* __restrict__ tH,
+                                                                const double* __restrict__ rMu, int ncols, double* __restrict__ ll,
+                                                                double* __restrict__ logjac, double c, double logdet,
                                                                 std::conditional_t<PRIOR, MhPriorJob, NoJob> J)
 {
     unsigned bid_off = 0;
@@ -48,9 +54,11 @@ __global__ void __launch_bounds__(64 * (CW + LW)) k_tree_logpdf(MvnDev M, TreeDe
     }
     MCD_ACC_DECL
     if (wave >= CW) {                                      // loader role
-        fwd_loader_role<R, LW, FS>(M, ring, wave - CW, lane, ncols MCD_ACC_ARGS);
+        fwd_loader_role<R, LW, FS>(F, ring, wave - CW, lane, ncols MCD_ACC_ARGS);
         return;
     }
+    const MvnView M(mu, invdiag, 0, c, logdet);
+    const TreeView T(n_nodes, root_right, slot_node, slot_parent);
     double d[R][BT], dist[R][BT];
     // a sampler's batch (two compute waves per workgroup) on trees up to 258 nodes: the state rows go through LDS (10 KiB beside
     // the ring: two workgroups still fit a CU); elsewhere the gather from global memory
@@ -74,21 +82,23 @@ __global__ void __launch_bounds__(64 * (CW + LW)) k_tree_logpdf(MvnDev M, TreeDe
 // Metropolis-Hastings step's likelihood launch) keeps the padded stream whatever MCD_FSTREAM says: its workgroups of both roles share
 // CUs two by two, which the LDS-DMA ring's four slots would not leave room for, and the compact stream staged through registers
 // measured no gain on the sweep
+template <int R, int BT, int CW, int LW, bool PRIOR, int FS, class JOB>
+static void launch_tree_fs_k(unsigned grid, hipStream_t st, const MvnDev& M, const TreeDev& T, const double* H, const double* Rt, int64_t lds,
+                             const double* tH, const double* rMu, int64_t batch, double* ll, double* logjac, const JOB& J)
+{
+    hipLaunchKernelGGL((k_tree_logpdf<R, BT, CW, LW, PRIOR, FS>), dim3(grid), dim3(64 * (CW + LW)), 0, st, fwd_stream_ptr(M, FS), H, Rt, lds,
+                       batch, T.n_nodes, T.root_right, T.slot_node, T.slot_parent, M.mu, M.invdiag, tH, rMu, M.ncols, ll, logjac, M.c, M.logdet, J);
+}
+
 template <int R, int BT, int CW, int LW, bool PRIOR, class... A>
-static void launch_tree_fs(unsigned grid, hipStream_t st, A... a)
+static void launch_tree_fs(unsigned grid, hipStream_t st, const A&... a)
 {
     if constexpr (fwd_stream_compact(R) && !PRIOR) {
         const int fs = fwd_stream<R>(CW);
-        if (fs == 1) {
-            hipLaunchKernelGGL((k_tree_logpdf<R, BT, CW, LW, PRIOR, 1>), dim3(grid), dim3(64 * (CW + LW)), 0, st, a...);
-            return;
-        }
-        if (fs == 2) {
-            hipLaunchKernelGGL((k_tree_logpdf<R, BT, CW, LW, PRIOR, 2>), dim3(grid), dim3(64 * (CW + LW)), 0, st, a...);
-            return;
-        }
+        if (fs == 1) return launch_tree_fs_k<R, BT, CW, LW, PRIOR, 1>(grid, st, a...);
+        if (fs == 2) return launch_tree_fs_k<R, BT, CW, LW, PRIOR, 2>(grid, st, a...);
     }
-    hipLaunchKernelGGL((k_tree_logpdf<R, BT, CW, LW, PRIOR, 0>), dim3(grid), dim3(64 * (CW + LW)), 0, st, a...);
+    launch_tree_fs_k<R, BT, CW, LW, PRIOR, 0>(grid, st, a...);
 }
 
 template <int R, bool PRIOR, class JOB>

@@ -551,43 +551,51 @@ __device__ __forceinline__ void fc_dma_chunks(const double* __restrict__ Fc, d2*
     }
 }
 
-// the whole loader role of FS = 2, first barrier included
+// the whole loader role of FS = 2, first barrier included.  The stream runs from the first instruction: chunks 0 .. NS-2 are requested
+// back to back, and only chunk 0 is waited for before the first barrier.
+//   slots: chunk c goes to slot c % NS, so chunks 0 .. NS-2 fill NS-1 different slots of a ring nobody has read yet; slot NS-1 stays
+//     free for chunk NS-1, which the loop requests at CI = 0 -- the state the loop has always started from.
+//   counter: a wave's LDS-DMAs complete in the order it issued them, and it issues at least fc_dma_min(R, LW, 1, NS-1) of them for
+//     chunks 1 .. NS-2 after its share of chunk 0.  Once vmcnt is down to that number, whatever is still in flight belongs to
+//     those later chunks: the wave's share of chunk 0 is in LDS.  (A wave that issued more than the minimum waits for a little more.)
+//   across launches: a workgroup's loaders end on vmcnt(0), so nothing of one launch is in flight into LDS when the next one starts.
 template <int R, int LW, int FS>
 __device__ __forceinline__ void fc_dma_loader(const double* __restrict__ Fc, d2* ring, int lw, int lane, int ncols)
 {
+    constexpr int NS = Ring<R, FS>::NS;
     if (lw == 0) ring[Ring<R, FS>::ZERO + lane] = d2{0.0, 0.0};
-    fc_dma_chunk<R, LW, FS, 0>(Fc, ring, lw, lane);
-    wait_vmcnt<0>();
+    fc_dma_chunks<R, LW, FS, 0, NS - 1>(Fc, ring, lw, lane);
+    wait_vmcnt<fc_dma_min(R, LW, 1, NS - 1)>();
     MCD_T(1);
     lds_barrier();
     MCD_T(2);
-    fc_dma_chunks<R, LW, FS, 1, Ring<R, FS>::NS - 1>(Fc, ring, lw, lane);
     fc_dma_loader_chunks<R, LW, FS, 0>(Fc, ring, lw, lane, ncols);
     wait_vmcnt<0>();                                       // (nothing in flight into the ring when the wave ends)
 }
 
 // The loader role of a forward sweep for stream FS, first barrier included (MCD_T: the milestones of the diagnostic builds).
+// F: the stream FS reads -- Ft (FS = 0) or Fc (fwd_stream_ptr).
 template <int R, int LW, int FS>
-__device__ __forceinline__ void fwd_loader_role(const MvnDev& M, d2* ring, int lw, int lane, int ncols MCD_ACC_PARAMS)
+__device__ __forceinline__ void fwd_loader_role(const double* __restrict__ F, d2* ring, int lw, int lane, int ncols MCD_ACC_PARAMS)
 {
     if constexpr (FS == 2) {
-        fc_dma_loader<R, LW, FS>(M.Fc, ring, lw, lane, ncols);
+        fc_dma_loader<R, LW, FS>(F, ring, lw, lane, ncols);
     } else if constexpr (FS == 1) {
         Stage<R, LW> st;
-        fc_loader_prologue<R, LW>(M.Fc, ring, st, lw, lane);
+        fc_loader_prologue<R, LW>(F, ring, st, lw, lane);
         MCD_T(1);
         lds_barrier();
         MCD_T(2);
-        fc_loader_start<R, LW>(M.Fc, st, lw, lane);
-        fc_loader<R, LW, 0>(M.Fc, ring, st, lw, lane, ncols MCD_ACC_ARGS);
+        fc_loader_start<R, LW>(F, st, lw, lane);
+        fc_loader<R, LW, 0>(F, ring, st, lw, lane, ncols MCD_ACC_ARGS);
     } else {
         Stage<R, LW> st;
-        fwd_loader_prologue<R, LW>(M.Ft, ring, st, lw, lane);
+        fwd_loader_prologue<R, LW>(F, ring, st, lw, lane);
         MCD_T(1);
         lds_barrier();
         MCD_T(2);
-        fwd_loader_start<R, LW>(M.Ft, st, lw, lane);
-        fwd_loader<R, LW, 0>(M.Ft, ring, st, lw, lane, ncols MCD_ACC_ARGS);
+        fwd_loader_start<R, LW>(F, st, lw, lane);
+        fwd_loader<R, LW, 0>(F, ring, st, lw, lane, ncols MCD_ACC_ARGS);
     }
 }
 
@@ -741,21 +749,72 @@ __device__ __forceinline__ void bwd_loader(const double* __restrict__ Ut, d2* ri
 // ---------------------------------------------------------------------------------------
 // state -> residual prologues (compute waves)
 // ---------------------------------------------------------------------------------------
-template <int R, int BT>
-__device__ __forceinline__ void load_rawx(double (&d)[R][BT], const MvnDev& M, const double* __restrict__ X, int64_t ldx,
+// What the prologues and finish_ll read of a handle and of a topology.  The likelihood kernels (k_logpdf.hip, k_tree_logpdf.hip)
+// build them from their leading scalar arguments, which the hardware hands over in SGPRs at wave launch (kernarg preload: a struct
+// passed by value in front of them would switch it off); the gradient kernels still pass their MvnDev / TreeDev.
+struct MvnView {
+    const double* mu;
+    const double* invdiag;
+    int n;                     // rows of x that exist (load_rawx only)
+    double c, logdet;          // finish_ll only
+    __device__ MvnView(const double* mu_, const double* invdiag_, int n_, double c_, double logdet_)
+        : mu(mu_), invdiag(invdiag_), n(n_), c(c_), logdet(logdet_) {}
+    __device__ MvnView(const MvnDev& M) : mu(M.mu), invdiag(M.invdiag), n(M.n), c(M.c), logdet(M.logdet) {}
+};
+struct TreeView {
+    int n_nodes, root_right;
+    const int32_t* slot_node;
+    const int32_t* slot_parent;
+    __device__ TreeView(int n_nodes_, int root_right_, const int32_t* slot_node_, const int32_t* slot_parent_)
+        : n_nodes(n_nodes_), root_right(root_right_), slot_node(slot_node_), slot_parent(slot_parent_) {}
+    __device__ TreeView(const TreeDev& T) : n_nodes(T.n_nodes), root_right(T.root_right), slot_node(T.slot_node), slot_parent(T.slot_parent) {}
+};
+
+// AHEAD: every load is issued before the first value is used -- a padded row or a chain beyond the batch reads a clamped address
+// and the value is dropped for mu.  (The load under `if (row < n)` with mu as the other branch makes each row block's x wait for its
+// mu: R dependent round trips.  Behind the register-staged loaders that chain hides under chunk 0's arrival and AHEAD measured no
+// gain; behind the LDS-DMA loaders, whose first NS-1 chunks are queued in front of every later load of the CU, it held the first
+// barrier back -- profiles/r10_headline_ab.txt.  k_logpdf sets it for FS = 2.)  Same values, same arithmetic, same bits.
+template <int R, int BT, bool AHEAD = false>
+__device__ __forceinline__ void load_rawx(double (&d)[R][BT], const MvnView& M, const double* __restrict__ X, int64_t ldx,
                                           int64_t b0, int64_t batch, int lane)
 {
+    if constexpr (AHEAD) {
+        double m[R], iv[R], xr[R][BT];
 #pragma unroll
-    for (int k = 0; k < R; ++k) {
-        const int row = 64 * k + lane;
-        const double m = M.mu[row];        // padded: 0
-        const double iv = M.invdiag[row];  // padded: 1
+        for (int k = 0; k < R; ++k) {
+            const int row = 64 * k + lane;
+            m[k] = M.mu[row];
+            iv[k] = M.invdiag[row];
+            const int rc = row < M.n ? row : M.n - 1;
 #pragma unroll
-        for (int c = 0; c < BT; ++c) {
-            const int64_t b = b0 + c;
-            double xv = m;
-            if (row < M.n && b < batch) xv = X[b * ldx + row];
-            d[k][c] = (xv - m) * iv;       // dxs = xs - mu  (app/Probability.hs:171), then row scaling
+            for (int c = 0; c < BT; ++c) {
+                const int64_t bc = (b0 + c < batch) ? b0 + c : batch - 1;
+                xr[k][c] = X[bc * ldx + rc];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            const int row = 64 * k + lane;
+#pragma unroll
+            for (int c = 0; c < BT; ++c) {
+                const double xv = (row < M.n && b0 + c < batch) ? xr[k][c] : m[k];
+                d[k][c] = (xv - m[k]) * iv[k];
+            }
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            const int row = 64 * k + lane;
+            const double m = M.mu[row];        // padded: 0
+            const double iv = M.invdiag[row];  // padded: 1
+#pragma unroll
+            for (int c = 0; c < BT; ++c) {
+                const int64_t b = b0 + c;
+                double xv = m;
+                if (row < M.n && b < batch) xv = X[b * ldx + row];
+                d[k][c] = (xv - m) * iv;       // dxs = xs - mu  (app/Probability.hs:171), then row scaling
+            }
         }
     }
 }
@@ -763,7 +822,7 @@ __device__ __forceinline__ void load_rawx(double (&d)[R][BT], const MvnDev& M, c
 // distances from the tree state -- app/Probability.hs:201-207 with app/Tools.hs:36-48 and
 // lib/Mcmc/Tree/Types.hs:224-233 folded into index tables (slot -> node, node -> parent).
 template <int R, int BT>
-__device__ __forceinline__ void load_tree(double (&d)[R][BT], double (&dist)[R][BT], const MvnDev& M, const TreeDev& T,
+__device__ __forceinline__ void load_tree(double (&d)[R][BT], double (&dist)[R][BT], const MvnView& M, const TreeView& T,
                                           const double* __restrict__ H, const double* __restrict__ Rt, int64_t lds,
                                           const double* __restrict__ tH, const double* __restrict__ rMu, int64_t b0,
                                           int64_t batch, int lane)
@@ -803,7 +862,7 @@ __device__ __forceinline__ void load_tree(double (&d)[R][BT], double (&dist)[R][
 // where load_tree gathers from global memory once the tables have arrived: two dependent round trips and a line per lane.
 // Same arithmetic, same bits.  One chain per wave (BT = 1).
 template <int R>
-__device__ __forceinline__ void load_tree_staged(double (&d)[R][1], double (&dist)[R][1], const MvnDev& M, const TreeDev& T,
+__device__ __forceinline__ void load_tree_staged(double (&d)[R][1], double (&dist)[R][1], const MvnView& M, const TreeView& T,
                                                  const double* __restrict__ H, const double* __restrict__ Rt, int64_t lds,
                                                  const double* __restrict__ tH, const double* __restrict__ rMu, int64_t b0,
                                                  int64_t batch, int lane, double* stage)
@@ -854,7 +913,7 @@ __device__ __forceinline__ void load_tree_staged(double (&d)[R][1], double (&dis
 }
 
 template <int R, int BT>
-__device__ __forceinline__ void finish_ll(const double (&d)[R][BT], const MvnDev& M, int64_t b0, int64_t batch,
+__device__ __forceinline__ void finish_ll(const double (&d)[R][BT], const MvnView& M, int64_t b0, int64_t batch,
                                           double* __restrict__ ll, int lane)
 {
 #pragma unroll
@@ -877,13 +936,15 @@ __device__ __forceinline__ void finish_ll(const double (&d)[R][BT], const MvnDev
 #ifndef MCD_BID
 #define MCD_BID blockIdx.x
 #endif
-#define MCD_KERNEL_HEAD MCD_KERNEL_HEAD_FS(0)
+// (MCD_KERNEL_HEAD_FS: for a kernel that takes `ncols` as an argument of its own)
+#define MCD_KERNEL_HEAD                                                         \
+    MCD_KERNEL_HEAD_FS(0)                                                       \
+    const int ncols = M.ncols;   /* swept columns: N rounded up to whole chunks (host: sweep_chunk_columns) */
 #define MCD_KERNEL_HEAD_FS(FS_)                                                 \
     __shared__ d2 ring[Ring<R, (FS_)>::D2];                                     \
     const int lane = threadIdx.x & 63;                                          \
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);          \
-    const int64_t b0 = ((int64_t)MCD_BID * CW + wave) * BT;                      \
-    const int ncols = M.ncols;   /* swept columns: N rounded up to whole chunks (host: sweep_chunk_columns) */
+    const int64_t b0 = ((int64_t)MCD_BID * CW + wave) * BT;
 
 // The forward factor stream of the column sweep (host side; mcd_set_option "MCD_FSTREAM", A/B and tests): compact streams at 129 ..
 // 256 dimensions (R = 3, 4), the padded one elsewhere.  By default the compact stream by LDS-DMA where a workgroup has a CU to itself
@@ -897,6 +958,8 @@ static inline int fwd_stream(int cw)
     const int f = opt_or(OPT_FSTREAM, cw == 2 ? 2 : 0);
     return (f == 1 || f == 2) ? f : 0;
 }
+// the factor a sweep with stream fs reads (the kernels' first argument)
+static inline const double* fwd_stream_ptr(const MvnDev& M, int fs) { return fs == 0 ? M.Ft : M.Fc; }
 
 // launch geometry by batch size (host side)
 struct Geometry {

@@ -1,4 +1,4 @@
-"""The budget of ONE graph-replayed headline launch (k_logpdf<4,1,2,2>: N = 256, 512 chains), from in-kernel s_memtime stamps kept
+"""The budget of ONE graph-replayed headline launch (k_logpdf<4,1,2,4,2>: N = 256, 512 chains), from in-kernel s_memtime stamps kept
 per launch (library: `make -C mcmc-date_amd/csrc stamp_headline` -> tools/microbench/libheadlinestamp.so; the sweep loop itself
 carries no stamps).  The harness is bench.py's: graphs of 100 launches alternating two input batches, replayed back to back.
 
@@ -74,6 +74,10 @@ def us(t):
     return t / ticks_per_us
 
 
+ccols = 2 * (32 if n <= 64 else 16 if n <= 128 else 8)         # columns per chunk (sweep_chunk_columns, R <= 4)
+nchunk = (n + ccols - 1) // ccols
+
+
 rows = []
 for k in range(8, 56):
     if not ok[k - 8]:
@@ -97,13 +101,13 @@ print(f"median over {len(rows)} launches, us (ticks):")
 lines = [
     ("a workgroup's exit in the previous launch -> its entry in this one (kernel end, dispatch, launch of the waves): median over the workgroups 8 i", "gap"),
     ("   smallest / largest over those workgroups", "gap_min"), ("", "gap_max"),
-    ("workgroup 0, compute wave 0: entry -> x, mu, 1/diag landed (one cold round trip)", "c_prologue"),
+    ("workgroup 0, compute wave 0: entry -> x, mu, 1/diag landed (one round trip: every load issued up front)", "c_prologue"),
     ("   entry -> first barrier passed (chunk 0 of the factor in LDS)", "c_barrier"),
-    ("   sweep of the 256 columns (32 chunks, one barrier each)", "c_sweep"),
+    (f"   sweep of the {n} columns ({nchunk} chunks, one barrier each)", "c_sweep"),
     ("   sum of squares, DPP reduction, store", "c_store"),
     ("workgroup 0, loader wave 0: its entry after the compute wave's", "l_entry"),
     ("   chunk 0 requested -> written to LDS", "l_chunk0"),
-    ("   stream of chunks 1 .. 31 (first barrier -> last barrier)", "l_stream"),
+    (f"   stream of chunks 1 .. {nchunk - 1} (first barrier -> last barrier)", "l_stream"),
     ("workgroup 0 entry -> exit", "wg0"),
     ("entry -> exit of a workgroup: median / smallest / largest over the workgroups 8 i", "dur_med"), ("", "dur_min"), ("", "dur_max"),
 ]
