@@ -615,6 +615,37 @@ int mcd_sparse_tree_grad_batch(const mcd_sparse_tree_t* t, const double* heights
 int mcd_hmc_create_sparse(mcd_hmc_t** out, const mcd_sparse_tree_t* tree, const mcd_prior_t* prior, int calibrations_available, int64_t batch);
 
 /* ------------------------------------------------------------------------------------------------
+ * The graphical lasso of `prepare` on the device (csrc/k_glasso.hip, csrc/glasso_capi.cpp).  Replaces: the glasso call behind
+ * `prepare --likelihood-spec "SparseMultivariateNormal rho"` (app/Main.hs:257-276), the step that turns a tree list into the sparse
+ * precision matrix of mcd_sparse_create, at the reference's production sizes (tutorial/goe: 2011 branch dimensions).
+ *   maximise  ln det Theta - tr(S Theta) - rho ||Theta||_1   (the l1 norm over all entries, or, penalize_diagonal = 0, the off-diagonal ones)
+ * by block coordinate descent over the columns of W = Theta^-1 with the lasso sub-problem of a column solved by cyclic coordinate descent
+ * and warm starts (Friedman, Hastie, Tibshirani 2008), the algorithm and the unique optimum of mcmc-date_amd/prepare.py: graphical_lasso.
+ *   mcd_glasso_components  exact screening, pure host code (no device needed): label[i] = the connected component of variable i in the
+ *                          graph {i != j : |S_ij| > rho}, numbered 0 .. *n_components - 1 by their smallest member.  The components are
+ *                          the blocks of the optimal Theta (Witten, Friedman, Simon 2011; Mazumder, Hastie 2012).
+ *   mcd_glasso             S, W, Theta: host arrays [n][n], row-major.  Every component of two or more variables is one independent problem
+ *                          of one workgroup; a singleton is W_ii = S_ii (+ rho), Theta_ii = 1 / W_ii; between components W and Theta are 0.
+ *                          One launch is one outer pass over the columns; between launches the host applies graphical_lasso's stopping rule
+ *                          max |W - W_old| <= tol max(1, mean |S - diag S|), at most max_iter passes; a column's descent ends at a sweep
+ *                          that changes no coefficient by more than tol, at most max_iter sweeps.  Theta is symmetrised and entries below
+ *                          1e-14 are set to 0.  Every sum in index order, no atomics: the same input gives the same bits on every call.
+ *   info[MCD_GLASSO_INFO_LEN]: 0 outer passes used, 1 converged (0 | 1), 2 number of components, 3 size of the largest component,
+ *                          4 coordinate updates over all passes, 5 1: some column's descent stopped at max_iter sweeps, 6 components of two
+ *                          or more variables (= workgroups per launch), 7 reserved (0).
+ * Refused before any launch (MCD_ERR_INVALID_ARG unless said otherwise): n < 1; rho negative or not finite; tol negative; max_iter < 1; a
+ * NULL array; a non-finite entry of S; |S_ij - S_ji| > MCD_GLASSO_SYMMETRY_TOL max(1, |S_ij|, |S_ji|); S_ii <= 0; a component of more than
+ * MCD_GLASSO_MAX_DIM variables (MCD_ERR_UNSUPPORTED); then no device (MCD_ERR_NO_DEVICE: no CPU fallback) or a bad device_id.  Reaching
+ * max_iter passes without meeting the stopping rule is NOT an error: MCD_OK with info[1] = 0 and the iterate reached.
+ */
+#define MCD_GLASSO_INFO_LEN 8
+#define MCD_GLASSO_MAX_DIM 2048 /* per component: the sparse samplers' limit of 2048 nodes */
+#define MCD_GLASSO_SYMMETRY_TOL 1e-10
+int mcd_glasso_components(int n, const double* S, double rho, int32_t* label, int32_t* n_components);
+int mcd_glasso(int n, const double* S, double rho, int penalize_diagonal, double tol, int max_iter, int device_id, double* W, double* Theta,
+               int64_t* info);
+
+/* ------------------------------------------------------------------------------------------------
  * Multi-GPU.  Chains are independent: every rank (one process per GPU) holds the operands and evaluates its own
  * contiguous block of chains; nothing is exchanged on the likelihood path.  The sampler-level exchange -- the per-chain ln
  * posterior that MC3's swap phase compares (`mc3 (MC3Settings (NChains 4) (SwapPeriod 2) (NSwaps 3))`, app/Main.hs:476-478; in

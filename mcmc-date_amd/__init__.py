@@ -10,6 +10,7 @@ from .likelihood import (Full, LikelihoodData, MvnLikelihood, set_logpdf_form, N
                          jacobian_root_branch, likelihood_function, read_data_file, write_data_file)
 from .hmc import DualAveraging, Leapfrog, hmc_transition, nuts_transition, nuts_warmup, run_cycle_with_nuts
 from .hamiltonian import from_vector_with, get_mask, grad_to_vector, target_grad, to_vector
+from .prepare import glasso_components, graphical_lasso, graphical_lasso_device
 from .prior import (Brace, Calibration, Constraint, PriorFunction, get_mean_root_height, load_braces,
                     load_calibrations, load_calibrations_from_tree, load_constraints, prior_function)
 from .diagnostics import Summary, ess, split_rhat, summary, trace_summary
@@ -28,5 +29,6 @@ __all__ = [
     "MC3", "Proposal", "Sampler", "cycle_schedule", "init_with", "proposals", "table_arrays", "weight_n_branches",
     "Leapfrog", "hmc_transition", "nuts_transition", "nuts_warmup", "run_cycle_with_nuts", "DualAveraging", "get_mask", "to_vector", "from_vector_with", "grad_to_vector", "target_grad",
     "diagnostics", "Summary", "RecordSummary", "split_rhat", "ess", "summary", "trace_summary",
+    "graphical_lasso", "graphical_lasso_device", "glasso_components",
     "McdError", "NotPositiveDefinite", "RootNotBifurcating", "NoDevice", "set_option", "get_option",
 ]

@@ -21,6 +21,8 @@ MCD_ERR_NO_DEVICE = -5
 MCD_ERR_UNSUPPORTED = -6
 MCD_SUMMARY_COLS = 9
 MCD_SUMMARY_MAX_LAG = 255
+MCD_GLASSO_INFO_LEN = 8
+MCD_GLASSO_MAX_DIM = 2048
 MCD_MAT_SIGMA = 0
 MCD_MAT_SIGMA_INV = 1
 
@@ -70,6 +72,8 @@ SYMBOLS = {
     "mcd_sparse_tree_destroy": (None, [_vp]),
     "mcd_sparse_tree_loglik_batch": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp]),
     "mcd_sparse_tree_grad_batch": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcd_glasso_components": (C.c_int, [C.c_int, _dp, C.c_double, _ip, _ip]),
+    "mcd_glasso": (C.c_int, [C.c_int, _dp, C.c_double, C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp, C.POINTER(C.c_int64)]),
     "mcd_hmc_create_sparse": (C.c_int, [C.POINTER(_vp), _vp, _vp, C.c_int, C.c_int64]),
     "mcd_hmc_create": (C.c_int, [C.POINTER(_vp), _vp, _vp, C.c_int, C.c_int64]),
     "mcd_hmc_destroy": (None, [_vp]),

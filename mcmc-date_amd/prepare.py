@@ -10,6 +10,12 @@ are not alphabetic, app/Main.hs:288-307, app/Tools.hs:75-81).
 
 This is host code by design (it runs once per analysis; the reference does it on the CPU through
 hmatrix/LAPACK); the per-step path is the HIP kernels.  Row SURVEY.md 8(f) f4 ("data contract").
+One step is also on the device: the graphical lasso of the sparse specification (`prepare(..., glasso="device")`,
+`graphical_lasso_device`; csrc/k_glasso.hip).  The host's three nested loops were written for the 11 branches of
+mtCDNApri and grow between p^2.5 and p^3; at the 2011 branch dimensions of the reference's own tutorial
+(tutorial/goe, 1007 genomes) they would run for hours, in front of the sparse samplers built for that size.
+Tree reading, mean and covariance, the rescaling and `slogdet` of the sparse covariance stay in numpy
+(sub-second at that size), and "host" stays the default.
 
 Re-rooting: the reference calls elynx-tree's `outgroup` [third party].  When a tree of the list is already
 rooted at the rooted tree's bipartition (every tree list shipped in the reference's tests/ except
@@ -20,12 +26,15 @@ sub-tree orders are those obtained by walking away from the new root (old parent
 """
 from __future__ import annotations
 
+import ctypes
 import re
+import warnings
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
 
 import numpy as np
 
+from . import _capi
 from .likelihood import Full, LikelihoodData, NoData, Sparse, Univariate, write_data_file
 from .tree import Topology, TreeError, get_branches, read_newick_file, sum_first_two
 
@@ -128,7 +137,11 @@ def reroot_at_outgroup(topo: Topology, lengths: np.ndarray, outgroup: frozenset)
 # ---------------------------------------------------------------------------------------------
 # prepare
 # ---------------------------------------------------------------------------------------------
-def prepare(tree_list_path: str, rooted_tree_path: str, likelihood_spec: str = "FullMultivariateNormal") -> Prepared:
+def prepare(tree_list_path: str, rooted_tree_path: str, likelihood_spec: str = "FullMultivariateNormal", glasso: str = "host") -> Prepared:
+    """`glasso`: where the graphical lasso of "SparseMultivariateNormal rho" runs: "host" (graphical_lasso, the default) or "device"
+    (graphical_lasso_device: needs a GPU, no fallback); the other specifications do not use it."""
+    if glasso not in ("host", "device"):
+        raise ValueError(f"prepare: glasso must be 'host' or 'device', not {glasso!r}")
     trees_all = read_newick_file(tree_list_path)                          # app/Main.hs:162
     n_trees = len(trees_all)
     n_burn = n_trees // 6                                                 # :166
@@ -170,7 +183,8 @@ def prepare(tree_list_path: str, rooted_tree_path: str, likelihood_spec: str = "
         rho = float(parts[1]) if len(parts) > 1 else 0.1                  # scripts/run:137 passes 0.1
         sd = np.sqrt(variances)
         corr = sigma / np.outer(sd, sd)
-        w_n, theta_n = graphical_lasso(corr, rho, penalize_diagonal=GLASSO_PENALIZE_DIAGONAL)
+        solver = graphical_lasso_device if glasso == "device" else graphical_lasso
+        w_n, theta_n = solver(corr, rho, penalize_diagonal=GLASSO_PENALIZE_DIAGONAL)
         sigma_s = w_n * np.outer(sd, sd)                                  # rescaleSWith
         prec_s = theta_n / np.outer(sd, sd)                               # rescalePWith
         sign, logdet = np.linalg.slogdet(sigma_s)
@@ -238,6 +252,45 @@ def graphical_lasso(S: np.ndarray, rho: float, penalize_diagonal: bool = True, t
     Theta = 0.5 * (Theta + Theta.T)
     Theta[np.abs(Theta) < 1e-14] = 0.0
     return W, Theta
+
+
+GLASSO_LANE_STRIDE = 256          # csrc/glasso_device.hpp: kGlassoThreads; a thread of the solver owns the coordinates t, t + 256, ...
+GLASSO_INFO_FIELDS = ("passes", "converged", "n_components", "largest_component", "coordinate_updates", "sweep_cap_hit", "n_problems")
+
+
+def glasso_components(S: np.ndarray, rho: float) -> np.ndarray:
+    """Exact screening (mcd_glasso_components, host code of the library): the connected component of every variable in the graph
+    {i != j : |S_ij| > rho}, numbered by smallest member.  The components are the blocks of the graphical lasso's optimum."""
+    S = np.ascontiguousarray(S, dtype=np.float64)
+    if S.ndim != 2 or S.shape[0] != S.shape[1]:
+        raise ValueError("glasso_components: S must be a square matrix")
+    n = S.shape[0]
+    label = np.zeros(max(n, 1), np.int32)
+    nc = ctypes.c_int32(0)
+    _capi.check(_capi.lib().mcd_glasso_components(n, S.ctypes.data_as(_capi._dp), float(rho), label.ctypes.data_as(_capi._ip), ctypes.byref(nc)))
+    return label[:n]
+
+
+def graphical_lasso_device(S: np.ndarray, rho: float, penalize_diagonal: bool = True, tol: float = 1e-10, max_iter: int = 10000,
+                           return_info: bool = False, device: int = 0):
+    """`graphical_lasso` on the device (mcd_glasso; csrc/k_glasso.hip): the same algorithm, stopping rule and unique optimum, one
+    workgroup per connected component of {|S_ij| > rho}; components of up to 2048 variables.  Returns (W, Theta), or (W, Theta, info)
+    with `return_info` (a dict of GLASSO_INFO_FIELDS).  Warns when `max_iter` outer passes did not meet the stopping rule; raises
+    McdError for what the library refuses and NoDevice without a GPU (there is no fallback to the host solver)."""
+    S = np.ascontiguousarray(S, dtype=np.float64)
+    if S.ndim != 2 or S.shape[0] != S.shape[1]:
+        raise ValueError("graphical_lasso_device: S must be a square matrix")
+    n = S.shape[0]
+    W = np.zeros((n, n))
+    Theta = np.zeros((n, n))
+    raw = (ctypes.c_int64 * _capi.MCD_GLASSO_INFO_LEN)()
+    _capi.check(_capi.lib().mcd_glasso(n, S.ctypes.data_as(_capi._dp), float(rho), int(bool(penalize_diagonal)), float(tol), int(max_iter),
+                                       int(device), W.ctypes.data_as(_capi._dp), Theta.ctypes.data_as(_capi._dp), raw))
+    info = {name: int(raw[i]) for i, name in enumerate(GLASSO_INFO_FIELDS)}
+    if not info["converged"]:
+        warnings.warn(f"graphical_lasso_device: not converged after {info['passes']} outer passes (max_iter = {max_iter})", RuntimeWarning,
+                      stacklevel=2)
+    return (W, Theta, info) if return_info else (W, Theta)
 
 
 def write_prepared(name: str, p: Prepared) -> None:
