@@ -1,12 +1,15 @@
 """The deterministic inputs of the graphical-lasso tests (tests/test_glasso_host.py, tests/test_gpu_glasso.py), rho = 0.1 throughout:
 AR(1)-correlated samples -> correlation matrices, drawn in one fixed order from one generator, and the host solver's results on them,
-computed once per session."""
+computed once per session.  The inputs added later (unequal diagonals, one component per stride count, the permuted blocks) each draw
+from a generator of their own, so the draws above them never move."""
 import functools
 
 import numpy as np
 
 RHO = 0.1
 BLOCKS = (33, 1, 30, 1, 5)
+STRIDE_SIZES = (256, 512, 513, 1025, 2048)                 # 1, 2, 3, 5, 8 coordinates per thread; 256, 512, 2048 fill their last stride
+PACKED_BLOCKS = (2, 3, 33, 65, 257, 600, 1, 1)             # stride counts 1, 1, 1, 1, 2, 3 in one launch, and two singletons
 
 
 def ar(rng, p, n, a=0.6):
@@ -14,6 +17,76 @@ def ar(rng, p, n, a=0.6):
     for i in range(1, p):
         z[:, i] = a * z[:, i - 1] + np.sqrt(1 - a * a) * z[:, i]
     return z
+
+
+def scaled_cov(seed, p, n):
+    """The covariance of n AR(1) samples of p variables, every variable scaled by exp(U(ln 0.5, ln 2))."""
+    rng = np.random.default_rng(seed)
+    z = ar(rng, p, n)
+    return np.cov(z * np.exp(rng.uniform(np.log(0.5), np.log(2.0), p)), rowvar=False)
+
+
+@functools.lru_cache(maxsize=None)
+def c300():
+    """C300: the recipe of C16 and C48 at p = 300 (600 samples), diagonal 0.23 ... 4.1; read-only."""
+    S = scaled_cov(13, 300, 600)
+    S.setflags(write=False)
+    return S
+
+
+@functools.lru_cache(maxsize=None)
+def stride_input(p):
+    """One component of p variables, built as tools/bench_glasso.py builds its problems (2 p samples); read-only."""
+    S = np.corrcoef(ar(np.random.default_rng(1000 + p), p, 2 * p), rowvar=False)
+    S.setflags(write=False)
+    return S
+
+
+@functools.lru_cache(maxsize=None)
+def packed():
+    """(S, label): independent AR(1) correlation blocks of PACKED_BLOCKS (max(150, 2 p) samples), off-block entries uniform in +-0.08 as
+    in "blocks", then one fixed permutation of rows and columns: every component's members are scattered over 0 ... n - 1.  label[i] is
+    the index into PACKED_BLOCKS of variable i's block.  Read-only."""
+    rng = np.random.default_rng(31)
+    n = sum(PACKED_BLOCKS)
+    S = np.eye(n)
+    inside = np.eye(n, dtype=bool)
+    at = 0
+    for b in PACKED_BLOCKS:
+        if b > 1:
+            S[at:at + b, at:at + b] = np.corrcoef(ar(rng, b, max(150, 2 * b)), rowvar=False)
+            inside[at:at + b, at:at + b] = True
+        at += b
+    U = np.triu(rng.uniform(-0.08, 0.08, (n, n)), 1)
+    U = U + U.T
+    S[~inside] = U[~inside]
+    perm = rng.permutation(n)
+    S = np.ascontiguousarray(S[np.ix_(perm, perm)])
+    label = np.repeat(np.arange(len(PACKED_BLOCKS)), PACKED_BLOCKS)[perm]
+    S.setflags(write=False)
+    label.setflags(write=False)
+    return S, label
+
+
+def by_smallest_member(label):
+    """The same partition numbered by each part's smallest member, as mcd_glasso_components numbers its components."""
+    _, first = np.unique(label, return_index=True)
+    rank = np.empty(len(first), int)
+    rank[np.argsort(first)] = np.arange(len(first))
+    return rank[label]
+
+
+def closed_form_2x2(S, rho):
+    """(W, Theta) of the graphical lasso at p = 2 with the diagonal penalised and |S_01| > rho: W = S + rho I with
+    W_01 = S_01 - rho sign S_01, Theta = W^-1 by the 2 x 2 formula."""
+    w = S[0, 1] - rho * np.sign(S[0, 1])
+    W = np.array([[S[0, 0] + rho, w], [w, S[1, 1] + rho]])
+    det = W[0, 0] * W[1, 1] - w * w
+    return W, np.array([[W[1, 1], -w], [-w, W[0, 0]]]) / det
+
+
+def two_by_two(s):
+    return np.array([[1.3, s], [s, 0.7]])
 
 
 @functools.lru_cache(maxsize=None)
@@ -43,6 +116,13 @@ def inputs():
     X[:, 3] += X[:, 2]
     X[:, 7] -= 0.7 * X[:, 1]
     out["S11"] = np.corrcoef(X, rowvar=False)
+    # covariances with unequal diagonals (0.26 ... 3.4): W_kk differs from coordinate to coordinate (c300() gives the second stride its own).
+    # The seeds of C16 and C48 were taken for the host solver's margins on them (tests/test_glasso_host.py: smallest non-zero |Theta|
+    # 3.0e-4, closest inactive entry 4.8e-4 below rho), which is what makes the pattern comparison with the device well posed
+    out["C16"] = scaled_cov(11, 16, 200)
+    out["C48"] = scaled_cov(16, 48, 300)
+    # 3 x 3, every |off-diagonal| above rho: one wave owns all three coordinates, three own none
+    out["S3"] = np.array([[1.0, 0.5, -0.3], [0.5, 1.0, 0.2], [-0.3, 0.2, 1.0]])
     for v in out.values():
         v.setflags(write=False)
     return out

@@ -147,3 +147,61 @@ def test_screening_claim_on_the_host_solver():
     print("screening: max |dW| %.3g, max |dTheta| %.3g" % (np.abs(W - W_all).max(), np.abs(T - T_all).max()))
     assert np.abs(W - W_all).max() <= 1e-8 and np.abs(T - T_all).max() <= 1e-7
     assert np.array_equal(T != 0, T_all != 0)
+
+
+# --- the host solver on the inputs that tests/test_gpu_glasso.py compares the device with: what makes it a reference there
+
+@pytest.mark.parametrize("name", ["C16", "C48", "S3"])
+@pytest.mark.parametrize("pen", [True, False])
+def test_host_solver_on_unequal_diagonals_and_three_variables(name, pen):
+    """tests/test_prepare.py:138-144's conditions with its tolerances, and the premise of the pattern comparison of the gpu tests: no
+    non-zero of the host's Theta below 4e-5."""
+    S = GI.inputs()[name]
+    d = np.diag(S)
+    assert name == "S3" or (d.min() < 0.3 and d.max() > 3.0)                  # the diagonal is far from constant
+    W, T = GI.host_solution(name, pen)
+    inv, diag, active, inactive, lam = GI.optimality_violations(S, W, T, GI.RHO, pen)
+    smallest = np.abs(T[T != 0]).min()
+    print(f"{name} pen={pen}: diagonal of S {d.min():.3g} ... {d.max():.3g}; |W Theta - I| {inv:.3g}, diagonal {diag:.3g}, active {active:.3g}, "
+          f"inactive - rho {inactive:.3g}, min eig {lam:.3g}; smallest non-zero |Theta| {smallest:.3g}, max |W| {np.abs(W).max():.3g}, "
+          f"max |Theta| {np.abs(T).max():.3g}")
+    assert inv <= 1e-8 and diag <= 1e-12 and active <= 1e-7 and inactive <= 1e-9
+    assert np.array_equal(T, T.T) and lam > 0
+    assert smallest > 4e-5
+    assert max(np.abs(W).max(), np.abs(T).max()) < 6.0                        # the absolute tolerances 1e-8, 1e-7 mean what they meant at 1
+
+
+@pytest.mark.parametrize("s", [0.5, -0.5, 0.1000001])
+def test_host_solver_two_variables_closed_form(s):
+    """p = 2, |s| > rho: W = S + rho I with W_01 = s - rho sign s, Theta = W^-1.  A handful of fp64 roundings on O(1) numbers:
+    16 eps max(1, max |Theta|) for both matrices."""
+    S = GI.two_by_two(s)
+    Wc, Tc = GI.closed_form_2x2(S, GI.RHO)
+    W, T = PP.graphical_lasso(S, GI.RHO)
+    bound = 16 * np.finfo(float).eps * max(1.0, np.abs(Tc).max())
+    print(f"s = {s}: host against the closed form |dW| {np.abs(W - Wc).max():.3g}, |dTheta| {np.abs(T - Tc).max():.3g}, bound {bound:.3g}")
+    assert np.abs(W - Wc).max() <= bound and np.abs(T - Tc).max() <= bound
+    assert T[0, 1] != 0 and np.sign(T[0, 1]) == -np.sign(s)
+
+
+def test_host_solver_without_a_penalty_inverts():
+    """rho = 0: the soft threshold zeroes nothing, the optimum is W = S, Theta = S^-1 (the stopping tolerance 1e-10 limits the
+    agreement, not rounding)."""
+    S = GI.inputs()["S16"]
+    W, T = PP.graphical_lasso(S, 0.0)
+    dW, dT = np.abs(W - S).max(), np.abs(T - np.linalg.inv(S)).max()
+    print(f"rho = 0: host |W - S| {dW:.3g}, |Theta - inv S| {dT:.3g}")
+    assert dW <= 1e-8 and dT <= 1e-7
+    assert np.all(T != 0)
+
+
+def test_the_permuted_blocks_are_what_the_screening_finds():
+    """GI.packed(): 8 components, every one of two or more variables scattered over the whole index range (no component is a run of
+    consecutive indices), numbered by smallest member."""
+    S, lab = GI.packed()
+    assert S.shape == (962, 962) and np.bincount(lab).tolist() == list(GI.PACKED_BLOCKS)
+    got = M.glasso_components(S, GI.RHO)
+    assert np.array_equal(got, GI.by_smallest_member(lab))
+    for c in range(got.max() + 1):
+        m = np.flatnonzero(got == c)
+        assert len(m) == 1 or m[-1] - m[0] > len(m) - 1                       # interleaved with the others, not a contiguous run
