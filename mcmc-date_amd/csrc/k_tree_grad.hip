@@ -1,6 +1,5 @@
 // k_tree_grad.hip -- tree state -> log-likelihood + gradient wrt the state (gfx950).  Device code: mvn_device.hpp.
 #include "mvn_device.hpp"
-#include <type_traits>
 
 namespace mcd {
 
@@ -89,95 +88,23 @@ static hipError_t launch_tree_grad_R(const MvnDev& M, const TreeDev& T, const do
                                      const double* tH, const double* rMu, int64_t batch, double* ll, double* gH,
                                      double* gR, double* gtH, double* grMu, hipStream_t st)
 {
-    // (as k_grad.hip: from R = 8 two compute waves per workgroup, from R = 12 two loader waves -- one wave per SIMD, no spilled registers)
-    auto go = [&](auto cw_tag) {
-        constexpr int CW = decltype(cw_tag)::value, LW = (R == 12) ? 2 : Cfg<R>::LW;
+    grad_launch_geometry<R>(batch, [&](auto cw_tag) {
+        constexpr int CW = decltype(cw_tag)::value, LW = grad_loader_waves(R);
         const unsigned grid = (unsigned)((batch + CW - 1) / CW);
         hipLaunchKernelGGL((k_tree_grad<R, CW, LW>), dim3(grid), dim3(64 * (CW + LW)), 0, st, M, T, H, Rt, lds, tH, rMu, batch,
                        ll, gH, gR, gtH, grMu);
-    };
-    if constexpr (R >= 8) {
-        go(std::integral_constant<int, 2>{});
-    } else {
-        if (pick_geometry(batch).cw == 2)
-            go(std::integral_constant<int, 2>{});
-        else
-            go(std::integral_constant<int, 4>{});
-    }
+    });
     return hipGetLastError();
 }
 
-// Each kernel file is compiled four times (-DMCD_RGROUP=0: R in {1,2,3,4}; 1: {6,8}; 2: {12}; 3: {16}) so that
-// the template instantiations build in parallel and the big ones never share a translation unit.
-#ifndef MCD_RGROUP
-#define MCD_RGROUP 0
-#endif
-#if MCD_RGROUP == 0
-#define MCD_DISPATCH_R(R_, CALL) \
-    switch (R_) { case 1: return CALL(1); case 2: return CALL(2); case 3: return CALL(3); case 4: return CALL(4); default: return hipErrorInvalidValue; }
-#elif MCD_RGROUP == 1
-#define MCD_DISPATCH_R(R_, CALL) \
-    switch (R_) { case 6: return CALL(6); case 8: return CALL(8); default: return hipErrorInvalidValue; }
-#elif MCD_RGROUP == 2
-#define MCD_DISPATCH_R(R_, CALL) \
-    switch (R_) { case 12: return CALL(12); default: return hipErrorInvalidValue; }
-#else
-#define MCD_DISPATCH_R(R_, CALL) \
-    switch (R_) { case 16: return CALL(16); default: return hipErrorInvalidValue; }
-#endif
-#define MCD_CAT2(a, b) a##b
-#define MCD_CAT(a, b) MCD_CAT2(a, b)
-
-#if MCD_RGROUP == 0
-hipError_t launch_tree_grad_g1(const MvnDev& M, const TreeDev& T, const double* H, const double* Rt, int64_t lds,
-                            const double* tH, const double* rMu, int64_t batch, double* ll, double* gH, double* gR,
-                            double* gtH, double* grMu, hipStream_t st);
-hipError_t launch_tree_grad_g2(const MvnDev& M, const TreeDev& T, const double* H, const double* Rt, int64_t lds,
-                            const double* tH, const double* rMu, int64_t batch, double* ll, double* gH, double* gR,
-                            double* gtH, double* grMu, hipStream_t st);
-hipError_t launch_tree_grad_g3(const MvnDev& M, const TreeDev& T, const double* H, const double* Rt, int64_t lds,
-                            const double* tH, const double* rMu, int64_t batch, double* ll, double* gH, double* gR,
-                            double* gtH, double* grMu, hipStream_t st);
-hipError_t launch_tree_grad(const MvnDev& M, const TreeDev& T, const double* H, const double* Rt, int64_t lds,
-                            const double* tH, const double* rMu, int64_t batch, double* ll, double* gH, double* gR,
-                            double* gtH, double* grMu, hipStream_t st)
-{
-    if (batch <= 0) return hipSuccess;
-    if (use_split_grad(M, batch) && (const double*)gH != Rt && (const double*)gR != H)   // (either output may be its own input, not the other's)
-        return launch_tree_grad_split(M, T, H, Rt, lds, tH, rMu, batch, ll, gH, gR, gtH, grMu, st);
-    if (use_wide_grad(M, batch)) {
-        if (M.n <= 256) return launch_tree_grad_wide(M, T, H, Rt, lds, tH, rMu, batch, ll, gH, gR, gtH, grMu, st);
-        if ((const double*)gH != H && (const double*)gH != Rt)      // (the height-gradient rows double as scratch above 256)
-            return launch_tree_grad_wide_mc(M, T, H, Rt, lds, tH, rMu, batch, ll, gH, gR, gtH, grMu, st);
-    }
-    if (M.R == 6 || M.R == 8) return launch_tree_grad_g1(M, T, H, Rt, lds, tH, rMu, batch, ll, gH, gR, gtH, grMu, st);
-    if (M.R == 12) return launch_tree_grad_g2(M, T, H, Rt, lds, tH, rMu, batch, ll, gH, gR, gtH, grMu, st);
-    if (M.R == 16) {
-        // N > 768: no sweep form of the tree gradient (k_grad.hip has the reason): the row split in pieces of at most 1024 chains, whatever
-        // the batch and the form asked for.  Its one restriction: an output that aliases the OTHER input array (the height gradient over the
-        // rates or the reverse) is refused -- include/mcmcdate_mvn.h says so.
-        if (M.split == nullptr || (const double*)gH == Rt || (const double*)gR == H) return hipErrorInvalidValue;
-        for (int64_t c0 = 0; c0 < batch; c0 += kSplitMaxBatch) {
-            const int64_t cnt = (batch - c0 < kSplitMaxBatch) ? batch - c0 : kSplitMaxBatch;
-            if (hipError_t e = launch_tree_grad_split(M, T, H + c0 * lds, Rt + c0 * lds, lds, tH + c0, rMu + c0, cnt, ll + c0, gH + c0 * lds, gR + c0 * lds,
-                                                      gtH + c0, grMu + c0, st))
-                return e;
-        }
-        return hipSuccess;
-    }
-#else
+// the sweep of this compile's R group (sweep_groups.hpp; R = 16 has none: launch_tree_grad, sweep_launch.cpp)
 hipError_t MCD_CAT(launch_tree_grad_g, MCD_RGROUP)(const MvnDev& M, const TreeDev& T, const double* H, const double* Rt, int64_t lds,
-                            const double* tH, const double* rMu, int64_t batch, double* ll, double* gH, double* gR,
-                            double* gtH, double* grMu, hipStream_t st)
+                                                   const double* tH, const double* rMu, int64_t batch, double* ll, double* gH, double* gR,
+                                                   double* gtH, double* grMu, hipStream_t st)
 {
-#endif
-#if MCD_RGROUP == 3
-    return hipErrorInvalidValue;                           // (R = 16: launch_tree_grad takes the row split, see there)
-#else
 #define CALL(R) launch_tree_grad_R<R>(M, T, H, Rt, lds, tH, rMu, batch, ll, gH, gR, gtH, grMu, st)
     MCD_DISPATCH_R(M.R, CALL)
 #undef CALL
-#endif
 }
 
 }  // namespace mcd

@@ -106,125 +106,46 @@ static hipError_t launch_tree_logpdf_R(const MvnDev& M, const TreeDev& T, const 
                                        const double* tH, const double* rMu, int64_t batch, double* ll, double* logjac, const JOB& job,
                                        hipStream_t st)
 {
-    const Geometry g = pick_geometry(batch);
+    const Geometry g = sweep_geometry(R, batch);
     constexpr int LW = Cfg<R>::LW;
+    const int waves = g.cw + LW;
+    int64_t wgs = (batch + g.cw * g.bt - 1) / (g.cw * g.bt);
     JOB J = job;
-    auto prior_wgs = [&](int waves) {                      // workgroups of the prior role in front of the sweeping ones
-        if constexpr (PRIOR) {
-            // two waves per chain while every workgroup of both roles is resident at once (two of these workgroups fit a CU)
-            const int per_wg = waves / 2;
-            const int bt_eff = (R >= 16) ? 1 : g.bt;
-            const int64_t like_wgs = (batch + g.cw * bt_eff - 1) / (g.cw * bt_eff);
-            const bool two = (waves % 2 == 0) && like_wgs + (J.M.batch + per_wg - 1) / per_wg <= 512 &&
-                             (size_t)per_wg * mh_prior_role2_doubles(J.M.n_nodes) * sizeof(double) <= (size_t)2 * Cfg<R>::SU * 64 * 16;
-            J.wpc = two ? 2 : 1;
-            const int chains = two ? per_wg : waves;
-            J.n_wgs = (int)((J.M.batch + chains - 1) / chains);
-            return (unsigned)J.n_wgs;
-        } else {
-            return 0u;
-        }
-    };
-    if (g.cw == 2) {
-        const unsigned grid = (unsigned)((batch + 1) / 2) + prior_wgs(2 + LW);
-        launch_tree_fs<R, 1, 2, LW, PRIOR>(grid, st, M, T, H, Rt, lds, tH, rMu, batch, ll, logjac, J);
-    } else if (g.bt == 1) {
-        const unsigned grid = (unsigned)((batch + 3) / 4) + prior_wgs(4 + LW);
-        launch_tree_fs<R, 1, 4, LW, PRIOR>(grid, st, M, T, H, Rt, lds, tH, rMu, batch, ll, logjac, J);
-    } else if constexpr (R >= 16) {
-        // (two chains per compute wave do not fit the register file at R = 16: 1 188 spilled registers; such a batch -- more than 4096 chains on
-        // the sweep -- is only reached with the form forced, the automatic choice takes the multiply form there)
-        const unsigned grid = (unsigned)((batch + 3) / 4) + prior_wgs(4 + LW);
-        launch_tree_fs<R, 1, 4, LW, PRIOR>(grid, st, M, T, H, Rt, lds, tH, rMu, batch, ll, logjac, J);
-    } else {                                               // large batches: two chains per compute wave share every factor read
-        const unsigned grid = (unsigned)((batch + 7) / 8) + prior_wgs(4 + LW);
-        launch_tree_fs<R, 2, 4, LW, PRIOR>(grid, st, M, T, H, Rt, lds, tH, rMu, batch, ll, logjac, J);
+    if constexpr (PRIOR) {                                 // workgroups of the prior role in front of the sweeping ones
+        // two waves per chain while every workgroup of both roles is resident at once (two of these workgroups fit a CU)
+        const int per_wg = waves / 2;
+        const bool two = (waves % 2 == 0) && wgs + (J.M.batch + per_wg - 1) / per_wg <= 512 &&
+                         (size_t)per_wg * mh_prior_role2_doubles(J.M.n_nodes) * sizeof(double) <= (size_t)2 * Cfg<R>::SU * 64 * 16;
+        J.wpc = two ? 2 : 1;
+        const int chains = two ? per_wg : waves;
+        J.n_wgs = (int)((J.M.batch + chains - 1) / chains);
+        wgs += J.n_wgs;
     }
+    const unsigned grid = (unsigned)wgs;
+    if (g.cw == 2)
+        launch_tree_fs<R, 1, 2, LW, PRIOR>(grid, st, M, T, H, Rt, lds, tH, rMu, batch, ll, logjac, J);
+    else if (g.bt == 1)
+        launch_tree_fs<R, 1, 4, LW, PRIOR>(grid, st, M, T, H, Rt, lds, tH, rMu, batch, ll, logjac, J);
+    else if constexpr (R < 16)                             // large batches: two chains per compute wave share every factor read
+        launch_tree_fs<R, 2, 4, LW, PRIOR>(grid, st, M, T, H, Rt, lds, tH, rMu, batch, ll, logjac, J);
     return hipGetLastError();
 }
 
-// Each kernel file is compiled four times (-DMCD_RGROUP=0: R in {1,2,3,4}; 1: {6,8}; 2: {12}; 3: {16}) so that
-// the template instantiations build in parallel and the big ones never share a translation unit.
-#ifndef MCD_RGROUP
-#define MCD_RGROUP 0
-#endif
-#if MCD_RGROUP == 0
-#define MCD_DISPATCH_R(R_, CALL) \
-    switch (R_) { case 1: return CALL(1); case 2: return CALL(2); case 3: return CALL(3); case 4: return CALL(4); default: return hipErrorInvalidValue; }
-#elif MCD_RGROUP == 1
-#define MCD_DISPATCH_R(R_, CALL) \
-    switch (R_) { case 6: return CALL(6); case 8: return CALL(8); default: return hipErrorInvalidValue; }
-#elif MCD_RGROUP == 2
-#define MCD_DISPATCH_R(R_, CALL) \
-    switch (R_) { case 12: return CALL(12); default: return hipErrorInvalidValue; }
-#else
-#define MCD_DISPATCH_R(R_, CALL) \
-    switch (R_) { case 16: return CALL(16); default: return hipErrorInvalidValue; }
-#endif
-#define MCD_CAT2(a, b) a##b
-#define MCD_CAT(a, b) MCD_CAT2(a, b)
-
-#if MCD_RGROUP == 0
-hipError_t launch_tree_logpdf_g1(const MvnDev& M, const TreeDev& T, const double* H, const double* Rt, int64_t lds,
-                              const double* tH, const double* rMu, int64_t batch, double* ll, double* logjac,
-                              hipStream_t st);
-hipError_t launch_tree_logpdf_g2(const MvnDev& M, const TreeDev& T, const double* H, const double* Rt, int64_t lds,
-                              const double* tH, const double* rMu, int64_t batch, double* ll, double* logjac,
-                              hipStream_t st);
-hipError_t launch_tree_logpdf_g3(const MvnDev& M, const TreeDev& T, const double* H, const double* Rt, int64_t lds,
-                              const double* tH, const double* rMu, int64_t batch, double* ll, double* logjac,
-                              hipStream_t st);
-hipError_t launch_tree_logpdf(const MvnDev& M, const TreeDev& T, const double* H, const double* Rt, int64_t lds,
-                              const double* tH, const double* rMu, int64_t batch, double* ll, double* logjac,
-                              hipStream_t st)
-{
-    if (batch <= 0) return hipSuccess;
-    if (use_split(M, batch)) return launch_tree_logpdf_split(M, T, H, Rt, lds, tH, rMu, batch, ll, logjac, st);
-    if (use_wide(M, batch)) return launch_tree_logpdf_wide(M, T, H, Rt, lds, tH, rMu, batch, ll, logjac, st);
-    if (M.R == 6 || M.R == 8) return launch_tree_logpdf_g1(M, T, H, Rt, lds, tH, rMu, batch, ll, logjac, st);
-    if (M.R == 12) return launch_tree_logpdf_g2(M, T, H, Rt, lds, tH, rMu, batch, ll, logjac, st);
-    if (M.R == 16) return launch_tree_logpdf_g3(M, T, H, Rt, lds, tH, rMu, batch, ll, logjac, st);
-#else
+// the sweep of this compile's R group (sweep_groups.hpp)
 hipError_t MCD_CAT(launch_tree_logpdf_g, MCD_RGROUP)(const MvnDev& M, const TreeDev& T, const double* H, const double* Rt, int64_t lds,
-                              const double* tH, const double* rMu, int64_t batch, double* ll, double* logjac,
-                              hipStream_t st)
+                                                     const double* tH, const double* rMu, int64_t batch, double* ll, double* logjac,
+                                                     hipStream_t st)
 {
-#endif
 #define CALL(R) launch_tree_logpdf_R<R, false, NoJob>(M, T, H, Rt, lds, tH, rMu, batch, ll, logjac, NoJob{}, st)
     MCD_DISPATCH_R(M.R, CALL)
 #undef CALL
 }
 
-// ---- the same launch with the prior role in front (Metropolis-Hastings, two-launch path) ----
-#if MCD_RGROUP == 0
-hipError_t launch_tree_logpdf_prior_g1(const MvnDev& M, const TreeDev& T, const double* H, const double* Rt, int64_t lds, const double* tH,
-                                       const double* rMu, int64_t batch, double* ll, double* logjac, const MhDev& J, const PriorDev& JP, hipStream_t st);
-hipError_t launch_tree_logpdf_prior_g2(const MvnDev& M, const TreeDev& T, const double* H, const double* Rt, int64_t lds, const double* tH,
-                                       const double* rMu, int64_t batch, double* ll, double* logjac, const MhDev& J, const PriorDev& JP, hipStream_t st);
-hipError_t launch_tree_logpdf_prior_g3(const MvnDev& M, const TreeDev& T, const double* H, const double* Rt, int64_t lds, const double* tH,
-                                       const double* rMu, int64_t batch, double* ll, double* logjac, const MhDev& J, const PriorDev& JP, hipStream_t st);
-// the sweep serves this launch, and the slices of the ring the prior waves use fit it
-bool tree_logpdf_can_carry_prior(const MvnFacts& M, int64_t batch, int n_nodes)
-{
-    if (batch <= 0 || use_split(M, batch) || use_wide(M, batch)) return false;
-    const Geometry g = pick_geometry(batch);
-    const int lw = (M.R >= 12) ? 4 : 2, su = (M.R >= 12) ? 64 : 32;
-    return (size_t)(g.cw + lw) * 2 * (size_t)n_nodes * sizeof(double) <= (size_t)2 * su * 64 * 16;
-}
-hipError_t launch_tree_logpdf_with_prior(const MvnDev& M, const TreeDev& T, const double* H, const double* Rt, int64_t lds, const double* tH,
-                                         const double* rMu, int64_t batch, double* ll, double* logjac, const MhDev& J, const PriorDev& JP,
-                                         hipStream_t st)
-{
-    if (!tree_logpdf_can_carry_prior(M, batch, J.n_nodes) || J.batch != batch) return hipErrorInvalidValue;
-    if (M.R == 6 || M.R == 8) return launch_tree_logpdf_prior_g1(M, T, H, Rt, lds, tH, rMu, batch, ll, logjac, J, JP, st);
-    if (M.R == 12) return launch_tree_logpdf_prior_g2(M, T, H, Rt, lds, tH, rMu, batch, ll, logjac, J, JP, st);
-    if (M.R == 16) return launch_tree_logpdf_prior_g3(M, T, H, Rt, lds, tH, rMu, batch, ll, logjac, J, JP, st);
-#else
+// ---- the same launch with the prior role in front (Metropolis-Hastings, two-launch path; launch_tree_logpdf_with_prior) ----
 hipError_t MCD_CAT(launch_tree_logpdf_prior_g, MCD_RGROUP)(const MvnDev& M, const TreeDev& T, const double* H, const double* Rt, int64_t lds,
-                                       const double* tH, const double* rMu, int64_t batch, double* ll, double* logjac, const MhDev& J,
-                                       const PriorDev& JP, hipStream_t st)
+                                                           const double* tH, const double* rMu, int64_t batch, double* ll, double* logjac,
+                                                           const MhDev& J, const PriorDev& JP, hipStream_t st)
 {
-#endif
     const MhPriorJob job{J, JP, 0, 1};
 #define CALL(R) launch_tree_logpdf_R<R, true, MhPriorJob>(M, T, H, Rt, lds, tH, rMu, batch, ll, logjac, job, st)
     MCD_DISPATCH_R(M.R, CALL)

@@ -37,6 +37,7 @@
 #include "fc_layout.hpp"
 #include "mvn_kernels.h"
 #include "options.h"
+#include "sweep_groups.hpp"
 
 namespace mcd {
 
@@ -157,12 +158,8 @@ __device__ __forceinline__ void mcd_acc(int idx, unsigned long long& tprev, unsi
 // ---------------------------------------------------------------------------------------
 template <int R>
 struct Cfg {
-    // 1-KiB units per LDS ring slot (two slots): 32 KiB slots up to N = 512; above that a chunk of 32 units is
-    // only 4 columns and the per-chunk barrier + loader bookkeeping dominate (measured at N = 1024: the compute
-    // waves spent half of the sweep waiting at barriers), so 64-unit slots (128 KiB of LDS, one workgroup per CU).
-    static constexpr int SU = (R >= 12) ? 64 : 32;
-    // loader waves per workgroup
-    static constexpr int LW = (R >= 12) ? 4 : 2;
+    static constexpr int SU = sweep_slot_units(R);          // 1-KiB units per LDS ring slot (two slots)
+    static constexpr int LW = sweep_loader_waves(R);        // loader waves per workgroup
     // column pairs per chunk: CP * R <= SU
     static constexpr int CP = (R == 1) ? 32 : (R == 2) ? 16 : (R <= 4) ? 8 : (R <= 8) ? 4 : (SU / 16);
     static constexpr int CPB = 32 / CP;                     // chunks per 64-column block
@@ -961,23 +958,24 @@ static inline int fwd_stream(int cw)
 // the factor a sweep with stream fs reads (the kernels' first argument)
 static inline const double* fwd_stream_ptr(const MvnDev& M, int fs) { return fs == 0 ? M.Ft : M.Fc; }
 
-// launch geometry by batch size (host side)
-struct Geometry {
-    int cw, lw, bt;
-};
-static inline Geometry pick_geometry(int64_t batch)
+// The workgroup of a gradient sweep (host side; k_grad.hip, k_tree_grad.hip): go(std::integral_constant<int, CW>) launches with CW compute
+// waves and grad_loader_waves(R) loaders.
+// (the gradient holds the forward AND the backward sweep's staging: above R = 6 four compute waves per workgroup, and at R = 12 four
+// loader waves, no longer fit two waves per SIMD -- 140 .. 1 219 spilled registers -- so those sizes take two compute waves, and two
+// loaders from R = 12: one wave per SIMD, the whole register file.  The sweeps are the fallback there: up to 1024 chains the row split
+// serves the gradient, from 2048 the multiply form.)
+constexpr int grad_loader_waves(int R) { return (R == 12) ? 2 : sweep_loader_waves(R); }
+template <int R, class GO>
+static inline void grad_launch_geometry(int64_t batch, GO go)
 {
-    // <= 512 chains (a sampler's usual batch): 2 compute waves + 2 loaders per workgroup, so that every
-    // chain gets a SIMD to itself and all 256 CUs take part in pulling the factor out of L2.
-    // Up to 4096 chains: 4 compute waves per workgroup keep the grid within one wave of workgroups
-    // per CU for longer (measured at N = 256, B = 1024: 9.5 us against 14.4 us).
-    // More: 4 compute waves x 2 chains share each pass over the factor.
-    const int force = opt_get(OPT_GEOM);                 // tuning (mcd_set_option "MCD_GEOM"): 21 | 41 | 42 = compute waves, chains per wave
-    if (force == 21) return {2, 2, 1};
-    if (force == 41 || force == 42) return {4, 2, force == 42 ? 2 : 1};
-    if (batch <= 512) return {2, 2, 1};
-    if (batch <= 4096) return {4, 2, 1};
-    return {4, 2, 2};
+    if constexpr (R >= 8) {
+        go(std::integral_constant<int, 2>{});
+    } else {
+        if (pick_geometry(batch).cw == 2)
+            go(std::integral_constant<int, 2>{});
+        else
+            go(std::integral_constant<int, 4>{});
+    }
 }
 
 }  // namespace mcd

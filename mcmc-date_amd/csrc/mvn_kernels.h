@@ -30,8 +30,9 @@ struct MvnDev {
 struct MvnFacts {
     int n, R, form;            // form: the one in force (effective_form)
     bool split, wide, cols;    // the row-split tables (split), the multiply form's tiles (Wt), the columns of W (Wc) exist
+    bool wide_bwd;             // ... and the tiles of W^T for the multiply form's gradient (Wtb)
     MvnFacts() = default;
-    MvnFacts(const MvnDev& M);   // (k_logpdf.hip)
+    MvnFacts(const MvnDev& M);   // (sweep_launch.cpp)
 };
 
 // Row-split multiply form (k_split.hip).  One tile stream per (handle, G): the row blocks of W = L^-1 dealt to G row groups of
@@ -307,6 +308,7 @@ hipError_t launch_hmc_record_stats(const MhRecDims& S, const MhRec& R, int64_t f
 // s1[k] += sum_b q[b][k], s2[k] += sum_b q[b][k]^2 in the order b = 0, 1, ... (what mcd_hmc_nuts_run adds per transition); s1, s2 [dim]
 hipError_t launch_hmc_moments(const HmcDev& D, double* s1, double* s2, hipStream_t st);
 
+// The choice of form and the public launch_logpdf / launch_grad / launch_tree_logpdf / launch_tree_grad: sweep_launch.cpp.
 int padded_blocks(int n);          // supported R for dimension n, or -1
 int sweep_chunk_columns(int R);    // columns per register buffer (ncols granularity)
 
@@ -342,12 +344,12 @@ hipError_t launch_grad_split(const MvnDev& M, const double* X, int64_t ldx, int6
 hipError_t launch_logpdf_split_z(const MvnDev& M, const double* X, int64_t ldx, int64_t batch, double* ll, const double** zt, int* nr, hipStream_t st);
 hipError_t launch_tree_grad_split(const MvnDev& M, const TreeDev& T, const double* H, const double* Rt, int64_t lds, const double* tH,
                                   const double* rMu, int64_t batch, double* ll, double* gH, double* gR, double* gtH, double* grMu, hipStream_t st);
-bool use_split_grad(const MvnDev& M, int64_t batch);
+bool use_split_grad(const MvnFacts& M, int64_t batch);
 int effective_form(const MvnDev& M);   // MCD_FORM_* in force for this handle
 hipError_t prepare_wide();            // per-device attribute set-up of the multiply-form kernels (current device)
 hipError_t prepare_wide_grad();
 hipError_t prepare_wide_grad_mc();
-bool use_wide_grad(const MvnDev& M, int64_t batch);
+bool use_wide_grad(const MvnFacts& M, int64_t batch);
 int wide_chain_tiles(int64_t batch);
 bool use_wide(const MvnFacts& M, int64_t batch);
 int set_logpdf_form(int form);

@@ -382,6 +382,86 @@ def test_mc3_swap_host_keeps_a_permutation_per_group():
     assert np.array_equal(r2, rank)
 
 
+# (entry, n, R, form, chains, alias, knobs, facts that do NOT hold, what the entry does): the choice of form of launch_logpdf (entry 0), launch_grad
+# (1), launch_tree_logpdf (2), launch_tree_grad (3) and launch_tree_logpdf_with_prior (4, on n + 2 nodes), read off use_split / use_wide /
+# use_split_grad / use_wide_grad and the launchers as they stood before the choice moved into sweep_launch.cpp.  form: MCD_FORM_* (0 automatic,
+# 1 sweep, 2 multiply); alias: 1 the (height) gradient over x (the heights), 2 the height gradient over the rates, 4 the rate gradient over
+# the heights; result: 0 .. 3 the sweep of that R group, 4 row split, 5 multiply form, 6 multiply form above 256 dimensions, 7 row split in
+# pieces of 1024 chains, 8 nothing to do, -1 refused
+FORM_CASES = [
+    # likelihood, raw x: the row split's window 240 < N <= 256 up to 128 chains, N > 256 up to 1024
+    (0, 240, 4, 0, 128, 0, {}, (), 0), (0, 241, 4, 0, 128, 0, {}, (), 4), (0, 241, 4, 0, 129, 0, {}, (), 0),
+    (0, 256, 4, 0, 128, 0, {}, (), 4), (0, 256, 4, 0, 129, 0, {}, (), 0), (0, 256, 4, 0, 1024, 0, {}, (), 0),
+    (0, 257, 6, 0, 1, 0, {}, (), 4), (0, 257, 6, 0, 1024, 0, {}, (), 4), (0, 257, 6, 0, 1025, 0, {}, (), 1),
+    (0, 257, 6, 0, 128, 0, {}, ("split",), 1), (0, 257, 6, 0, 0, 0, {}, (), 8),
+    # ... the multiply form from 2048 chains at N >= 96, from 8192 at N >= 32
+    (0, 257, 6, 0, 2047, 0, {}, (), 1), (0, 257, 6, 0, 2048, 0, {}, (), 5), (0, 95, 2, 0, 2048, 0, {}, (), 0),
+    (0, 96, 2, 0, 2048, 0, {}, (), 5), (0, 96, 2, 0, 2047, 0, {}, (), 0), (0, 95, 2, 0, 8191, 0, {}, (), 0),
+    (0, 95, 2, 0, 8192, 0, {}, (), 5), (0, 31, 1, 0, 8192, 0, {}, (), 0), (0, 32, 1, 0, 8192, 0, {}, (), 5),
+    (0, 32, 1, 0, 8191, 0, {}, (), 0), (0, 96, 2, 0, 2048, 0, {}, ("wide",), 0), (0, 1000, 16, 0, 4097, 0, {}, (), 5),
+    # ... forms 1 and 2, MCD_SPLIT, an R that no group holds
+    (0, 257, 6, 1, 128, 0, {}, (), 1), (0, 96, 2, 1, 8192, 0, {}, (), 0), (0, 1000, 16, 1, 4097, 0, {}, (), 3),
+    (0, 31, 1, 2, 1, 0, {}, (), 5), (0, 31, 1, 2, 1, 0, {}, ("wide",), 0), (0, 300, 6, 2, 100, 0, {}, (), 5),
+    (0, 257, 6, 0, 128, 0, {"MCD_SPLIT": 0}, (), 1), (0, 1000, 16, 0, 512, 0, {"MCD_SPLIT": 0}, (), 3), (0, 700, 12, 0, 1025, 0, {}, (), 2),
+    (0, 240, 4, 0, 1024, 0, {"MCD_SPLIT": 1}, (), 4), (0, 240, 4, 0, 1025, 0, {"MCD_SPLIT": 1}, (), 0),
+    (0, 100, 2, 0, 1, 0, {"MCD_SPLIT": 1}, (), 4), (0, 100, 2, 0, 1, 0, {"MCD_SPLIT": 1}, ("split",), 0),
+    (0, 300, 5, 0, 10, 0, {}, ("split",), -1), (0, 300, 5, 0, 10, 0, {}, (), 4),
+    # tree states: the same choice
+    (2, 241, 4, 0, 128, 0, {}, (), 4), (2, 241, 4, 0, 129, 0, {}, (), 0), (2, 257, 6, 0, 1025, 0, {}, (), 1),
+    (2, 257, 6, 0, 2048, 0, {}, (), 5), (2, 32, 1, 0, 8192, 0, {}, (), 5), (2, 1000, 16, 1, 4097, 0, {}, (), 3), (2, 257, 6, 0, 0, 0, {}, (), 8),
+    # gradient, raw x: the row split at 240 < N <= 256 up to 512 chains; in place (alias 1) above 256 dimensions keeps the sweep
+    (1, 240, 4, 0, 512, 0, {}, (), 0), (1, 241, 4, 0, 512, 0, {}, (), 4), (1, 241, 4, 0, 513, 0, {}, (), 0),
+    (1, 256, 4, 0, 512, 0, {}, (), 4), (1, 256, 4, 0, 513, 0, {}, (), 0), (1, 257, 6, 0, 513, 0, {}, (), 4),
+    (1, 257, 6, 0, 1024, 0, {}, (), 4), (1, 257, 6, 0, 1025, 0, {}, (), 1), (1, 257, 6, 0, 2047, 0, {}, (), 1),
+    (1, 257, 6, 0, 2048, 0, {}, (), 6), (1, 257, 6, 0, 2048, 1, {}, (), 1), (1, 256, 4, 0, 2048, 0, {}, (), 5),
+    (1, 256, 4, 0, 2048, 1, {}, (), 5), (1, 256, 4, 0, 2048, 0, {}, ("wide_bwd",), 0), (1, 700, 12, 0, 1025, 0, {}, (), 2),
+    (1, 96, 2, 2, 1, 0, {}, (), 5), (1, 257, 6, 1, 512, 0, {}, (), 1), (1, 257, 6, 0, 512, 0, {"MCD_SPLIT": 0}, (), 1),
+    (1, 100, 2, 0, 1024, 0, {"MCD_SPLIT": 1}, (), 4), (1, 257, 6, 0, 0, 0, {}, (), 8),
+    # ... R = 16 has no sweep: the row split in pieces wherever neither the split itself nor the multiply form takes the call
+    (1, 1000, 16, 0, 512, 0, {}, (), 4), (1, 1000, 16, 0, 1025, 0, {}, (), 7), (1, 1000, 16, 0, 2048, 0, {}, (), 6),
+    (1, 1000, 16, 0, 2048, 1, {}, (), 7), (1, 1000, 16, 1, 512, 0, {}, (), 7), (1, 1000, 16, 0, 512, 0, {"MCD_SPLIT": 0}, (), 7),
+    (1, 1000, 16, 0, 512, 0, {}, ("split",), -1), (1, 1000, 16, 0, 2048, 0, {}, ("split",), 6), (1, 1000, 16, 0, 2048, 1, {}, ("split",), -1),
+    # gradient, tree states: an output over the OTHER input (alias 2, 4) is not for the row split, the height gradient over either input
+    # (alias 1, 2) not for the multiply form above 256 dimensions
+    (3, 241, 4, 0, 512, 0, {}, (), 4), (3, 241, 4, 0, 513, 0, {}, (), 0), (3, 257, 6, 0, 512, 0, {}, (), 4),
+    (3, 257, 6, 0, 512, 1, {}, (), 4), (3, 257, 6, 0, 512, 2, {}, (), 1), (3, 257, 6, 0, 512, 4, {}, (), 1),
+    (3, 257, 6, 0, 2048, 0, {}, (), 6), (3, 257, 6, 0, 2048, 1, {}, (), 1), (3, 257, 6, 0, 2048, 2, {}, (), 1),
+    (3, 257, 6, 0, 2048, 4, {}, (), 6), (3, 256, 4, 0, 2048, 2, {}, (), 5), (3, 256, 4, 0, 2047, 2, {}, (), 0),
+    (3, 1000, 16, 0, 512, 0, {}, (), 4), (3, 1000, 16, 0, 512, 1, {}, (), 4), (3, 1000, 16, 0, 512, 2, {}, (), -1),
+    (3, 1000, 16, 0, 1025, 0, {}, (), 7), (3, 1000, 16, 0, 1025, 4, {}, (), -1), (3, 1000, 16, 0, 2048, 1, {}, (), 7),
+    (3, 1000, 16, 0, 2048, 2, {}, (), -1), (3, 1000, 16, 0, 2048, 4, {}, (), 6), (3, 1000, 16, 0, 512, 0, {}, ("split",), -1),
+    (3, 257, 6, 0, 0, 0, {}, (), 8),
+    # the likelihood launch that carries the prior: only the sweep, and only while the prior waves' state slices fit the ring
+    # ((compute + loader waves) x 16 (n + 2) bytes against two slots of 32 KiB, 64 KiB from R = 12; four loader waves from R = 12)
+    (4, 255, 4, 0, 512, 0, {}, (), 0), (4, 255, 4, 0, 128, 0, {}, (), -1), (4, 255, 4, 0, 2048, 0, {}, (), -1), (4, 255, 4, 0, 0, 0, {}, (), -1),
+    (4, 680, 8, 1, 1025, 0, {}, (), 1), (4, 681, 8, 1, 1025, 0, {}, (), -1), (4, 700, 12, 1, 1025, 0, {}, (), 2),
+    (4, 1022, 16, 1, 1025, 0, {}, (), 3), (4, 1023, 16, 1, 1025, 0, {}, (), -1), (4, 1023, 16, 1, 512, 0, {}, (), 3),
+    (4, 1022, 16, 1, 8192, 0, {}, (), 3), (4, 1023, 16, 1, 8192, 0, {}, (), -1),
+]
+
+
+def test_form_choice_table(knobs):
+    """Which form serves a likelihood or gradient call is host code (sweep_launch.cpp).  mcd_form_selftest_ decides from plain facts, no
+    device and no handle: every threshold of the choice on both sides, both forced forms, MCD_SPLIT = 0 and 1, the in-place calls and the
+    gradients at R = 16, against what the launchers did before the choice was gathered in one file."""
+    L = C.CDLL(M._capi.LIB_PATH)
+    f = L.mcd_form_selftest_
+    f.restype = C.c_int
+    f.argtypes = [C.c_int] * 8 + [C.c_int64, C.c_int]
+    seen = set()
+    for case in FORM_CASES:
+        entry, n, R, form, B, alias, opts, lacks, want = case
+        for k, v in opts.items():
+            knobs.setenv(k, v)
+        got = f(entry, n, R, form, *(int(name not in lacks) for name in ("split", "wide", "wide_bwd", "cols")), B, alias)
+        for k in opts:
+            knobs.delenv(k)
+        assert got == want, case
+        seen.add((entry, want))
+    assert {w for e, w in seen if e == 0} == {-1, 0, 1, 2, 3, 4, 5, 8} and {w for e, w in seen if e == 1} == {-1, 0, 1, 2, 4, 5, 6, 7, 8}
+    assert {w for e, w in seen if e == 3} == {-1, 0, 1, 4, 5, 6, 7, 8}
+
+
 # (dimension, chains, sparse likelihood, knobs, proposals, path): the launch structure (mcd_mh_last_path) that a run of bench.py's synthetic
 # tree of that dimension takes, recorded on the GPU with the library before its run planner was split out of mcd_mh_run (0: the run is
 # refused); the knobs are set before the handle is created

@@ -4,9 +4,8 @@
 cd "$(dirname "$0")/../mcmc-date_amd/csrc" || exit 1
 files=("$@"); [ ${#files[@]} -eq 0 ] && files=(k_*.hip)
 for f in "${files[@]}"; do
-  case "$f" in k_mh.hip|k_mh_chain.hip|k_mh_chain_big.hip|k_mh_segment.hip|k_mh_segment_sparse.hip) extra="-mllvm -disable-machine-licm";; k_logpdf.hip|k_tree_logpdf.hip) extra="-mllvm -amdgpu-kernarg-preload-count=16";; *) extra="";; esac   # (the Makefile's NOLICM and PRELOAD)
-  for g in 0 1 2 3; do
-    case "$f" in k_logpdf.hip|k_grad.hip|k_tree_logpdf.hip|k_tree_grad.hip) def="-DMCD_RGROUP=$g";; *) def=""; [ $g -gt 0 ] && continue;; esac
+  { read -r extra; mapfile -t defs; } < <(make -s flags SRC="$f")   # the Makefile's flags of this source, and the defines of each object it makes
+  for def in "${defs[@]}"; do
     /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -fno-fast-math -ffp-contract=off --cuda-device-only $def $extra -c "$f" -o /dev/null \
       -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs:|AGPRs:|VGPRs Spill|ScratchSize|LDS Size|Occupancy" \
       | sed 's/.*remark: *//; s/ *\[-Rpass.*//' | paste - - - - - - - | while IFS=$'\t' read -r name v a sc oc sp lds; do
