@@ -39,6 +39,7 @@ module McmcDate.GpuSampler
     GpuSampler,
     withGpuSampler,
     runMetropolisHastingsGreenGpu,
+    runMarginalLikelihoodGpu,
     runRecorded,
     recordSummary,
     runMc3Gpu,
@@ -121,6 +122,12 @@ foreign import ccall unsafe "mcd_mh_get_age_sums"
 
 foreign import ccall unsafe "mcd_mh_reset_age_sums"
   c_mh_reset_age_sums :: Ptr McdMh -> IO CInt
+
+foreign import ccall unsafe "mcd_mh_set_power"
+  c_mh_set_power :: Ptr McdMh -> Ptr CDouble -> IO CInt
+
+foreign import ccall safe "mcd_mh_record_marginal"
+  c_mh_record_marginal :: Ptr McdMh -> CInt -> Ptr CDouble -> Int64 -> Int64 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
 
 foreign import ccall unsafe "mcd_mh_last_path"
   c_mh_last_path :: Ptr McdMh -> IO CInt
@@ -441,6 +448,36 @@ runMetropolisHastingsGreenGpu s g burnInPeriods iterations period onSample = do
           i <- VSM.read it 0
           when (k == period) (getStates s >>= onSample i)
           go (left - k)
+
+-- | Replacement of @runMarginalLikelihood@ (app/Main.hs:511-543: @marginalLikelihood mlS p l c m i g@) over a sampler of nPoints x
+-- replicates chains: chain b runs at the path point b mod nPoints with the target prior x likelihood^beta (mcd_mh_set_power), all points in
+-- lock step -- no walk along the path.
+--   nPoints         'Definitions.nPoints' (128, :452-453); the sampler's chain count must be a multiple
+--   burnInPeriods   'Definitions.repetitiveBurnIn' (fast ++ slow: [20, 40, 60, 80] ++ replicate 6 100, :461-465): every chain tunes at its own beta
+--   iterations      'Definitions.iterationsMarginalLh' (4000, :448-449); every @period@-th is recorded on the device
+-- Returns (ln Z by stepping stones, its standard error, ln Z by thermodynamic integration, its standard error): out[4] of
+-- mcd_mh_record_marginal, the errors over the replicates (NaN with one replicate).  The points (k / (K - 1))^(1 / 0.3), the estimators and
+-- the errors are the library's definitions (include/mcmcdate_mvn.h), unpinned against package mcmc's own marginalLikelihood.
+runMarginalLikelihoodGpu :: StatefulGen g IO => GpuSampler -> g -> Int -> [Int] -> Int -> Int -> IO (Double, Double, Double, Double)
+runMarginalLikelihoodGpu s g nPoints burnInPeriods iterations period = do
+  let b = gsChains s
+      k1 = fromIntegral (nPoints - 1) :: Double
+      betas = VS.generate nPoints $ \k ->
+        if k == 0 then 0 else if k == nPoints - 1 then 1 else CDouble ((fromIntegral k / k1) ** (1 / 0.3))
+      perChain = VS.generate b (\c -> betas VS.! (c `mod` nPoints))
+  when (b `mod` nPoints /= 0) $ error "runMarginalLikelihoodGpu: the chains are not whole groups of nPoints."
+  VS.unsafeWith perChain $ \p -> check "mcd_mh_set_power" =<< c_mh_set_power (gsHandle s) p
+  forM_ burnInPeriods $ \n -> do
+    runBlock s g n False
+    check "mcd_mh_tune" =<< c_mh_tune (gsHandle s)
+  check "mcd_mh_record_begin" =<< c_mh_record_begin (gsHandle s) (fromIntegral period) (fromIntegral (iterations `div` period))
+  runBlock s g iterations False
+  out <- VSM.new 4
+  VS.unsafeWith betas $ \pb -> VSM.unsafeWith out $ \po -> alloca $ \pn ->
+    check "mcd_mh_record_marginal" =<< c_mh_record_marginal (gsHandle s) (fromIntegral nPoints) pb 0 (-1) pn nullPtr nullPtr po
+  check "mcd_mh_record_end" =<< c_mh_record_end (gsHandle s)
+  [a, ea, t, et] <- mapM (fmap realToFrac . VSM.read out) [0 .. 3]
+  pure (a, ea, t, et)
 
 -- | 'runMetropolisHastingsGreenGpu' with the samples kept on the device (the recorder of include/mcmcdate_mvn.h): every tuning period
 -- and the iterations run in calls of up to @chunk@ iterations instead of @period@, and the monitor action is called from what

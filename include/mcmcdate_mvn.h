@@ -449,6 +449,17 @@ int mcd_mh_reset_counters(mcd_mh_t* m);
 /* Reciprocal temperatures beta[batch] in (0, 1] (default 1): chain b accepts with (prior x likelihood)^beta[b], the
  * heated chains of Metropolis-coupled MCMC (`mc3`, app/Main.hs:476-478; package `mcmc`). */
 int mcd_mh_set_temperatures(mcd_mh_t* m, const double* beta);
+/* The power posterior: exponents beta[batch] in [0, 1]; chain b accepts with prior x likelihood^beta[b], the target of a path point of the
+ * marginal-likelihood analysis below (mcd_ml_estimate) -- the likelihood ALONE is heated, and beta = 0 (the prior) is allowed.  The ln
+ * acceptance ratio is ((lp1 - lp) + beta (ll1 - ll)) + ln(q-ratio x Jacobian) in this mode; the mode is the handle's: this call sets it,
+ * mcd_mh_set_temperatures and mcd_mh_mc3_init set the other one ((prior x likelihood)^beta), and a handle on which this call is never
+ * made behaves as before, bit for bit.  Nothing else of a run changes; the recorder keeps storing beta[b] with every sample -- in this
+ * mode the likelihood's exponent.  Not-a-number and infinities: a proposal of prior 0 (lp1 = -inf) is rejected; a NaN anywhere in the
+ * ratio rejects; beta = 0 with a ln likelihood of the proposal that is not finite gives 0 x inf = NaN and rejects (the prior-only
+ * chain does not wander where the likelihood cannot be evaluated).  Refused, the handle untouched: a value outside [0, 1] or a NaN
+ * (MCD_ERR_INVALID_ARG); MC3 initialised on the handle (MCD_ERR_UNSUPPORTED).  mcd_mh_record_summary keeps refusing chains whose beta is
+ * not 1, in either mode. */
+int mcd_mh_set_power(mcd_mh_t* m, const double* beta);
 /*
  * The swap phase of Metropolis-coupled MCMC on the device.  Replaces: the swap bookkeeping of `mc3 (MC3Settings (NChains 4)
  * (SwapPeriod 2) (NSwaps 3))`, app/Main.hs:476-478 (package `mcmc`; its initial ladder and ladder tuning are not restated).
@@ -561,6 +572,45 @@ int mcd_mh_record_quantities(const mcd_mh_t* m, int64_t* q);
 int mcd_mh_record_summary(mcd_mh_t* m, int64_t skip, int64_t n_samples, int32_t max_lag, int64_t* n_used, double* pooled, double* per_chain);
 int mcd_mh_record_summary_mc3(mcd_mh_t* m, int rung, int64_t skip, int64_t n_samples, int32_t max_lag, int64_t* n_used, double* pooled,
                               double* per_group, int32_t* holder, int64_t* visits, int64_t* round_trips);
+/*
+ * The marginal likelihood ln Z = ln integral prior x likelihood from power-posterior chains, computed on the device (k_marginal.hip).
+ * Replaces: `marginalLikelihood mlS p l c m i g` (runMarginalLikelihood, app/Main.hs:511-543; 128 points, app/Definitions.hs:447-472).
+ * What package `mcmc` does in detail (its point spacing, its walk along the path forward and backward) is not restated: the definitions
+ * below are this library's, and the estimate is unpinned against `mcmc`'s own implementation.
+ * Layout: K = n_points path points with the exponents betas[K], betas[0] = 0 < ... < betas[K - 1] = 1.  The chain with the GLOBAL number
+ * g (first chain of the handle + b; b itself for a plain array) runs at point g mod K and is replicate g / K; batch and the first chain
+ * are multiples of K, so the C = batch / K replicates each hold the whole path (mcd_mh_set_power with beta[b] = betas[g mod K]).
+ * With delta_p = betas[p + 1] - betas[p] and x the n ln likelihoods of a chain -- per (point p, replicate r): mean m, M2 = sum (x - m)^2
+ * (two passes, never sum x^2 - ...), mx = max x and, for p < K - 1, S = sum exp(delta_p (x - mx)).
+ *   point[K][MCD_ML_COLS], pooled over the n C values of a point: 0 mean, 1 unbiased variance, 2 minimum, 3 maximum,
+ *     4 ln r_p = delta_p MX + ln(sum_r S_r exp(delta_p (mx_r - MX)) / (n C)), MX the point's maximum (NaN for p = K - 1): the stepping
+ *     stone ln E_{beta_p}[likelihood^delta_p] (Xie et al. 2011);
+ *   replicate[C][2], from replicate r's chain of every point alone: 0 lnZ_ss_r = sum_p [delta_p mx_{p,r} + ln(S_{p,r} / n)],
+ *     1 lnZ_ti_r = sum_p delta_p (m_{p,r} + m_{p+1,r}) / 2 (thermodynamic integration, trapezoid);
+ *   out[4]: 0 the pooled stepping-stone estimate sum_p ln r_p, 1 its standard error sd(lnZ_ss_r) / sqrt(C) (unbiased sd), 2 the pooled
+ *     trapezoid sum_p delta_p (mean_p + mean_{p+1}) / 2, 3 sd(lnZ_ti_r) / sqrt(C).
+ * The replicates are independent chains, so the standard errors hold whatever the autocorrelation inside a chain; C = 1 gives NaN.  The
+ * trapezoid carries a discretisation bias that the standard error does not show.  A chain or point whose values are all equal has that
+ * value as its mean and the variance 0 exactly; equal replicate estimates give the standard error 0 exactly.  A NaN in a point's values
+ * makes that point's columns NaN and every total that uses them NaN.  No floating-point atomics and a fixed order of every sum: two calls
+ * on the same data return the same bits.  Limits: 2 <= K <= 4096, n >= 1, n C in [2, 2^32) (MCD_ERR_INVALID_ARG otherwise, as for betas
+ * that do not start at 0, end at 1 and increase strictly, or a batch that is no multiple of K).  Any of point / replicate / out may be NULL.
+ *   mcd_ml_estimate         a plain array ll[n][batch] on the host (copied) or on device device_id (read in place).
+ *   mcd_mh_record_marginal  the waiting samples [skip, skip + n_samples) of the handle's recorder (n_samples < 0: all after skip;
+ *                           *n_used = their number), ln likelihood read in the ring where it lies -- also where the window wraps.  The
+ *                           contract is mcd_mh_record_summary's: waits for the handle's stream, frees no slot, changes nothing a later
+ *                           call can see; window errors (and its limits: n batch < 2^32) and betas errors are refused before any launch,
+ *                           the handle untouched and *n_used = 0.  The exponent stored with every (sample, chain) of the window must
+ *                           equal betas[g mod K] bit for bit: a window that reaches back before mcd_mh_set_power, or chains run at other
+ *                           exponents, is found by the first kernel -- MCD_ERR_INVALID_ARG, the message names one such sample and chain,
+ *                           and no output other than *n_used = 0 is written.  The same bits as mcd_ml_estimate on the fetched ln
+ *                           likelihoods of the same window.
+ */
+#define MCD_ML_COLS 5
+int mcd_ml_estimate(int64_t n, int64_t batch, const double* ll, int on_device, int device_id, int n_points, const double* betas, double* point,
+                    double* replicate, double* out);
+int mcd_mh_record_marginal(mcd_mh_t* m, int n_points, const double* betas, int64_t skip, int64_t n_samples, int64_t* n_used, double* point,
+                           double* replicate, double* out);
 
 /* ------------------------------------------------------------------------------------------------
  * The sparse form: the precision matrix as it is, in CSR on the device, no densification; N up to MCD_MAX_SPARSE_DIM.

@@ -13,8 +13,10 @@ from .hamiltonian import from_vector_with, get_mask, grad_to_vector, target_grad
 from .prepare import glasso_components, graphical_lasso, graphical_lasso_device
 from .prior import (Brace, Calibration, Constraint, PriorFunction, get_mean_root_height, load_braces,
                     load_calibrations, load_calibrations_from_tree, load_constraints, prior_function)
-from .diagnostics import Summary, ess, split_rhat, summary, trace_summary
+from .diagnostics import (MarginalLikelihoodEstimate, Summary, ess, marginal_likelihood, marginal_likelihood_device, power_posterior_points, split_rhat,
+                          summary, trace_summary)
 from .sampler import MC3, Proposal, RecordSummary, Sampler, cycle_schedule, init_with, proposals, table_arrays, weight_n_branches
+from .marginal import MarginalLikelihood
 from .state import State, StateBatch
 from .tree import (Topology, TreeError, branch_slots, get_branches, height_tree_to_length_tree, parse_newick,
                    read_newick_file, sum_first_two)
@@ -29,6 +31,7 @@ __all__ = [
     "MC3", "Proposal", "Sampler", "cycle_schedule", "init_with", "proposals", "table_arrays", "weight_n_branches",
     "Leapfrog", "hmc_transition", "nuts_transition", "nuts_warmup", "run_cycle_with_nuts", "DualAveraging", "get_mask", "to_vector", "from_vector_with", "grad_to_vector", "target_grad",
     "diagnostics", "Summary", "RecordSummary", "split_rhat", "ess", "summary", "trace_summary",
+    "MarginalLikelihood", "MarginalLikelihoodEstimate", "marginal_likelihood", "marginal_likelihood_device", "power_posterior_points",
     "graphical_lasso", "graphical_lasso_device", "glasso_components",
     "McdError", "NotPositiveDefinite", "RootNotBifurcating", "NoDevice", "set_option", "get_option",
 ]

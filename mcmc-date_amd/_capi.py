@@ -21,6 +21,7 @@ MCD_ERR_NO_DEVICE = -5
 MCD_ERR_UNSUPPORTED = -6
 MCD_SUMMARY_COLS = 9
 MCD_SUMMARY_MAX_LAG = 255
+MCD_ML_COLS = 5
 MCD_GLASSO_INFO_LEN = 8
 MCD_GLASSO_MAX_DIM = 2048
 MCD_MAT_SIGMA = 0
@@ -105,6 +106,7 @@ SYMBOLS = {
     "mcd_mh_set_tuning": (C.c_int, [_vp, _dp]),
     "mcd_mh_reset_counters": (C.c_int, [_vp]),
     "mcd_mh_set_temperatures": (C.c_int, [_vp, _dp]),
+    "mcd_mh_set_power": (C.c_int, [_vp, _dp]),
     "mcd_mh_last_path": (C.c_int, [_vp]),
     "mcd_mh_last_dynamic_lds": (C.c_int64, [_vp]),
     "mcd_mh_mc3_init": (C.c_int, [_vp, C.c_int, _dp, C.c_int64, C.c_uint64]),
@@ -121,6 +123,8 @@ SYMBOLS = {
     "mcd_mh_record_summary": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64), _dp, _dp]),
     "mcd_mh_record_summary_mc3": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64), _dp, _dp, _ip,
                                             C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mcd_ml_estimate": (C.c_int, [C.c_int64, C.c_int64, _vp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
+    "mcd_mh_record_marginal": (C.c_int, [_vp, C.c_int, _dp, C.c_int64, C.c_int64, C.POINTER(C.c_int64), _dp, _dp, _dp]),
     "mcd_hmc_record_begin": (C.c_int, [_vp, C.c_int32, C.c_int64]),
     "mcd_hmc_record_count": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "mcd_hmc_record_fetch": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _dp, _dp, _dp, _dp, _dp]),

@@ -75,7 +75,8 @@ __global__ __launch_bounds__(256) void k_mh_step(MhDev M, PriorDev P, int p_acc,
         const int p = p_acc;
         const double lp = M.post[b], ll = M.post[B + b], lj = M.post[2 * B + b];
         const double lp1 = M.post1[b], ll1 = M.post1[B + b], lj1 = M.post1[2 * B + b];
-        double la = M.beta[b] * ((lp1 + ll1) - (lp + ll)) + M.lnqj[b];     // heated chains of MC3: posterior^beta; beta = 1 is exact
+        // heated chains of MC3: posterior^beta; beta = 1 is exact.  Power posterior (mcd_mh_set_power): prior x likelihood^beta
+        double la = (M.lik_only ? (lp1 - lp) + M.beta[b] * (ll1 - ll) : M.beta[b] * ((lp1 + ll1) - (lp + ll))) + M.lnqj[b];
         if (jac_root_acc) la += (double)jac_root_acc * (lj1 - lj);   // +1: jf(y) / jf(x); -1 (experiments): the reciprocal
         double ua, ub;
         philox_block(mh_rng(seed, M.chain0 + b, step_acc), 0xFFFFFFFFu, ua, ub);
@@ -303,7 +304,8 @@ __global__ __launch_bounds__(64 * MHW, 2) void k_mh_step_wg(MhDev M, PriorDev P,
     // ---- the decision (every wave for itself: the same bits)
     bool ok = false;
     if (p_acc >= 0) {
-        double la = be * ((po1[0] + po1[1]) - (po[0] + po[1])) + lq;     // heated chains of MC3: posterior^beta; beta = 1 is exact
+        // heated chains of MC3: posterior^beta; beta = 1 is exact.  Power posterior (mcd_mh_set_power): prior x likelihood^beta
+        double la = (M.lik_only ? (po1[0] - po[0]) + be * (po1[1] - po[1]) : be * ((po1[0] + po1[1]) - (po[0] + po[1]))) + lq;
         if (jac_root_acc) la += (double)jac_root_acc * (po1[2] - po[2]);   // +1: jf(y) / jf(x); -1 (experiments): the reciprocal
         double ua, ub;
         philox_block(mh_rng(seed, M.chain0 + b, step_acc), 0xFFFFFFFFu, ua, ub);

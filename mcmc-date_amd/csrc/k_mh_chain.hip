@@ -152,6 +152,7 @@ __global__ __launch_bounds__(64 * WPB * (LW ? 2 : 1)) void k_mh_chain(MhDev M, M
     double lp = c0 + c1 + c2;
     double age_s = 0.0, age_q = 0.0;
     const double beta = M.beta[b];
+    const bool lik_only = M.lik_only != 0;                 // kernel-uniform: the power posterior's acceptance ratio
 #ifdef MCD_MH_STAMP
     uint64_t tk[6] = {0, 0, 0, 0, 0, 0};
 #define MH_TICK(i)                                        \
@@ -225,7 +226,8 @@ __global__ __launch_bounds__(64 * WPB * (LW ? 2 : 1)) void k_mh_chain(MhDev M, M
             ll1 = V.c + (-0.5) * (V.logdet + q);                           // :169
         }
         MH_TICK(3)
-        double la = beta * ((lp1 + ll1) - (lp + ll)) + lnqj;           // heated chains of MC3: posterior^beta; beta = 1 is exact
+        // heated chains of MC3: posterior^beta; beta = 1 is exact.  Power posterior (mcd_mh_set_power): prior x likelihood^beta
+        double la = (lik_only ? (lp1 - lp) + beta * (ll1 - ll) : beta * ((lp1 + ll1) - (lp + ll))) + lnqj;
         if (row.jac_root) la += (double)row.jac_root * (lj1 - lj);
         const bool ok = (la >= 0) || (dr.Uacc < exp(la));
         if (ok) {

@@ -126,7 +126,10 @@ __device__ __forceinline__ void mhb_stream_pass(const double* __restrict__ Ft, d
 
 template <int R> struct MhbCols { static constexpr int N = (R <= 4) ? 4 : 2; };   // columns of L^-1 in flight per batch of moved distances
 
-template <int R>
+// LIK: the handle's mode (MhDev::lik_only) as a compile-time constant.  This kernel has no register to spare (256 + 246 at R = 4, SGPRs kept in
+// VGPR lanes): the mode as one more live scalar across the loop cost 1.7 % per lock step at 257 nodes x 512 chains against 1.0 % as an
+// instantiation of its own ("Marginal likelihood": what is left comes with MhDev's new member, not with this loop).
+template <int R, bool LIK>
 __global__ __launch_bounds__(256, 1) void k_mh_chain_big(MhDev M, MvnDev V, TreeDev T, PriorDev P, const int32_t* __restrict__ sched,
                                                       int64_t n_steps, int32_t S, int accumulate, uint64_t step0, uint64_t seed,
                                                       double* __restrict__ trace_alpha, int8_t* __restrict__ trace_accept)
@@ -861,7 +864,8 @@ __global__ __launch_bounds__(256, 1) void k_mh_chain_big(MhDev M, MvnDev V, Tree
 #ifdef MCD_MHB_STAMP
         if (sparse_step) { MHB_TICK(6) tk[7] += 1; } else { MHB_TICK(4) }
 #endif
-        double la = beta * ((lp1 + ll1) - (lp + ll)) + lnqj;           // heated chains of MC3: posterior^beta; beta = 1 is exact
+        // heated chains of MC3: posterior^beta; beta = 1 is exact.  Power posterior (mcd_mh_set_power): prior x likelihood^beta
+        double la = (LIK ? (lp1 - lp) + beta * (ll1 - ll) : beta * ((lp1 + ll1) - (lp + ll))) + lnqj;
         if (row.jac_root) la += (double)row.jac_root * (lj1 - lj);
         const bool ok = (la >= 0) || (dr.Uacc < exp(la));
         if (HLP && sparse_step) post(&words->dec, 2 * tag + (ok ? 1 : 0));
@@ -988,7 +992,7 @@ bool mh_chain_big_available(const MvnFacts& V, int n_nodes, int n_prop, int64_t 
     return mhb_lds_bytes(n_nodes, n_prop, V.R) + 64 * 1024 <= 160 * 1024;
 }
 
-template <int R>
+template <int R, bool LIK>
 static hipError_t launch_big_R(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const int32_t* sched, int64_t n_steps,
                                int32_t S, int accumulate, uint64_t step0, uint64_t seed, double* trace_alpha, int8_t* trace_accept, hipStream_t st)
 {
@@ -998,13 +1002,19 @@ static hipError_t launch_big_R(const MhDev& M, const MvnDev& V, const TreeDev& T
     if (hipError_t e = hipGetDevice(&dev)) return e;
     if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
     if (!((allowed.load(std::memory_order_acquire) >> dev) & 1ull)) {
-        if (hipError_t e = hipFuncSetAttribute((const void*)k_mh_chain_big<R>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)) return e;
+        if (hipError_t e = hipFuncSetAttribute((const void*)k_mh_chain_big<R, LIK>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)) return e;
         allowed.fetch_or(1ull << dev, std::memory_order_release);
     }
     note_dynamic_lds(dynb + 64 * 1024);                      // (+ the sweep's static LDS ring)
-    hipLaunchKernelGGL(k_mh_chain_big<R>, dim3((unsigned)((M.batch + 1) / 2)), dim3(256), dynb, st, M, V, T, P, sched, n_steps, S, accumulate,
+    hipLaunchKernelGGL((k_mh_chain_big<R, LIK>), dim3((unsigned)((M.batch + 1) / 2)), dim3(256), dynb, st, M, V, T, P, sched, n_steps, S, accumulate,
                        step0, seed, trace_alpha, trace_accept);
     return hipGetLastError();
+}
+
+template <int R, class... A>
+static hipError_t launch_big_mode(const MhDev& M, const A&... a)
+{
+    return M.lik_only ? launch_big_R<R, true>(M, a...) : launch_big_R<R, false>(M, a...);
 }
 
 hipError_t launch_mh_chain_big(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const int32_t* sched, int64_t n_steps,
@@ -1017,18 +1027,18 @@ hipError_t launch_mh_chain_big(const MhDev& M, const MvnDev& V, const TreeDev& T
         MvnDev V0 = V;
         V0.Wc = nullptr;
         switch (V.R) {
-        case 1: return launch_big_R<1>(M, V0, T, P, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, st);
-        case 2: return launch_big_R<2>(M, V0, T, P, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, st);
-        case 3: return launch_big_R<3>(M, V0, T, P, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, st);
-        case 4: return launch_big_R<4>(M, V0, T, P, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, st);
+        case 1: return launch_big_mode<1>(M, V0, T, P, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, st);
+        case 2: return launch_big_mode<2>(M, V0, T, P, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, st);
+        case 3: return launch_big_mode<3>(M, V0, T, P, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, st);
+        case 4: return launch_big_mode<4>(M, V0, T, P, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, st);
         default: return hipErrorInvalidValue;
         }
     }
     switch (V.R) {
-    case 1: return launch_big_R<1>(M, V, T, P, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, st);       // (65 and 66 nodes: one more than the small-tree kernel holds)
-    case 2: return launch_big_R<2>(M, V, T, P, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, st);
-    case 3: return launch_big_R<3>(M, V, T, P, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, st);
-    case 4: return launch_big_R<4>(M, V, T, P, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, st);
+    case 1: return launch_big_mode<1>(M, V, T, P, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, st);       // (65 and 66 nodes: one more than the small-tree kernel holds)
+    case 2: return launch_big_mode<2>(M, V, T, P, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, st);
+    case 3: return launch_big_mode<3>(M, V, T, P, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, st);
+    case 4: return launch_big_mode<4>(M, V, T, P, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, st);
     default: return hipErrorInvalidValue;
     }
 }

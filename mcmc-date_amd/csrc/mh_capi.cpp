@@ -17,9 +17,12 @@
 #include "options.h"
 #include "recorder.hpp"
 #include "summary_device.hpp"
+#include "marginal_device.hpp"
 
 int mcd_summary_run_(const mcd::SumSrc& S, int32_t max_lag, hipStream_t st, double* pooled, double* per_chain);   // summary_capi.cpp
 int mcd_summary_check_(const char* who, int64_t n, int64_t batch, int64_t q, int32_t max_lag);
+int mcd_marginal_check_(const char* who, int64_t n, int64_t batch, int64_t chain0, int n_points, const double* betas);   // marginal_capi.cpp
+int mcd_marginal_run_(const char* who, const mcd::MlSrc& S, const double* betas, hipStream_t st, double* point, double* replicate, double* out);
 extern "C" int mcd_set_last_error_(int code, const char* msg);   // mvn_capi.cpp
 struct mcd_sparse;
 struct mcd_sparse_tree;
@@ -506,6 +509,7 @@ int mcd_mh_mc3_init(mcd_mh_t* m, int n_chains, const double* betas, int64_t tota
     MHIP_TRY(hipMemcpy(ladder, betas, sizeof(double) * (size_t)n_chains, hipMemcpyHostToDevice));
     MHIP_TRY(hipMemcpy(C.rank, rank.data(), sizeof(int32_t) * rank.size(), hipMemcpyHostToDevice));
     MHIP_TRY(hipMemcpy(D.beta, beta.data(), sizeof(double) * beta.size(), hipMemcpyHostToDevice));
+    m->dev.lik_only = 0;
     m->mc3_seed = seed;
     m->mc3_phase = 0;
     return MCD_OK;
@@ -1089,6 +1093,23 @@ int mcd_mh_set_temperatures(mcd_mh_t* m, const double* beta)
     MHIP_TRY(hipSetDevice(m->device));
     MHIP_TRY(hipStreamSynchronize(m->stream));
     MHIP_TRY(hipMemcpy(D.beta, beta, sizeof(double) * (size_t)D.batch, hipMemcpyHostToDevice));
+    m->dev.lik_only = 0;
+    return MCD_OK;
+}
+
+// The power posterior prior x likelihood^beta: the same beta array, read by the acceptance ratio's other arm (MhDev::lik_only).
+int mcd_mh_set_power(mcd_mh_t* m, const double* beta)
+{
+    if (!m || !beta) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_set_power: NULL argument");
+    const mcd::MhDev& D = m->dev;
+    if (m->mc3.n_chains != 0)
+        return mfail(MCD_ERR_UNSUPPORTED, "mcd_mh_set_power: Metropolis-coupled MCMC is initialised on this handle: its swaps exchange temperatures of (prior x likelihood)^beta");
+    for (int64_t b = 0; b < D.batch; ++b)
+        if (!(beta[b] >= 0) || !(beta[b] <= 1.0)) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_set_power: the likelihood's exponents must be in [0, 1] (chain %lld: %g)", (long long)b, beta[b]);
+    MHIP_TRY(hipSetDevice(m->device));
+    MHIP_TRY(hipStreamSynchronize(m->stream));
+    MHIP_TRY(hipMemcpy(D.beta, beta, sizeof(double) * (size_t)D.batch, hipMemcpyHostToDevice));
+    m->dev.lik_only = 1;
     return MCD_OK;
 }
 
@@ -1166,6 +1187,27 @@ int mcd_mh_record_summary(mcd_mh_t* m, int64_t skip, int64_t n_samples, int32_t 
         if (beta[(size_t)b] != 1.0)
             return mfail(MCD_ERR_UNSUPPORTED, "mcd_mh_record_summary: chain %lld has the reciprocal temperature %g: only cold chains (1) are summarised", (long long)b, beta[(size_t)b]);
     if (int rc = mcd_summary_run_(S, max_lag, m->stream, pooled, per_chain)) return rc;
+    if (n_used) *n_used = n;
+    return MCD_OK;
+}
+
+// The marginal likelihood from the window's ln likelihoods, read in the ring (k_marginal.hip): chain g = first_chain + b ran at betas[g mod n_points].
+int mcd_mh_record_marginal(mcd_mh_t* m, int n_points, const double* betas, int64_t skip, int64_t n_samples, int64_t* n_used, double* point,
+                           double* replicate, double* out)
+{
+    const char* who = "mcd_mh_record_marginal";
+    if (!m || !betas) return mfail(MCD_ERR_INVALID_ARG, "%s: NULL argument", who);
+    if (n_used) *n_used = 0;
+    const mcd::MhDev& D = m->dev;
+    mcd::SumSrc R{};
+    int64_t n = 0;
+    if (int rc = m->rec.window(who, m->rec_on(), skip, n_samples, 0, &R, &n)) return rc;
+    if (int rc = mcd_marginal_check_(who, n, D.batch, D.chain0, n_points, betas)) return rc;
+    MHIP_TRY(hipSetDevice(m->device));
+    MHIP_TRY(hipStreamSynchronize(m->stream));
+    // base, n, B, ring, K, then the ring's fields
+    const mcd::MlSrc S{R.base, n, D.batch, 1, n_points, R.first, R.cap, R.stride, R.ld};
+    if (int rc = mcd_marginal_run_(who, S, betas, m->stream, point, replicate, out)) return rc;
     if (n_used) *n_used = n;
     return MCD_OK;
 }

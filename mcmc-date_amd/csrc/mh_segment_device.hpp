@@ -93,7 +93,7 @@ __device__ __forceinline__ bool seg_accept_pending(const MhDev& M, const MhSegPe
     const int64_t B = M.batch;
     const double lp = M.post[b], ll = M.post[B + b], lj = M.post[2 * B + b];
     const double lp1 = M.post1[b], ll1 = M.post1[B + b], lj1 = M.post1[2 * B + b];
-    double la = M.beta[b] * ((lp1 + ll1) - (lp + ll)) + M.lnqj[b];
+    double la = (M.lik_only ? (lp1 - lp) + M.beta[b] * (ll1 - ll) : M.beta[b] * ((lp1 + ll1) - (lp + ll))) + M.lnqj[b];
     if (Q.jac_root) la += (double)Q.jac_root * (lj1 - lj);
     double ua, ub;
     philox_block(mh_rng(seed, M.chain0 + b, Q.step), 0xFFFFFFFFu, ua, ub);
@@ -465,6 +465,7 @@ __device__ __forceinline__ void seg_chain_wave(const MhDev& M, const PriorDev& P
     const double* psrc = took ? M.post1 : M.post;
     double lp = psrc[b], ll = psrc[B + b], lj = psrc[2 * B + b];
     const double beta = M.beta[b];
+    const bool lik_only = M.lik_only != 0;                 // kernel-uniform: the power posterior's acceptance ratio
     __builtin_amdgcn_s_waitcnt(0xc07f);                      // lgkmcnt(0): this wave's LDS writes have landed (one wave: in order)
     __builtin_amdgcn_wave_barrier();
     // the three blocks of the ln prior of the current state and the summands of two of them: from the step kernel's kept ones
@@ -800,7 +801,8 @@ __device__ __forceinline__ void seg_chain_wave(const MhDev& M, const PriorDev& P
                                                              // on (nothing is accepted, mcd_mh_get_posterior shows it), not a silently wrong value
                 ll1 = (cnt < 0) ? __builtin_nan("") : L.c + (-0.5) * (L.logdet + q);      // :169 (finish_ll)
             }
-            double la = beta * ((lp1 + ll1) - (lp + ll)) + lnqj;           // heated chains of MC3: posterior^beta; beta = 1 is exact
+            // heated chains of MC3: posterior^beta; beta = 1 is exact.  Power posterior (mcd_mh_set_power): prior x likelihood^beta
+            double la = (lik_only ? (lp1 - lp) + beta * (ll1 - ll) : beta * ((lp1 + ll1) - (lp + ll))) + lnqj;
             if (jac_root) la += (double)jac_root * (lj1 - lj);
             // (every lane holds the same numbers: the decision as a scalar, so that the loop's control flow -- what is in flight, whether the
             // proposal drawn ahead is used -- stays the wave's, not per lane)

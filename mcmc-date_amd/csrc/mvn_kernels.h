@@ -119,6 +119,7 @@ struct MhDev {
     const double *p0, *p1;
     const int32_t *brace_ptr, *brace_nodes;                  // CSR of the braces (shared with the prior tables)
     int n_brace;
+    int32_t lik_only;          // 0: beta heats prior x likelihood (MC3); 1: the likelihood alone (power posterior, mcd_mh_set_power)
     double *sc, *H, *R;        // current state: scalars [5][batch] (birth, death, tH, rMu, rVar), heights/rates [batch][ld]
     double *sc1, *H1, *R1;     // proposed state
     double *post, *post1;      // [3][batch] ln prior, ln likelihood, ln jacobianRootBranch (current, proposed)

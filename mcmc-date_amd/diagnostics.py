@@ -4,6 +4,8 @@ Three things live here:
   * a plain-numpy restatement of the definitions of include/mcmcdate_mvn.h (mcd_trace_summary) -- `split_rhat`, `ess`, `summary` --: the host
     mirror of csrc/k_summary.hip and the reference of its tests;
   * `trace_summary`: the same numbers from the device kernels, through the C ABI;
+  * `power_posterior_points`, `marginal_likelihood`, `marginal_likelihood_device`: the marginal likelihood from power-posterior chains --
+    the path points, the numpy restatement of mcd_ml_estimate (csrc/k_marginal.hip) and the kernels through the C ABI;
   * `rung_trace`, `replica_flow`: under Metropolis-coupled MCMC, the sequence of one temperature through the swaps and how the chains travel
     over the ladder -- the restatement of csrc/k_mc3_summary.hip (Sampler.record_summary_mc3).
 
@@ -229,3 +231,130 @@ def trace_summary(X, max_lag: int = 0, device=True, per_chain: bool = True, q: O
     _capi.check(_capi.lib().mcd_trace_summary(n, B, Q, ldq, ptr, int(on_device), dev, int(max_lag), pooled.ctypes.data_as(dp),
                                               pc.ctypes.data_as(dp) if per_chain else None))
     return Summary(pooled, pc)
+
+
+# ---- the marginal likelihood from power-posterior chains (include/mcmcdate_mvn.h: mcd_ml_estimate) ------------------------------------
+ML_COLUMNS = ("mean", "variance", "minimum", "maximum", "ln_ratio")
+
+
+def power_posterior_points(n_points: int, alpha: float = 0.3) -> np.ndarray:
+    """The exponents (k / (K - 1))^(1 / alpha), k = 0 .. K - 1, of K path points: 0 (the prior) ... 1 (the posterior), dense near the prior
+    where the ln likelihood changes fastest (Xie et al. 2011 take the quantiles of Beta(alpha, 1), alpha = 0.3).  This project's choice:
+    what package `mcmc` spaces its points by is not restated."""
+    K = int(n_points)
+    if K < 2:
+        raise ValueError("power_posterior_points: at least 2 points (the prior and the posterior)")
+    if not alpha > 0:
+        raise ValueError("power_posterior_points: alpha must be positive")
+    b = (np.arange(K) / (K - 1.0)) ** (1.0 / alpha)
+    b[0], b[-1] = 0.0, 1.0
+    return b
+
+
+@dataclass
+class MarginalLikelihoodEstimate:
+    """point [K, 5] (ML_COLUMNS, pooled over a point's values), replicate [C, 2] (stepping stones, trapezoid of each replicate's own chains),
+    the pooled stepping-stone estimate ln_z_ss and trapezoid ln_z_ti with the standard errors sd(replicate column) / sqrt(C)."""
+    point: np.ndarray
+    replicate: np.ndarray
+    ln_z_ss: float
+    se_ss: float
+    ln_z_ti: float
+    se_ti: float
+    n_samples: int = 0
+
+    @classmethod
+    def from_arrays(cls, point, replicate, out, n_samples=0):
+        return cls(point, replicate, float(out[0]), float(out[1]), float(out[2]), float(out[3]), int(n_samples))
+
+
+def _check_betas(betas, batch: int) -> np.ndarray:
+    betas = np.ascontiguousarray(betas, dtype=np.float64)
+    K = betas.size
+    if betas.ndim != 1 or K < 2 or K > 4096:
+        raise ValueError("marginal likelihood: betas must hold 2 .. 4096 points")
+    if betas[0] != 0.0 or betas[-1] != 1.0 or not np.all(np.diff(betas) > 0):
+        raise ValueError("marginal likelihood: betas must start at 0, end at 1 and increase strictly")
+    if batch % K != 0:
+        raise ValueError(f"marginal likelihood: {batch} chains are not whole groups of {K} points")
+    return betas
+
+
+def _mean_exact(x: np.ndarray, axis) -> np.ndarray:
+    """Mean along `axis`; equal values have that value as their mean, whatever the rounding of the sum."""
+    mx, mn = x.max(axis=axis), x.min(axis=axis)
+    return np.where(mx == mn, mx, x.mean(axis=axis))
+
+
+def _se(v: np.ndarray) -> float:
+    """sd(v) / sqrt(C), unbiased; equal values: 0 exactly; C = 1 or a NaN: NaN."""
+    C_ = v.size
+    if C_ < 2 or np.isnan(v).any():
+        return float("nan")
+    if v.max() == v.min():
+        return 0.0
+    return float(np.sqrt(((v - v.mean()) ** 2).sum() / (C_ - 1)) / np.sqrt(C_))
+
+
+def marginal_likelihood(ll: np.ndarray, betas) -> MarginalLikelihoodEstimate:
+    """The definitions of mcd_ml_estimate in numpy: ll [n, batch], chain b at point b mod K, replicate b // K."""
+    ll = np.asarray(ll, dtype=np.float64)
+    if ll.ndim != 2:
+        raise ValueError("marginal_likelihood: expected ll [n, batch]")
+    n, B = ll.shape
+    betas = _check_betas(betas, B)
+    K = betas.size
+    C_ = B // K
+    if n < 1 or n * C_ < 2:
+        raise ValueError("marginal_likelihood: need at least 2 values per point")
+    delta = np.append(np.diff(betas), 0.0)                                       # [K]; the last point has no stone
+    x = ll.reshape(n, C_, K)                                                     # [sample, replicate, point]
+    with np.errstate(all="ignore"):
+        bad = np.isnan(x).any(axis=0)                                            # [C, K]
+        mx = np.where(bad, np.nan, x.max(axis=0))
+        m = np.where(bad, np.nan, _mean_exact(x, 0))
+        S = np.exp(delta * (x - mx)).sum(axis=0)                                 # [C, K]
+        pbad = bad.any(axis=0)                                                   # [K]
+        pooled = x.reshape(n * C_, K)
+        MX, MN = pooled.max(axis=0), pooled.min(axis=0)
+        mean = _mean_exact(pooled, 0)
+        var = np.where(MX == MN, 0.0, ((pooled - mean) ** 2).sum(axis=0) / (n * C_ - 1.0))
+        lnr = delta * MX + np.log((S * np.exp(delta * (mx - MX))).sum(axis=0) / (n * C_))
+        lnr[K - 1] = np.nan
+        point = np.stack([mean, var, MN, MX, lnr], axis=1)
+        point[pbad] = np.nan
+        d = delta[:K - 1]
+        rep = np.stack([(d * mx[:, :K - 1] + np.log(S[:, :K - 1] / n)).sum(axis=1),
+                        (d * (m[:, :K - 1] + m[:, 1:]) / 2.0).sum(axis=1)], axis=1)
+        out = [point[:K - 1, 4].sum(), _se(rep[:, 0]), (d * (point[:K - 1, 0] + point[1:, 0]) / 2.0).sum(), _se(rep[:, 1])]
+    return MarginalLikelihoodEstimate.from_arrays(point, rep, out, n)
+
+
+def marginal_likelihood_device(ll, betas, device=True) -> MarginalLikelihoodEstimate:
+    """mcd_ml_estimate on ll [n, batch]: a numpy array (copied to device 0, or to device `device` if that is an int) or a contiguous float64
+    torch tensor on a GPU (read in place).  There is no host path: the host restatement is `marginal_likelihood`."""
+    if device is False:
+        raise ValueError("marginal_likelihood_device: the kernels run on the device; diagnostics.marginal_likelihood is the host restatement")
+    on_device = hasattr(ll, "data_ptr")
+    if on_device:
+        if not ll.is_cuda or not ll.is_contiguous() or str(ll.dtype) != "torch.float64" or ll.dim() != 2:
+            raise ValueError("marginal_likelihood_device: expected a contiguous float64 GPU tensor [n, batch]")
+        ptr, dev = C.c_void_p(ll.data_ptr()), ll.device.index or 0
+        import torch
+
+        torch.cuda.current_stream(ll.device).synchronize()
+    else:
+        ll = np.ascontiguousarray(ll, dtype=np.float64)
+        if ll.ndim != 2:
+            raise ValueError("marginal_likelihood_device: expected [n, batch]")
+        ptr, dev = C.c_void_p(ll.ctypes.data), 0 if device is True else int(device)
+    n, B = (int(s) for s in ll.shape)
+    betas = np.ascontiguousarray(betas, dtype=np.float64)
+    K = int(betas.size)
+    point = np.empty((max(K, 0), _capi.MCD_ML_COLS))
+    rep = np.empty((max(B // K if K else 0, 1), 2))
+    out = np.empty(4)
+    dp = C.POINTER(C.c_double)
+    _capi.check(_capi.lib().mcd_ml_estimate(n, B, ptr, int(on_device), dev, K, betas.ctypes.data_as(dp), point.ctypes.data_as(dp),
+                                            rep.ctypes.data_as(dp), out.ctypes.data_as(dp)))
+    return MarginalLikelihoodEstimate.from_arrays(point, rep, out, n)

@@ -21,6 +21,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _capi
+from .diagnostics import MarginalLikelihoodEstimate
 from .likelihood import TreeLikelihood
 from .prior import PriorFunction
 from .recorder import RecorderCalls
@@ -334,6 +335,14 @@ class Sampler(RecorderCalls):
             raise ValueError("set_temperatures: expected [batch]")
         _capi.check(_capi.lib().mcd_mh_set_temperatures(self._h, beta.ctypes.data_as(_dp)))
 
+    def set_power(self, beta: np.ndarray):
+        """The likelihood's exponents in [0, 1] per chain: chain b accepts with prior x likelihood^beta[b], the power posterior of a path
+        point of the marginal-likelihood analysis (mcd_mh_set_power; 0 = the prior).  set_temperatures goes back to (prior x likelihood)^beta."""
+        beta = np.ascontiguousarray(beta, dtype=np.float64)
+        if beta.shape != (self.batch,):
+            raise ValueError("set_power: expected [batch]")
+        _capi.check(_capi.lib().mcd_mh_set_power(self._h, beta.ctypes.data_as(_dp)))
+
     def age_sums(self):
         """(sum, sum of squares [B, n_nodes], n): running sums of the absolute node ages tH * h_v."""
         B, nn = self.batch, self.topo.n_nodes
@@ -396,6 +405,21 @@ class Sampler(RecorderCalls):
         if not known or used.value != count:
             raise RuntimeError("record_summary_mc3: the handle's MC3 was not set up by sampler.MC3, or the recorder moved during the call")
         return RecordSummary(pooled, self.topo.n_nodes, int(used.value), lag, pg, None, holder, visits, trips)
+
+    def record_marginal(self, betas, skip: int = 0, n: Optional[int] = None) -> MarginalLikelihoodEstimate:
+        """The marginal likelihood from the ln likelihoods of the waiting samples [skip, skip + n) (n None: all after skip), computed on the
+        device from the ring where they lie (mcd_mh_record_marginal; definitions: diagnostics.marginal_likelihood): chain first_chain + b ran
+        at betas[(first_chain + b) % len(betas)] (set_power), every record of the window at exactly that exponent.  Nothing is fetched and no
+        slot is freed."""
+        betas = np.ascontiguousarray(betas, dtype=np.float64)
+        K = int(betas.size)
+        point = np.empty((max(K, 1), _capi.MCD_ML_COLS))
+        rep = np.empty((max(self.batch // K if K else 0, 1), 2))
+        out = np.empty(4)
+        used = C.c_int64(0)
+        _capi.check(_capi.lib().mcd_mh_record_marginal(self._h, K, betas.ctypes.data_as(_dp), int(skip), -1 if n is None else int(n), C.byref(used),
+                                                       point.ctypes.data_as(_dp), rep.ctypes.data_as(_dp), out.ctypes.data_as(_dp)))
+        return MarginalLikelihoodEstimate.from_arrays(point[:K], rep[:self.batch // K], out, int(used.value))
 
     def node_age_summary(self):
         """Posterior mean and variance of every node age pooled over chains and accumulated iterations, plus the
