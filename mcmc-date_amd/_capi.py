@@ -175,6 +175,25 @@ def lib():
     return _lib
 
 
+class OwnsHandle:
+    """Mixin of an object that owns one handle of the C ABI: _HANDLE = (the attribute holding it, a c_void_p; the symbol that destroys it).
+    close() may be called any number of times; the destructor calls it."""
+    _HANDLE = ("_h", None)
+
+    def close(self):
+        attr, destroy = self._HANDLE
+        h = getattr(self, attr, None)
+        if h is not None and h.value:
+            getattr(lib(), destroy)(h)
+            setattr(self, attr, C.c_void_p())
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def record_ring_selftest(period: int, cap: int, it: int, fetched: int, n: int, skip: int):
     """Test hook mcd_record_ring_selftest_ (csrc/recorder.cpp; outside the header, no device, no handle): (samples that n more iterations add,
     free slots, waiting samples, slot of waiting sample `skip`) of a ring in this state, by the counts every mcd_*_record_* call uses."""

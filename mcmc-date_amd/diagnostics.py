@@ -22,7 +22,6 @@ A constant sequence has the variance 0 exactly.  W = 0, var+ = 0 or n_h < 2: rha
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from dataclasses import dataclass
 from typing import Optional, Sequence
@@ -30,6 +29,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _capi
+from ._arrays import dp, reduction_source
 
 COLUMNS = ("mean", "variance", "minimum", "maximum", "ci_lower", "ci_upper", "rhat", "ess", "last_lag")
 
@@ -210,26 +210,11 @@ def trace_summary(X, max_lag: int = 0, device=True, per_chain: bool = True, q: O
     is refused -- the host restatement is `summary`."""
     if device is False:
         raise ValueError("trace_summary: the kernels run on the device; diagnostics.summary is the host restatement")
-    on_device = hasattr(X, "data_ptr")
-    if on_device:
-        if not X.is_cuda or not X.is_contiguous() or str(X.dtype) != "torch.float64" or X.dim() != 3:
-            raise ValueError("trace_summary: expected a contiguous float64 GPU tensor [n, B, ldq]")
-        ptr, dev = C.c_void_p(X.data_ptr()), X.device.index or 0
-        import torch
-
-        torch.cuda.current_stream(X.device).synchronize()
-    else:
-        X = np.ascontiguousarray(X, dtype=np.float64)
-        if X.ndim != 3:
-            raise ValueError("trace_summary: expected [n, B, ldq]")
-        ptr, dev = C.c_void_p(X.ctypes.data), 0 if device is True else int(device)
-    n, B, ldq = (int(s) for s in X.shape)
+    ptr, on_device, dev, (n, B, ldq) = reduction_source(X, 3, device, "trace_summary", "[n, B, ldq]")
     Q = ldq if q is None else int(q)
     pooled = np.empty((max(Q, 0), len(COLUMNS)))
     pc = np.empty((B, max(Q, 0), 4)) if per_chain else None
-    dp = C.POINTER(C.c_double)
-    _capi.check(_capi.lib().mcd_trace_summary(n, B, Q, ldq, ptr, int(on_device), dev, int(max_lag), pooled.ctypes.data_as(dp),
-                                              pc.ctypes.data_as(dp) if per_chain else None))
+    _capi.check(_capi.lib().mcd_trace_summary(n, B, Q, ldq, ptr, on_device, dev, int(max_lag), dp(pooled), dp(pc) if per_chain else None))
     return Summary(pooled, pc)
 
 
@@ -335,26 +320,11 @@ def marginal_likelihood_device(ll, betas, device=True) -> MarginalLikelihoodEsti
     torch tensor on a GPU (read in place).  There is no host path: the host restatement is `marginal_likelihood`."""
     if device is False:
         raise ValueError("marginal_likelihood_device: the kernels run on the device; diagnostics.marginal_likelihood is the host restatement")
-    on_device = hasattr(ll, "data_ptr")
-    if on_device:
-        if not ll.is_cuda or not ll.is_contiguous() or str(ll.dtype) != "torch.float64" or ll.dim() != 2:
-            raise ValueError("marginal_likelihood_device: expected a contiguous float64 GPU tensor [n, batch]")
-        ptr, dev = C.c_void_p(ll.data_ptr()), ll.device.index or 0
-        import torch
-
-        torch.cuda.current_stream(ll.device).synchronize()
-    else:
-        ll = np.ascontiguousarray(ll, dtype=np.float64)
-        if ll.ndim != 2:
-            raise ValueError("marginal_likelihood_device: expected [n, batch]")
-        ptr, dev = C.c_void_p(ll.ctypes.data), 0 if device is True else int(device)
-    n, B = (int(s) for s in ll.shape)
+    ptr, on_device, dev, (n, B) = reduction_source(ll, 2, device, "marginal_likelihood_device", "[n, batch]")
     betas = np.ascontiguousarray(betas, dtype=np.float64)
     K = int(betas.size)
     point = np.empty((max(K, 0), _capi.MCD_ML_COLS))
     rep = np.empty((max(B // K if K else 0, 1), 2))
     out = np.empty(4)
-    dp = C.POINTER(C.c_double)
-    _capi.check(_capi.lib().mcd_ml_estimate(n, B, ptr, int(on_device), dev, K, betas.ctypes.data_as(dp), point.ctypes.data_as(dp),
-                                            rep.ctypes.data_as(dp), out.ctypes.data_as(dp)))
+    _capi.check(_capi.lib().mcd_ml_estimate(n, B, ptr, on_device, dev, K, dp(betas), dp(point), dp(rep), dp(out)))
     return MarginalLikelihoodEstimate.from_arrays(point, rep, out, n)

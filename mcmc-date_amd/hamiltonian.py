@@ -6,7 +6,7 @@ timeBirthRate, timeDeathRate, timeHeight, timeTree heights (pre-order), rateMean
 rateTree branches (pre-order).  Masked out (`getMask`, :33-47): the root height of the time tree, all leaf
 heights, the stem of the rate tree, and timeHeight when no calibrations are available.
 
-`grad_to_vector` arranges the device gradient of the LIKELIHOOD (mcd_tree_grad_batch) in that position
+`grad_to_vector` arranges the device gradient of the LIKELIHOOD (TreeLikelihood.grad) in that position
 vector; the likelihood does not depend on timeBirthRate, timeDeathRate, rateVariance, so their entries are 0
 (their gradients come from the prior: `PriorFunction.grad`, mcd_prior_grad_batch).  `target_grad` assembles the gradient
 of the whole Hamiltonian target ln (prior x likelihood x jacobianRootBranch) (`htargetWith`, :72-92) for a batch.
@@ -63,7 +63,7 @@ def target_grad(mask: np.ndarray, tree_lik, prior, states):
     """Value and gradient of the Hamiltonian target of the reference, ln [prior x likelihood x jacobianRootBranch]
     (`htargetWith`, app/Hamiltonian.hs:72-92), for every chain of `states`, in the position-vector layout of
     `to_vector`: (value [B], gradient [B, mask.sum()]).  Prior and likelihood (values and gradients) come from the device
-    (mcd_prior_grad_batch, mcd_tree_grad_batch); the Jacobian factor 1 / rootBranch (app/Probability.hs:393-410),
+    (PriorFunction.grad, TreeLikelihood.grad); the Jacobian factor 1 / rootBranch (app/Probability.hs:393-410),
     rootBranch = tH rMu (t_l r_l + t_r r_r), is five numbers per chain and is differentiated here."""
     lp, gp = prior.grad(states)
     ll, gH, gR, gt, gm = tree_lik.grad(states)

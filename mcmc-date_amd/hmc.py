@@ -18,69 +18,35 @@ The product path is `Leapfrog.nuts` / `Leapfrog.nuts_run`: the same algorithm as
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Optional
 
 import numpy as np
 
 from . import _capi
+from ._arrays import dp, ip
 from .likelihood import SparseTreeLikelihood, TreeLikelihood
 from .prior import PriorFunction
-from .recorder import RecorderCalls
+from .recorder import DriverCalls
 from .state import StateBatch
 
-_dp = C.POINTER(C.c_double)
-
-
-def _p(a):
-    return a.ctypes.data_as(_dp)
-
-
-class Leapfrog(RecorderCalls):
+class Leapfrog(DriverCalls):
     """B chains on one GPU.  `tree_lik` (a TreeLikelihood, or a SparseTreeLikelihood: the precision matrix stays sparse on the device,
     mcd_hmc_create_sparse, trees of up to 2048 nodes) and `prior` must live on the same device and outlive this object."""
+    _API, _HANDLE = "mcd_hmc", ("_h", "mcd_hmc_destroy")
 
     def __init__(self, tree_lik: "TreeLikelihood | SparseTreeLikelihood", prior: PriorFunction, calibrations_available: bool, batch: int):
         self.topo = tree_lik.topo
         self.batch = int(batch)
         self._keep = (tree_lik, prior)
-        self._h = C.c_void_p()
-        create = _capi.lib().mcd_hmc_create_sparse if isinstance(tree_lik, SparseTreeLikelihood) else _capi.lib().mcd_hmc_create
-        _capi.check(create(C.byref(self._h), tree_lik._t, prior._p, int(bool(calibrations_available)), self.batch))
+        self._create(tree_lik, prior._p, int(bool(calibrations_available)), self.batch)
         self.dim = int(_capi.lib().mcd_hmc_dim(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            _capi.lib().mcd_hmc_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_state(self, s: StateBatch):
-        nn = self.topo.n_nodes
-        f = lambda x: np.ascontiguousarray(x, dtype=np.float64)
-        arr = [f(s.time_birth_rate), f(s.time_death_rate), f(s.time_height), f(s.heights), f(s.rate_mean), f(s.rate_variance), f(s.rates)]
-        if arr[3].shape != (self.batch, nn) or arr[6].shape != (self.batch, nn):
-            raise ValueError("set_state: inconsistent state shapes")
-        _capi.check(_capi.lib().mcd_hmc_set_state(self._h, *[_p(a) for a in arr], nn))
-
-    def state(self) -> StateBatch:
-        nn, B = self.topo.n_nodes, self.batch
-        birth, death, tH, rMu, rVar = (np.empty(B) for _ in range(5))
-        H, R = np.empty((B, nn)), np.empty((B, nn))
-        _capi.check(_capi.lib().mcd_hmc_get_state(self._h, *[_p(a) for a in (birth, death, tH, H, rMu, rVar, R)], nn))
-        return StateBatch(H, R, tH, rMu, birth, death, rVar)
 
     def position(self):
         """(q [B, dim], ln target [B], gradient [B, dim]) of the current state."""
         q, g = np.empty((self.batch, self.dim)), np.empty((self.batch, self.dim))
         v = np.empty(self.batch)
-        _capi.check(_capi.lib().mcd_hmc_get_position(self._h, _p(q), _p(v), _p(g)))
+        _capi.check(_capi.lib().mcd_hmc_get_position(self._h, dp(q), dp(v), dp(g)))
         return q, v, g
 
     def leapfrog(self, p, eps, inv_mass, n_steps: int, direction=None):
@@ -92,7 +58,7 @@ class Leapfrog(RecorderCalls):
         d = None if direction is None else np.ascontiguousarray(direction, dtype=np.float64)
         if p.shape != (self.batch, self.dim):
             raise ValueError("leapfrog: p must be [batch, dim]")
-        _capi.check(_capi.lib().mcd_hmc_leapfrog(self._h, _p(p), _p(eps), _p(d) if d is not None else None, _p(inv_mass), int(n_steps)))
+        _capi.check(_capi.lib().mcd_hmc_leapfrog(self._h, dp(p), dp(eps), dp(d) if d is not None else None, dp(inv_mass), int(n_steps)))
         return p
 
 
@@ -104,8 +70,8 @@ class Leapfrog(RecorderCalls):
         inv_mass = np.ascontiguousarray(np.broadcast_to(np.asarray(inv_mass, np.float64), (self.dim,)))
         alpha = np.empty(self.batch)
         depth = np.empty(self.batch, np.int32)
-        _capi.check(_capi.lib().mcd_hmc_nuts(self._h, _p(eps), _p(inv_mass), int(max_depth), int(seed), int(chain_offset), int(transition),
-                                             _p(alpha), depth.ctypes.data_as(C.POINTER(C.c_int32))))
+        _capi.check(_capi.lib().mcd_hmc_nuts(self._h, dp(eps), dp(inv_mass), int(max_depth), int(seed), int(chain_offset), int(transition),
+                                             dp(alpha), ip(depth)))
         return alpha, depth
 
     def nuts_run(self, n_transitions: int, eps, inv_mass, adapt: bool = False, delta: float = 0.65, max_depth: int = 8, seed: int = 0,
@@ -116,8 +82,8 @@ class Leapfrog(RecorderCalls):
         eps = np.array(np.broadcast_to(np.asarray(eps, np.float64), (self.batch,)), dtype=np.float64, order="C")
         inv_mass = np.ascontiguousarray(np.broadcast_to(np.asarray(inv_mass, np.float64), (self.dim,)))
         ma, qm, qv = np.empty(self.batch), np.empty(self.dim), np.empty(self.dim)
-        _capi.check(_capi.lib().mcd_hmc_nuts_run(self._h, int(n_transitions), int(bool(adapt)), _p(eps), _p(inv_mass), float(delta), int(max_depth),
-                                                 int(seed), int(chain_offset), int(first_transition), _p(ma), _p(qm), _p(qv)))
+        _capi.check(_capi.lib().mcd_hmc_nuts_run(self._h, int(n_transitions), int(bool(adapt)), dp(eps), dp(inv_mass), float(delta), int(max_depth),
+                                                 int(seed), int(chain_offset), int(first_transition), dp(ma), dp(qm), dp(qv)))
         return eps, ma, qm, qv
 
     def nuts_warmup(self, eps, inv_mass, windows: int = 3, window: int = 60, delta: float = 0.65, max_depth: int = 6, seed: int = 0,
@@ -127,8 +93,8 @@ class Leapfrog(RecorderCalls):
         eps = np.array(np.broadcast_to(np.asarray(eps, np.float64), (self.batch,)), dtype=np.float64, order="C")
         inv_mass = np.array(np.broadcast_to(np.asarray(inv_mass, np.float64), (self.dim,)), dtype=np.float64, order="C")
         ma = np.empty(self.batch)
-        _capi.check(_capi.lib().mcd_hmc_nuts_warmup(self._h, int(windows), int(window), _p(eps), _p(inv_mass), float(delta), int(max_depth), int(seed),
-                                                    int(chain_offset), int(first_transition), _p(ma)))
+        _capi.check(_capi.lib().mcd_hmc_nuts_warmup(self._h, int(windows), int(window), dp(eps), dp(inv_mass), float(delta), int(max_depth), int(seed),
+                                                    int(chain_offset), int(first_transition), dp(ma)))
         return eps, inv_mass, ma
 
     # -- the sample recorder (mcd_hmc_record_*) ------------------------------------------------------------------------------
@@ -169,8 +135,8 @@ class Leapfrog(RecorderCalls):
         inv_mass = np.ascontiguousarray(np.broadcast_to(np.asarray(inv_mass, np.float64), (self.dim,)))
         d = None if direction is None else np.ascontiguousarray(direction, dtype=np.float64)
         v = np.empty(self.batch)
-        _capi.check(_capi.lib().mcd_hmc_step_from(self._h, _p(q), _p(p), _p(g), int(bool(have_grad)), _p(eps),
-                                                  _p(d) if d is not None else None, _p(inv_mass), _p(v)))
+        _capi.check(_capi.lib().mcd_hmc_step_from(self._h, dp(q), dp(p), dp(g), int(bool(have_grad)), dp(eps),
+                                                  dp(d) if d is not None else None, dp(inv_mass), dp(v)))
         return q, p, g, v
 
 

@@ -20,10 +20,9 @@ from typing import Callable, List, Sequence, Tuple, Union
 import numpy as np
 
 from . import _capi
+from ._arrays import LIKELIHOOD_FIELDS, Staged, _check_cuda, _host, _is_torch, _ptr, _stream_ptr, dp, ip    # (the underscored names: importable from here as before)
 from .state import State, StateBatch
 from .tree import Topology
-
-_dp = C.POINTER(C.c_double)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -97,39 +96,6 @@ def write_data_file(path: str, lhd: LikelihoodData) -> None:
 
 
 # ----------------------------------------------------------------------------------------------
-# array plumbing
-# ----------------------------------------------------------------------------------------------
-def _is_torch(a) -> bool:
-    return type(a).__module__.startswith("torch")
-
-
-def _host(a, shape_tail=None):
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    return a
-
-
-def _ptr(a):
-    if _is_torch(a):
-        return C.c_void_p(a.data_ptr())
-    return C.c_void_p(a.ctypes.data)
-
-
-def _stream_ptr(dev_index: int):
-    import torch
-
-    return C.c_void_p(torch.cuda.current_stream(dev_index).cuda_stream)
-
-
-def _check_cuda(t, device: int, name: str):
-    import torch
-
-    if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
-        raise TypeError(f"{name}: need a contiguous float64 CUDA tensor")
-    if t.device.index != device:
-        raise ValueError(f"{name}: tensor is on cuda:{t.device.index}, likelihood lives on cuda:{device}")
-
-
-# ----------------------------------------------------------------------------------------------
 # the likelihood object (owns the C handle)
 # ----------------------------------------------------------------------------------------------
 FORMS = {"auto": 0, "sweep": 1, "multiply": 2}    # MCD_FORM_* (include/mcmcdate_mvn.h)
@@ -147,11 +113,44 @@ def set_logpdf_form(form: str) -> str:
     return {v: k for k, v in FORMS.items()}[prev]
 
 
-class MvnLikelihood:
+class _Calls(_capi.OwnsHandle):
+    """A handle whose entry points share the symbol prefix _API (the dense and the sparse classes differ in nothing else)."""
+
+    def _call(self, op):
+        return getattr(_capi.lib(), f"{self._API}_{op}")
+
+
+class _VectorLikelihood(_Calls):
+    """logpdf / grad on raw vectors over the handle `_h` of dimension `n` on `device` (<_API>_logpdf_batch, <_API>_grad_batch)."""
+    _nodata = False
+
+    def logpdf(self, X):
+        """Batch of independent evaluations: X [batch, n] chain-major (numpy or CUDA tensor) -> ll[batch]."""
+        s = Staged("logpdf", self.device, X=X).check_matrix(None if self._nodata else self.n)
+        if self._nodata:
+            return s.zeros(s.batch)
+        X, = s.arrays
+        ll = s.empty(s.batch)
+        _capi.check(self._call("logpdf_batch")(self._h, _ptr(X), s.ld(X), s.batch, s.on_device, s.stream, _ptr(ll)))
+        return ll
+
+    def grad(self, X):
+        """(ll, G) with G[b] = d ll / d x_b = -Sigma^-1 (x_b - mu)."""
+        if self._nodata:
+            raise ValueError("grad: NoData has no gradient path (the reference offers likelihoodFunctionG for Full only)")
+        s = Staged("grad", self.device, X=X).check_matrix(self.n)
+        X, = s.arrays
+        ll, G = s.empty(s.batch), s.empty_like(X)
+        _capi.check(self._call("grad_batch")(self._h, _ptr(X), s.ld(X), s.batch, s.on_device, s.stream, _ptr(ll), _ptr(G), s.ld(G)))
+        return ll, G
+
+
+class MvnLikelihood(_VectorLikelihood):
     """`likelihoodFunction lhd` with its operands staged once on one GPU.
 
     Equivalent of the closure built in getLikelihoodFunction (app/Main.hs:333-347).
     """
+    _API, _HANDLE = "mcd_mvn", ("_h", "mcd_mvn_destroy")
 
     def __init__(self, lhd: LikelihoodData, device: int = 0):
         self._h = C.c_void_p()
@@ -182,9 +181,7 @@ class MvnLikelihood:
         if mat.shape != (n, n):
             raise ValueError("LikelihoodData: matrix shape does not match the mean vector")
         self.n = n
-        L = _capi.lib()
-        _capi.check(L.mcd_mvn_create(C.byref(self._h), n, mu.ctypes.data_as(_dp), mat.ctypes.data_as(_dp), kind,
-                                     C.c_double(logdet), self.device))
+        _capi.check(_capi.lib().mcd_mvn_create(C.byref(self._h), n, dp(mu), dp(mat), kind, C.c_double(logdet), self.device))
 
     @classmethod
     def from_covariance(cls, mu, sigma, device: int = 0) -> "MvnLikelihood":
@@ -199,22 +196,9 @@ class MvnLikelihood:
         self.n = len(mu)
         if sigma.shape != (self.n, self.n):
             raise ValueError("from_covariance: matrix shape does not match the mean vector")
-        _capi.check(_capi.lib().mcd_mvn_create(C.byref(self._h), self.n, mu.ctypes.data_as(_dp),
-                                               sigma.ctypes.data_as(_dp), _capi.MCD_MAT_SIGMA, C.c_double(0.0),
+        _capi.check(_capi.lib().mcd_mvn_create(C.byref(self._h), self.n, dp(mu), dp(sigma), _capi.MCD_MAT_SIGMA, C.c_double(0.0),
                                                self.device))
         return self
-
-    # -- lifetime ------------------------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            _capi.lib().mcd_mvn_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def release_stream(self, stream) -> None:
         """mcd_mvn_release_stream: the scratch set the row-split kernels keep for `stream` (a torch.cuda.Stream or a raw
@@ -240,10 +224,10 @@ class MvnLikelihood:
 
     def cholesky_factor(self) -> np.ndarray:
         out = np.empty((self.n, self.n))
-        _capi.check(_capi.lib().mcd_mvn_get_factor(self._h, out.ctypes.data_as(_dp)))
+        _capi.check(_capi.lib().mcd_mvn_get_factor(self._h, dp(out)))
         return out
 
-    # -- evaluation ----------------------------------------------------------------------------
+    # -- evaluation (logpdf and grad: _VectorLikelihood) ---------------------------------------
     def logpdf1(self, x: Sequence[float]) -> float:
         """One evaluation: drop-in for logDensityFullMultivariateNormal (app/Probability.hs:166-173)."""
         if self._nodata:
@@ -252,158 +236,73 @@ class MvnLikelihood:
         if x.shape != (self.n,):
             raise ValueError("logpdf1: wrong vector length")
         out = C.c_double()
-        _capi.check(_capi.lib().mcd_mvn_logpdf(self._h, x.ctypes.data_as(_dp), C.byref(out)))
+        _capi.check(_capi.lib().mcd_mvn_logpdf(self._h, dp(x), C.byref(out)))
         return out.value
 
-    def logpdf(self, X):
-        """Batch of independent evaluations; X is [batch, n] chain-major (numpy or CUDA tensor)."""
-        L = _capi.lib()
-        if _is_torch(X):
-            import torch
-
-            if self._nodata:
-                return torch.zeros(X.shape[0], dtype=torch.float64, device=X.device)
-            _check_cuda(X, self.device, "X")
-            if X.dim() != 2 or X.shape[1] != self.n:
-                raise ValueError("logpdf: X must be [batch, n]")
-            ll = torch.empty(X.shape[0], dtype=torch.float64, device=X.device)
-            _capi.check(L.mcd_mvn_logpdf_batch(self._h, _ptr(X), X.stride(0), X.shape[0], 1, _stream_ptr(self.device),
-                                               _ptr(ll)))
-            return ll
-        X = _host(X)
-        if self._nodata:
-            return np.zeros(X.shape[0])
-        if X.ndim != 2 or X.shape[1] != self.n:
-            raise ValueError("logpdf: X must be [batch, n]")
-        ll = np.empty(X.shape[0])
-        _capi.check(L.mcd_mvn_logpdf_batch(self._h, _ptr(X), X.shape[1], X.shape[0], 0, None, _ptr(ll)))
-        return ll
-
     def logpdf_into(self, X, ll):
-        """Device-resident variant writing into a caller-provided CUDA tensor (no allocation)."""
+        """Device-resident variant writing into a caller-provided CUDA tensor (no allocation).  The unchecked fast path: nothing about
+        X or ll is verified here (logpdf is the checked call); both must be contiguous float64 CUDA tensors on this handle's device,
+        X [batch, n] and ll [batch]."""
         _capi.check(_capi.lib().mcd_mvn_logpdf_batch(self._h, _ptr(X), X.stride(0), X.shape[0], 1,
                                                      _stream_ptr(self.device), _ptr(ll)))
         return ll
-
-    def grad(self, X):
-        """(ll, G) with G[b] = d ll / d x_b = -Sigma^-1 (x_b - mu)."""
-        L = _capi.lib()
-        if self._nodata:
-            raise ValueError("grad: NoData has no gradient path (the reference offers likelihoodFunctionG for Full only)")
-        if _is_torch(X):
-            import torch
-
-            _check_cuda(X, self.device, "X")
-            ll = torch.empty(X.shape[0], dtype=torch.float64, device=X.device)
-            G = torch.empty_like(X)
-            _capi.check(L.mcd_mvn_grad_batch(self._h, _ptr(X), X.stride(0), X.shape[0], 1, _stream_ptr(self.device),
-                                             _ptr(ll), _ptr(G), G.stride(0)))
-            return ll, G
-        X = _host(X)
-        if X.ndim != 2 or X.shape[1] != self.n:
-            raise ValueError("grad: X must be [batch, n]")
-        ll = np.empty(X.shape[0])
-        G = np.empty_like(X)
-        _capi.check(L.mcd_mvn_grad_batch(self._h, _ptr(X), X.shape[1], X.shape[0], 0, None, _ptr(ll), _ptr(G), X.shape[1]))
-        return ll, G
 
     def bind_tree(self, topo: Topology) -> "TreeLikelihood":
         return TreeLikelihood(self, topo)
 
 
-class TreeLikelihood:
-    """State -> log-likelihood: likelihoodFunctionWrapper (app/Probability.hs:195-207) on device."""
+class _StateLikelihood(_Calls):
+    """State -> ln likelihood and ln jacobianRootBranch over the tree handle `_t` bound to a vector likelihood (<_API>_create,
+    <_API>_loglik_batch, <_API>_grad_batch).  `sparse` is what the drivers choose their constructor by."""
 
-    def __init__(self, mvn: MvnLikelihood, topo: Topology):
-        self.mvn = mvn
+    def __init__(self, lik: _VectorLikelihood, topo: Topology):
+        self._lik = lik
         self.topo = topo
         self._t = C.c_void_p()
-        if mvn._nodata:
+        if lik._nodata:
             topo.root_children()
             return
         par = np.ascontiguousarray(topo.parent, dtype=np.int32)
-        _capi.check(_capi.lib().mcd_tree_create(C.byref(self._t), mvn._h, len(par),
-                                                par.ctypes.data_as(C.POINTER(C.c_int32))))
+        _capi.check(self._call("create")(C.byref(self._t), lik._h, len(par), ip(par)))
 
-    def close(self):
-        if getattr(self, "_t", None) is not None and self._t.value:
-            _capi.lib().mcd_tree_destroy(self._t)
-            self._t = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _unpack(self, s: StateBatch):
-        return s.heights, s.rates, s.time_height, s.rate_mean
+    def _stage(self, what: str, states: StateBatch) -> Staged:
+        return Staged.state(what, self._lik.device, states, LIKELIHOOD_FIELDS).check_state(self.topo.n_nodes)
 
     def loglik(self, states: StateBatch, want_jacobian: bool = True):
         """(ll[batch], log jacobianRootBranch[batch] or None)."""
-        H, R, tH, rMu = self._unpack(states)
-        L = _capi.lib()
-        nn = self.topo.n_nodes
-        if _is_torch(H):
-            import torch
-
-            dev = self.mvn.device
-            for t, nm in ((H, "heights"), (R, "rates"), (tH, "time_height"), (rMu, "rate_mean")):
-                _check_cuda(t, dev, nm)
-            B = H.shape[0]
-            if self.mvn._nodata:
-                return torch.zeros(B, dtype=torch.float64, device=H.device), None
-            ll = torch.empty(B, dtype=torch.float64, device=H.device)
-            lj = torch.empty(B, dtype=torch.float64, device=H.device) if want_jacobian else None
-            _capi.check(L.mcd_tree_loglik_batch(self._t, _ptr(H), _ptr(R), H.stride(0), _ptr(tH), _ptr(rMu), B, 1,
-                                                _stream_ptr(dev), _ptr(ll), _ptr(lj) if want_jacobian else None))
-            return ll, lj
-        H, R, tH, rMu = (_host(a) for a in (H, R, tH, rMu))
-        B = H.shape[0]
-        if H.shape != (B, nn) or R.shape != (B, nn) or tH.shape != (B,) or rMu.shape != (B,):
-            raise ValueError("loglik: inconsistent state shapes")
-        if self.mvn._nodata:
-            return np.zeros(B), None
-        ll = np.empty(B)
-        lj = np.empty(B) if want_jacobian else None
-        _capi.check(L.mcd_tree_loglik_batch(self._t, _ptr(H), _ptr(R), nn, _ptr(tH), _ptr(rMu), B, 0, None, _ptr(ll),
-                                            _ptr(lj) if want_jacobian else None))
+        s = self._stage("loglik", states)
+        if self._lik._nodata:
+            return s.zeros(s.batch), None
+        H, R, tH, rMu = s.arrays
+        ll = s.empty(s.batch)
+        lj = s.empty(s.batch) if want_jacobian else None
+        _capi.check(self._call("loglik_batch")(self._t, _ptr(H), _ptr(R), s.ld(H), _ptr(tH), _ptr(rMu), s.batch, s.on_device, s.stream,
+                                               _ptr(ll), _ptr(lj) if want_jacobian else None))
         return ll, lj
 
     def grad(self, states: StateBatch):
-        """(ll, g_heights[batch, n_nodes], g_rates[batch, n_nodes], g_time_height[batch], g_rate_mean[batch])."""
-        if self.mvn._nodata:
+        """(ll, g_heights[batch, n_nodes], g_rates[batch, n_nodes], g_time_height[batch], g_rate_mean[batch]): one launch; the sparse form
+        (csrc/k_sparse_grad.hip) takes trees of up to 2048 nodes."""
+        if self._lik._nodata:
             raise ValueError("grad: NoData has no gradient path")
-        H, R, tH, rMu = self._unpack(states)
-        L = _capi.lib()
-        nn = self.topo.n_nodes
-        if _is_torch(H):
-            import torch
-
-            dev = self.mvn.device
-            for t, nm in ((H, "heights"), (R, "rates"), (tH, "time_height"), (rMu, "rate_mean")):
-                _check_cuda(t, dev, nm)
-            B = H.shape[0]
-            ll = torch.empty(B, dtype=torch.float64, device=H.device)
-            gH = torch.empty_like(H)
-            gR = torch.empty_like(R)
-            gt = torch.empty_like(tH)
-            gm = torch.empty_like(rMu)
-            _capi.check(L.mcd_tree_grad_batch(self._t, _ptr(H), _ptr(R), H.stride(0), _ptr(tH), _ptr(rMu), B, 1,
-                                              _stream_ptr(dev), _ptr(ll), _ptr(gH), _ptr(gR), _ptr(gt), _ptr(gm)))
-            return ll, gH, gR, gt, gm
-        H, R, tH, rMu = (_host(a) for a in (H, R, tH, rMu))
-        B = H.shape[0]
-        if H.shape != (B, nn) or R.shape != (B, nn) or tH.shape != (B,) or rMu.shape != (B,):
-            raise ValueError("grad: inconsistent state shapes")
-        ll = np.empty(B)
-        gH = np.empty_like(H)
-        gR = np.empty_like(R)
-        gt = np.empty(B)
-        gm = np.empty(B)
-        _capi.check(L.mcd_tree_grad_batch(self._t, _ptr(H), _ptr(R), nn, _ptr(tH), _ptr(rMu), B, 0, None, _ptr(ll),
-                                          _ptr(gH), _ptr(gR), _ptr(gt), _ptr(gm)))
+        s = self._stage("grad", states)
+        H, R, tH, rMu = s.arrays
+        ll = s.empty(s.batch)
+        gH, gR, gt, gm = (s.empty_like(a) for a in s.arrays)
+        if s.ld(gH) != s.ld(H) or s.ld(gR) != s.ld(H):         # (the call takes one row stride for heights, rates and both gradients)
+            raise ValueError("grad: heights and rates must share one row stride")
+        _capi.check(self._call("grad_batch")(self._t, _ptr(H), _ptr(R), s.ld(H), _ptr(tH), _ptr(rMu), s.batch, s.on_device, s.stream,
+                                             _ptr(ll), _ptr(gH), _ptr(gR), _ptr(gt), _ptr(gm)))
         return ll, gH, gR, gt, gm
+
+
+class TreeLikelihood(_StateLikelihood):
+    """State -> log-likelihood: likelihoodFunctionWrapper (app/Probability.hs:195-207) on device."""
+    _API, _HANDLE, sparse = "mcd_tree", ("_t", "mcd_tree_destroy"), False
+
+    def __init__(self, mvn: MvnLikelihood, topo: Topology):
+        super().__init__(mvn, topo)
+        self.mvn = mvn
 
 
 # ----------------------------------------------------------------------------------------------
@@ -412,12 +311,13 @@ class TreeLikelihood:
 MAX_SPARSE_DIM = 8192
 
 
-class SparseLikelihood:
+class SparseLikelihood(_VectorLikelihood):
     """`likelihoodFunction (Sparse mu sigmaInvSparse logDetSigma)` (app/Probability.hs:279, 178-184) with the precision matrix kept
     sparse on the device (csrc/k_sparse.hip, mcd_sparse_*): the reference's route for trees with thousands of branches.  Takes the
     `Sparse` record of a `.data` file (read_data_file) or of `prepare`.  logpdf / grad on raw vectors, bind_tree(topo).loglik on
     states, bind_tree(topo).grad for the gradient of states (trees of up to 2048 nodes); `Sampler` and `hmc.Leapfrog` take the bound tree
     as it is.  `MvnLikelihood(Sparse ...)` densifies instead (N <= 1024)."""
+    _API, _HANDLE = "mcd_sparse", ("_h", "mcd_sparse_destroy")
 
     def __init__(self, lhd: Sparse, device: int = 0):
         if not isinstance(lhd, Sparse):
@@ -430,149 +330,21 @@ class SparseLikelihood:
         row = np.ascontiguousarray([ij[0] for ij, _ in lhd.sigma_inv_assoc], dtype=np.int32)
         col = np.ascontiguousarray([ij[1] for ij, _ in lhd.sigma_inv_assoc], dtype=np.int32)
         val = np.ascontiguousarray([v for _, v in lhd.sigma_inv_assoc], dtype=np.float64)
-        ip = C.POINTER(C.c_int32)
-        _capi.check(_capi.lib().mcd_sparse_create(C.byref(self._h), self.n, mu.ctypes.data_as(_dp), len(val), row.ctypes.data_as(ip),
-                                                  col.ctypes.data_as(ip), val.ctypes.data_as(_dp), C.c_double(float(lhd.logdet_sigma)),
-                                                  self.device))
+        _capi.check(_capi.lib().mcd_sparse_create(C.byref(self._h), self.n, dp(mu), len(val), ip(row), ip(col), dp(val),
+                                                  C.c_double(float(lhd.logdet_sigma)), self.device))
         self.nnz = int(_capi.lib().mcd_sparse_nnz(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            _capi.lib().mcd_sparse_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def logpdf(self, X):
-        """[batch, n] chain-major (numpy or CUDA tensor) -> ll[batch]."""
-        L = _capi.lib()
-        if _is_torch(X):
-            import torch
-
-            _check_cuda(X, self.device, "X")
-            if X.dim() != 2 or X.shape[1] != self.n:
-                raise ValueError("logpdf: X must be [batch, n]")
-            ll = torch.empty(X.shape[0], dtype=torch.float64, device=X.device)
-            _capi.check(L.mcd_sparse_logpdf_batch(self._h, _ptr(X), X.stride(0), X.shape[0], 1, _stream_ptr(self.device), _ptr(ll)))
-            return ll
-        X = _host(X)
-        if X.ndim != 2 or X.shape[1] != self.n:
-            raise ValueError("logpdf: X must be [batch, n]")
-        ll = np.empty(X.shape[0])
-        _capi.check(L.mcd_sparse_logpdf_batch(self._h, _ptr(X), X.shape[1], X.shape[0], 0, None, _ptr(ll)))
-        return ll
-
-    def grad(self, X):
-        """(ll, G) with G[b] = d ll / d x_b = -P (x_b - mu)."""
-        L = _capi.lib()
-        if _is_torch(X):
-            import torch
-
-            _check_cuda(X, self.device, "X")
-            ll = torch.empty(X.shape[0], dtype=torch.float64, device=X.device)
-            G = torch.empty_like(X)
-            _capi.check(L.mcd_sparse_grad_batch(self._h, _ptr(X), X.stride(0), X.shape[0], 1, _stream_ptr(self.device), _ptr(ll), _ptr(G),
-                                                G.stride(0)))
-            return ll, G
-        X = _host(X)
-        if X.ndim != 2 or X.shape[1] != self.n:
-            raise ValueError("grad: X must be [batch, n]")
-        ll = np.empty(X.shape[0])
-        G = np.empty_like(X)
-        _capi.check(L.mcd_sparse_grad_batch(self._h, _ptr(X), X.shape[1], X.shape[0], 0, None, _ptr(ll), _ptr(G), X.shape[1]))
-        return ll, G
 
     def bind_tree(self, topo: Topology) -> "SparseTreeLikelihood":
         return SparseTreeLikelihood(self, topo)
 
 
-class SparseTreeLikelihood:
+class SparseTreeLikelihood(_StateLikelihood):
     """State -> ln likelihood and ln jacobianRootBranch over a sparse precision matrix (mcd_sparse_tree_*)."""
+    _API, _HANDLE, sparse = "mcd_sparse_tree", ("_t", "mcd_sparse_tree_destroy"), True
 
     def __init__(self, sp: SparseLikelihood, topo: Topology):
+        super().__init__(sp, topo)
         self.sp = sp
-        self.topo = topo
-        self._t = C.c_void_p()
-        par = np.ascontiguousarray(topo.parent, dtype=np.int32)
-        _capi.check(_capi.lib().mcd_sparse_tree_create(C.byref(self._t), sp._h, len(par), par.ctypes.data_as(C.POINTER(C.c_int32))))
-
-    def close(self):
-        if getattr(self, "_t", None) is not None and self._t.value:
-            _capi.lib().mcd_sparse_tree_destroy(self._t)
-            self._t = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def loglik(self, states: StateBatch, want_jacobian: bool = True):
-        """(ll[batch], log jacobianRootBranch[batch] or None)."""
-        H, R, tH, rMu = states.heights, states.rates, states.time_height, states.rate_mean
-        L = _capi.lib()
-        nn = self.topo.n_nodes
-        if _is_torch(H):
-            import torch
-
-            dev = self.sp.device
-            for t, nm in ((H, "heights"), (R, "rates"), (tH, "time_height"), (rMu, "rate_mean")):
-                _check_cuda(t, dev, nm)
-            B = H.shape[0]
-            ll = torch.empty(B, dtype=torch.float64, device=H.device)
-            lj = torch.empty(B, dtype=torch.float64, device=H.device) if want_jacobian else None
-            _capi.check(L.mcd_sparse_tree_loglik_batch(self._t, _ptr(H), _ptr(R), H.stride(0), _ptr(tH), _ptr(rMu), B, 1, _stream_ptr(dev),
-                                                       _ptr(ll), _ptr(lj) if want_jacobian else None))
-            return ll, lj
-        H, R, tH, rMu = (_host(a) for a in (H, R, tH, rMu))
-        B = H.shape[0]
-        if H.shape != (B, nn) or R.shape != (B, nn) or tH.shape != (B,) or rMu.shape != (B,):
-            raise ValueError("loglik: inconsistent state shapes")
-        ll = np.empty(B)
-        lj = np.empty(B) if want_jacobian else None
-        _capi.check(L.mcd_sparse_tree_loglik_batch(self._t, _ptr(H), _ptr(R), nn, _ptr(tH), _ptr(rMu), B, 0, None, _ptr(ll),
-                                                   _ptr(lj) if want_jacobian else None))
-        return ll, lj
-
-    def grad(self, states: StateBatch):
-        """(ll, g_heights[batch, n_nodes], g_rates[batch, n_nodes], g_time_height[batch], g_rate_mean[batch]), as TreeLikelihood.grad: one
-        launch over the sparse matrix (mcd_sparse_tree_grad_batch, csrc/k_sparse_grad.hip), trees of up to 2048 nodes."""
-        H, R, tH, rMu = states.heights, states.rates, states.time_height, states.rate_mean
-        L = _capi.lib()
-        nn = self.topo.n_nodes
-        if _is_torch(H):
-            import torch
-
-            dev = self.sp.device
-            for t, nm in ((H, "heights"), (R, "rates"), (tH, "time_height"), (rMu, "rate_mean")):
-                _check_cuda(t, dev, nm)
-            B = H.shape[0]
-            ll = torch.empty(B, dtype=torch.float64, device=H.device)
-            gH = torch.empty_like(H)
-            gR = torch.empty_like(R)
-            gt = torch.empty_like(tH)
-            gm = torch.empty_like(rMu)
-            if gH.stride(0) != H.stride(0) or gR.stride(0) != H.stride(0) or R.stride(0) != H.stride(0):
-                raise ValueError("grad: heights and rates must share one row stride")
-            _capi.check(L.mcd_sparse_tree_grad_batch(self._t, _ptr(H), _ptr(R), H.stride(0), _ptr(tH), _ptr(rMu), B, 1, _stream_ptr(dev),
-                                                     _ptr(ll), _ptr(gH), _ptr(gR), _ptr(gt), _ptr(gm)))
-            return ll, gH, gR, gt, gm
-        H, R, tH, rMu = (_host(a) for a in (H, R, tH, rMu))
-        B = H.shape[0]
-        if H.shape != (B, nn) or R.shape != (B, nn) or tH.shape != (B,) or rMu.shape != (B,):
-            raise ValueError("grad: inconsistent state shapes")
-        ll = np.empty(B)
-        gH = np.empty_like(H)
-        gR = np.empty_like(R)
-        gt = np.empty(B)
-        gm = np.empty(B)
-        _capi.check(L.mcd_sparse_tree_grad_batch(self._t, _ptr(H), _ptr(R), nn, _ptr(tH), _ptr(rMu), B, 0, None, _ptr(ll), _ptr(gH), _ptr(gR),
-                                                 _ptr(gt), _ptr(gm)))
-        return ll, gH, gR, gt, gm
 
 
 # ----------------------------------------------------------------------------------------------

@@ -35,6 +35,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _capi
+from ._arrays import dp, ip
 from .likelihood import Full, LikelihoodData, NoData, Sparse, Univariate, write_data_file
 from .tree import Topology, TreeError, get_branches, read_newick_file, sum_first_two
 
@@ -267,7 +268,7 @@ def glasso_components(S: np.ndarray, rho: float) -> np.ndarray:
     n = S.shape[0]
     label = np.zeros(max(n, 1), np.int32)
     nc = ctypes.c_int32(0)
-    _capi.check(_capi.lib().mcd_glasso_components(n, S.ctypes.data_as(_capi._dp), float(rho), label.ctypes.data_as(_capi._ip), ctypes.byref(nc)))
+    _capi.check(_capi.lib().mcd_glasso_components(n, dp(S), float(rho), ip(label), ctypes.byref(nc)))
     return label[:n]
 
 
@@ -284,8 +285,8 @@ def graphical_lasso_device(S: np.ndarray, rho: float, penalize_diagonal: bool = 
     W = np.zeros((n, n))
     Theta = np.zeros((n, n))
     raw = (ctypes.c_int64 * _capi.MCD_GLASSO_INFO_LEN)()
-    _capi.check(_capi.lib().mcd_glasso(n, S.ctypes.data_as(_capi._dp), float(rho), int(bool(penalize_diagonal)), float(tol), int(max_iter),
-                                       int(device), W.ctypes.data_as(_capi._dp), Theta.ctypes.data_as(_capi._dp), raw))
+    _capi.check(_capi.lib().mcd_glasso(n, dp(S), float(rho), int(bool(penalize_diagonal)), float(tol), int(max_iter),
+                                       int(device), dp(W), dp(Theta), raw))
     info = {name: int(raw[i]) for i, name in enumerate(GLASSO_INFO_FIELDS)}
     if not info["converged"]:
         warnings.warn(f"graphical_lasso_device: not converged after {info['passes']} outer passes (max_iter = {max_iter})", RuntimeWarning,

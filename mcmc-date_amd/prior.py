@@ -18,7 +18,7 @@ from typing import Callable, List, Optional, Sequence
 import numpy as np
 
 from . import _capi
-from .likelihood import _check_cuda, _is_torch, _ptr, _stream_ptr
+from ._arrays import Staged, _ptr, dp, ip
 from .state import State, StateBatch
 from .tree import Topology, TreeError
 
@@ -192,8 +192,9 @@ def get_mean_root_height(cals: Sequence[Calibration]) -> Optional[float]:
     return c.upper / 2.0 if c.lower is None else (c.lower + c.upper) / 2.0
 
 
-class PriorFunction:
+class PriorFunction(_capi.OwnsHandle):
     """`priorFunction ht md cb cs bs` with its tables staged once on one GPU."""
+    _HANDLE = ("_p", "mcd_prior_destroy")
 
     def __init__(self, ht: float, model: str, calibrations: Sequence[Calibration], constraints: Sequence[Constraint],
                  braces: Sequence[Brace], topo: Topology, device: int = 0):
@@ -212,8 +213,6 @@ class PriorFunction:
                 ia(k.young for k in con), ia(k.old for k in con), da(k.p for k in con),
                 np.concatenate([[0], np.cumsum([len(b.nodes) for b in br])]).astype(np.int32),
                 ia(n for b in br for n in b.nodes), da(b.sd for b in br)]
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
         par = np.ascontiguousarray(topo.parent, dtype=np.int32)
         _capi.check(_capi.lib().mcd_prior_create(
             C.byref(self._p), len(par), ip(par), C.c_double(ht), CLOCK_MODELS[model],
@@ -221,64 +220,25 @@ class PriorFunction:
             len(con), ip(arrs[7]), ip(arrs[8]), dp(arrs[9]),
             len(br), ip(arrs[10]), ip(arrs[11]), dp(arrs[12]), self.device))
 
-    def close(self):
-        if getattr(self, "_p", None) is not None and self._p.value:
-            _capi.lib().mcd_prior_destroy(self._p)
-            self._p = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def logprior(self, s: StateBatch, want_components: bool = False):
         """ln prior per chain (and, optionally, [batch, 3]: node priors, birth-death block, clock block)."""
-        if s.time_birth_rate is None or s.time_death_rate is None or s.rate_variance is None:
-            raise ValueError("logprior: the state batch lacks time_birth_rate / time_death_rate / rate_variance")
-        L = _capi.lib()
-        nn = self.topo.n_nodes
-        fields = (s.time_birth_rate, s.time_death_rate, s.time_height, s.heights, s.rate_mean, s.rate_variance, s.rates)
-        if _is_torch(s.heights):
-            import torch
-
-            for t in fields:
-                _check_cuda(t, self.device, "state field")
-            B = s.heights.shape[0]
-            lp = torch.empty(B, dtype=torch.float64, device=s.heights.device)
-            comp = torch.empty(B, 3, dtype=torch.float64, device=s.heights.device) if want_components else None
-            _capi.check(L.mcd_prior_logprior_batch(self._p, *[_ptr(t) for t in fields[:4]], _ptr(fields[4]), _ptr(fields[5]),
-                                                   _ptr(fields[6]), s.heights.stride(0), B, 1, _stream_ptr(self.device),
-                                                   _ptr(lp), _ptr(comp) if want_components else None))
-            return (lp, comp) if want_components else lp
-        arr = [np.ascontiguousarray(a, dtype=np.float64) for a in fields]
-        B = arr[3].shape[0]
-        if arr[3].shape != (B, nn) or arr[6].shape != (B, nn) or any(a.shape != (B,) for a in (arr[0], arr[1], arr[2], arr[4], arr[5])):
-            raise ValueError("logprior: inconsistent state shapes")
-        lp = np.empty(B)
-        comp = np.empty((B, 3)) if want_components else None
-        _capi.check(L.mcd_prior_logprior_batch(self._p, *[_ptr(a) for a in arr], nn, B, 0, None, _ptr(lp),
-                                               _ptr(comp) if want_components else None))
+        st = Staged.state("logprior", self.device, s).check_state(self.topo.n_nodes)
+        lp = st.empty(st.batch)
+        comp = st.empty(st.batch, 3) if want_components else None
+        _capi.check(_capi.lib().mcd_prior_logprior_batch(self._p, *st.pointers(), st.ld(st["heights"]), st.batch, st.on_device, st.stream,
+                                                         _ptr(lp), _ptr(comp) if want_components else None))
         return (lp, comp) if want_components else lp
-
 
     def grad(self, s: StateBatch):
         """ln prior and its gradient with respect to the seven fields of the state (host arrays):
         (lp [B], dict(time_birth_rate, time_death_rate, time_height, heights [B, n_nodes], rate_mean, rate_variance,
         rates [B, n_nodes])).  NaN outside the support."""
-        if s.time_birth_rate is None or s.time_death_rate is None or s.rate_variance is None:
-            raise ValueError("grad: the state batch lacks time_birth_rate / time_death_rate / rate_variance")
-        nn = self.topo.n_nodes
-        fields = (s.time_birth_rate, s.time_death_rate, s.time_height, s.heights, s.rate_mean, s.rate_variance, s.rates)
-        arr = [np.ascontiguousarray(a, dtype=np.float64) for a in fields]
-        B = arr[3].shape[0]
-        if arr[3].shape != (B, nn) or arr[6].shape != (B, nn) or any(a.shape != (B,) for a in (arr[0], arr[1], arr[2], arr[4], arr[5])):
-            raise ValueError("grad: inconsistent state shapes")
-        lp, gb, gd, gt, gm, gv = (np.empty(B) for _ in range(6))
-        gH, gR = np.empty((B, nn)), np.empty((B, nn))
-        _capi.check(_capi.lib().mcd_prior_grad_batch(self._p, *[_ptr(a) for a in arr], nn, B, 0, None, _ptr(lp), _ptr(gb), _ptr(gd), _ptr(gt),
-                                                     _ptr(gH), _ptr(gm), _ptr(gv), _ptr(gR)))
-        return lp, dict(time_birth_rate=gb, time_death_rate=gd, time_height=gt, heights=gH, rate_mean=gm, rate_variance=gv, rates=gR)
+        st = Staged.state("grad", None, s).check_state(self.topo.n_nodes)
+        lp = st.empty(st.batch)
+        g = {name: st.empty_like(a) for name, a in zip(st.names, st.arrays)}
+        _capi.check(_capi.lib().mcd_prior_grad_batch(self._p, *st.pointers(), st.ld(st["heights"]), st.batch, 0, None, _ptr(lp),
+                                                     *[_ptr(a) for a in g.values()]))
+        return lp, g
 
 
 def prior_function(ht: float, model: str, calibrations, constraints, braces, topo: Topology,

@@ -21,10 +21,11 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _capi
+from ._arrays import dp, ip
 from .diagnostics import MarginalLikelihoodEstimate
 from .likelihood import TreeLikelihood
 from .prior import PriorFunction
-from .recorder import RecorderCalls
+from .recorder import DriverCalls
 from .state import State, StateBatch
 from .tree import Topology
 
@@ -201,12 +202,9 @@ BURN_IN_FAST = [10, 10] + list(range(10, 131, 10))
 BURN_IN_SLOW = list(range(100, 401, 20))
 ITERATIONS = 8000   # :440-441
 
-_dp = C.POINTER(C.c_double)
-_ip = C.POINTER(C.c_int32)
-
-
-class Sampler(RecorderCalls):
+class Sampler(DriverCalls):
     """B chains on one GPU.  `tree_lik` and `prior` must live on the same device and outlive the sampler."""
+    _API, _HANDLE = "mcd_mh", ("_h", "mcd_mh_destroy")
 
     def __init__(self, tree_lik: TreeLikelihood, prior: PriorFunction, table: Sequence[Proposal], batch: int, seed: int,
                  first_chain: int = 0):
@@ -216,58 +214,24 @@ class Sampler(RecorderCalls):
         self.seed = int(seed)
         self.first_chain = int(first_chain)        # global index of chain 0 (shards.shard_sampler): the random-stream id
         self._keep = (tree_lik, prior)
-        self._h = C.c_void_p()
         a = table_arrays(self.table)
-        ip = lambda x: x.ctypes.data_as(_ip)
-        dp = lambda x: x.ctypes.data_as(_dp)
-        L = _capi.lib()
-        # a SparseTreeLikelihood (precision matrix kept sparse on the device: trees beyond 1024 branches) takes mcd_mh_create_sparse
-        create = L.mcd_mh_create_sparse if type(tree_lik).__name__ == "SparseTreeLikelihood" else L.mcd_mh_create
-        _capi.check(create(C.byref(self._h), tree_lik._t, prior._p, len(self.table), ip(a["kind"]), ip(a["node"]),
-                           ip(a["n1"]), ip(a["n2"]), ip(a["jac_root"]), ip(a["dim"]), dp(a["p0"]), dp(a["p1"]),
-                           self.batch, C.c_uint64(seed)))
+        # (a SparseTreeLikelihood -- precision matrix kept sparse on the device: trees beyond 1024 branches -- takes mcd_mh_create_sparse)
+        self._create(tree_lik, prior._p, len(self.table), ip(a["kind"]), ip(a["node"]), ip(a["n1"]), ip(a["n2"]), ip(a["jac_root"]),
+                     ip(a["dim"]), dp(a["p0"]), dp(a["p1"]), self.batch, C.c_uint64(seed))
         if first_chain:
-            _capi.check(L.mcd_mh_set_chain_offset(self._h, int(first_chain)))
+            _capi.check(_capi.lib().mcd_mh_set_chain_offset(self._h, int(first_chain)))
         self._sched_rng = np.random.default_rng([int(seed), 0x5EED])
         self.iterations_done = 0
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            _capi.lib().mcd_mh_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    # -- state --------------------------------------------------------------------------------------------------
-    def set_state(self, s: StateBatch):
-        nn = self.topo.n_nodes
-        f = lambda x: np.ascontiguousarray(x, dtype=np.float64)
-        if s.time_birth_rate is None or s.time_death_rate is None or s.rate_variance is None:
-            raise ValueError("set_state: the state batch lacks time_birth_rate / time_death_rate / rate_variance")
-        arr = [f(s.time_birth_rate), f(s.time_death_rate), f(s.time_height), f(s.heights), f(s.rate_mean), f(s.rate_variance), f(s.rates)]
-        if arr[3].shape != (self.batch, nn) or arr[6].shape != (self.batch, nn) or any(a.shape != (self.batch,) for a in (arr[0], arr[1], arr[2], arr[4], arr[5])):
-            raise ValueError("set_state: inconsistent state shapes")
-        _capi.check(_capi.lib().mcd_mh_set_state(self._h, *[a.ctypes.data_as(_dp) for a in arr], nn))
-
+    # -- state (set_state, state: DriverCalls) ----------------------------------------------------------------------
     def set_initial_state(self, x: State):
         """Every chain starts from the same state (the reference starts its single chain from `initWith`)."""
         self.set_state(StateBatch.from_states([x] * self.batch))
 
-    def state(self) -> StateBatch:
-        nn, B = self.topo.n_nodes, self.batch
-        birth, death, tH, rMu, rVar = (np.empty(B) for _ in range(5))
-        H, R = np.empty((B, nn)), np.empty((B, nn))
-        _capi.check(_capi.lib().mcd_mh_get_state(self._h, *[a.ctypes.data_as(_dp) for a in (birth, death, tH, H, rMu, rVar, R)], nn))
-        return StateBatch(H, R, tH, rMu, birth, death, rVar)
-
     def posterior(self) -> np.ndarray:
         """[B, 3]: ln prior, ln likelihood, ln jacobianRootBranch of the current states."""
         post = np.empty((self.batch, 3))
-        _capi.check(_capi.lib().mcd_mh_get_posterior(self._h, post.ctypes.data_as(_dp)))
+        _capi.check(_capi.lib().mcd_mh_get_posterior(self._h, dp(post)))
         return post
 
     # -- stepping -----------------------------------------------------------------------------------------------
@@ -278,8 +242,8 @@ class Sampler(RecorderCalls):
         n_iter, S = sched.shape
         ta = np.empty((n_iter * S, self.batch)) if trace else None
         tk = np.empty((n_iter * S, self.batch), np.int8) if trace else None
-        _capi.check(_capi.lib().mcd_mh_run(self._h, sched.ctypes.data_as(_ip), n_iter, S, int(bool(accumulate)),
-                                           ta.ctypes.data_as(_dp) if trace else None,
+        _capi.check(_capi.lib().mcd_mh_run(self._h, ip(sched), n_iter, S, int(bool(accumulate)),
+                                           dp(ta) if trace else None,
                                            tk.ctypes.data_as(C.POINTER(C.c_int8)) if trace else None))
         self.iterations_done += n_iter
         return (ta, tk) if trace else None
@@ -316,14 +280,14 @@ class Sampler(RecorderCalls):
         t = np.empty((B, P))
         a = np.empty((B, P), np.int32)
         n = np.empty((B, P), np.int32)
-        _capi.check(_capi.lib().mcd_mh_get_tuning(self._h, t.ctypes.data_as(_dp), a.ctypes.data_as(_ip), n.ctypes.data_as(_ip)))
+        _capi.check(_capi.lib().mcd_mh_get_tuning(self._h, dp(t), ip(a), ip(n)))
         return t, a, n
 
     def set_tuning(self, t: np.ndarray):
         t = np.ascontiguousarray(t, dtype=np.float64)
         if t.shape != (self.batch, len(self.table)):
             raise ValueError("set_tuning: expected [batch, n_prop]")
-        _capi.check(_capi.lib().mcd_mh_set_tuning(self._h, t.ctypes.data_as(_dp)))
+        _capi.check(_capi.lib().mcd_mh_set_tuning(self._h, dp(t)))
 
     def reset_counters(self):
         _capi.check(_capi.lib().mcd_mh_reset_counters(self._h))
@@ -333,7 +297,7 @@ class Sampler(RecorderCalls):
         beta = np.ascontiguousarray(beta, dtype=np.float64)
         if beta.shape != (self.batch,):
             raise ValueError("set_temperatures: expected [batch]")
-        _capi.check(_capi.lib().mcd_mh_set_temperatures(self._h, beta.ctypes.data_as(_dp)))
+        _capi.check(_capi.lib().mcd_mh_set_temperatures(self._h, dp(beta)))
 
     def set_power(self, beta: np.ndarray):
         """The likelihood's exponents in [0, 1] per chain: chain b accepts with prior x likelihood^beta[b], the power posterior of a path
@@ -341,14 +305,14 @@ class Sampler(RecorderCalls):
         beta = np.ascontiguousarray(beta, dtype=np.float64)
         if beta.shape != (self.batch,):
             raise ValueError("set_power: expected [batch]")
-        _capi.check(_capi.lib().mcd_mh_set_power(self._h, beta.ctypes.data_as(_dp)))
+        _capi.check(_capi.lib().mcd_mh_set_power(self._h, dp(beta)))
 
     def age_sums(self):
         """(sum, sum of squares [B, n_nodes], n): running sums of the absolute node ages tH * h_v."""
         B, nn = self.batch, self.topo.n_nodes
         s, q = np.empty((B, nn)), np.empty((B, nn))
         n = C.c_int64(0)
-        _capi.check(_capi.lib().mcd_mh_get_age_sums(self._h, s.ctypes.data_as(_dp), q.ctypes.data_as(_dp), C.byref(n)))
+        _capi.check(_capi.lib().mcd_mh_get_age_sums(self._h, dp(s), dp(q), C.byref(n)))
         return s, q, int(n.value)
 
     def reset_age_sums(self):
@@ -399,8 +363,8 @@ class Sampler(RecorderCalls):
         used = C.c_int64(0)
         lp = C.POINTER(C.c_int64)
         _capi.check(_capi.lib().mcd_mh_record_summary_mc3(self._h, int(rung), int(skip), -1 if n is None else int(n), lag, C.byref(used),
-                                                          pooled.ctypes.data_as(_dp), pg.ctypes.data_as(_dp) if per_group else None,
-                                                          holder.ctypes.data_as(_ip), visits.ctypes.data_as(lp) if flow else None,
+                                                          dp(pooled), dp(pg) if per_group else None,
+                                                          ip(holder), visits.ctypes.data_as(lp) if flow else None,
                                                           trips.ctypes.data_as(lp) if flow else None))
         if not known or used.value != count:
             raise RuntimeError("record_summary_mc3: the handle's MC3 was not set up by sampler.MC3, or the recorder moved during the call")
@@ -417,8 +381,8 @@ class Sampler(RecorderCalls):
         rep = np.empty((max(self.batch // K if K else 0, 1), 2))
         out = np.empty(4)
         used = C.c_int64(0)
-        _capi.check(_capi.lib().mcd_mh_record_marginal(self._h, K, betas.ctypes.data_as(_dp), int(skip), -1 if n is None else int(n), C.byref(used),
-                                                       point.ctypes.data_as(_dp), rep.ctypes.data_as(_dp), out.ctypes.data_as(_dp)))
+        _capi.check(_capi.lib().mcd_mh_record_marginal(self._h, K, dp(betas), int(skip), -1 if n is None else int(n), C.byref(used),
+                                                       dp(point), dp(rep), dp(out)))
         return MarginalLikelihoodEstimate.from_arrays(point[:K], rep[:self.batch // K], out, int(used.value))
 
     def node_age_summary(self):
@@ -572,7 +536,7 @@ class MC3:
         self.phase = 0
         self.device = isinstance(backend, Sampler)
         if self.device:
-            _capi.check(_capi.lib().mcd_mh_mc3_init(backend._h, self.n, self.ladder.ctypes.data_as(_dp), self.total, C.c_uint64(self.seed)))
+            _capi.check(_capi.lib().mcd_mh_mc3_init(backend._h, self.n, dp(self.ladder), self.total, C.c_uint64(self.seed)))
             backend._mc3_chains = self.n                               # (Sampler.record_summary_mc3 sizes its arrays by it)
         else:
             self._rank = (np.arange(self.total) % self.n).astype(np.int32)
@@ -585,7 +549,7 @@ class MC3:
         rank = np.empty(self.total, np.int32)
         tried = np.empty(self.n - 1, np.int64)
         acc = np.empty(self.n - 1, np.int64)
-        _capi.check(_capi.lib().mcd_mh_mc3_get(self.backend._h, rank.ctypes.data_as(_ip), tried.ctypes.data_as(C.POINTER(C.c_int64)),
+        _capi.check(_capi.lib().mcd_mh_mc3_get(self.backend._h, ip(rank), tried.ctypes.data_as(C.POINTER(C.c_int64)),
                                                acc.ctypes.data_as(C.POINTER(C.c_int64)), None))
         return rank, tried, acc
 
