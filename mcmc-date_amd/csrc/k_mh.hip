@@ -26,7 +26,7 @@
 #include "mh_inc_device.hpp"
 #include "options.h"
 
-#include <atomic>
+#include "lds_optin.hpp"
 #include <type_traits>
 #include "prior_device.hpp"
 
@@ -783,49 +783,37 @@ bool mh_step_wg_fits(int n_nodes)
     return n_nodes <= 2048 && mh_step_wg_lds(n_nodes) + sizeof(IncShared) <= 144 * 1024;   // (above 64 KiB: allowed at launch)
 }
 
-hipError_t launch_mh_step(const MhDev& M, const PriorDev& P, int p_acc, int jac_root_acc, int p_prop, const MhRow& r, int draw_slot,
-                          uint64_t step_acc, uint64_t seed, int accumulate_now, double* trace_alpha, int8_t* trace_accept, int prior_inline,
-                          bool wg, const TreeDev* T, int n_dim, double* X1, int64_t ldx, hipStream_t st, const MhInc* inc, const MvnDev* V, int summands_init)
+hipError_t launch_mh_step(const MhDev& M, const PriorDev& P, const MhStepRun& run, const MhStep& s, uint64_t seed, hipStream_t st)
 {
-    if (summands_init < 0) summands_init = p_acc < 0 ? 1 : 0;
-    const PropRow row_{r.kind, r.node, r.n1, r.n2, r.jac_root, r.p0, r.p1};
-    if (wg) {
+    const PropRow row{s.row.kind, s.row.node, s.row.n1, s.row.n2, s.row.jac_root, s.row.p0, s.row.p1};
+    if (run.wg) {
         if (!mh_step_wg_fits(M.n_nodes)) return hipErrorInvalidValue;
-        const bool dist = T != nullptr && X1 != nullptr;
-        const TreeDev Tv = dist ? *T : TreeDev{};
-        double* Xv = dist ? X1 : (double*)nullptr;
-        const MhInc Iv = (dist && inc && V) ? *inc : MhInc{};
-        const MvnDev Vv = (dist && inc && V) ? *V : MvnDev{};
+        const bool dist = run.T != nullptr && run.X1 != nullptr;
+        const TreeDev Tv = dist ? *run.T : TreeDev{};
+        double* Xv = dist ? run.X1 : (double*)nullptr;
+        const MhInc Iv = (dist && run.inc && run.V) ? *run.inc : MhInc{};
+        const MvnDev Vv = (dist && run.inc && run.V) ? *run.V : MvnDev{};
         auto go = [&](auto km) -> hipError_t {
             constexpr int KM = decltype(km)::value;
             const size_t lds = mh_step_wg_lds(M.n_nodes);
-            if (lds + sizeof(IncShared) > 64 * 1024) {       // more than 64 KiB of LDS has to be allowed once per device
-                static std::atomic<unsigned long long> allowed{0};
-                int dev = 0;
-                if (hipError_t e = hipGetDevice(&dev)) return e;
-                if (dev < 0 || dev >= 64) return hipErrorInvalidValue;
-                if (!((allowed.load(std::memory_order_acquire) >> dev) & 1ull)) {
-                    if (hipError_t e = hipFuncSetAttribute((const void*)k_mh_step_wg<KM>, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024)) return e;
-                    allowed.fetch_or(1ull << dev, std::memory_order_release);
-                }
-            }
-            hipLaunchKernelGGL(k_mh_step_wg<KM>, dim3((unsigned)M.batch), dim3(64 * MHW), lds, st, M, P, p_acc, jac_root_acc, p_prop, row_, draw_slot,
-                               step_acc, seed, accumulate_now, trace_alpha, trace_accept, prior_inline, Tv, n_dim, Xv, ldx, Iv, Vv, summands_init);
+            if (lds + sizeof(IncShared) > 64 * 1024)         // more than 64 KiB of LDS has to be allowed once per device
+                if (hipError_t e = allow_dynamic_lds<k_mh_step_wg<KM>>(144 * 1024)) return e;
+            hipLaunchKernelGGL(k_mh_step_wg<KM>, dim3((unsigned)M.batch), dim3(64 * MHW), lds, st, M, P, s.p_acc, s.jac_root_acc, s.p_prop, row, s.draw_slot,
+                               s.step_acc, seed, s.accumulate_now, s.trace_alpha, s.trace_accept, run.prior_inline, Tv, run.n_dim, Xv, run.ldx, Iv, Vv, s.summands_init);
             return hipGetLastError();
         };
-        if (dist && n_dim > M.n_nodes) return hipErrorInvalidValue;
+        if (dist && run.n_dim > M.n_nodes) return hipErrorInvalidValue;
         if (M.n_nodes <= 256 * 3) return go(std::integral_constant<int, 3>{});
         if (M.n_nodes <= 256 * 5) return go(std::integral_constant<int, 5>{});
         return go(std::integral_constant<int, 8>{});
     }
-    if (X1 != nullptr) return hipErrorInvalidValue;        // (the caller asked for distances: only the workgroup kernel writes them)
+    if (run.X1 != nullptr) return hipErrorInvalidValue;      // (the caller asked for distances: only the workgroup kernel writes them)
     const size_t per_wave = sizeof(double) * 4 * (size_t)M.n_nodes;
     int wpb = 4;
     while (wpb > 1 && per_wave * wpb > 60 * 1024) wpb >>= 1;
     if (per_wave * wpb > 64 * 1024) return hipErrorInvalidValue;
-    const PropRow row{r.kind, r.node, r.n1, r.n2, r.jac_root, r.p0, r.p1};
-    hipLaunchKernelGGL(k_mh_step, dim3((unsigned)((M.batch + wpb - 1) / wpb)), dim3(64 * wpb), per_wave * wpb, st, M, P, p_acc, jac_root_acc, p_prop,
-                       row, draw_slot, step_acc, seed, accumulate_now, trace_alpha, trace_accept, prior_inline);
+    hipLaunchKernelGGL(k_mh_step, dim3((unsigned)((M.batch + wpb - 1) / wpb)), dim3(64 * wpb), per_wave * wpb, st, M, P, s.p_acc, s.jac_root_acc, s.p_prop,
+                       row, s.draw_slot, s.step_acc, seed, s.accumulate_now, s.trace_alpha, s.trace_accept, run.prior_inline);
     return hipGetLastError();
 }
 hipError_t launch_mh_tune(const MhDev& M, hipStream_t st)

@@ -305,25 +305,24 @@ size_t mh_chain_lds_bytes(int n, int n_prop, int wpb)
     return sizeof(double) * ((size_t)n * 64 + (size_t)wpb * (4 * 64 + 2 * (size_t)n_prop) + 8);       // (+ the hand-over words of the two-wave form; the caller adds the node priors' tables)
 }
 
-hipError_t launch_mh_chain(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const double* Fp,
-                           const int32_t* sched, int64_t n_steps, int32_t S, int accumulate, uint64_t step0, uint64_t seed,
-                           double* trace_alpha, int8_t* trace_accept, bool likelihood_wave, hipStream_t st)
+hipError_t launch_mh_chain(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const double* Fp, const MhSpan& s,
+                           bool likelihood_wave, hipStream_t st)
 {
-    if (n_steps <= 0) return hipSuccess;
+    if (s.n_steps <= 0) return hipSuccess;
     if (M.batch >= 1024) {
         constexpr int WPB = 4;
         const size_t sh = mh_chain_lds_bytes(V.n, M.n_prop, WPB) + sizeof(double) * prior_node_tables_doubles(P.n_cal, P.n_con);
-        hipLaunchKernelGGL((k_mh_chain<WPB, false>), dim3((unsigned)((M.batch + WPB - 1) / WPB)), dim3(64 * WPB), sh, st, M, V, T, P, Fp, sched,
-                           n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept);
+        hipLaunchKernelGGL((k_mh_chain<WPB, false>), dim3((unsigned)((M.batch + WPB - 1) / WPB)), dim3(64 * WPB), sh, st, M, V, T, P, Fp, s.sched,
+                           s.n_steps, s.S, s.accumulate, s.step0, s.seed, s.trace_alpha, s.trace_accept);
     } else {
         constexpr int WPB = 1;
         const size_t sh = mh_chain_lds_bytes(V.n, M.n_prop, WPB) + sizeof(double) * prior_node_tables_doubles(P.n_cal, P.n_con);
         if (!likelihood_wave)
-            hipLaunchKernelGGL((k_mh_chain<WPB, false>), dim3((unsigned)M.batch), dim3(64), sh, st, M, V, T, P, Fp, sched, n_steps, S, accumulate,
-                               step0, seed, trace_alpha, trace_accept);
+            hipLaunchKernelGGL((k_mh_chain<WPB, false>), dim3((unsigned)M.batch), dim3(64), sh, st, M, V, T, P, Fp, s.sched, s.n_steps, s.S,
+                               s.accumulate, s.step0, s.seed, s.trace_alpha, s.trace_accept);
         else
-            hipLaunchKernelGGL((k_mh_chain<WPB, true>), dim3((unsigned)M.batch), dim3(128), sh, st, M, V, T, P, Fp, sched, n_steps, S, accumulate,
-                               step0, seed, trace_alpha, trace_accept);
+            hipLaunchKernelGGL((k_mh_chain<WPB, true>), dim3((unsigned)M.batch), dim3(128), sh, st, M, V, T, P, Fp, s.sched, s.n_steps, s.S,
+                               s.accumulate, s.step0, s.seed, s.trace_alpha, s.trace_accept);
     }
     return hipGetLastError();
 }

@@ -37,7 +37,7 @@
 #include "mh_device.hpp"
 #include "prior_device.hpp"
 
-#include <atomic>
+#include "lds_optin.hpp"
 
 namespace mcd {
 
@@ -993,52 +993,34 @@ bool mh_chain_big_available(const MvnFacts& V, int n_nodes, int n_prop, int64_t 
 }
 
 template <int R, bool LIK>
-static hipError_t launch_big_R(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const int32_t* sched, int64_t n_steps,
-                               int32_t S, int accumulate, uint64_t step0, uint64_t seed, double* trace_alpha, int8_t* trace_accept, hipStream_t st)
+static hipError_t launch_big_R(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const MhSpan& s, hipStream_t st)
 {
     const size_t dynb = mhb_lds_bytes(M.n_nodes, M.n_prop, R) + mhb_node_tables_bytes(M.n_nodes, M.n_prop, R, P.n_cal, P.n_con);
-    static std::atomic<unsigned long long> allowed{0};       // more than 64 KiB of LDS in total has to be allowed once per device
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev)) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!((allowed.load(std::memory_order_acquire) >> dev) & 1ull)) {
-        if (hipError_t e = hipFuncSetAttribute((const void*)k_mh_chain_big<R, LIK>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)) return e;
-        allowed.fetch_or(1ull << dev, std::memory_order_release);
-    }
+    // more than 64 KiB of LDS in total has to be allowed once per device
+    if (hipError_t e = allow_dynamic_lds<k_mh_chain_big<R, LIK>>(96 * 1024)) return e;
     note_dynamic_lds(dynb + 64 * 1024);                      // (+ the sweep's static LDS ring)
-    hipLaunchKernelGGL((k_mh_chain_big<R, LIK>), dim3((unsigned)((M.batch + 1) / 2)), dim3(256), dynb, st, M, V, T, P, sched, n_steps, S, accumulate,
-                       step0, seed, trace_alpha, trace_accept);
+    hipLaunchKernelGGL((k_mh_chain_big<R, LIK>), dim3((unsigned)((M.batch + 1) / 2)), dim3(256), dynb, st, M, V, T, P, s.sched, s.n_steps, s.S,
+                       s.accumulate, s.step0, s.seed, s.trace_alpha, s.trace_accept);
     return hipGetLastError();
 }
 
-template <int R, class... A>
-static hipError_t launch_big_mode(const MhDev& M, const A&... a)
+template <int R>
+static hipError_t launch_big_mode(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const MhSpan& s, hipStream_t st)
 {
-    return M.lik_only ? launch_big_R<R, true>(M, a...) : launch_big_R<R, false>(M, a...);
+    return M.lik_only ? launch_big_R<R, true>(M, V, T, P, s, st) : launch_big_R<R, false>(M, V, T, P, s, st);
 }
 
-hipError_t launch_mh_chain_big(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const int32_t* sched, int64_t n_steps,
-                               int32_t S, int accumulate, uint64_t step0, uint64_t seed, double* trace_alpha, int8_t* trace_accept,
-                               bool incremental, hipStream_t st)
+hipError_t launch_mh_chain_big(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const MhSpan& s, bool incremental, hipStream_t st)
 {
-    if (n_steps <= 0) return hipSuccess;
+    if (s.n_steps <= 0) return hipSuccess;
     if (!mh_chain_big_available(V, M.n_nodes, M.n_prop, M.batch)) return hipErrorInvalidValue;
-    if (!incremental) {                                      // (every proposal through the full sweep)
-        MvnDev V0 = V;
-        V0.Wc = nullptr;
-        switch (V.R) {
-        case 1: return launch_big_mode<1>(M, V0, T, P, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, st);
-        case 2: return launch_big_mode<2>(M, V0, T, P, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, st);
-        case 3: return launch_big_mode<3>(M, V0, T, P, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, st);
-        case 4: return launch_big_mode<4>(M, V0, T, P, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, st);
-        default: return hipErrorInvalidValue;
-        }
-    }
+    MvnDev V0 = V;
+    if (!incremental) V0.Wc = nullptr;                       // (every proposal through the full sweep)
     switch (V.R) {
-    case 1: return launch_big_mode<1>(M, V, T, P, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, st);       // (65 and 66 nodes: one more than the small-tree kernel holds)
-    case 2: return launch_big_mode<2>(M, V, T, P, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, st);
-    case 3: return launch_big_mode<3>(M, V, T, P, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, st);
-    case 4: return launch_big_mode<4>(M, V, T, P, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, st);
+    case 1: return launch_big_mode<1>(M, V0, T, P, s, st);   // (65 and 66 nodes: one more than the small-tree kernel holds)
+    case 2: return launch_big_mode<2>(M, V0, T, P, s, st);
+    case 3: return launch_big_mode<3>(M, V0, T, P, s, st);
+    case 4: return launch_big_mode<4>(M, V0, T, P, s, st);
     default: return hipErrorInvalidValue;
     }
 }

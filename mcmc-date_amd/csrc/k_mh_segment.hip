@@ -37,7 +37,7 @@
 #include "mh_segment_device.hpp"
 #include "options.h"
 
-#include <atomic>
+#include "lds_optin.hpp"
 
 namespace mcd {
 
@@ -400,52 +400,40 @@ bool mh_segment_available(const MvnFacts& V, int n_nodes, int64_t batch)
 }
 
 template <int R, bool HELP>
-static hipError_t launch_segment_RH(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const MhInc& I, const int32_t* sched,
-                                   int64_t n_steps, int32_t S, int accumulate, uint64_t step0, uint64_t seed, double* trace_alpha,
-                                   int8_t* trace_accept, int64_t gs_base, int summands_kept, const MhSegPending& Q, hipStream_t st)
+static hipError_t launch_segment_RH(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const MhInc& I, const MhSpan& s, int64_t gs_base,
+                                   int summands_kept, const MhSegPending& Q, hipStream_t st)
 {
     const size_t dynb = seg_lds_bytes(M.n_nodes, 64 * R) + seg_node_tables_bytes(M.n_nodes, 64 * R, P.n_cal, P.n_con);
-    static std::atomic<unsigned long long> allowed{0};       // more than 64 KiB of LDS has to be allowed once per device
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev)) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!((allowed.load(std::memory_order_acquire) >> dev) & 1ull)) {
-        if (hipError_t e = hipFuncSetAttribute((const void*)k_mh_segment<R, HELP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) return e;
-        allowed.fetch_or(1ull << dev, std::memory_order_release);
-    }
+    if (hipError_t e = allow_dynamic_lds<k_mh_segment<R, HELP>>(160 * 1024)) return e;   // more than 64 KiB of LDS has to be allowed once per device
     note_dynamic_lds(dynb);
-    hipLaunchKernelGGL((k_mh_segment<R, HELP>), dim3((unsigned)((M.batch + 1) / 2)), dim3(HELP ? 512 : 256), dynb, st, M, V, T, P, I, sched, n_steps, S, accumulate, step0,
-                       seed, trace_alpha, trace_accept, gs_base, summands_kept, Q);
+    hipLaunchKernelGGL((k_mh_segment<R, HELP>), dim3((unsigned)((M.batch + 1) / 2)), dim3(HELP ? 512 : 256), dynb, st, M, V, T, P, I, s.sched, s.n_steps, s.S,
+                       s.accumulate, s.step0, s.seed, s.trace_alpha, s.trace_accept, gs_base, summands_kept, Q);
     return hipGetLastError();
 }
 
 template <int R>
-static hipError_t launch_segment_R(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const MhInc& I, const int32_t* sched,
-                                   int64_t n_steps, int32_t S, int accumulate, uint64_t step0, uint64_t seed, double* trace_alpha,
-                                   int8_t* trace_accept, int64_t gs_base, int summands_kept, const MhSegPending& Q, bool prior_waves, hipStream_t st)
+static hipError_t launch_segment_R(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const MhInc& I, const MhSpan& s, int64_t gs_base,
+                                   int summands_kept, const MhSegPending& Q, bool prior_waves, hipStream_t st)
 {
-    if (!prior_waves)                                        // (the chain wave evaluates the whole ln prior)
-        return launch_segment_RH<R, false>(M, V, T, P, I, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, gs_base, summands_kept, Q, st);
-    return launch_segment_RH<R, true>(M, V, T, P, I, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, gs_base, summands_kept, Q, st);
+    if (!prior_waves) return launch_segment_RH<R, false>(M, V, T, P, I, s, gs_base, summands_kept, Q, st);   // (the chain wave evaluates the whole ln prior)
+    return launch_segment_RH<R, true>(M, V, T, P, I, s, gs_base, summands_kept, Q, st);
 }
 
-// steps [0, n_steps) of `sched` (device memory), none of which moves more than kSegList distances; step0 = the step number of
-// sched[0], gs_base its position in the run's schedule (iterations close at multiples of S); summands_kept: MhDev::psum holds the
-// current states' summands; Q: the dense proposal whose likelihood has been evaluated and which is decided here (p_acc < 0: none), the one
+// the steps of the span s, none of which moves more than kSegList distances; gs_base: the position of s.sched[0] in the run's schedule
+// (iterations close at multiples of S); summands_kept: MhDev::psum holds the current states' summands; Q: the dense proposal whose likelihood has been evaluated and which is decided here (p_acc < 0: none), the one
 // the segment proposes after its last step (p_tail < 0: none), how the chain wave draws ahead; prior_waves: the kernel with its prior waves
-hipError_t launch_mh_segment(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const MhInc& I, const int32_t* sched,
-                             int64_t n_steps, int32_t S, int accumulate, uint64_t step0, uint64_t seed, double* trace_alpha, int8_t* trace_accept,
-                             int64_t gs_base, int summands_kept, const MhSegPending& Q, bool prior_waves, hipStream_t st)
+hipError_t launch_mh_segment(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const MhInc& I, const MhSpan& s, int64_t gs_base,
+                             int summands_kept, const MhSegPending& Q, bool prior_waves, hipStream_t st)
 {
-    if (n_steps <= 0) return Q.p_acc >= 0 ? hipErrorInvalidValue : hipSuccess;
+    if (s.n_steps <= 0) return Q.p_acc >= 0 ? hipErrorInvalidValue : hipSuccess;
     if (Q.p_acc >= 0 && (Q.X1 == nullptr || (Q.z_in_zprop ? I.zprop == nullptr : I.zt == nullptr) || !summands_kept)) return hipErrorInvalidValue;
     if (Q.p_tail >= M.n_prop || (Q.p_tail >= 0 && (Q.X1_tail == nullptr || M.psum == nullptr || M.psel == nullptr))) return hipErrorInvalidValue;
-    if (n_steps > (1 << 28)) return hipErrorInvalidValue;    // (the hand-over words count steps in 30 bits)
+    if (s.n_steps > (1 << 28)) return hipErrorInvalidValue;  // (the hand-over words count steps in 30 bits)
     if (!mh_segment_available(V, M.n_nodes, M.batch) || I.X0 == nullptr || I.zcur == nullptr || I.NPz != 64 * V.R) return hipErrorInvalidValue;
-    if (V.R == 6) return launch_segment_R<6>(M, V, T, P, I, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, gs_base, summands_kept, Q, prior_waves, st);
-    if (V.R == 8) return launch_segment_R<8>(M, V, T, P, I, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, gs_base, summands_kept, Q, prior_waves, st);
-    if (V.R == 12) return launch_segment_R<12>(M, V, T, P, I, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, gs_base, summands_kept, Q, prior_waves, st);
-    return launch_segment_R<16>(M, V, T, P, I, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, gs_base, summands_kept, Q, prior_waves, st);
+    if (V.R == 6) return launch_segment_R<6>(M, V, T, P, I, s, gs_base, summands_kept, Q, prior_waves, st);
+    if (V.R == 8) return launch_segment_R<8>(M, V, T, P, I, s, gs_base, summands_kept, Q, prior_waves, st);
+    if (V.R == 12) return launch_segment_R<12>(M, V, T, P, I, s, gs_base, summands_kept, Q, prior_waves, st);
+    return launch_segment_R<16>(M, V, T, P, I, s, gs_base, summands_kept, Q, prior_waves, st);
 }
 
 }  // namespace mcd

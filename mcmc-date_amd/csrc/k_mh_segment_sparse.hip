@@ -25,7 +25,7 @@
 #include "mh_segment_device.hpp"
 #include "options.h"
 
-#include <atomic>
+#include "lds_optin.hpp"
 
 namespace mcd {
 
@@ -512,49 +512,40 @@ bool mh_segment_sparse_available(const SparseFacts& Sp, int n_nodes, int64_t bat
 int mh_segment_sparse_list() { return kSsegList; }
 
 template <int CPW, bool HELP>
-static hipError_t launch_sseg(const MhDev& M, const SparseDev& Sp, const TreeDev& T, const PriorDev& P, const MhInc& I, const int32_t* sched, int64_t n_steps,
-                              int32_t S, int accumulate, uint64_t step0, uint64_t seed, double* trace_alpha, int8_t* trace_accept, int64_t gs_base,
+static hipError_t launch_sseg(const MhDev& M, const SparseDev& Sp, const TreeDev& T, const PriorDev& P, const MhInc& I, const MhSpan& s, int64_t gs_base,
                               int summands_kept, const MhSegPending& Q, int size_in_lds, int list_all, hipStream_t st)
 {
     const int np = (Sp.n + 63) / 64 * 64;
     const size_t dynb = sseg_lds_bytes(M.n_nodes, np, CPW, size_in_lds) + sseg_node_tables_bytes(M.n_nodes, np, CPW, size_in_lds, P.n_cal, P.n_con);
-    static std::atomic<unsigned long long> allowed{0};       // more than 64 KiB of LDS has to be allowed once per device
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev)) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!((allowed.load(std::memory_order_acquire) >> dev) & 1ull)) {
-        if (hipError_t e = hipFuncSetAttribute((const void*)k_mh_segment_sparse<CPW, HELP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSsegLdsMax)) return e;
-        allowed.fetch_or(1ull << dev, std::memory_order_release);
-    }
+    if (hipError_t e = allow_dynamic_lds<k_mh_segment_sparse<CPW, HELP>>((int)kSsegLdsMax)) return e;   // more than 64 KiB of LDS has to be allowed once per device
     note_dynamic_lds(dynb);
-    hipLaunchKernelGGL((k_mh_segment_sparse<CPW, HELP>), dim3((unsigned)((M.batch + CPW - 1) / CPW)), dim3(64 * CPW * (HELP ? 4 : 2)), dynb, st, M, Sp, T, P, I, sched, n_steps, S, accumulate,
-                       step0, seed, trace_alpha, trace_accept, gs_base, summands_kept, Q, size_in_lds, list_all);
+    hipLaunchKernelGGL((k_mh_segment_sparse<CPW, HELP>), dim3((unsigned)((M.batch + CPW - 1) / CPW)), dim3(64 * CPW * (HELP ? 4 : 2)), dynb, st, M, Sp, T, P, I, s.sched,
+                       s.n_steps, s.S, s.accumulate, s.step0, s.seed, s.trace_alpha, s.trace_accept, gs_base, summands_kept, Q, size_in_lds, list_all);
     return hipGetLastError();
 }
 
-// steps [0, n_steps) of `sched` (device memory), none of which moves more than kSsegList distances; I: X0 = the current distances
+// the steps of the span s, none of which moves more than kSsegList distances; I: X0 = the current distances
 // [batch][n], zcur / zprop = the quadratic forms q [batch] of the current states / of the pending dense proposal (NPz = 1); list_all:
-// the tree's distance slots all fit the list, so a proposal that moves tH or rMu (every distance) may be part of a segment; Q and
+// the tree's distance slots all fit the list, so a proposal that moves tH or rMu (every distance) may be part of a segment; gs_base, Q and
 // prior_waves as for launch_mh_segment
-hipError_t launch_mh_segment_sparse(const MhDev& M, const SparseDev& Sp, const TreeDev& T, const PriorDev& P, const MhInc& I, const int32_t* sched,
-                                    int64_t n_steps, int32_t S, int accumulate, uint64_t step0, uint64_t seed, double* trace_alpha, int8_t* trace_accept,
+hipError_t launch_mh_segment_sparse(const MhDev& M, const SparseDev& Sp, const TreeDev& T, const PriorDev& P, const MhInc& I, const MhSpan& s,
                                     int64_t gs_base, int summands_kept, const MhSegPending& Q, int list_all, bool prior_waves, hipStream_t st)
 {
-    if (n_steps <= 0) return Q.p_acc >= 0 ? hipErrorInvalidValue : hipSuccess;
+    if (s.n_steps <= 0) return Q.p_acc >= 0 ? hipErrorInvalidValue : hipSuccess;
     if (Q.p_acc >= 0 && (Q.X1 == nullptr || I.zprop == nullptr || !summands_kept)) return hipErrorInvalidValue;
     if (Q.p_tail >= M.n_prop || (Q.p_tail >= 0 && (Q.X1_tail == nullptr || M.psum == nullptr || M.psel == nullptr))) return hipErrorInvalidValue;
     // (a slot's mark is tag << 8 in an int32, the tags 2 (step + 1) + pass of the steps 0 .. n_steps - 1: the largest, 2 n_steps + 1, must stay
     // below 2^23)
-    if (n_steps >= (1 << 22)) return hipErrorInvalidValue;
+    if (s.n_steps >= (1 << 22)) return hipErrorInvalidValue;
     if (!mh_segment_sparse_available(Sp, M.n_nodes, M.batch) || I.X0 == nullptr || I.zcur == nullptr || I.NPz != 1) return hipErrorInvalidValue;
     if (list_all && Sp.n > kSsegList) return hipErrorInvalidValue;
     int cpw = 0, sz = 0;
     sseg_geometry(M.n_nodes, (Sp.n + 63) / 64 * 64, cpw, sz);
     const bool help = prior_waves;
-    if (cpw == 2 && help) return launch_sseg<2, true>(M, Sp, T, P, I, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, gs_base, summands_kept, Q, sz, list_all, st);
-    if (cpw == 2) return launch_sseg<2, false>(M, Sp, T, P, I, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, gs_base, summands_kept, Q, sz, list_all, st);
-    if (help) return launch_sseg<1, true>(M, Sp, T, P, I, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, gs_base, summands_kept, Q, sz, list_all, st);
-    return launch_sseg<1, false>(M, Sp, T, P, I, sched, n_steps, S, accumulate, step0, seed, trace_alpha, trace_accept, gs_base, summands_kept, Q, sz, list_all, st);
+    if (cpw == 2 && help) return launch_sseg<2, true>(M, Sp, T, P, I, s, gs_base, summands_kept, Q, sz, list_all, st);
+    if (cpw == 2) return launch_sseg<2, false>(M, Sp, T, P, I, s, gs_base, summands_kept, Q, sz, list_all, st);
+    if (help) return launch_sseg<1, true>(M, Sp, T, P, I, s, gs_base, summands_kept, Q, sz, list_all, st);
+    return launch_sseg<1, false>(M, Sp, T, P, I, s, gs_base, summands_kept, Q, sz, list_all, st);
 }
 
 }  // namespace mcd

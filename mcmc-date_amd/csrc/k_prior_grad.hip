@@ -19,7 +19,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include <atomic>
+#include "lds_optin.hpp"
 
 #include "mvn_kernels.h"
 #include "prior_device.hpp"
@@ -338,18 +338,8 @@ hipError_t launch_prior_grad(const PriorDev& P, const double* birth, const doubl
     if (batch <= 0) return hipSuccess;
     if (P.n_nodes > kPriorGradMaxNodes) return hipErrorInvalidValue;      // (mcd_prior_grad_batch and mcd_hmc_create* refuse by the same constant)
     const size_t bytes = sizeof(double) * (7 * (size_t)P.n_nodes + 2);
-    if (bytes > 64 * 1024) {                                 // more than 64 KiB of LDS (from 1170 nodes) has to be allowed once per device
-        static std::atomic<unsigned long long> allowed{0};
-        int dev = 0;
-        if (hipError_t e = hipGetDevice(&dev)) return e;
-        if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-        if (!((allowed.load(std::memory_order_acquire) >> dev) & 1ull)) {
-            if (hipError_t e = hipFuncSetAttribute((const void*)k_prior_grad, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)(sizeof(double) * (7 * (size_t)kPriorGradMaxNodes + 2))))
-                return e;
-            allowed.fetch_or(1ull << dev, std::memory_order_release);
-        }
-    }
+    if (bytes > 64 * 1024)                                   // more than 64 KiB of LDS (from 1170 nodes) has to be allowed once per device
+        if (hipError_t e = allow_dynamic_lds<k_prior_grad>((int)(sizeof(double) * (7 * (size_t)kPriorGradMaxNodes + 2)))) return e;
     // waves per chain: as many as the tree has 64-node slices (at most 4) while the whole batch is resident at once (2 waves
     // per SIMD: 2048 on the chip); beyond that more waves per chain only add rounds (4096 chains x 255 nodes: 115 us with one
     // wave per chain, 143 with four)

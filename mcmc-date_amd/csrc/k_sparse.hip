@@ -24,7 +24,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <atomic>
+#include "lds_optin.hpp"
 
 #include "mvn_kernels.h"
 #include "options.h"
@@ -305,16 +305,8 @@ static hipError_t launch_quad_C(const SparseDev& S, const SparseTreeDev& T, cons
                                 int64_t batch, double* ll, double* logjac, double* qout, hipStream_t st)
 {
     const size_t lds = sparse_quad_lds(S.n, C);
-    if (lds > 64 * 1024) {                                   // more than 64 KiB of LDS has to be allowed once per device
-        static std::atomic<unsigned long long> allowed{0};
-        int dev = 0;
-        if (hipError_t e = hipGetDevice(&dev)) return e;
-        if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-        if (!((allowed.load(std::memory_order_acquire) >> dev) & 1ull)) {
-            if (hipError_t e = hipFuncSetAttribute((const void*)k_sparse_quad<C, TREE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) return e;
-            allowed.fetch_or(1ull << dev, std::memory_order_release);
-        }
-    }
+    if (lds > 64 * 1024)                                     // more than 64 KiB of LDS has to be allowed once per device
+        if (hipError_t e = allow_dynamic_lds<k_sparse_quad<C, TREE>>(160 * 1024)) return e;
     hipLaunchKernelGGL((k_sparse_quad<C, TREE>), dim3((unsigned)((batch + C - 1) / C)), dim3(256), lds, st, S, T, X, Rt, ld, tH, rMu, batch, ll, logjac, qout);
     return hipGetLastError();
 }

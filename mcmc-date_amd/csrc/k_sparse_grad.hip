@@ -25,7 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <atomic>
+#include "lds_optin.hpp"
 
 #include "mvn_kernels.h"
 #include "options.h"
@@ -184,18 +184,8 @@ hipError_t launch_grad_C(const SparseDev& S, const SparseTreeDev& T, const doubl
                          int64_t batch, double* ll, double* gH, double* gR, double* gtH, double* grMu, hipStream_t st)
 {
     const size_t lds = sparse_grad_lds(S.n, T.n_nodes, C);
-    if (lds > 64 * 1024) {                                   // more than 64 KiB of LDS has to be allowed once per device
-        static std::atomic<unsigned long long> allowed{0};
-        int dev = 0;
-        if (hipError_t e = hipGetDevice(&dev)) return e;
-        if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-        if (!((allowed.load(std::memory_order_acquire) >> dev) & 1ull)) {
-            if (hipError_t e = hipFuncSetAttribute((const void*)k_sparse_tree_grad<C>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)sparse_grad_lds(kSparseGradMaxNodes - 2, kSparseGradMaxNodes, C)))
-                return e;
-            allowed.fetch_or(1ull << dev, std::memory_order_release);
-        }
-    }
+    if (lds > 64 * 1024)                                     // more than 64 KiB of LDS has to be allowed once per device
+        if (hipError_t e = allow_dynamic_lds<k_sparse_tree_grad<C>>((int)sparse_grad_lds(kSparseGradMaxNodes - 2, kSparseGradMaxNodes, C))) return e;
     hipLaunchKernelGGL((k_sparse_tree_grad<C>), dim3((unsigned)((batch + C - 1) / C)), dim3(256), lds, st, S, T, H, Rt, ld, tH, rMu, batch, ll, gH, gR, gtH,
                        grMu);
     return hipGetLastError();

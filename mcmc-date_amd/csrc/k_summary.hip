@@ -10,11 +10,11 @@
 //   k_sum_final    combines all of it per quantity
 // Lanes = 64 consecutive quantities everywhere: a wave's load of one (sample, chain) is one contiguous 512-byte row.
 #include <hip/hip_runtime.h>
-
 #include <cmath>
 #include <cstdint>
 #include <limits>
 
+#include "lds_optin.hpp"
 #include "mvn_kernels.h"
 #include "summary_device.hpp"
 
@@ -418,12 +418,12 @@ hipError_t launch_summary(const SumSrc& S, int max_lag, double* work, double* d_
     const double lf = (double)l;
     const int64_t i_ci = (int64_t)floor(lf * 0.025), n_ci = (int64_t)floor(lf * 0.95);
     static const size_t sel_lds = 2 * 256 * 64 * sizeof(uint32_t), acov_lds = (size_t)kAcovRows * 64 * sizeof(double);
-    if (hipError_t e = hipFuncSetAttribute((const void*)k_sum_select, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_lds)) return e;
+    if (hipError_t e = allow_dynamic_lds<k_sum_select>((int)sel_lds)) return e;
     hipLaunchKernelGGL(k_sum_select, dim3((unsigned)G), dim3(64 * kSelWaves), sel_lds, st, S, W, (uint32_t)i_ci, (uint32_t)(i_ci + n_ci - 1));
     const int64_t chunks = summary_chunks(S.B, S.Q);
     if (n_lags > 0 && S.n / 2 >= 2) {
         const int64_t per = (2 * S.B + chunks - 1) / chunks;
-        if (hipError_t e = hipFuncSetAttribute((const void*)k_sum_acov, hipFuncAttributeMaxDynamicSharedMemorySize, (int)acov_lds)) return e;
+        if (hipError_t e = allow_dynamic_lds<k_sum_acov>((int)acov_lds)) return e;
         hipLaunchKernelGGL(k_sum_acov, dim3((unsigned)G, (unsigned)chunks), dim3(256), acov_lds, st, S, W, n_lags, per);
     }
     hipLaunchKernelGGL(k_sum_final, dim3((unsigned)G), dim3(64), 0, st, S, W, (n_lags > 0 && S.n / 2 >= 2) ? max_lag : 0, chunks, d_pooled, d_per_chain);

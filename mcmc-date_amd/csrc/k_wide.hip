@@ -18,7 +18,7 @@
 //   * with 16 or 32 chains per workgroup the kernel stays within 128 VGPRs and 68 KiB of LDS, so two workgroups share
 //     a CU: while one stages its chunk (a cold trip to HBM) the other keeps the matrix pipe busy.
 #include "wide_device.hpp"
-#include <atomic>
+#include "lds_optin.hpp"
 
 namespace mcd {
 
@@ -109,15 +109,7 @@ template <int CT, bool TREE>
 static hipError_t allow_lds()
 {
     constexpr size_t bytes = (size_t)(CT * 16 * WD_LD + WD_WAVES * CT * 16 + CT * 16) * sizeof(double);
-    static std::atomic<bool> allowed[64];
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev)) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!allowed[dev].load(std::memory_order_acquire)) {
-        if (hipError_t e = hipFuncSetAttribute((const void*)k_wide<CT, TREE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)) return e;
-        allowed[dev].store(true, std::memory_order_release);
-    }
-    return hipSuccess;
+    return allow_dynamic_lds<k_wide<CT, TREE>>((int)bytes);
 }
 
 template <int CT, bool TREE>

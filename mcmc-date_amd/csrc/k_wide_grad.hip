@@ -14,7 +14,7 @@
 // runs on the LDS copy: e[v] = s g[slot(v)] r_v is scattered into the same rows by node id, then every node gathers its
 // children.
 #include "wide_device.hpp"
-#include <atomic>
+#include "lds_optin.hpp"
 
 namespace mcd {
 
@@ -227,15 +227,7 @@ template <int CT, bool TREE>
 static hipError_t allow_lds()
 {
     constexpr size_t bytes = (size_t)(CT * 16 * WD_LD + WD_WAVES * CT * 16 + CT * 16 + CT * 16 * 5) * sizeof(double);
-    static std::atomic<bool> allowed[64];
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev)) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!allowed[dev].load(std::memory_order_acquire)) {
-        if (hipError_t e = hipFuncSetAttribute((const void*)k_wide_grad<CT, TREE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)) return e;
-        allowed[dev].store(true, std::memory_order_release);
-    }
-    return hipSuccess;
+    return allow_dynamic_lds<k_wide_grad<CT, TREE>>((int)bytes);
 }
 
 template <int CT, bool TREE>

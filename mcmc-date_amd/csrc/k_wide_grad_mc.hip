@@ -12,7 +12,7 @@
 //             doubles per chain), every node gathers its children and overwrites the buffer row with d ll / d h_v.
 // Only the waves of one workgroup ever touch a chain's rows, ordered by workgroup barriers.
 #include "wide_device.hpp"
-#include <atomic>
+#include "lds_optin.hpp"
 
 namespace mcd {
 
@@ -233,15 +233,7 @@ template <int CT, bool TREE>
 static hipError_t allow_lds()
 {
     constexpr size_t bytes = (size_t)(CT * 16 * WD_LD + WD_WAVES * CT * 16 + CT * 16) * sizeof(double);
-    static std::atomic<bool> allowed[64];
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev)) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!allowed[dev].load(std::memory_order_acquire)) {
-        if (hipError_t e = hipFuncSetAttribute((const void*)k_wide_grad_mc<CT, TREE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)) return e;
-        allowed[dev].store(true, std::memory_order_release);
-    }
-    return hipSuccess;
+    return allow_dynamic_lds<k_wide_grad_mc<CT, TREE>>((int)bytes);
 }
 
 template <int CT, bool TREE>

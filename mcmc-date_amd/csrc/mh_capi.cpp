@@ -756,6 +756,16 @@ struct MhRun {
     }
     double* alpha(int64_t gs) const { return trace ? m->d_trace_alpha + gs * m->dev.batch : nullptr; }
     int8_t* accept(int64_t gs) const { return trace ? m->d_trace_accept + gs * m->dev.batch : nullptr; }
+    // the schedule positions [first, first + count) as one launch of a persistent kernel takes them
+    mcd::MhSpan span(int64_t first, int64_t n) const { return {m->d_sched + first, n, S, accumulate ? 1 : 0, step_base + (uint64_t)first, m->seed, alpha(first), accept(first)}; }
+    // the step launch that only proposes schedule position gs (nothing is pending, so no uniform is drawn from the step number; init: MhDev::psum
+    // does not hold the current states' summands yet), and the one that decides position gs and proposes row pn (< 0: none) for position gs + 1
+    mcd::MhStep propose(int64_t gs, bool init) const { return {-1, 0, schedule[gs], m->rows[(size_t)schedule[gs]], (int)(gs & 63), m->step, 0, nullptr, nullptr, init ? 1 : 0}; }
+    mcd::MhStep decide(int64_t gs, int pn) const
+    {
+        return {schedule[gs], m->rows[(size_t)schedule[gs]].jac_root, pn, pn >= 0 ? m->rows[(size_t)pn] : kNoRow, (int)((gs + 1) & 63), m->step,
+                (accumulate && (gs + 1) % S == 0) ? 1 : 0, alpha(gs), accept(gs), 0};
+    }
 
     // the draws of schedule positions [64 k, 64 k + 64) are computed when position 64 k is about to be proposed
     int draws_for(int64_t idx) const
@@ -811,8 +821,7 @@ int run_chain(const MhRun& r)
 {
     mcd_mh* m = r.m;
     r.rec_launch(0);
-    MHIP_TRY(mcd::launch_mh_chain(m->dev, *m->mvn, *m->tree, *m->prior, m->d_Fp, m->d_sched, r.total, r.S, r.accumulate, m->step, m->seed,
-                                  r.alpha(0), r.accept(0), r.p.likelihood_wave, m->stream));
+    MHIP_TRY(mcd::launch_mh_chain(m->dev, *m->mvn, *m->tree, *m->prior, m->d_Fp, r.span(0, r.total), r.p.likelihood_wave, m->stream));
     m->step += (uint64_t)r.total;
     if (r.accumulate) m->n_samples += r.total / r.S;
     return MCD_OK;
@@ -827,8 +836,7 @@ int run_streamed(const MhRun& r)
     for (int64_t done = 0; done < r.total; done += per_launch) {
         const int64_t now = (r.total - done < per_launch) ? r.total - done : per_launch;
         r.rec_launch(done);
-        MHIP_TRY(mcd::launch_mh_chain_big(m->dev, *m->mvn, *m->tree, *m->prior, m->d_sched + done, now, r.S, r.accumulate, m->step, m->seed,
-                                          r.alpha(done), r.accept(done), r.p.incremental, m->stream));
+        MHIP_TRY(mcd::launch_mh_chain_big(m->dev, *m->mvn, *m->tree, *m->prior, r.span(done, now), r.p.incremental, m->stream));
         m->step += (uint64_t)now;
     }
     if (r.accumulate) m->n_samples += r.total / r.S;
@@ -846,7 +854,7 @@ int run_segments(const MhRun& r)
     const int64_t total = r.total;
     if (int rc = r.begin()) return rc;
     static const mcd::MvnDev no_mvn{};                   // (k_mh_step_wg takes the incremental bookkeeping only with an MvnDev beside it)
-    const mcd::MvnDev* Vinc = m->mvn ? m->mvn : &no_mvn;
+    const mcd::MhStepRun steps{r.prior_inline, p.step_wg, r.Tx, r.n_dim, r.X1, r.n_dim, &I, m->mvn ? m->mvn : &no_mvn};
     bool summands_kept = false;                      // MhDev::psum holds the current states' summands
     int64_t draws_block = 0;                         // (begin: draws_for(0))
     auto need_draws = [&](int64_t idx) -> int {
@@ -877,13 +885,10 @@ int run_segments(const MhRun& r)
             proposed = pending.p_tail >= 0;
             r.rec_launch(0);                         // (the segment kernels count from the call's first step: gs_base + their own)
             if (p.inc_sparse)
-                MHIP_TRY(mcd::launch_mh_segment_sparse(D, *m->sp, *m->tree, *m->prior, I, m->d_sched + gs, e - gs, r.S, r.accumulate ? 1 : 0,
-                                                       r.step_base + (uint64_t)gs, m->seed, r.alpha(gs), r.accept(gs), gs, summands_kept ? 1 : 0, pending,
+                MHIP_TRY(mcd::launch_mh_segment_sparse(D, *m->sp, *m->tree, *m->prior, I, r.span(gs, e - gs), gs, summands_kept ? 1 : 0, pending,
                                                        m->list_all ? 1 : 0, p.prior_waves, m->stream));
             else
-                MHIP_TRY(mcd::launch_mh_segment(D, *m->mvn, *m->tree, *m->prior, I, m->d_sched + gs, e - gs, r.S, r.accumulate ? 1 : 0,
-                                                r.step_base + (uint64_t)gs, m->seed, r.alpha(gs), r.accept(gs), gs, summands_kept ? 1 : 0, pending,
-                                                p.prior_waves, m->stream));
+                MHIP_TRY(mcd::launch_mh_segment(D, *m->mvn, *m->tree, *m->prior, I, r.span(gs, e - gs), gs, summands_kept ? 1 : 0, pending, p.prior_waves, m->stream));
             have_pending = false;
             if (D.psum != nullptr) summands_kept = true;
             if (r.accumulate) m->n_samples += (e / r.S) - (gs / r.S);      // iterations closed by steps gs .. e - 1
@@ -899,8 +904,7 @@ int run_segments(const MhRun& r)
             I.mode = 0;
             I.prop_mode = 2;
             r.rec_step(-1);
-            MHIP_TRY(mcd::launch_mh_step(D, *m->prior, -1, 0, schedule[gs], m->rows[schedule[gs]], (int)(gs & 63), m->step, m->seed, 0, nullptr,
-                                         nullptr, r.prior_inline, p.step_wg, r.Tx, r.n_dim, r.X1, r.n_dim, m->stream, &I, Vinc, summands_kept ? 0 : 1));
+            MHIP_TRY(mcd::launch_mh_step(D, *m->prior, steps, r.propose(gs, !summands_kept), m->seed, m->stream));
             if (D.psum != nullptr) summands_kept = true;
         }
         proposed = false;
@@ -930,9 +934,7 @@ int run_segments(const MhRun& r)
             }
             I.prop_mode = 2;
             r.rec_step(gs);
-            MHIP_TRY(mcd::launch_mh_step(D, *m->prior, pa, m->rows[pa].jac_root, pn, pn >= 0 ? m->rows[pn] : kNoRow, (int)((gs + 1) & 63), m->step,
-                                         m->seed, (r.accumulate && closes) ? 1 : 0, r.alpha(gs), r.accept(gs), r.prior_inline, p.step_wg, r.Tx, r.n_dim, r.X1,
-                                         r.n_dim, m->stream, &I, Vinc, 0));
+            MHIP_TRY(mcd::launch_mh_step(D, *m->prior, steps, r.decide(gs, pn), m->seed, m->stream));
             if (refresh_now && gs + 1 < total)
                 if (int rc = r.refresh_z()) return rc;
             m->step += 1;
@@ -952,10 +954,10 @@ int run_steps(const MhRun& r)
     mcd::MhInc& I = m->inc;
     const int32_t* schedule = r.schedule;
     if (int rc = r.begin()) return rc;
+    const mcd::MhStepRun steps{r.prior_inline, r.p.step_wg, r.Tx, r.n_dim, r.X1, r.n_dim, r.inc ? &I : nullptr, m->mvn};
     I.prop_mode = r.inc ? r.inc_mode(schedule[0]) : 0;
     r.rec_step(-1);
-    MHIP_TRY(mcd::launch_mh_step(D, *m->prior, -1, 0, schedule[0], m->rows[schedule[0]], 0, m->step - 1, m->seed, 0, nullptr, nullptr,
-                                 r.prior_inline, r.p.step_wg, r.Tx, r.n_dim, r.X1, r.n_dim, m->stream, r.inc ? &I : nullptr, m->mvn));
+    MHIP_TRY(mcd::launch_mh_step(D, *m->prior, steps, r.propose(0, true), m->seed, m->stream));
     for (int64_t gs = 0; gs < r.total; ++gs) {
         const int pa = schedule[gs];
         if (r.inc) {
@@ -983,9 +985,7 @@ int run_steps(const MhRun& r)
         const bool refresh_now = r.inc && ((gs + 1) & 255) == 0;
         I.prop_mode = r.inc ? r.inc_mode(pn) : 0;
         r.rec_step(gs);
-        MHIP_TRY(mcd::launch_mh_step(D, *m->prior, pa, m->rows[pa].jac_root, pn, pn >= 0 ? m->rows[pn] : kNoRow, (int)((gs + 1) & 63), m->step,
-                                     m->seed, (r.accumulate && closes) ? 1 : 0, r.alpha(gs), r.accept(gs), r.prior_inline, r.p.step_wg, r.Tx, r.n_dim,
-                                     r.X1, r.n_dim, m->stream, r.inc ? &I : nullptr, m->mvn));
+        MHIP_TRY(mcd::launch_mh_step(D, *m->prior, steps, r.decide(gs, pn), m->seed, m->stream));
         if (refresh_now)                                 // (X0 is exact; z has been updated column by column since the last full product)
             if (int rc = r.refresh_z()) return rc;
         m->step += 1;

@@ -228,6 +228,20 @@ struct Mc3Dev {
     unsigned long long *tried, *accepted;   // [n_chains - 1] swaps between the ranks i and i + 1
 };
 
+// A run of consecutive schedule positions handed to ONE launch of a persistent Metropolis-Hastings kernel (k_mh_chain, k_mh_chain_big,
+// k_mh_segment, k_mh_segment_sparse): what their launchers share.  mh_capi.cpp builds it in one place (MhRun::span); the launchers pass it
+// on untouched and unpack it only into the kernel's arguments.
+struct MhSpan {
+    const int32_t* sched;      // [n_steps] proposal rows (device), the span's first position at [0]
+    int64_t n_steps;
+    int32_t S;                 // steps per iteration of the cycle
+    int accumulate;            // 0 / 1: the node ages of every closed iteration go into the running sums
+    uint64_t step0;            // step number of sched[0] (the random streams' counter)
+    uint64_t seed;
+    double* trace_alpha;       // [n_steps][batch] from the span's first position, or null
+    int8_t* trace_accept;
+};
+
 // Incremental likelihood of the two-launch Metropolis-Hastings path on large trees (k_mh_inc.hip): distances and z = L^-1 (d - mu) of
 // every chain's CURRENT state, z' of the pending proposal; mode = how the pending proposal's z' reaches zcur when it is accepted.
 struct MhInc {
@@ -262,12 +276,10 @@ bool mh_segment_available(const MvnFacts& V, int n_nodes, int64_t batch);
 // forms q [batch] of the current states / of the pending dense proposal (NPz = 1)
 bool mh_segment_sparse_available(const SparseFacts& Sp, int n_nodes, int64_t batch);
 int mh_segment_sparse_list();      // moved distances of one proposal at most
-hipError_t launch_mh_segment_sparse(const MhDev& M, const SparseDev& Sp, const TreeDev& T, const PriorDev& P, const MhInc& I, const int32_t* sched,
-                                    int64_t n_steps, int32_t S, int accumulate, uint64_t step0, uint64_t seed, double* trace_alpha, int8_t* trace_accept,
+hipError_t launch_mh_segment_sparse(const MhDev& M, const SparseDev& Sp, const TreeDev& T, const PriorDev& P, const MhInc& I, const MhSpan& span,
                                     int64_t gs_base, int summands_kept, const MhSegPending& pending, int list_all, bool prior_waves, hipStream_t st);
-hipError_t launch_mh_segment(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const MhInc& I, const int32_t* sched,
-                             int64_t n_steps, int32_t S, int accumulate, uint64_t step0, uint64_t seed, double* trace_alpha, int8_t* trace_accept,
-                             int64_t gs_base, int summands_kept, const MhSegPending& pending, bool prior_waves, hipStream_t st);
+hipError_t launch_mh_segment(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const MhInc& I, const MhSpan& span, int64_t gs_base,
+                             int summands_kept, const MhSegPending& pending, bool prior_waves, hipStream_t st);
 hipError_t launch_mh_inc_init(const MhDev& M, const TreeDev& T, const MhInc& I, int n_dim, int64_t ldx, hipStream_t st);   // X0 from the current states
 hipError_t launch_mh_inc_take_z(const MhInc& I, double* dst, int64_t b0, int64_t count, hipStream_t st);                 // dst[b0 ..] <- zt of `count` chains
 
@@ -385,13 +397,33 @@ struct MhRow {
     int kind, node, n1, n2, jac_root;
     double p0, p1;
 };
-// accept the pending step of proposal p_acc (< 0: none) and propose proposal p_prop (< 0: none) with the ln prior of its proposed state
-hipError_t launch_mh_step(const MhDev& M, const PriorDev& P, int p_acc, int jac_root_acc, int p_prop, const MhRow& row_prop, int draw_slot,
-                          uint64_t step_acc, uint64_t seed, int accumulate_now, double* trace_alpha, int8_t* trace_accept, int prior_inline,
-                          bool wg, const TreeDev* T, int n_dim, double* X1, int64_t ldx, hipStream_t st, const MhInc* inc = nullptr, const MvnDev* V = nullptr,
-                          int summands_init = -1);   // 1: MhDev::psum does not hold the current states' summands yet (-1: when nothing is pending)
-// wg: the workgroup-per-chain kernel, which can also leave the proposed states' distances in X1 [batch][ldx] (T, n_dim, X1 given) for a
-// plain-vector likelihood launch; it exists for the trees where mh_step_wg_fits(n_nodes)
+// launch_mh_step: accept the pending step of proposal p_acc (< 0: none) and propose proposal p_prop (< 0: none) with the ln prior of its
+// proposed state.  MhStepRun: what every step launch of one run shares.  wg: the workgroup-per-chain kernel, which can also leave the proposed
+// states' distances in X1 [batch][ldx] (T, n_dim, X1 given) for a plain-vector likelihood launch -- with inc and V beside them it keeps the
+// incremental likelihood's bookkeeping; it exists for the trees where mh_step_wg_fits(n_nodes)
+struct MhStepRun {
+    int prior_inline;
+    bool wg;
+    const TreeDev* T;
+    int n_dim;
+    double* X1;
+    int64_t ldx;
+    const MhInc* inc;
+    const MvnDev* V;
+};
+// ... and what one launch has of its own
+struct MhStep {
+    int p_acc, jac_root_acc;
+    int p_prop;
+    MhRow row;                 // of p_prop
+    int draw_slot;             // the proposal's draws in MhDev::draws
+    uint64_t step_acc;         // step number of the pending step (the acceptance uniform's stream)
+    int accumulate_now;        // the pending step closes an iteration: the node ages go into the running sums
+    double* trace_alpha;       // [batch] or null: of the pending step
+    int8_t* trace_accept;
+    int summands_init;         // 1: MhDev::psum does not hold the current states' summands yet
+};
+hipError_t launch_mh_step(const MhDev& M, const PriorDev& P, const MhStepRun& run, const MhStep& s, uint64_t seed, hipStream_t st);
 bool mh_step_wg_fits(int n_nodes);
 hipError_t launch_mh_tune(const MhDev& M, hipStream_t st);
 // `count` samples of the recorder's ring from slot `first` on, into the sample-major arrays that mcd_mh_record_fetch hands out (device
@@ -429,15 +461,13 @@ hipError_t launch_mh_draws(const MhDev& M, const int32_t* sched, int64_t idx0, i
 // the factor streamed through the sweep's LDS ring once per step
 bool mh_chain_big_available(const MvnFacts& V, int n_nodes, int n_prop, int64_t batch);
 // incremental: the proposals that move few distances by columns of L^-1 on a kept z (else every one through the full sweep)
-hipError_t launch_mh_chain_big(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const int32_t* sched, int64_t n_steps,
-                               int32_t S, int accumulate, uint64_t step0, uint64_t seed, double* trace_alpha, int8_t* trace_accept,
-                               bool incremental, hipStream_t st);
+hipError_t launch_mh_chain_big(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const MhSpan& span, bool incremental,
+                               hipStream_t st);
 // whole schedule in one launch (k_mh_chain.hip); needs n_nodes <= 64 and mh_chain_lds_bytes(...) <= 64 KB; likelihood_wave: below 1024
 // chains a second wave per chain evaluates the likelihood beside the prior (else one wave per chain, the same bits)
 size_t mh_chain_lds_bytes(int n, int n_prop, int wpb);
-hipError_t launch_mh_chain(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const double* Fp,
-                           const int32_t* sched, int64_t n_steps, int32_t S, int accumulate, uint64_t step0, uint64_t seed,
-                           double* trace_alpha, int8_t* trace_accept, bool likelihood_wave, hipStream_t st);
+hipError_t launch_mh_chain(const MhDev& M, const MvnDev& V, const TreeDev& T, const PriorDev& P, const double* Fp, const MhSpan& span,
+                           bool likelihood_wave, hipStream_t st);
 
 }  // namespace mcd
 

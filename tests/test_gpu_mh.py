@@ -400,6 +400,68 @@ def test_streaming_chain_kernel_over_many_steps_against_the_twin(gpu):
     assert np.allclose(smp.posterior()[:, 1], twin.post[:, 1], rtol=1e-10, atol=0)
 
 
+@pytest.mark.parametrize("incremental", ["0", "1"])
+def test_streaming_chain_kernel_second_launch_of_a_long_call(gpu, incremental, knobs):
+    """A call of more than 65 536 steps is cut into launches of whole iterations (mh_capi.cpp: run_streamed); from the second launch on the
+    schedule, the step counter, the traces and the recorder start at non-zero offsets.  65 nodes (the smallest tree the streaming kernel
+    takes) x 3 chains (one workgroup half empty), total steps > 65 536 + S, traced, accumulated, recorded at a coarse period: the whole
+    schedule in one call against the same schedule in two calls cut at an iteration that is no launch boundary (every launch of those two
+    starts at offset zero of its call).  MCD_MH_INCREMENTAL=0 (every proposal through the full sweep): bit-identical traces, states,
+    posteriors, tuning counters and recorded samples; the age sums are formed per call and then added, so they agree to 1e-13 relative
+    (test_streaming_chain_kernel_equals_two_launch_path's rule).  Default: the kept z = L^-1 (d - mu) is recomputed in full at the start of
+    a launch and every 256 steps from there, so where the launches start decides the roundings of the ln likelihood -- that test's rule for
+    this mode: ln acceptance ratios within the twin's tolerance, ln likelihoods to 1e-12, everything else still the same bits."""
+    from mcmc_date_amd import synthetic as S
+
+    knobs.setenv("MCD_MH_INCREMENTAL", incremental)
+    exact = incremental == "0"
+    B, period = 3, 8
+    topo = S.random_topology(33, seed=71)
+    assert topo.n_nodes == 65
+    mu, sigma = S.random_spd_problem(topo.n_nodes - 2, seed=71)
+    s0 = S.random_states(topo, B, seed=72)
+    s0.time_birth_rate = np.full(B, 1.0); s0.time_death_rate = np.full(B, 0.8); s0.rate_variance = np.full(B, 0.3)
+    cal = [M.Calibration("root", 0, 0.9, 0.025, 1.1, 0.025)]
+    ps, _ = M.proposals(topo, [], calibrations_available=True)
+    steps = M.cycle_schedule(ps, 1, np.random.default_rng(0)).shape[1]
+    per_launch = 65536 // steps                              # iterations of a full launch
+    n_iter = per_launch + period                             # the second launch closes `period` iterations: it records a sample
+    assert per_launch >= 4 and n_iter * steps > 65536 + steps and (n_iter // period) * period > per_launch
+    sched = M.cycle_schedule(ps, n_iter, np.random.default_rng(1))
+    cut = per_launch // 2 + 1                                # both parts fit one launch each; the cut is not where the one call is cut
+    assert 0 < cut < per_launch and n_iter - cut <= per_launch
+    runs = []
+    for parts in ([sched], [sched[:cut], sched[cut:]]):
+        lik = M.MvnLikelihood.from_covariance(mu, sigma).bind_tree(topo)
+        smp = M.Sampler(lik, M.PriorFunction(1.0, "UncorrelatedGamma", cal, [], [], topo), ps, B, seed=13)
+        smp.set_state(s0)
+        tol = 1e-8 + 1e-12 * np.abs(smp.posterior()[:, :2]).max()
+        smp.record_begin(period, n_iter // period + 1)
+        traces = [smp.run_schedule(part, accumulate=True, trace=True) for part in parts]
+        assert smp.last_path().startswith("whole schedule in one launch, two chains per workgroup"), smp.last_path()
+        rec = smp.record_fetch()
+        smp.record_end()
+        runs.append((np.concatenate([t[0] for t in traces]), np.concatenate([t[1] for t in traces]), smp.state(), smp.posterior(), smp.tuning(),
+                     smp.age_sums(), rec))
+    (a1, k1, s1, p1, t1, g1, r1), (a2, k2, s2, p2, t2, g2, r2) = runs
+    assert a1.shape == (n_iter * steps, B) and np.array_equal(k1, k2) and 0.02 < k1.mean() < 0.98
+    fin = np.isfinite(a2)
+    assert np.array_equal(np.isfinite(a1), fin)
+    post1, post2 = r1[4], r2[4]                              # recorded [n, B, 3]: ln prior, ln likelihood, ln jacobianRootBranch
+    if exact:
+        assert np.array_equal(a1, a2, equal_nan=True) and np.array_equal(p1, p2) and np.array_equal(post1, post2)
+    else:
+        assert alpha_close(a1[fin], a2[fin], tol), np.max(np.abs(a1[fin] - a2[fin]))
+        for x, y in ((p1, p2), (post1.reshape(-1, 3), post2.reshape(-1, 3))):
+            assert np.array_equal(x[:, [0, 2]], y[:, [0, 2]]) and np.allclose(x[:, 1], y[:, 1], rtol=1e-12, atol=tol)
+    for f in ("heights", "rates", "time_height", "rate_mean", "rate_variance", "time_birth_rate", "time_death_rate"):
+        assert np.array_equal(getattr(s1, f), getattr(s2, f)), f
+    assert all(np.array_equal(x, y) for x, y in zip(t1, t2))
+    assert np.array_equal(r1[0], period * np.arange(1, n_iter // period + 1))
+    assert all(np.array_equal(r1[i], r2[i]) for i in (0, 1, 2, 3, 5))
+    assert g1[2] == g2[2] == n_iter and all(np.allclose(x, y, rtol=1e-13, atol=0) for x, y in zip(g1[:2], g2[:2]))
+
+
 @pytest.mark.parametrize("n_leaves,B,n_steps", [(70, 6, 400), (128, 64, 150), (70, 2100, 24), (140, 33, 150), (150, 512, 60), (160, 64, 100),
                                                 (513, 512, 24), (513, 32, 600), (300, 16, 600), (513, 8, 3000)])
 def test_large_tree_uses_the_per_phase_path(gpu, n_leaves, B, n_steps):
