@@ -92,7 +92,10 @@ const char* mcd_last_error(void);
  * "MCD_SPLIT_SCATTER", "MCD_SPLIT_NOROT", "MCD_SPLIT_PROBE", "MCD_GEOM", "MCD_WIDE_CT", "MCD_SPARSE_QUAD", "MCD_MH_PRIOR_WAVES", "MCD_LOADERS",
  * "MCD_MH_SEG_TAIL" (0: a dense proposal after a segment is proposed by the step kernel), "MCD_MH_AHEAD_FROM" (nodes from which a segment's chain
  * wave draws the next proposal ahead of the decision), "MCD_MH_PRIOR_DRAWS" (0: no prior wave draws the next proposal's rejected branch),
- * "MCD_FSTREAM" (the column sweep's forward factor stream at 129 .. 256 dimensions: 0 = padded, 1 = compact, 2 = compact by LDS-DMA),
+ * "MCD_FSTREAM" (the column sweep's forward factor stream at 129 .. 256 dimensions: 0 = padded, 1 = compact, 2 = compact by LDS-DMA,
+ * 3 = the inverse stream -- W = L^-1 in the compact layout, z = W (x - mu) without the substitution's dependent chain; it exists for
+ * mcd_mvn_logpdf_batch at up to 512 chains, where 3 selects it under any form, and is the default there for 240 < N <= 256 at 129 .. 512
+ * chains under form auto; elsewhere 3 means the default),
  * "MCD_SPARSE_GRAD_CHAINS" (1 | 2: chains per workgroup of mcd_sparse_tree_grad_batch; the same bits); value = a decimal integer, NULL or ""
  * = back to the default.  What each knob does is said where it acts (mcd_mh_run, the forms above).  The environment variables of the same
  * names are read ONCE, when the library is loaded, as initial values -- never afterwards.  No knob changes a result beyond rounding.

@@ -140,6 +140,15 @@ void pack_compact_forward(int R, const std::vector<double>& Ft, std::vector<doub
     }
 }
 
+void pack_inverse_forward(int n, int R, const std::vector<double>& W, std::vector<double>& Fw)
+{
+    const int NP = 64 * R;
+    std::vector<double> Wp((size_t)NP * NP, 0.0);         // the padded stream's layout first: pack_compact_forward owns the compact one
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < i; ++j) Wp[packed_index(R, i, j)] = W[(size_t)i * n + j];
+    pack_compact_forward(R, Wp, Fw);
+}
+
 void invert_factor(int n, const std::vector<double>& L, std::vector<double>& W)
 {
     // rows of W one after the other: W_i: = (e_i - sum_{k<i} L_ik W_k:) / L_ii, long double accumulation
@@ -384,5 +393,26 @@ extern "C" int mcd_compact_stream_selftest_(int n, unsigned seed)
             if ((col < row && row < n) && (D[at] == 0.0 || std::fabs(D[at] - want) > 1e-15 * std::fabs(want))) return -7;
             if (!(col < row && row < n) && D[at] != 0.0) return -8;
         }
+    return mcd::fc_total_units(R);
+}
+
+// Host-only hook of the inverse stream (tests/test_inverse_stream_host.py, no GPU): packs the lower-triangular W (row-major n x n) as
+// pack_inverse_forward does into Fw, and into Fc_ref what pack_compact_forward makes of a padded stream laid out here from the same
+// matrix by the layout's definition (mvn_device.hpp, "Factor stream").  Both hold fc_total_units(R) units of 128 doubles; returns that
+// number, < 0 where no compact stream exists (R other than 3, 4).
+extern "C" int mcd_inverse_stream_pack_(int n, const double* W, double* Fw_out, double* Fc_ref)
+{
+    if (n < 1 || !W || !Fw_out || !Fc_ref) return -1;
+    const int R = (n + 63) / 64;
+    if (n > 256 || !mcd::fwd_stream_compact(R)) return -1;
+    const std::vector<double> Wv(W, W + (size_t)n * n);
+    std::vector<double> Fw, Wp((size_t)64 * R * 64 * R, 0.0), Fc;
+    mcd::pack_inverse_forward(n, R, Wv, Fw);
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < i; ++j) Wp[((((size_t)(j >> 1) * R + (i >> 6)) * 64 + (i & 63)) << 1) + (j & 1)] = Wv[(size_t)i * n + j];
+    mcd::pack_compact_forward(R, Wp, Fc);
+    if (Fw.size() != (size_t)mcd::fc_total_units(R) * 128 || Fc.size() != Fw.size()) return -2;
+    std::memcpy(Fw_out, Fw.data(), Fw.size() * sizeof(double));
+    std::memcpy(Fc_ref, Fc.data(), Fc.size() * sizeof(double));
     return mcd::fc_total_units(R);
 }

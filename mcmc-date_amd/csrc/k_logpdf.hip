@@ -7,7 +7,7 @@ namespace mcd {
 // The leading arguments are what the first memory instructions of either role need, scalars and pointers only: gfx950 preloads
 // them into SGPRs at wave launch (-mllvm -amdgpu-kernarg-preload-count, Makefile), so the loads of x and the first LDS-DMA of the
 // factor do not wait for a scalar load from a cold kernarg segment first.  14 dwords fit beside the kernarg pointer in the 16 user
-// SGPRs: F (the stream FS reads, fwd_stream_ptr) .. ncols.  ll, c and logdet are used by finish_ll only and arrive the ordinary way.
+// SGPRs: F (the stream FS reads, fwd_stream_ptr: FS = 3 is the inverse stream, mvn_device.hpp inv_apply) .. ncols.  ll, c and logdet are used by finish_ll only and arrive the ordinary way.
 template <int R, int BT, int CW, int LW, int FS>
 __global__ void __launch_bounds__(64 * (CW + LW)) k_logpdf(const double* __restrict__ F, const double* __restrict__ mu,
                                                            const double* __restrict__ invdiag, const double* __restrict__ X, int64_t ldx,
@@ -25,11 +25,20 @@ __global__ void __launch_bounds__(64 * (CW + LW)) k_logpdf(const double* __restr
     }
     const MvnView M(mu, invdiag, n, c, logdet);
     double d[R][BT];
-    load_rawx<R, BT, FS == 2>(d, M, X, ldx, b0, batch, lane);
-    MCD_T(1);
-    lds_barrier();
-    MCD_T(2);
-    fwd_compute<R, BT, 0, FS>(d, ring, lane, ncols MCD_ACC_ARGS);
+    if constexpr (FS == 3) {                               // the inverse stream: z = W (x - mu) accumulated in d, no substitution
+        double r[R][BT];
+        load_rawx_inv<R, BT>(r, d, M, X, ldx, b0, batch, lane);
+        MCD_T(1);
+        lds_barrier();
+        MCD_T(2);
+        inv_compute<R, BT, 0>(r, d, ring, lane, ncols);
+    } else {
+        load_rawx<R, BT, FS == 2>(d, M, X, ldx, b0, batch, lane);
+        MCD_T(1);
+        lds_barrier();
+        MCD_T(2);
+        fwd_compute<R, BT, 0, FS>(d, ring, lane, ncols MCD_ACC_ARGS);
+    }
     MCD_T(3);
     finish_ll<R, BT>(d, M, b0, batch, ll, lane);
     MCD_T(4);
@@ -49,9 +58,12 @@ template <int R, int BT, int CW, int LW>
 static void launch_geom(const MvnDev& M, const double* X, int64_t ldx, int64_t batch, double* ll, hipStream_t st)
 {
     if constexpr (fwd_stream_compact(R)) {
-        const int fs = fwd_stream<R>(CW);
+        constexpr bool INV = CW == 2 && BT == 1;           // the geometry the inverse stream is built for (one workgroup per CU)
+        const int fs = fwd_stream<R>(CW, INV, INV && logpdf_inverse_window(MvnFacts(M), batch));
         if (fs == 1) return launch_fs<R, BT, CW, LW, 1>(M, X, ldx, batch, ll, st);
         if (fs == 2) return launch_fs<R, BT, CW, LW, 2>(M, X, ldx, batch, ll, st);
+        if constexpr (INV)
+            if (fs == 3) return launch_fs<R, BT, CW, LW, 3>(M, X, ldx, batch, ll, st);
     }
     launch_fs<R, BT, CW, LW, 0>(M, X, ldx, batch, ll, st);
 }
@@ -101,5 +113,12 @@ extern "C" int mcd_debug_hist(unsigned long long* hist, unsigned long long* span
     if (hipMemcpyFromSymbol(hist, HIP_SYMBOL(mcd::g_hist), 64 * 8 * 8 * sizeof(unsigned long long)) != hipSuccess) return -1;
     if (hipMemcpyFromSymbol(span, HIP_SYMBOL(mcd::g_span), 64 * 64 * 2 * sizeof(unsigned long long)) != hipSuccess) return -1;
     return (int)hipMemcpyFromSymbol(n, HIP_SYMBOL(mcd::g_launch), sizeof(unsigned int));
+}
+#endif
+#if defined(MCD_STAMP_CHUNKS) && MCD_RGROUP == 0
+// ... and the per-chunk barrier stamps of workgroup 0's compute wave 0, [64][16]
+extern "C" int mcd_debug_chunks(unsigned long long* out)
+{
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(mcd::g_chunk), 64 * 16 * sizeof(unsigned long long));
 }
 #endif

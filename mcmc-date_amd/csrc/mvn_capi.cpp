@@ -133,7 +133,7 @@ struct mcd_mvn {
     int n = 0, R = 0, device = 0;
     double logdet = 0.0;
     mcd::MvnDev dev{};
-    double *d_mu = nullptr, *d_invdiag = nullptr, *d_Ft = nullptr, *d_Fc = nullptr, *d_Ut = nullptr, *d_Wt = nullptr, *d_Wtb = nullptr, *d_Wc = nullptr;
+    double *d_mu = nullptr, *d_invdiag = nullptr, *d_Ft = nullptr, *d_Fc = nullptr, *d_Fw = nullptr, *d_Ut = nullptr, *d_Wt = nullptr, *d_Wtb = nullptr, *d_Wc = nullptr;
     std::vector<double> L;  // host copy of the factor (row-major lower)
     mutable WorkspacePool pool;
     mcd::SplitHost* split = nullptr;   // k_split.hip: schedules of the row-split form + scratch sets per stream
@@ -147,6 +147,7 @@ struct mcd_mvn {
         if (d_invdiag) (void)hipFree(d_invdiag);
         if (d_Ft) (void)hipFree(d_Ft);
         if (d_Fc) (void)hipFree(d_Fc);
+        if (d_Fw) (void)hipFree(d_Fw);
         if (d_Ut) (void)hipFree(d_Ut);
         if (d_Wt) (void)hipFree(d_Wt);
         mcd::split_host_destroy(split);
@@ -273,6 +274,10 @@ int mcd_mvn_create(mcd_mvn_t** out, int n, const double* mu, const double* mat, 
         mcd::pack_compact_forward(h->R, Ft, Fc);
         HIP_TRY(hipMalloc((void**)&h->d_Fc, Fc.size() * sizeof(double)));
         HIP_TRY(hipMemcpy(h->d_Fc, Fc.data(), Fc.size() * sizeof(double), hipMemcpyHostToDevice));
+        std::vector<double> Fw;            // ... and W = L^-1 in the same layout: the inverse stream of k_logpdf (FS = 3)
+        mcd::pack_inverse_forward(n, h->R, W, Fw);
+        HIP_TRY(hipMalloc((void**)&h->d_Fw, Fw.size() * sizeof(double)));
+        HIP_TRY(hipMemcpy(h->d_Fw, Fw.data(), Fw.size() * sizeof(double), hipMemcpyHostToDevice));
     }
 
     const int ch = mcd::sweep_chunk_columns(h->R);
@@ -285,6 +290,7 @@ int mcd_mvn_create(mcd_mvn_t** out, int n, const double* mu, const double* mat, 
     h->dev.invdiag = h->d_invdiag;
     h->dev.Ft = h->d_Ft;
     h->dev.Fc = h->d_Fc;
+    h->dev.Fw = h->d_Fw;
     h->dev.Ut = h->d_Ut;
     {   // multiply form for large batches (k_wide.hip): W = L^-1 as MFMA operand tiles
         std::vector<double> Wt, Wtb;

@@ -18,7 +18,9 @@ struct MvnDev {
     const double* Ft;       // forward factor  L[i][j]/L[i][i], pair-interleaved column layout, NP*NP
     const double* Fc;       // the same factor as the compact stream of the sweep (fc_layout.hpp): no stored zeros on or above the diagonal;
                             // NULL unless fwd_stream_compact(R)
-    const double* Ut;       // backward factor L[i][r]/L[r][r], same layout, NP*NP
+    const double* Fw;       // the strictly lower triangle of W = L^-1, unscaled, in the layout of Fc (host_factor.h: pack_inverse_forward): the
+                            // inverse stream of k_logpdf (FS = 3: z = W (x - mu), no column waits for another); NULL unless fwd_stream_compact(R)
+    const double* Ut;      // backward factor L[i][r]/L[r][r], same layout, NP*NP
     const double* Wt;       // W = L^-1 as 16 x 4 MFMA operand tiles (host_factor.h: pack_w_tiles), for k_wide.hip
     const double* Wtb;      // the tiles of W^T for the gradient's second product (k_wide_grad.hip)
     const double* Wc;       // W = L^-1 column by column, [N][NP] (column j = NP doubles, zero above row j and in the padding): the
@@ -350,6 +352,7 @@ SplitHost* split_host_create(int n, const double* W_rowmajor, hipError_t* err); 
 void split_host_destroy(SplitHost* s);
 hipError_t split_release_stream(SplitHost* s, hipStream_t st);   // the stream's eager scratch set back to the pool (mcd_mvn_release_stream)
 bool use_split(const MvnFacts& M, int64_t batch);
+bool logpdf_inverse_window(const MvnFacts& M, int64_t batch);   // raw-x launch_logpdf on the sweep: the inverse stream is the default (sweep_launch.cpp)
 hipError_t launch_logpdf_split(const MvnDev& M, const double* X, int64_t ldx, int64_t batch, double* ll, hipStream_t st);
 hipError_t launch_tree_logpdf_split(const MvnDev& M, const TreeDev& T, const double* H, const double* Rt, int64_t lds, const double* tH,
                                     const double* rMu, int64_t batch, double* ll, double* logjac, hipStream_t st);

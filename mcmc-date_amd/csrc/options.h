@@ -31,7 +31,9 @@ enum Option {
     OPT_MH_AHEAD_FROM,      // nodes from which a segment kernel's chain wave draws the next proposal ahead of the decision (default: kSegAheadFrom)
     OPT_MH_PRIOR_DRAWS,     // 0: the next step's proposal is not drawn by a prior wave (the chain wave draws ahead itself from MCD_MH_AHEAD_FROM nodes; A/B, tests)
     OPT_FSTREAM,            // the column sweep's forward factor stream at 129 .. 256 dimensions: 0 = padded (Ft), register-staged; 1 = compact (Fc),
-                            // register-staged; 2 = compact, LDS-DMA (A/B, tests; fc_layout.hpp, mvn_device.hpp)
+                            // register-staged; 2 = compact, LDS-DMA; 3 = the inverse stream (W = L^-1 in the compact layout by LDS-DMA, raw-x
+                            // log-density with two compute waves only; elsewhere 3 means the geometry's default) (A/B, tests; fc_layout.hpp,
+                            // mvn_device.hpp, sweep_groups.hpp: sweep_fwd_stream)
     OPT_SPARSE_GRAD_CHAINS, // 1 | 2: chains per workgroup of the sparse tree gradient (k_sparse_grad.hip; default: 2 from 512 chains; the same bits)
     OPT_COUNT
 };

@@ -7,6 +7,7 @@
 // entry of its group; the public launch_* (sweep_launch.cpp) pick the form and hand the sweep to the group of the handle's R.
 #include <type_traits>
 
+#include "fc_layout.hpp"
 #include "mvn_kernels.h"
 #include "options.h"
 
@@ -84,6 +85,20 @@ static inline Geometry sweep_geometry(int R, int64_t batch)
     Geometry g = pick_geometry(batch);
     if (R >= 16) g.bt = 1;
     return g;
+}
+
+// The forward factor stream of a likelihood sweep with cw compute waves (mcd_set_option "MCD_FSTREAM"; mvn_device.hpp: Ring, fwd_stream):
+// 0 padded, 1 compact, 2 compact by LDS-DMA, 3 the inverse stream (k_logpdf only).  has_inverse: the launch has an FS = 3 kernel at
+// all -- raw x, two compute waves, R = 3, 4; inverse_window: ... and the call lies where it is the default (logpdf_inverse_window).
+// MCD_FSTREAM = 3 selects it wherever it exists, under any form, and means the geometry's default where it does not.
+static inline int sweep_fwd_stream(int R, int cw, bool has_inverse, bool inverse_window)
+{
+    if (!fwd_stream_compact(R)) return 0;
+    const int dflt = cw == 2 ? 2 : 0;
+    const bool inv = has_inverse && cw == 2;
+    const int f = opt_or(OPT_FSTREAM, inv && inverse_window ? 3 : dflt);
+    if (f == 3) return inv ? 3 : dflt;
+    return (f == 1 || f == 2) ? f : 0;
 }
 
 }  // namespace mcd

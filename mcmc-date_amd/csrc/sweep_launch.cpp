@@ -63,6 +63,16 @@ bool use_split(const MvnFacts& M, int64_t batch)
     return M.n > 240 && batch <= 128;
 }
 
+bool logpdf_inverse_window(const MvnFacts& M, int64_t batch)
+{
+    // Where raw-x launch_logpdf, once it is on the column sweep, streams W = L^-1 (k_logpdf FS = 3) instead of substituting: form auto
+    // only -- form "sweep" stays the substitution sweep, bit for bit -- and the headline sizes only, 240 < N <= 256 at 129 .. 512
+    // chains (measured: profiles/r12_inverse_stream_ab.txt).  Elsewhere auto keeps the substitution sweep's bits, which the gradient
+    // sweep's ll shares; inside the window the gradient takes the row split anyway.  Tree states, the prior variant and the samplers'
+    // kernels keep substitution.
+    return M.form == 0 && M.n > 240 && M.n <= 256 && batch > 128 && batch <= 512;
+}
+
 bool use_split_grad(const MvnFacts& M, int64_t batch)
 {
     // the gradient on the row-split schedule: two (tree states: three) launches over 8 row groups x batch / 16 workgroups, where
@@ -247,4 +257,24 @@ extern "C" int mcd_form_selftest_(int entry, int n, int R, int form, int split, 
     case 4: return mcd::tree_logpdf_can_carry_prior(M, batch, n + 2) ? mcd::sweep_group(R) : -1;
     default: return -2;
     }
+}
+
+// Test hook (tests/test_inverse_stream_host.py; no device, no handle): the forward factor stream a raw-x launch_logpdf takes under the
+// knobs as they stand for a handle of these facts (0 padded, 1 compact, 2 compact by LDS-DMA, 3 inverse: sweep_groups.hpp
+// sweep_fwd_stream), -1 where the column sweep does not serve the call.
+extern "C" int mcd_stream_selftest_(int n, int R, int form, int split, int wide, int64_t batch)
+{
+    mcd::MvnFacts M;
+    M.n = n;
+    M.R = R;
+    M.form = form;
+    M.split = split != 0;
+    M.wide = wide != 0;
+    M.wide_bwd = false;
+    M.cols = false;
+    const int take = mcd::logpdf_take(M, batch);
+    if (take < 0 || take >= mcd::kSweepGroups) return -1;
+    const mcd::Geometry g = mcd::sweep_geometry(R, batch);
+    const bool inv = g.cw == 2 && g.bt == 1;
+    return mcd::sweep_fwd_stream(R, g.cw, inv, inv && mcd::logpdf_inverse_window(M, batch));
 }
