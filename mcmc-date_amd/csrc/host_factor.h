@@ -21,7 +21,7 @@ void pack_factors(int n, int R, const std::vector<double>& L, std::vector<double
                   std::vector<double>& invdiag, std::vector<double>& Ft, std::vector<double>& Ut);
 // The compact forward stream (fc_layout.hpp) from the padded one: fc_total_units(R) units of 128 doubles.
 void pack_compact_forward(int R, const std::vector<double>& Ft, std::vector<double>& Fc);
-// The inverse stream Fw of the column sweep (k_logpdf.hip, FS = 3) from W = L^-1 (row-major n x n, lower triangular): entry (i, j), j < i,
+// The inverse stream Fw of the column sweep (k_logpdf.hip: k_logpdf_stripe, FS = 3) from W = L^-1 (row-major n x n, lower triangular): entry (i, j), j < i,
 // sits where Fc holds L_ij / L_ii -- fc_layout.hpp unchanged: the same chunks, diagonal-part packing and unit counts, fc_total_units(R)
 // units of 128 doubles.  The entries are UNSCALED (the kernel broadcasts the raw residual x_j - mu_j and starts row i's sum at
 // W_ii (x_i - mu_i) with W_ii = 1 / L_ii = invdiag_i: one rounding per entry fewer than storing W_ij L_jj against the scaled residual);

@@ -1,13 +1,14 @@
 // k_logpdf.hip -- batched log-density, raw x (gfx950).  Device code: mvn_device.hpp.
 // (The choice of form -- use_split, use_wide, the MCD_WIDE default -- and the public launch_logpdf live in sweep_launch.cpp.)
 #include "mvn_device.hpp"
+#include "stripe_device.hpp"
 
 namespace mcd {
 
 // The leading arguments are what the first memory instructions of either role need, scalars and pointers only: gfx950 preloads
 // them into SGPRs at wave launch (-mllvm -amdgpu-kernarg-preload-count, Makefile), so the loads of x and the first LDS-DMA of the
 // factor do not wait for a scalar load from a cold kernarg segment first.  14 dwords fit beside the kernarg pointer in the 16 user
-// SGPRs: F (the stream FS reads, fwd_stream_ptr: FS = 3 is the inverse stream, mvn_device.hpp inv_apply) .. ncols.  ll, c and logdet are used by finish_ll only and arrive the ordinary way.
+// SGPRs: F (the stream FS reads, fwd_stream_ptr) .. ncols.  ll, c and logdet are used by finish_ll only and arrive the ordinary way.
 template <int R, int BT, int CW, int LW, int FS>
 __global__ void __launch_bounds__(64 * (CW + LW)) k_logpdf(const double* __restrict__ F, const double* __restrict__ mu,
                                                            const double* __restrict__ invdiag, const double* __restrict__ X, int64_t ldx,
@@ -25,24 +26,37 @@ __global__ void __launch_bounds__(64 * (CW + LW)) k_logpdf(const double* __restr
     }
     const MvnView M(mu, invdiag, n, c, logdet);
     double d[R][BT];
-    if constexpr (FS == 3) {                               // the inverse stream: z = W (x - mu) accumulated in d, no substitution
-        double r[R][BT];
-        load_rawx_inv<R, BT>(r, d, M, X, ldx, b0, batch, lane);
-        MCD_T(1);
-        lds_barrier();
-        MCD_T(2);
-        inv_compute<R, BT, 0>(r, d, ring, lane, ncols);
-    } else {
-        load_rawx<R, BT, FS == 2>(d, M, X, ldx, b0, batch, lane);
-        MCD_T(1);
-        lds_barrier();
-        MCD_T(2);
-        fwd_compute<R, BT, 0, FS>(d, ring, lane, ncols MCD_ACC_ARGS);
-    }
+    load_rawx<R, BT, FS == 2>(d, M, X, ldx, b0, batch, lane);
+    MCD_T(1);
+    lds_barrier();
+    MCD_T(2);
+    fwd_compute<R, BT, 0, FS>(d, ring, lane, ncols MCD_ACC_ARGS);
     MCD_T(3);
     finish_ll<R, BT>(d, M, b0, batch, ll, lane);
     MCD_T(4);
     MCD_ACC_FLUSH(5);
+}
+
+// The inverse stream (FS = 3; R = 3, 4, up to 512 chains): S stripe waves, two chains per workgroup, every wave a share of Fw of its
+// own (stripe_device.hpp).  The same arguments, preloaded the same way.
+template <int R, int S>
+__global__ void __launch_bounds__(64 * S) k_logpdf_stripe(const double* __restrict__ Fw, const double* __restrict__ mu,
+                                                          const double* __restrict__ invdiag, const double* __restrict__ X, int64_t ldx,
+                                                          int64_t batch, int n, int ncols, double* __restrict__ ll, double c, double logdet)
+{
+    __shared__ d2 ring[Stripe<R, S>::D2];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    MCD_T(0);
+    const MvnView M(mu, invdiag, n, c, logdet);
+    stripe_dispatch<R, S, 0>(wave, Fw, ring, M, X, ldx, (int64_t)blockIdx.x * 2, batch, ncols, ll, lane);
+}
+
+template <int R>
+static void launch_stripe(const MvnDev& M, const double* X, int64_t ldx, int64_t batch, double* ll, hipStream_t st)
+{
+    hipLaunchKernelGGL((k_logpdf_stripe<R, kStripeWaves>), dim3((unsigned)((batch + 1) / 2)), dim3(64 * kStripeWaves), 0, st, M.Fw, M.mu, M.invdiag,
+                       X, ldx, batch, M.n, M.ncols, ll, M.c, M.logdet);
 }
 
 template <int R, int BT, int CW, int LW, int FS>
@@ -58,12 +72,12 @@ template <int R, int BT, int CW, int LW>
 static void launch_geom(const MvnDev& M, const double* X, int64_t ldx, int64_t batch, double* ll, hipStream_t st)
 {
     if constexpr (fwd_stream_compact(R)) {
-        constexpr bool INV = CW == 2 && BT == 1;           // the geometry the inverse stream is built for (one workgroup per CU)
+        constexpr bool INV = CW == 2 && BT == 1;           // the geometry the inverse stream replaces (one workgroup per CU)
         const int fs = fwd_stream<R>(CW, INV, INV && logpdf_inverse_window(MvnFacts(M), batch));
         if (fs == 1) return launch_fs<R, BT, CW, LW, 1>(M, X, ldx, batch, ll, st);
         if (fs == 2) return launch_fs<R, BT, CW, LW, 2>(M, X, ldx, batch, ll, st);
         if constexpr (INV)
-            if (fs == 3) return launch_fs<R, BT, CW, LW, 3>(M, X, ldx, batch, ll, st);
+            if (fs == 3) return launch_stripe<R>(M, X, ldx, batch, ll, st);   // (whatever LW: it has no loader waves)
     }
     launch_fs<R, BT, CW, LW, 0>(M, X, ldx, batch, ll, st);
 }
@@ -113,12 +127,5 @@ extern "C" int mcd_debug_hist(unsigned long long* hist, unsigned long long* span
     if (hipMemcpyFromSymbol(hist, HIP_SYMBOL(mcd::g_hist), 64 * 8 * 8 * sizeof(unsigned long long)) != hipSuccess) return -1;
     if (hipMemcpyFromSymbol(span, HIP_SYMBOL(mcd::g_span), 64 * 64 * 2 * sizeof(unsigned long long)) != hipSuccess) return -1;
     return (int)hipMemcpyFromSymbol(n, HIP_SYMBOL(mcd::g_launch), sizeof(unsigned int));
-}
-#endif
-#if defined(MCD_STAMP_CHUNKS) && MCD_RGROUP == 0
-// ... and the per-chunk barrier stamps of workgroup 0's compute wave 0, [64][16]
-extern "C" int mcd_debug_chunks(unsigned long long* out)
-{
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(mcd::g_chunk), 64 * 16 * sizeof(unsigned long long));
 }
 #endif

@@ -114,17 +114,6 @@ __device__ unsigned int g_launch;                          // launches completed
 #define MCD_ACC_PARAMS
 #define MCD_ACC_ARGS
 #define MCD_ACC_FLUSH(base) do { } while (0)
-// -DMCD_STAMP_CHUNKS on top (`make stamp_headline_chunks`, tools/microbench/headline_chunks.py): compute wave 0 of workgroup 0 also stamps
-// the barrier behind every chunk -- the wave has just waited for its LDS reads there, so the stamp's own wait costs the loop nothing else.
-#ifdef MCD_STAMP_CHUNKS
-__device__ unsigned long long g_chunk[64][16];             // [launch % 64][chunk]: the barrier behind the chunk passed
-#define MCD_TC(ci)                                                                               \
-    do {                                                                                         \
-        unsigned long long t_;                                                                   \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");              \
-        if (blockIdx.x == 0 && threadIdx.x == 0) g_chunk[__atomic_load_n(&g_launch, __ATOMIC_RELAXED) & 63u][(ci) & 15] = t_; \
-    } while (0)
-#endif
 #elif defined(MCD_STAMP)
 __device__ unsigned long long g_dbg[64];
 #define MCD_T(idx)                                                                               \
@@ -159,10 +148,6 @@ __device__ __forceinline__ void mcd_acc(int idx, unsigned long long& tprev, unsi
 #define MCD_ACC_PARAMS
 #define MCD_ACC_ARGS
 #define MCD_ACC_FLUSH(base) do { } while (0)
-#endif
-
-#ifndef MCD_TC
-#define MCD_TC(ci) do { } while (0)
 #endif
 
 // ---------------------------------------------------------------------------------------
@@ -234,16 +219,16 @@ __device__ __forceinline__ void stage_store(const Stage<R, LW>& st, d2* slot, in
 // is fc_chunk_units consecutive units, copied as they are; the diagonal units' lanes on or above the diagonal are read from a
 // zero unit behind the slots (fwd_unit), written once before the first barrier.  Compact streams serve R <= 4 (every chunk's
 // diagonal part is a whole number of units there, and the loaders' schedule is compile-time: at most four chunks per block).
-// FS 3 (k_logpdf, two compute waves): the ring, the loaders and the layout of FS 2 over the inverse stream Fw (MvnDev::Fw) -- the
-// compute waves multiply instead of substituting (inv_apply).
+// (FS 3, the inverse stream Fw of the raw-x log-density, has a kernel of its own without this ring: stripe_device.hpp.)
 template <int R, int FS>
 struct Ring {
     // slots: LDS-DMA keeps two chunks in flight across a barrier beside the one being read and the one waited for, as register
     // staging does (measured at N = 256 x 512 chains: 3 slots 7.20 us per step, 4 slots 7.18-7.20, 5 slots 7.78)
-    static constexpr int NS = FS >= 2 ? 4 : 2;
-    static constexpr int STRIDE = FS >= 2 ? fc_chunk_units(R, 0) : Cfg<R>::SU;   // units per slot (chunk 0 is the largest)
+    static constexpr int NS = FS == 2 ? 4 : 2;
+    static constexpr int STRIDE = FS == 2 ? fc_chunk_units(R, 0) : Cfg<R>::SU;   // units per slot (chunk 0 is the largest)
     static constexpr int ZERO = NS * STRIDE * 64;                            // the zero unit (d2 index; FS > 0)
     static constexpr int D2 = ZERO + (FS > 0 ? 64 : 0);
+    static_assert(FS >= 0 && FS <= 2, "the ring's streams");
     static_assert(FS == 0 || (R <= 4 && fc_chunk_units(R, 0) <= Cfg<R>::SU), "compact streams: R <= 4");
 };
 
@@ -379,7 +364,6 @@ __device__ __forceinline__ bool fwd_compute_chunks(double (&d)[R][BT], const d2*
         MCD_ACC(0);
         lds_barrier();
         MCD_ACC(1);
-        MCD_TC(CI);
         return fwd_compute_chunks<R, BT, JB, LC + 1, FS>(d, ring, lane, ncols MCD_ACC_ARGS);
     } else {
         return true;
@@ -392,91 +376,6 @@ __device__ __forceinline__ void fwd_compute(double (&d)[R][BT], const d2* ring, 
     if constexpr (JB < R) {
         if (!fwd_compute_chunks<R, BT, JB, 0, FS>(d, ring, lane, ncols MCD_ACC_ARGS)) return;
         fwd_compute<R, BT, JB + 1, FS>(d, ring, lane, ncols MCD_ACC_ARGS);
-    }
-}
-
-// ---- compute role, inverse stream (FS = 3) ---------------------------------------------------------------------------------
-// z = W r with W = L^-1 and r = x - mu: the same chunks, units and column order as the substitution above, but column j's broadcast
-// comes from the residual registers r, which never change, and the multiply-adds go into accumulators a (started at W_ii r_i =
-// r_i invdiag_i by load_rawx_inv).  No broadcast waits for a multiply-add: the pair p + 1's four v_readlane are issued in front of
-// pair p's multiply-adds, and the only dependent chain left is each accumulator's own, NK = R - JB of them in turn.  Lanes on or above
-// the diagonal read the zero unit as before (fwd_unit).  The order of additions into a row is the column order, fixed.
-template <int R, int BT, int JB, int JJ0>
-__device__ __forceinline__ void inv_apply(const double (&r)[R][BT], double (&a)[R][BT], const d2* slot, const d2* zu, int lane)
-{
-    constexpr int jj0 = JJ0;
-    constexpr int LC = JJ0 / Cfg<R>::CCOLS;
-    constexpr int CP = Cfg<R>::CP;
-    constexpr int NK = R - JB;
-    // LDS -> VGPR prefetch distance: with nothing but its own accumulators to wait for, a wave's pair costs the LDS latency over the
-    // distance -- two pairs ahead (LdsPd) held EVERY chunk at 630 - 800 ticks whatever its bytes (tools/microbench/headline_chunks.py).
-    // The same eight to twelve 16-byte buffers as NK = 3, 4 use at distance 2 go deeper where a pair has fewer row blocks: 4 pairs at
-    // NK = 2, the whole chunk at NK = 1.
-    constexpr int LDS_PD = NK >= 3 ? LdsPd<R>::PD : NK == 2 ? 4 : CP;
-    constexpr int NBUF = LDS_PD < CP ? LDS_PD + 1 : CP;
-    d2 l[NBUF][NK];
-#pragma unroll
-    for (int p = 0; p < LDS_PD && p < CP; ++p)
-#pragma unroll
-        for (int k = 0; k < NK; ++k) l[p % NBUF][k] = fwd_unit<R, JB, LC, 3>(slot, zu, p, k, lane);
-    double z[2][BT];
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int b = 0; b < BT; ++b) z[h][b] = readlane64(r[JB][b], jj0 + h);
-#pragma unroll
-    for (int p = 0; p < CP; ++p) {
-        if (p + LDS_PD < CP) {
-#pragma unroll
-            for (int k = 0; k < NK; ++k) l[(p + LDS_PD) % NBUF][k] = fwd_unit<R, JB, LC, 3>(slot, zu, p + LDS_PD, k, lane);
-        }
-        MCD_SB;
-        double zn[2][BT];
-        if (p + 1 < CP) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int b = 0; b < BT; ++b) zn[h][b] = readlane64(r[JB][b], jj0 + 2 * (p + 1) + h);
-        }
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int k = 0; k < NK; ++k)
-#pragma unroll
-                for (int b = 0; b < BT; ++b)
-                    a[JB + k][b] = fma(h ? l[p % NBUF][k].y : l[p % NBUF][k].x, z[h][b], a[JB + k][b]);
-        MCD_SB;
-        if (p + 1 < CP) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int b = 0; b < BT; ++b) z[h][b] = zn[h][b];
-        }
-    }
-}
-
-template <int R, int BT, int JB, int LC>
-__device__ __forceinline__ bool inv_compute_chunks(const double (&r)[R][BT], double (&a)[R][BT], const d2* ring, int lane, int ncols)
-{
-    using C = Cfg<R>;
-    if constexpr (LC < C::CPB) {
-        constexpr int CI = JB * C::CPB + LC;
-        if (CI * C::CCOLS >= ncols) return false;        // workgroup-uniform
-        inv_apply<R, BT, JB, LC * C::CCOLS>(r, a, ring + (CI % Ring<R, 3>::NS) * Ring<R, 3>::STRIDE * 64, ring + Ring<R, 3>::ZERO, lane);
-        lds_barrier();
-        MCD_TC(CI);
-        return inv_compute_chunks<R, BT, JB, LC + 1>(r, a, ring, lane, ncols);
-    } else {
-        return true;
-    }
-}
-
-template <int R, int BT, int JB>
-__device__ __forceinline__ void inv_compute(const double (&r)[R][BT], double (&a)[R][BT], const d2* ring, int lane, int ncols)
-{
-    if constexpr (JB < R) {
-        if (!inv_compute_chunks<R, BT, JB, 0>(r, a, ring, lane, ncols)) return;
-        inv_compute<R, BT, JB + 1>(r, a, ring, lane, ncols);
     }
 }
 
@@ -674,11 +573,11 @@ __device__ __forceinline__ void fc_dma_loader(const double* __restrict__ Fc, d2*
 }
 
 // The loader role of a forward sweep for stream FS, first barrier included (MCD_T: the milestones of the diagnostic builds).
-// F: the stream FS reads -- Ft (FS = 0), Fc or Fw (FS = 3) (fwd_stream_ptr).
+// F: the stream FS reads -- Ft (FS = 0) or Fc (fwd_stream_ptr).
 template <int R, int LW, int FS>
 __device__ __forceinline__ void fwd_loader_role(const double* __restrict__ F, d2* ring, int lw, int lane, int ncols MCD_ACC_PARAMS)
 {
-    if constexpr (FS >= 2) {
+    if constexpr (FS == 2) {
         fc_dma_loader<R, LW, FS>(F, ring, lw, lane, ncols);
     } else if constexpr (FS == 1) {
         Stage<R, LW> st;
@@ -919,37 +818,6 @@ __device__ __forceinline__ void load_rawx(double (&d)[R][BT], const MvnView& M, 
     }
 }
 
-// The same loads (AHEAD) for the inverse stream: the raw residual r = x - mu beside a = r invdiag, the start of row i's sum W_ii r_i
-// (a is what load_rawx calls d: same values, same bits).  Padded rows and chains beyond the batch: r = a = 0.
-template <int R, int BT>
-__device__ __forceinline__ void load_rawx_inv(double (&r)[R][BT], double (&a)[R][BT], const MvnView& M, const double* __restrict__ X,
-                                              int64_t ldx, int64_t b0, int64_t batch, int lane)
-{
-    double m[R], iv[R], xr[R][BT];
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-        const int row = 64 * k + lane;
-        m[k] = M.mu[row];
-        iv[k] = M.invdiag[row];
-        const int rc = row < M.n ? row : M.n - 1;
-#pragma unroll
-        for (int c = 0; c < BT; ++c) {
-            const int64_t bc = (b0 + c < batch) ? b0 + c : batch - 1;
-            xr[k][c] = X[bc * ldx + rc];
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-        const int row = 64 * k + lane;
-#pragma unroll
-        for (int c = 0; c < BT; ++c) {
-            const double xv = (row < M.n && b0 + c < batch) ? xr[k][c] : m[k];
-            r[k][c] = xv - m[k];
-            a[k][c] = r[k][c] * iv[k];
-        }
-    }
-}
-
 // distances from the tree state -- app/Probability.hs:201-207 with app/Tools.hs:36-48 and
 // lib/Mcmc/Tree/Types.hs:224-233 folded into index tables (slot -> node, node -> parent).
 template <int R, int BT>
@@ -1082,7 +950,7 @@ __device__ __forceinline__ void finish_ll(const double (&d)[R][BT], const MvnVie
 // anyway (two compute waves: up to 512 chains), and the padded stream with four compute waves: there two workgroups share a CU on
 // the two-slot ring, which the four DMA slots would not leave room for, and the compact stream staged through registers measured no
 // gain on the sweep; MCD_FSTREAM = 1 or 2 forces a compact stream in every geometry (tests).  The choice itself
-// is sweep_fwd_stream (sweep_groups.hpp); inverse: the launch may take the inverse stream (k_logpdf with two compute waves) and the
+// is sweep_fwd_stream (sweep_groups.hpp); inverse: the launch may take the inverse stream (raw x in the two-compute-wave geometry: k_logpdf_stripe) and the
 // call lies in the window where it is the default (logpdf_inverse_window) -- without it MCD_FSTREAM = 3 means the geometry's default.
 template <int R>
 static inline int fwd_stream(int cw, bool has_inverse = false, bool inverse_window = false)

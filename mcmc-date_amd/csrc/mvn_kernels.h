@@ -19,7 +19,7 @@ struct MvnDev {
     const double* Fc;       // the same factor as the compact stream of the sweep (fc_layout.hpp): no stored zeros on or above the diagonal;
                             // NULL unless fwd_stream_compact(R)
     const double* Fw;       // the strictly lower triangle of W = L^-1, unscaled, in the layout of Fc (host_factor.h: pack_inverse_forward): the
-                            // inverse stream of k_logpdf (FS = 3: z = W (x - mu), no column waits for another); NULL unless fwd_stream_compact(R)
+                            // inverse stream of k_logpdf_stripe (FS = 3: z = W (x - mu), no column waits for another); NULL unless fwd_stream_compact(R)
     const double* Ut;      // backward factor L[i][r]/L[r][r], same layout, NP*NP
     const double* Wt;       // W = L^-1 as 16 x 4 MFMA operand tiles (host_factor.h: pack_w_tiles), for k_wide.hip
     const double* Wtb;      // the tiles of W^T for the gradient's second product (k_wide_grad.hip)

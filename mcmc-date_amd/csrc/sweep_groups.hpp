@@ -88,7 +88,7 @@ static inline Geometry sweep_geometry(int R, int64_t batch)
 }
 
 // The forward factor stream of a likelihood sweep with cw compute waves (mcd_set_option "MCD_FSTREAM"; mvn_device.hpp: Ring, fwd_stream):
-// 0 padded, 1 compact, 2 compact by LDS-DMA, 3 the inverse stream (k_logpdf only).  has_inverse: the launch has an FS = 3 kernel at
+// 0 padded, 1 compact, 2 compact by LDS-DMA, 3 the inverse stream (raw x only: k_logpdf.hip, k_logpdf_stripe).  has_inverse: the launch has an FS = 3 kernel at
 // all -- raw x, two compute waves, R = 3, 4; inverse_window: ... and the call lies where it is the default (logpdf_inverse_window).
 // MCD_FSTREAM = 3 selects it wherever it exists, under any form, and means the geometry's default where it does not.
 static inline int sweep_fwd_stream(int R, int cw, bool has_inverse, bool inverse_window)

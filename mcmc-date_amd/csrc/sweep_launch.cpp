@@ -3,6 +3,7 @@
 // launch_tree_logpdf / launch_tree_grad / launch_tree_logpdf_with_prior, which hand a sweep to the entry of the handle's R group
 // (sweep_groups.hpp).
 #include "sweep_groups.hpp"
+#include "stripe_deal.hpp"
 #include <stdlib.h>
 #include <atomic>
 
@@ -65,7 +66,7 @@ bool use_split(const MvnFacts& M, int64_t batch)
 
 bool logpdf_inverse_window(const MvnFacts& M, int64_t batch)
 {
-    // Where raw-x launch_logpdf, once it is on the column sweep, streams W = L^-1 (k_logpdf FS = 3) instead of substituting: form auto
+    // Where raw-x launch_logpdf, once it is on the column sweep, streams W = L^-1 (k_logpdf_stripe, FS = 3) instead of substituting: form auto
     // only -- form "sweep" stays the substitution sweep, bit for bit -- and the headline sizes only, 240 < N <= 256 at 129 .. 512
     // chains (measured: profiles/r12_inverse_stream_ab.txt).  Elsewhere auto keeps the substitution sweep's bits, which the gradient
     // sweep's ll shares; inside the window the gradient takes the row split anyway.  Tree states, the prior variant and the samplers'
@@ -277,4 +278,28 @@ extern "C" int mcd_stream_selftest_(int n, int R, int form, int split, int wide,
     const mcd::Geometry g = mcd::sweep_geometry(R, batch);
     const bool inv = g.cw == 2 && g.bt == 1;
     return mcd::sweep_fwd_stream(R, g.cw, inv, inv && mcd::logpdf_inverse_window(M, batch));
+}
+
+// Test hook (tests/test_stripe_deal_host.py; no device): the list of stripe wave w of S for R row blocks (stripe_deal.hpp), cut as a
+// sweep over ncols columns cuts it (the chunks with 16 CI < ncols stay).  piece[i] = {chunk, pair in the chunk or -1 for the chunk's
+// diagonal part, first unit in Fw, units, position in the wave's list}.  Returns the pieces kept, -1 for a deal that does not exist,
+// -2 if `cap` pieces are too few.
+extern "C" int mcd_stripe_deal_selftest_(int R, int S, int w, int ncols, int* piece, int cap)
+{
+    if ((R != 3 && R != 4) || (S != 4 && S != 8) || w < 0 || w >= S) return -1;
+    const mcd::StripeDeal d = mcd::stripe_deal(R, S);
+    int np = 0;
+    auto put = [&](int ci, int p, int pos, int units) {
+        if (np < cap) {
+            int* q = piece + 5 * np;
+            q[0] = ci, q[1] = p, q[2] = d.unit[w][pos], q[3] = units, q[4] = pos;
+        }
+        ++np;
+    };
+    for (int ci = 0; ci < mcd::fc_nchunk(R) && 16 * ci < ncols; ++ci) {
+        if (d.diag_pos[w][ci] >= 0) put(ci, -1, d.diag_pos[w][ci], mcd::fc_diag_units(R, ci % mcd::fc_cpb(R)));
+        for (int p = 0; p < mcd::fc_cp(R); ++p)
+            if (d.pair_pos[w][ci][p] >= 0) put(ci, p, d.pair_pos[w][ci][p], R - 1 - ci / mcd::fc_cpb(R));
+    }
+    return np <= cap ? np : -2;
 }

@@ -1,4 +1,5 @@
-"""The budget of ONE graph-replayed headline launch (k_logpdf<4,1,2,4,2>: N = 256, 512 chains), from in-kernel s_memtime stamps kept
+"""The budget of ONE graph-replayed launch of the substitution sweep (k_logpdf<4,1,2,4,2>: N = 256, 512 chains with MCD_FSTREAM=2 in the
+environment; the default there is the stripe kernel: headline_stripes.py), from in-kernel s_memtime stamps kept
 per launch (library: `make -C mcmc-date_amd/csrc stamp_headline` -> tools/microbench/libheadlinestamp.so; the sweep loop itself
 carries no stamps).  The harness is bench.py's: graphs of 100 launches alternating two input batches, replayed back to back.
 
