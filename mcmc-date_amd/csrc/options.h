@@ -35,6 +35,8 @@ enum Option {
                             // log-density with two compute waves only; elsewhere 3 means the geometry's default) (A/B, tests; fc_layout.hpp,
                             // mvn_device.hpp, sweep_groups.hpp: sweep_fwd_stream)
     OPT_SPARSE_GRAD_CHAINS, // 1 | 2: chains per workgroup of the sparse tree gradient (k_sparse_grad.hip; default: 2 from 512 chains; the same bits)
+    OPT_STRIPE_PROLOGUE,    // the inverse stream's stripe kernel (stripe_device.hpp): 1 = x, mu and 1/diag loaded once per workgroup and exchanged through
+                            // LDS, 0 = by every stripe wave for itself (A/B, tests; the same bits)
     OPT_COUNT
 };
 constexpr int MCD_OPT_UNSET = -2147483647 - 1;

@@ -6,7 +6,7 @@
 //     dealt to it (stripe_deal.hpp).  Nothing forces two waves to read the same bytes, so each wave loads its own units by LDS-DMA
 //     into a ring of D units that only it reads: the u-th unit of its list lives at slot u mod D.
 //   * Ordering inside a wave is the wave's own counters.  A wave's LDS-DMAs land in issue order, so once vmcnt is down to the number
-//     of DMAs issued behind unit u, unit u is in LDS; the DMA of unit u + D is issued once the ds_reads of unit u have returned.
+//     of DMAs issued behind unit u, unit u is in LDS; the DMA of unit u + A (A <= D) is issued once the ds_reads of unit u have returned.
 //     The compiler does not know which DMA a ds_read depends on and would wait for all of them, so the ring is read by ds_read_b128
 //     in asm statements, with the waits written out; for the same reason the loads of x, mu and 1/diag, issued before the first
 //     DMA, are asm loads waited for by count.
@@ -18,7 +18,14 @@
 //   * Every wave's code is its own instantiation (W is a template parameter): list positions, ring slots, wait counts and the
 //     v_readlane lane selects of the column broadcasts are immediates.
 //   * The waves end on vmcnt(0): nothing of one launch is in flight into LDS when the next one starts.  A sweep that stops early
-//     (ncols < 64 R) has requested up to D units behind the cut; they land in the wave's own ring and are never read.
+//     (ncols < 64 R) has requested up to A units behind the cut; they land in the wave's own ring and are never read.
+//   * The prologue (SH, the default; MCD_STRIPE_PROLOGUE = 0 keeps every wave loading everything for itself): row block k belongs to
+//     wave k mod S, which loads mu_k, 1/diag_k and both chains' x_k in front of its first DMA, forms r = x - mu and t = r invdiag with
+//     the operations of the private prologue and stores both into an exchange area behind the zero units ([r | t][R][64 lanes][2
+//     chains], one 16-byte access per lane for both chains).  One barrier that waits for LDS only -- the DMAs stay in flight across
+//     it -- then every wave reads all of r and wave 0 also t.  The exchange accesses are asm like the ring reads, for the same reason.
+//   * The lookahead A (kStripeAhead <= D, -DMCD_STRIPE_AHEAD): units requested ahead of the unit being read, and the prologue's burst.
+//     Slots stay u mod D.
 #include "mvn_device.hpp"
 #include "stripe_deal.hpp"
 
@@ -28,15 +35,28 @@ namespace mcd {
 #define MCD_STRIPE_WAVES 4
 #endif
 constexpr int kStripeWaves = MCD_STRIPE_WAVES;
+// Measured (profiles/r14_stripe_prologue_ab.txt; N = 256 x 512 chains, us per launch): A = 32, the whole ring, 5.96; 24 5.73; 20 5.66;
+// 16 5.54; 14 5.47; 12 5.44; 10 5.49; 8 5.61.  With A = 32 a CU's four waves requested 128 KiB before they looked at anything, and the
+// loads of x stood in that queue; 4 x 12 KiB still covers the latency-bandwidth product (about 28 KiB) with room to spare.
+#ifndef MCD_STRIPE_AHEAD
+#define MCD_STRIPE_AHEAD 12
+#endif
+constexpr int kStripeAhead = MCD_STRIPE_AHEAD;
+constexpr int kStripePrologueDefault = 1;                  // MCD_STRIPE_PROLOGUE unset: the shared prologue
 
 template <int R, int S>
 struct Stripe {
     static_assert((R == 3 || R == 4) && (S == 4 || S == 8), "stripe kernel: R = 3, 4; S = 4, 8");
     // ring units per wave: S D KiB + the waves' zero units within 160 KiB, and x loads + D DMAs within the 6 bits of vmcnt
     static constexpr int D = 128 / S;
+    static constexpr int A = kStripeAhead < D ? kStripeAhead : D;   // the lookahead (units), at most the ring
+    static_assert(A >= 1, "MCD_STRIPE_AHEAD");
     static constexpr int ZERO = S * D * 64;               // the waves' zero units (d2 index)
     static constexpr int D2 = ZERO + S * 64;
-    static_assert(D2 * 16 <= 160 * 1024, "LDS");
+    static constexpr int EXCH = D2;                       // the shared prologue's exchange area [r | t][R][64] (d2 index: both chains)
+    static constexpr int D3 = EXCH + 2 * R * 64;
+    static_assert(D3 * 16 <= 160 * 1024, "LDS");
+    // leading loads in front of the DMAs: 4 R (private prologue, wave 0), 4 per row block owned (shared)
     static_assert(4 * R + D < 64, "vmcnt");
     static constexpr StripeDeal T = stripe_deal(R, S);
 };
@@ -60,6 +80,12 @@ __device__ __forceinline__ void lds_read16(d2& v, unsigned addr)
 {
     static_assert(OFF >= 0 && OFF < 65536, "ds offset");
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
+}
+template <int OFF>
+__device__ __forceinline__ void lds_write16(unsigned addr, d2 v)
+{
+    static_assert(OFF >= 0 && OFF < 65536, "ds offset");
+    asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(addr), "v"(v), "n"(OFF) : "memory");
 }
 template <int N, int M>
 __device__ __forceinline__ void lds_landed(d2 (&v)[M])
@@ -92,6 +118,7 @@ __device__ __forceinline__ void stripe_issue(const double* __restrict__ Fw, unsi
 }
 
 constexpr int stripe_min(int a, int b) { return a < b ? a : b; }
+constexpr int stripe_max(int a, int b) { return a > b ? a : b; }
 
 // off-diagonal pairs P .. 7 of chunk CI that wave W owns: reads of all of them first, then the multiply-adds
 template <int R, int S, int W, int CI, int P, int NREAD>
@@ -151,7 +178,8 @@ constexpr int stripe_pairs_units()
 }
 
 // Chunk CI and the ones behind it.  ISSUED: DMAs issued so far (list positions 0 .. ISSUED - 1); every wait leaves the DMAs behind the
-// last unit it needs in flight, and every group of reads is followed by the DMAs into the slots it has just freed.
+// last unit it needs in flight, and every group of reads is followed by the DMAs up to A units behind it.  (A lookahead shorter than
+// a group: the rest of the group is requested in front of its wait; everything before the group has been read, so its slots are free.)
 template <int R, int S, int W, int CI, int ISSUED>
 __device__ __forceinline__ void stripe_chunks(const double* __restrict__ Fw, unsigned my, unsigned la, unsigned za, const double (&r)[R][2],
                                               double (&a)[R][2], int lane, int ncols)
@@ -159,11 +187,13 @@ __device__ __forceinline__ void stripe_chunks(const double* __restrict__ Fw, uns
     using G = Stripe<R, S>;
     if constexpr (CI < fc_nchunk(R)) {
         if (CI * 16 >= ncols) return;                      // workgroup-uniform: a suffix of every wave's list
-        constexpr int D = G::D, NU = G::T.n[W], JB = CI / 4, LC = CI % 4;
+        constexpr int D = G::D, A = G::A, NU = G::T.n[W], JB = CI / 4, LC = CI % 4;
         constexpr int dpos = G::T.diag_pos[W][CI];
         constexpr int dend = dpos >= 0 ? dpos + fc_diag_units(R, LC) : 0;
-        constexpr int issued1 = dpos >= 0 ? stripe_min(NU, dend + D) : ISSUED;
+        constexpr int issued0 = stripe_max(ISSUED, dend);
+        constexpr int issued1 = dpos >= 0 ? stripe_max(issued0, stripe_min(NU, dend + A)) : ISSUED;
         if constexpr (dpos >= 0) {
+            static_assert(fc_diag_units(R, LC) <= D, "a group within the ring");
             // the diagonal part: pair p's lanes 2 pl + 1 .. 63 lie back to back in the part, the others read the wave's zero unit
             constexpr bool WRAP = dpos % D + fc_diag_units(R, LC) > D;
             d2 l[8];
@@ -175,12 +205,13 @@ __device__ __forceinline__ void stripe_chunks(const double* __restrict__ Fw, uns
                 if (WRAP) i = i >= D * 64 ? i - D * 64 : i;
                 ad[p] = lane > 2 * pl ? la - 16u * (unsigned)lane + 16u * (unsigned)i : za;
             }
-            asm_wait_vmcnt<ISSUED - dend>();
+            stripe_issue<R, S, W, ISSUED, issued0>(Fw, my, lane);
+            asm_wait_vmcnt<issued0 - dend>();
             if constexpr (CI == 0) MCD_T(2);
 #pragma unroll
             for (int p = 0; p < 8; ++p) lds_read16<0>(l[p], ad[p]);
             lds_landed<8>(l);
-            stripe_issue<R, S, W, ISSUED, issued1>(Fw, my, lane);
+            stripe_issue<R, S, W, issued0, issued1>(Fw, my, lane);
 #pragma unroll
             for (int p = 0; p < 8; ++p)
 #pragma unroll
@@ -190,31 +221,31 @@ __device__ __forceinline__ void stripe_chunks(const double* __restrict__ Fw, uns
                         a[JB][b] = fma(h ? l[p].y : l[p].x, readlane64(r[JB][b], (LC * 8 + p) * 2 + h), a[JB][b]);
         }
         constexpr int pend = stripe_pairs_end<R, S, W, CI>();
-        constexpr int issued2 = pend >= 0 ? stripe_min(NU, pend + D) : issued1;
+        constexpr int issued1p = stripe_max(issued1, pend);
+        constexpr int issued2 = pend >= 0 ? stripe_max(issued1p, stripe_min(NU, pend + A)) : issued1;
         if constexpr (pend >= 0) {
+            static_assert(stripe_pairs_units<R, S, W, CI>() <= D, "a group within the ring");
             d2 l[8 * 3];
-            asm_wait_vmcnt<issued1 - pend>();
+            stripe_issue<R, S, W, issued1, issued1p>(Fw, my, lane);
+            asm_wait_vmcnt<issued1p - pend>();
             if constexpr (CI == 0 && dpos < 0) MCD_T(2);
             stripe_pairs_read<R, S, W, CI, 0, 0>(l, la);
             lds_landed<stripe_pairs_units<R, S, W, CI>()>(l);
-            stripe_issue<R, S, W, issued1, issued2>(Fw, my, lane);
+            stripe_issue<R, S, W, issued1p, issued2>(Fw, my, lane);
             stripe_pairs_apply<R, S, W, CI, 0, 0>(l, r, a);
         }
         stripe_chunks<R, S, W, CI + 1, issued2>(Fw, my, la, za, r, a, lane, ncols);
     }
 }
 
+// The private prologue: x, mu and (wave 0) 1/diag of both chains in front of the first DMA: a padded row or a chain beyond the batch
+// reads a clamped address and the value is dropped for mu (load_rawx)
 template <int R, int S, int W>
-__device__ __forceinline__ void stripe_wave(const double* __restrict__ Fw, d2* ring, const MvnView& M, const double* __restrict__ X, int64_t ldx,
-                                            int64_t b0, int64_t batch, int ncols, double* __restrict__ ll, int lane)
+__device__ __forceinline__ void stripe_prologue_private(const double* __restrict__ Fw, unsigned mya, const MvnView& M, const double* __restrict__ X,
+                                                        int64_t ldx, int64_t b0, int64_t batch, double (&r)[R][2], double (&a)[R][2], int lane)
 {
     using G = Stripe<R, S>;
-    constexpr int D = G::D, NU = G::T.n[W], PRO = stripe_min(D, NU);
-    d2* my = ring + W * D * 64;
-    d2* zu = ring + G::ZERO + W * 64;
-    zu[lane] = d2{0.0, 0.0};
-    // x, mu and (wave 0) 1/diag of both chains in front of the first DMA: a padded row or a chain beyond the batch reads a clamped
-    // address and the value is dropped for mu (load_rawx)
+    constexpr int PRO = stripe_min(G::A, G::T.n[W]);
     double xr[R][2], m[R], iv[R];
 #pragma unroll
     for (int k = 0; k < R; ++k) {
@@ -228,7 +259,6 @@ __device__ __forceinline__ void stripe_wave(const double* __restrict__ Fw, d2* r
             asm_load8(xr[k][c], X + bc * ldx + rc);
         }
     }
-    const unsigned mya = lds_addr(my);
     stripe_issue<R, S, W, 0, PRO>(Fw, mya, lane);
     asm_wait_vmcnt<PRO>();                                 // the loads in front of the DMAs have returned
 #pragma unroll
@@ -236,7 +266,6 @@ __device__ __forceinline__ void stripe_wave(const double* __restrict__ Fw, d2* r
         asm volatile("" : "+v"(m[k]), "+v"(xr[k][0]), "+v"(xr[k][1]));
         if constexpr (W == 0) asm volatile("" : "+v"(iv[k]));
     }
-    double r[R][2], a[R][2];
 #pragma unroll
     for (int k = 0; k < R; ++k) {
         const int row = 64 * k + lane;
@@ -249,6 +278,98 @@ __device__ __forceinline__ void stripe_wave(const double* __restrict__ Fw, d2* r
         }
     }
     MCD_T(1);
+}
+
+// The exchange area: r of row block k at ea + 1024 k, t at ea + 1024 (R + k) (ea: the lane's byte address in the area), .x chain 0.
+// put: the owned row blocks I .. NO - 1 of wave W, r and t formed exactly as the private prologue forms them
+template <int R, int S, int W, int I, int NO>
+__device__ __forceinline__ void stripe_exchange_put(const double (&xr)[NO + 1][2], const double (&m)[NO + 1], const double (&iv)[NO + 1], unsigned ea,
+                                                    int n, int64_t b0, int64_t batch, int lane)
+{
+    if constexpr (I < NO) {
+        constexpr int k = W + I * S;
+        const int row = 64 * k + lane;
+        double rr[2], tt[2];
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const double xv = (row < n && b0 + c < batch) ? xr[I][c] : m[I];
+            rr[c] = xv - m[I];
+            tt[c] = rr[c] * iv[I];
+        }
+        lds_write16<k * 1024>(ea, d2{rr[0], rr[1]});
+        lds_write16<(R + k) * 1024>(ea, d2{tt[0], tt[1]});
+        stripe_exchange_put<R, S, W, I + 1, NO>(xr, m, iv, ea, n, b0, batch, lane);
+    }
+}
+// get: all R row blocks of r (Q = 0) or t (Q = 1); lds_landed() before the first use
+template <int R, int Q, int K>
+__device__ __forceinline__ void stripe_exchange_get(d2 (&e)[R], unsigned ea)
+{
+    if constexpr (K < R) {
+        lds_read16<(Q * R + K) * 1024>(e[K], ea);
+        stripe_exchange_get<R, Q, K + 1>(e, ea);
+    }
+}
+
+// The shared prologue: the same loads, selection and operations, but only for the row blocks k = W, W + S, ... < R this wave owns
+// (four loads each); r and t = r invdiag go through the exchange area, one LDS-only barrier, every wave reads r and wave 0 t.
+template <int R, int S, int W>
+__device__ __forceinline__ void stripe_prologue_shared(const double* __restrict__ Fw, unsigned mya, unsigned ea, const MvnView& M,
+                                                       const double* __restrict__ X, int64_t ldx, int64_t b0, int64_t batch, double (&r)[R][2],
+                                                       double (&a)[R][2], int lane)
+{
+    using G = Stripe<R, S>;
+    constexpr int PRO = stripe_min(G::A, G::T.n[W]);
+    constexpr int NO = W < R ? (R - W + S - 1) / S : 0;    // row blocks owned
+    double xr[NO + 1][2], m[NO + 1], iv[NO + 1];
+#pragma unroll
+    for (int i = 0; i < NO; ++i) {
+        const int row = 64 * (W + i * S) + lane;
+        asm_load8(m[i], M.mu + row);
+        asm_load8(iv[i], M.invdiag + row);
+        const int rc = row < M.n ? row : M.n - 1;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const int64_t bc = (b0 + c < batch) ? b0 + c : batch - 1;
+            asm_load8(xr[i][c], X + bc * ldx + rc);
+        }
+    }
+    stripe_issue<R, S, W, 0, PRO>(Fw, mya, lane);
+    asm_wait_vmcnt<PRO>();                                 // the loads in front of the DMAs have returned
+#pragma unroll
+    for (int i = 0; i < NO; ++i) asm volatile("" : "+v"(m[i]), "+v"(iv[i]), "+v"(xr[i][0]), "+v"(xr[i][1]));
+    MCD_T(1);
+    stripe_exchange_put<R, S, W, 0, NO>(xr, m, iv, ea, M.n, b0, batch, lane);
+    lds_barrier();                                         // (lgkmcnt only: the DMAs stay in flight)
+    d2 e[R], et[R];
+    stripe_exchange_get<R, 0, 0>(e, ea);
+    if constexpr (W == 0) stripe_exchange_get<R, 1, 0>(et, ea);
+    lds_landed<R>(e);
+    if constexpr (W == 0) lds_landed<R>(et);
+#pragma unroll
+    for (int k = 0; k < R; ++k)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            r[k][c] = c ? e[k].y : e[k].x;
+            if constexpr (W == 0) a[k][c] = c ? et[k].y : et[k].x;
+            else a[k][c] = 0.0;
+        }
+    MCD_T(5);
+}
+
+template <int R, int S, int W, bool SH>
+__device__ __forceinline__ void stripe_wave(const double* __restrict__ Fw, d2* ring, const MvnView& M, const double* __restrict__ X, int64_t ldx,
+                                            int64_t b0, int64_t batch, int ncols, double* __restrict__ ll, int lane)
+{
+    using G = Stripe<R, S>;
+    constexpr int D = G::D, NU = G::T.n[W], PRO = stripe_min(G::A, NU);
+    d2* my = ring + W * D * 64;
+    d2* zu = ring + G::ZERO + W * 64;
+    zu[lane] = d2{0.0, 0.0};
+    const unsigned mya = lds_addr(my);
+    double r[R][2], a[R][2];
+    if constexpr (SH) stripe_prologue_shared<R, S, W>(Fw, mya, lds_addr(ring + G::EXCH) + 16u * (unsigned)lane, M, X, ldx, b0, batch, r, a, lane);
+    else stripe_prologue_private<R, S, W>(Fw, mya, M, X, ldx, b0, batch, r, a, lane);
     const unsigned la = mya + 16u * (unsigned)lane;
     const unsigned za = lds_addr(zu) + 16u * (unsigned)lane;
     stripe_chunks<R, S, W, 0, PRO>(Fw, mya, la, za, r, a, lane, ncols);
@@ -276,14 +397,14 @@ __device__ __forceinline__ void stripe_wave(const double* __restrict__ Fw, d2* r
     }
 }
 
-template <int R, int S, int W>
+template <int R, int S, int W, bool SH>
 __device__ __forceinline__ void stripe_dispatch(int wave, const double* __restrict__ Fw, d2* ring, const MvnView& M, const double* __restrict__ X,
                                                 int64_t ldx, int64_t b0, int64_t batch, int ncols, double* __restrict__ ll, int lane)
 {
     if (wave == W) {
-        stripe_wave<R, S, W>(Fw, ring, M, X, ldx, b0, batch, ncols, ll, lane);
+        stripe_wave<R, S, W, SH>(Fw, ring, M, X, ldx, b0, batch, ncols, ll, lane);
     } else {
-        if constexpr (W + 1 < S) stripe_dispatch<R, S, W + 1>(wave, Fw, ring, M, X, ldx, b0, batch, ncols, ll, lane);
+        if constexpr (W + 1 < S) stripe_dispatch<R, S, W + 1, SH>(wave, Fw, ring, M, X, ldx, b0, batch, ncols, ll, lane);
     }
 }
 

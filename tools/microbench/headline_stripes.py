@@ -2,8 +2,9 @@
 every stripe wave of workgroup 0 keeps per launch (library: `make -C mcmc-date_amd/csrc stamp_headline` ->
 tools/microbench/libheadlinestamp.so; STAMPLIB names another file beside it, such as a build with another number of stripe waves).
 The harness is headline_phases.py's: graphs of 100 launches alternating two input batches, replayed back to back; the last 64
-launches are kept.  Milestones of a wave: 0 entry, 1 x / mu / 1/diag landed (behind the first D LDS-DMAs' issue), 2 first unit
-landed, 3 last unit applied, and on wave 0: 4 ll stored.  A wave's stream rate is its units x 1024 bytes over 2 -> 3; the CU's is the
+launches are kept.  Milestones of a wave: 0 entry, 1 its loads of x / mu / 1/diag landed (behind the issue of the prologue's LDS-DMAs),
+5 exchange barrier passed and r read (the shared prologue only; MCD_STRIPE_PROLOGUE=0 in the environment: the private one), 2 first
+unit landed, 3 last unit applied, and on wave 0: 4 ll stored.  A wave's stream rate is its units x 1024 bytes over 2 -> 3; the CU's is the
 whole stream over (first wave's 2) -> (last wave's 3), and over entry -> (last wave's 3).
 
 usage: python tools/microbench/headline_stripes.py [N [chains [waves]]]"""
@@ -53,12 +54,13 @@ e = H[:, 0:1, 0]
 t = H - e[:, :, None]                                                          # ticks since wave 0's entry
 ok = (t[:, :, 1:4] > 0).all(axis=(1, 2)) & (t[:, :, 1:4] < 100000).all(axis=(1, 2)) & (np.diff(t[:, :, 0:4], axis=2) >= 0).all(axis=(1, 2))
 t = t[ok]
+shared = bool((H[ok][:, :, 5] != 0).all())                                     # milestone 5 is stamped by the shared prologue only
 print(f"N = {n}, {B} chains, {NW} stripe waves: {len(t)} launches; ticks after wave 0's entry, median (min .. max)")
 for w in range(NW):
     def m(i):
         return f"{np.median(t[:, w, i]):6.0f} ({t[:, w, i].min():6d} .. {t[:, w, i].max():6d})"
-    print(f"  wave {w}: entry {m(0)}  x landed {m(1)}  first unit landed {m(2)}  last unit applied {m(3)}  "
-          f"first -> last {np.median(t[:, w, 3] - t[:, w, 2]):6.0f}")
+    print(f"  wave {w}: entry {m(0)}  loads landed {m(1)}  " + (f"barrier passed, r read {m(5)}  " if shared else "") +
+          f"first unit landed {m(2)}  last unit applied {m(3)}  first -> last {np.median(t[:, w, 3] - t[:, w, 2]):6.0f}")
 first, last = t[:, :, 2].min(axis=1), t[:, :, 3].max(axis=1)
 print(f"  workgroup: first unit landed {np.median(first):6.0f}, last unit applied {np.median(last):6.0f}, ll stored {np.median(t[:, 0, 4]):6.0f}")
 print(f"  stream: {total} units; {total * 1024 / np.median(last - first):5.1f} B/clk first landed -> last applied, "
