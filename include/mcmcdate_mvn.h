@@ -264,7 +264,8 @@ int mcd_prior_grad_batch(const mcd_prior_t* p, const double* birth, const double
  *   mcd_hmc_nuts_run    n transitions; adapt != 0: dual averaging of the step sizes towards the acceptance statistic delta
  *                       (Algorithm 6; eps in: starting value, out: the averaged value); mean_alpha[batch]; q_mean / q_var[dim]:
  *                       position means and variances pooled over chains and transitions (what a mass adaptation needs:
- *                       the reference tunes `HTuneLeapfrog HTuneAllMasses`, app/Hamiltonian.hs:62-63).
+ *                       the reference tunes `HTuneLeapfrog HTuneAllMasses`, app/Hamiltonian.hs:62-63; the diagonal form of that
+ *                       tuning is mcd_hmc_nuts_warmup, the full mass matrix mcd_hmc_set_metric / mcd_hmc_nuts_warmup_dense below).
  * `mcmc`'s own defaults and tuning schedule are not available here: parity of this part rests on the CPU twin
  * (tests/test_gpu_nuts.py) and on the agreement with Metropolis-Hastings chains.
  */
@@ -288,6 +289,35 @@ int mcd_hmc_nuts_run(mcd_hmc_t* m, int n_transitions, int adapt, double* eps, co
  * first_transition + (windows + 1) window - 1 of the random streams.  eps, inv_mass: in = starting values, out = tuned. */
 int mcd_hmc_nuts_warmup(mcd_hmc_t* m, int windows, int window, double* eps, double* inv_mass, double delta, int max_depth, uint64_t seed,
                         int64_t chain_offset, uint64_t first_transition, double* mean_alpha);
+/*
+ * The FULL mass matrix (`HTuneAllMasses`): a dense metric set on the handle replaces the vector inv_mass of every entry point.
+ * With C = M^-1 = U U^T (U the lower Cholesky factor, taken on the host): momenta p = U^-T z from the normal draws z of the diagonal
+ * form (so cov p = C^-1 = M), kinetic energy 1/2 p^T C p, drift q += eps (C p), U-turn test (q+ - q-)^T C r >= 0 at both ends; slice,
+ * doubling, reservoir, merge, divergence test and random streams are those of the diagonal form.  Every product v = C x is one
+ * workgroup's sum over j ascending with one accumulator per coordinate: a chain's bits depend on nothing but the chain.
+ *   mcd_hmc_set_metric   inv_mass_dense = C [dim][dim] row-major (host); NULL clears the dense metric, and the handle is again what it
+ *                        was before.  Refused with MCD_ERR_INVALID_ARG, the handle untouched, the message naming the first offender:
+ *                        a non-finite entry; |C_ij - C_ji| > 1e-10 sqrt(C_ii C_jj); not positive definite (the pivot).  Refused with
+ *                        MCD_ERR_UNSUPPORTED: dim > MCD_HMC_DENSE_MAX_DIM (C is read once per product and chain out of the L2; beyond,
+ *                        the right form is one multiply across the lock-step chains, which is not built).  The handle keeps
+ *                        (C + C^T) / 2, exactly symmetric, and U^-1 on its device.
+ *   mcd_hmc_get_metric   *is_dense = 0 / 1; inv_mass_dense (may be NULL) receives the stored symmetrised C when dense.
+ * While a dense metric is set, mcd_hmc_leapfrog, mcd_hmc_step_from, mcd_hmc_nuts and mcd_hmc_nuts_run require inv_mass == NULL
+ * (a vector is MCD_ERR_INVALID_ARG: no caller silently runs the other metric); with none set, NULL stays the error it was.
+ *   mcd_hmc_nuts_warmup_dense   the schedule of mcd_hmc_nuts_warmup (windows >= 1, window >= 1) from the diagonal inv_mass0[dim] -- a
+ *                        dense metric on the handle is cleared first --: after every window
+ *                        C = n / (n + 5) Cov + 1e-3 5 / (n + 5) I, n = batch window, Cov the centred covariance (divided by n) of the
+ *                        n positions the window visited, computed on the device in a fixed order (k_hmc_cov.hip); a window whose
+ *                        covariance is not finite or has no Cholesky factor leaves the metric as it was.  A closing window adapts eps
+ *                        to the final metric, which stays SET ON THE HANDLE and is copied to inv_mass_dense_out [dim][dim] (may be
+ *                        NULL); eps: in = starting values, out = tuned.  Transitions first_transition .. first_transition +
+ *                        (windows + 1) window - 1; the recorder's room is checked up front for all of them.
+ */
+#define MCD_HMC_DENSE_MAX_DIM 512
+int mcd_hmc_set_metric(mcd_hmc_t* m, const double* inv_mass_dense);
+int mcd_hmc_get_metric(const mcd_hmc_t* m, int* is_dense, double* inv_mass_dense);
+int mcd_hmc_nuts_warmup_dense(mcd_hmc_t* m, int windows, int window, double* eps, const double* inv_mass0, double delta, int max_depth,
+                              uint64_t seed, int64_t chain_offset, uint64_t first_transition, double* mean_alpha, double* inv_mass_dense_out);
 /*
  * The sample recorder of the NUTS driver: thinned samples of every chain AND the diagnostics of the transitions behind them kept ON THE
  * DEVICE while mcd_hmc_nuts / _nuts_run / _nuts_warmup run.  Replaces: the `monitor` of app/Definitions.hs:288-417 (`mcmc`'s MonitorFile

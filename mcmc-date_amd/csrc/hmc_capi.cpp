@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/mcmcdate_mvn.h"
+#include "host_factor.h"
 #include "mvn_kernels.h"
 #include "recorder.hpp"
 #include "summary_device.hpp"
@@ -51,6 +52,10 @@ struct mcd_hmc {
     mcd::NutsDev nuts{};           // allocated by the first NUTS transition (mcd_hmc_nuts)
     int* d_active = nullptr;
     double *d_s1 = nullptr, *d_s2 = nullptr;   // [dim] position moments of one mcd_hmc_nuts_run (k_hmc_moments)
+    // the dense metric (mcd_hmc_set_metric): [dim][dim] device buffers behind dev.metric / dev.metric_uinv, allocated by the first
+    // metric set; h_metric is the host copy of the stored symmetrised C.  dev.metric == nullptr: the diagonal metric.
+    double *d_metric = nullptr, *d_uinv = nullptr;
+    std::vector<double> h_metric;
     bool have_state = false;
     hipStream_t stream = nullptr;
     std::vector<void*> allocs;
@@ -91,6 +96,91 @@ int eval_gradients(mcd_hmc* m)
         HHIP_TRY(mcd::launch_tree_grad(*m->mvn, *m->tree, D.H, D.R, D.ld, D.sc + 2 * B, D.sc + 3 * B, B, D.ll, D.gl_H, D.gl_R, D.gl_tH, D.gl_rMu,
                                        m->stream));
     return MCD_OK;
+}
+
+// The metric argument of an entry point: positive inverse masses [dim] -- or NULL while a dense metric is set on the handle, so that
+// no caller runs another metric than the one it names.
+int check_inv_mass(const mcd_hmc* m, const char* who, const double* inv_mass)
+{
+    if (m->dev.metric) {
+        if (inv_mass) return hfail(MCD_ERR_INVALID_ARG, "%s: a dense metric is set on this handle (mcd_hmc_set_metric): inv_mass must be NULL", who);
+        return MCD_OK;
+    }
+    if (!inv_mass) return hfail(MCD_ERR_INVALID_ARG, "%s: NULL argument", who);
+    for (int k = 0; k < m->dev.dim; ++k)
+        if (!(inv_mass[k] > 0) || !std::isfinite(inv_mass[k])) return hfail(MCD_ERR_INVALID_ARG, "%s: inverse masses must be positive", who);
+    return MCD_OK;
+}
+
+// the diagonal metric's inverse masses go to the device; a dense metric is there already
+int upload_inv_mass(mcd_hmc* m, const double* inv_mass)
+{
+    if (!m->dev.metric) HHIP_TRY(hipMemcpyAsync(m->d_inv_mass, inv_mass, sizeof(double) * m->dev.dim, hipMemcpyHostToDevice, m->stream));
+    return MCD_OK;
+}
+
+// C [dim][dim] as a metric: sym = (C + C^T) / 2, uinv = U^-1 of sym = U U^T (lower triangular).  false, with the reason in `why`: a
+// non-finite entry, an asymmetric pair, not positive definite -- the first offender named.
+bool metric_factors(int dim, const double* C, std::vector<double>& sym, std::vector<double>& uinv, char* why, size_t len)
+{
+    const size_t n = (size_t)dim;
+    for (size_t i = 0; i < n; ++i)
+        for (size_t j = 0; j < n; ++j)
+            if (!std::isfinite(C[i * n + j])) {
+                snprintf(why, len, "C[%zu][%zu] = %g is not finite", i, j, C[i * n + j]);
+                return false;
+            }
+    for (size_t i = 0; i < n; ++i)
+        if (!(C[i * n + i] > 0.0)) {
+            snprintf(why, len, "C is not positive definite: C[%zu][%zu] = %g", i, i, C[i * n + i]);
+            return false;
+        }
+    for (size_t i = 0; i < n; ++i)
+        for (size_t j = i + 1; j < n; ++j) {
+            const double a = C[i * n + j], b = C[j * n + i];
+            if (std::fabs(a - b) > 1e-10 * std::sqrt(C[i * n + i] * C[j * n + j])) {
+                snprintf(why, len, "C is not symmetric: C[%zu][%zu] = %.17g, C[%zu][%zu] = %.17g", i, j, a, j, i, b);
+                return false;
+            }
+        }
+    sym.resize(n * n);
+    for (size_t i = 0; i < n; ++i) {
+        sym[i * n + i] = C[i * n + i];
+        for (size_t j = i + 1; j < n; ++j) sym[i * n + j] = sym[j * n + i] = 0.5 * (C[i * n + j] + C[j * n + i]);
+    }
+    std::vector<double> U;
+    if (!mcd::cholesky_lower(dim, sym, U)) {
+        size_t piv = 0;                                   // the rows are factored in order: the first row without a diagonal entry failed
+        while (piv < n && U[piv * n + piv] > 0.0) ++piv;
+        snprintf(why, len, "C is not positive definite: the Cholesky factorisation fails at pivot %zu", piv);
+        return false;
+    }
+    mcd::invert_factor(dim, U, uinv);
+    return true;
+}
+
+// the prepared metric becomes the handle's
+int metric_install(mcd_hmc* m, std::vector<double>& sym, const std::vector<double>& uinv)
+{
+    const size_t nn = (size_t)m->dev.dim * (size_t)m->dev.dim;
+    HHIP_TRY(hipSetDevice(m->device));
+    if (!m->d_metric) {
+        if (int rc = halloc(m, &m->d_metric, nn)) return rc;
+        if (int rc = halloc(m, &m->d_uinv, nn)) return rc;
+    }
+    HHIP_TRY(hipStreamSynchronize(m->stream));
+    HHIP_TRY(hipMemcpy(m->d_metric, sym.data(), sizeof(double) * nn, hipMemcpyHostToDevice));
+    HHIP_TRY(hipMemcpy(m->d_uinv, uinv.data(), sizeof(double) * nn, hipMemcpyHostToDevice));
+    m->h_metric.swap(sym);
+    m->dev.metric = m->d_metric;
+    m->dev.metric_uinv = m->d_uinv;
+    return MCD_OK;
+}
+
+void metric_clear(mcd_hmc* m)
+{
+    m->dev.metric = m->dev.metric_uinv = nullptr;
+    m->h_metric.clear();
 }
 
 // the part of mcd_hmc_create / mcd_hmc_create_sparse behind the handles: the likelihood and the prior of `m` are set, `parent` is the host
@@ -247,17 +337,16 @@ int mcd_hmc_get_position(const mcd_hmc_t* cm, double* q, double* value, double* 
 
 int mcd_hmc_leapfrog(mcd_hmc_t* m, double* p, const double* eps, const double* dir, const double* inv_mass, int n_steps)
 {
-    if (!m || !p || !eps || !inv_mass) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_leapfrog: NULL argument");
+    if (!m || !p || !eps) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_leapfrog: NULL argument");
     if (!m->have_state) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_leapfrog: call mcd_hmc_set_state first");
     if (n_steps < 0) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_leapfrog: negative number of steps");
     mcd::HmcDev& D = m->dev;
     const size_t B = (size_t)D.batch, BD = B * (size_t)D.dim;
-    for (int k = 0; k < D.dim; ++k)
-        if (!(inv_mass[k] > 0) || !std::isfinite(inv_mass[k])) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_leapfrog: inverse masses must be positive");
+    if (int rc = check_inv_mass(m, "mcd_hmc_leapfrog", inv_mass)) return rc;
     HHIP_TRY(hipSetDevice(m->device));
     HHIP_TRY(hipMemcpyAsync(D.p, p, sizeof(double) * BD, hipMemcpyHostToDevice, m->stream));
     HHIP_TRY(hipMemcpyAsync(m->d_eps, eps, sizeof(double) * B, hipMemcpyHostToDevice, m->stream));
-    HHIP_TRY(hipMemcpyAsync(m->d_inv_mass, inv_mass, sizeof(double) * D.dim, hipMemcpyHostToDevice, m->stream));
+    if (int rc = upload_inv_mass(m, inv_mass)) return rc;
     if (dir) {
         HHIP_TRY(hipMemcpyAsync(m->d_dir, dir, sizeof(double) * B, hipMemcpyHostToDevice, m->stream));
         D.dir = m->d_dir;
@@ -282,17 +371,16 @@ int mcd_hmc_leapfrog(mcd_hmc_t* m, double* p, const double* eps, const double* d
 int mcd_hmc_step_from(mcd_hmc_t* m, double* q, double* p, double* grad, int have_grad, const double* eps, const double* dir,
                       const double* inv_mass, double* value)
 {
-    if (!m || !q || !p || !grad || !eps || !inv_mass) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_step_from: NULL argument");
+    if (!m || !q || !p || !grad || !eps) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_step_from: NULL argument");
     if (!m->have_state) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_step_from: call mcd_hmc_set_state first (fixes the masked entries)");
     mcd::HmcDev& D = m->dev;
     const size_t B = (size_t)D.batch, BD = B * (size_t)D.dim;
-    for (int k = 0; k < D.dim; ++k)
-        if (!(inv_mass[k] > 0) || !std::isfinite(inv_mass[k])) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_step_from: inverse masses must be positive");
+    if (int rc = check_inv_mass(m, "mcd_hmc_step_from", inv_mass)) return rc;
     HHIP_TRY(hipSetDevice(m->device));
     HHIP_TRY(hipMemcpyAsync(D.q, q, sizeof(double) * BD, hipMemcpyHostToDevice, m->stream));
     HHIP_TRY(hipMemcpyAsync(D.p, p, sizeof(double) * BD, hipMemcpyHostToDevice, m->stream));
     HHIP_TRY(hipMemcpyAsync(m->d_eps, eps, sizeof(double) * B, hipMemcpyHostToDevice, m->stream));
-    HHIP_TRY(hipMemcpyAsync(m->d_inv_mass, inv_mass, sizeof(double) * D.dim, hipMemcpyHostToDevice, m->stream));
+    if (int rc = upload_inv_mass(m, inv_mass)) return rc;
     if (dir) {
         HHIP_TRY(hipMemcpyAsync(m->d_dir, dir, sizeof(double) * B, hipMemcpyHostToDevice, m->stream));
         D.dir = m->d_dir;
@@ -324,6 +412,7 @@ int mcd_hmc_step_from(mcd_hmc_t* m, double* q, double* p, double* grad, int have
 namespace {
 
 constexpr int kNutsMaxDepth = 12;
+static_assert(mcd::kHmcDenseMaxDim == MCD_HMC_DENSE_MAX_DIM, "the kernels' bound is the header's");
 
 int nuts_alloc(mcd_hmc* m)
 {
@@ -381,20 +470,19 @@ extern "C" {
 int mcd_hmc_nuts(mcd_hmc_t* m, const double* eps, const double* inv_mass, int max_depth, uint64_t seed, int64_t chain_offset,
                  uint64_t transition, double* alpha, int32_t* depth)
 {
-    if (!m || !eps || !inv_mass) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts: NULL argument");
+    if (!m || !eps) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts: NULL argument");
     if (!m->have_state) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts: call mcd_hmc_set_state first");
     if (max_depth < 1 || max_depth > kNutsMaxDepth) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts: max_depth must be 1 .. %d", kNutsMaxDepth);
     mcd::HmcDev& D = m->dev;
     const size_t B = (size_t)D.batch;
-    for (int k = 0; k < D.dim; ++k)
-        if (!(inv_mass[k] > 0) || !std::isfinite(inv_mass[k])) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts: inverse masses must be positive");
+    if (int rc = check_inv_mass(m, "mcd_hmc_nuts", inv_mass)) return rc;
     for (size_t b = 0; b < B; ++b)
         if (!(eps[b] > 0) || !std::isfinite(eps[b])) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts: step sizes must be positive");
     if (int rc = m->rec.room("mcd_hmc_nuts", 1)) return rc;
     HHIP_TRY(hipSetDevice(m->device));
     if (int rc = nuts_alloc(m)) return rc;
     HHIP_TRY(hipMemcpyAsync(m->d_eps, eps, sizeof(double) * B, hipMemcpyHostToDevice, m->stream));
-    HHIP_TRY(hipMemcpyAsync(m->d_inv_mass, inv_mass, sizeof(double) * D.dim, hipMemcpyHostToDevice, m->stream));
+    if (int rc = upload_inv_mass(m, inv_mass)) return rc;
     if (int rc = nuts_transition(m, max_depth, seed, chain_offset, transition)) return rc;
     std::vector<double> a(B);
     std::vector<int> na(B), dp(B);
@@ -409,10 +497,16 @@ int mcd_hmc_nuts(mcd_hmc_t* m, const double* eps, const double* inv_mass, int ma
     return MCD_OK;
 }
 
-int mcd_hmc_nuts_run(mcd_hmc_t* m, int n_transitions, int adapt, double* eps, const double* inv_mass, double delta, int max_depth,
-                     uint64_t seed, int64_t chain_offset, uint64_t first_transition, double* mean_alpha, double* q_mean, double* q_var)
+}  // extern "C"
+
+namespace {
+
+// mcd_hmc_nuts_run; q_store (device, [n_transitions][batch][dim], or null) receives the positions after every transition
+int nuts_run(mcd_hmc_t* m, int n_transitions, int adapt, double* eps, const double* inv_mass, double delta, int max_depth, uint64_t seed,
+             int64_t chain_offset, uint64_t first_transition, double* mean_alpha, double* q_mean, double* q_var, double* q_store)
 {
-    if (!m || !eps || !inv_mass) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_run: NULL argument");
+    if (!m || !eps) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_run: NULL argument");
+    if (int rc = check_inv_mass(m, "mcd_hmc_nuts_run", inv_mass)) return rc;
     if (n_transitions < 0) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_run: negative number of transitions");
     if (adapt && !(delta > 0 && delta < 1)) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_run: delta must be in (0, 1)");
     if (int rc = m->rec.room("mcd_hmc_nuts_run", n_transitions)) return rc;
@@ -446,6 +540,7 @@ int mcd_hmc_nuts_run(mcd_hmc_t* m, int n_transitions, int adapt, double* eps, co
             }
             HHIP_TRY(mcd::launch_hmc_moments(D, m->d_s1, m->d_s2, m->stream));
         }
+        if (q_store) HHIP_TRY(hipMemcpyAsync(q_store + (size_t)(t - 1) * B * dim, D.q, sizeof(double) * B * dim, hipMemcpyDeviceToDevice, m->stream));
     }
     if (moments && n_transitions > 0) {
         HHIP_TRY(hipMemcpyAsync(s1.data(), m->d_s1, sizeof(double) * dim, hipMemcpyDeviceToHost, m->stream));
@@ -462,6 +557,96 @@ int mcd_hmc_nuts_run(mcd_hmc_t* m, int n_transitions, int adapt, double* eps, co
         if (q_mean) q_mean[k] = mean;
         if (q_var) q_var[k] = s2[k] / cnt - mean * mean;          // pooled over chains and transitions (what mass tuning uses)
     }
+    return MCD_OK;
+}
+
+// device memory of one call
+struct Scratch {
+    double* p = nullptr;
+    ~Scratch() { (void)hipFree(p); }
+};
+
+}  // namespace
+
+extern "C" {
+
+int mcd_hmc_nuts_run(mcd_hmc_t* m, int n_transitions, int adapt, double* eps, const double* inv_mass, double delta, int max_depth,
+                     uint64_t seed, int64_t chain_offset, uint64_t first_transition, double* mean_alpha, double* q_mean, double* q_var)
+{
+    return nuts_run(m, n_transitions, adapt, eps, inv_mass, delta, max_depth, seed, chain_offset, first_transition, mean_alpha, q_mean, q_var, nullptr);
+}
+
+int mcd_hmc_set_metric(mcd_hmc_t* m, const double* inv_mass_dense)
+{
+    if (!m) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_set_metric: NULL handle");
+    if (!inv_mass_dense) {
+        metric_clear(m);
+        return MCD_OK;
+    }
+    if (m->dev.dim > MCD_HMC_DENSE_MAX_DIM)
+        return hfail(MCD_ERR_UNSUPPORTED, "mcd_hmc_set_metric: dim = %d, a dense metric serves positions of up to MCD_HMC_DENSE_MAX_DIM = %d coordinates",
+                     m->dev.dim, MCD_HMC_DENSE_MAX_DIM);
+    std::vector<double> sym, uinv;
+    char why[256];
+    if (!metric_factors(m->dev.dim, inv_mass_dense, sym, uinv, why, sizeof why)) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_set_metric: %s", why);
+    return metric_install(m, sym, uinv);
+}
+
+int mcd_hmc_get_metric(const mcd_hmc_t* m, int* is_dense, double* inv_mass_dense)
+{
+    if (!m || !is_dense) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_get_metric: NULL argument");
+    *is_dense = m->dev.metric ? 1 : 0;
+    if (m->dev.metric && inv_mass_dense) std::copy(m->h_metric.begin(), m->h_metric.end(), inv_mass_dense);
+    return MCD_OK;
+}
+
+// mcd_hmc_nuts_warmup with the FULL covariance of the window's positions as the inverse mass matrix (k_hmc_cov.hip), the same shrinkage
+// (its diagonal is the rule below) and the same rule for a window that cannot be used.
+int mcd_hmc_nuts_warmup_dense(mcd_hmc_t* m, int windows, int window, double* eps, const double* inv_mass0, double delta, int max_depth,
+                              uint64_t seed, int64_t chain_offset, uint64_t first_transition, double* mean_alpha, double* inv_mass_dense_out)
+{
+    if (!m || !eps || !inv_mass0) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_warmup_dense: NULL argument");
+    if (windows < 1 || window < 1) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_warmup_dense: need windows >= 1 and window >= 1");
+    const size_t B = (size_t)m->dev.batch, dim = (size_t)m->dev.dim;
+    if (m->dev.dim > MCD_HMC_DENSE_MAX_DIM)
+        return hfail(MCD_ERR_UNSUPPORTED, "mcd_hmc_nuts_warmup_dense: dim = %d, a dense metric serves positions of up to MCD_HMC_DENSE_MAX_DIM = %d coordinates",
+                     m->dev.dim, MCD_HMC_DENSE_MAX_DIM);
+    for (size_t k = 0; k < dim; ++k)
+        if (!(inv_mass0[k] > 0) || !std::isfinite(inv_mass0[k])) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_warmup_dense: inverse masses must be positive");
+    if (int rc = m->rec.room("mcd_hmc_nuts_warmup_dense", ((int64_t)windows + 1) * (int64_t)window)) return rc;
+    metric_clear(m);
+    HHIP_TRY(hipSetDevice(m->device));
+    const size_t n = B * (size_t)window;
+    Scratch Q, mom;                                                   // [window][batch][dim] positions; [dim] means + [dim][dim] covariance
+    HHIP_TRY(hipMalloc((void**)&Q.p, sizeof(double) * n * dim));
+    HHIP_TRY(hipMalloc((void**)&mom.p, sizeof(double) * (dim + dim * dim)));
+    std::vector<double> alpha(B), cov(dim * dim), sym, uinv;
+    char why[256];
+    uint64_t t = first_transition;
+    for (int w = 0; w < windows; ++w) {
+        if (int rc = nuts_run(m, window, 1, eps, m->dev.metric ? nullptr : inv_mass0, delta, max_depth, seed, chain_offset, t, alpha.data(), nullptr,
+                              nullptr, Q.p))
+            return rc;
+        t += (uint64_t)window;
+        HHIP_TRY(mcd::launch_hmc_cov(Q.p, (int64_t)n, (int)dim, mom.p, mom.p + dim, m->stream));
+        HHIP_TRY(hipMemcpyAsync(cov.data(), mom.p + dim, sizeof(double) * dim * dim, hipMemcpyDeviceToHost, m->stream));
+        HHIP_TRY(hipStreamSynchronize(m->stream));
+        const double n_eff = (double)n, keep = n_eff / (n_eff + 5.0), floor_ = 1e-3 * (5.0 / (n_eff + 5.0));
+        for (size_t i = 0; i < dim; ++i)
+            for (size_t j = 0; j < dim; ++j) cov[i * dim + j] = keep * cov[i * dim + j] + (i == j ? floor_ : 0.0);
+        // a chain outside the support leaves NaN positions, a degenerate window no factor: keep the metric
+        if (metric_factors((int)dim, cov.data(), sym, uinv, why, sizeof why))
+            if (int rc = metric_install(m, sym, uinv)) return rc;
+    }
+    if (!m->dev.metric) {                                             // no window could be used: the starting masses as the dense metric
+        std::fill(cov.begin(), cov.end(), 0.0);
+        for (size_t k = 0; k < dim; ++k) cov[k * dim + k] = inv_mass0[k];
+        if (!metric_factors((int)dim, cov.data(), sym, uinv, why, sizeof why)) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_warmup_dense: %s", why);
+        if (int rc = metric_install(m, sym, uinv)) return rc;
+    }
+    if (int rc = nuts_run(m, window, 1, eps, nullptr, delta, max_depth, seed, chain_offset, t, alpha.data(), nullptr, nullptr, nullptr)) return rc;
+    if (mean_alpha) std::copy(alpha.begin(), alpha.end(), mean_alpha);
+    if (inv_mass_dense_out) std::copy(m->h_metric.begin(), m->h_metric.end(), inv_mass_dense_out);
     return MCD_OK;
 }
 

@@ -5,6 +5,8 @@
 //            pos_field[i] in {0 birth, 1 death, 2 tH, 3 height, 4 rMu, 5 rVar, 6 rate}, pos_index[i] = node id.
 // One leapfrog step (step size eps_b per chain, diagonal inverse masses):
 //     p += eps/2 grad(q);   q += eps Minv p;   p += eps/2 grad(q)
+// With a dense metric on the handle (D.metric = C = M^-1, mcd_hmc_set_metric) the drift is q += eps (C p), the product of
+// metric_device.hpp by one workgroup per chain; the diagonal kernels and their expressions are untouched.
 // The gradient comes from the batched kernels (k_prior_grad.hip for the prior, k_tree_grad.hip for the likelihood) plus
 // the five-number Jacobian term evaluated here; this file holds the element-wise part: assemble the gradient in the
 // position layout, kick, drift and scatter the new position into the state arrays.  One thread per (chain, coordinate).
@@ -12,6 +14,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "metric_device.hpp"
 #include "mvn_kernels.h"
 
 namespace mcd {
@@ -119,11 +122,30 @@ __global__ __launch_bounds__(256) void k_hmc_collect(HmcDev D)
     }
 }
 
+// q += e (C p) for chain b under the dense metric: the chain's momenta D.p are final (a barrier or a launch boundary lies behind)
+__device__ __forceinline__ void hmc_drift_dense(const HmcDev& D, int64_t b, double e, double* xs)
+{
+    const int64_t o = b * D.dim;
+    double v[kMetricOwned];
+    metric_apply(D.metric, D.dim, false, xs, [&](int k, int) { return D.p[o + k]; }, v);
+    for (int c = 0; c < kMetricOwned; ++c) {
+        const int k = (int)threadIdx.x + 256 * c;
+        if (k >= D.dim) break;
+        double* slot = hmc_state_slot(D, b, D.pos_field[k], D.pos_index[k]);
+        const double q = *slot + e * v[c];
+        *slot = q;
+        D.q[o + k] = q;
+    }
+}
+
 // kick and drift of one leapfrog step in ONE launch: a workgroup per chain, so that a barrier separates "every gradient entry of
 // the chain has been read" (the Jacobian term of a coordinate reads state entries that belong to other coordinates) from "the
 // new position is written into the state".  p += kick eps g;  q += eps M^-1 p.
+// Dense: M^-1 = D.metric (metric_device.hpp), q += eps (C p); the diagonal form keeps its expressions.
+template <bool Dense>
 __global__ __launch_bounds__(256) void k_hmc_kick_drift(HmcDev D, double kick)
 {
+    __shared__ double xs[Dense ? kHmcDenseMaxDim : 1];
     const int64_t b = blockIdx.x;
     const int64_t o = b * D.dim;
     const double e = D.eps[b] * (D.dir ? D.dir[b] : 1.0);
@@ -133,12 +155,24 @@ __global__ __launch_bounds__(256) void k_hmc_kick_drift(HmcDev D, double kick)
         D.p[o + k] = D.p[o + k] + kick * e * g;
     }
     __syncthreads();
-    for (int k = threadIdx.x; k < D.dim; k += blockDim.x) {
-        double* slot = hmc_state_slot(D, b, D.pos_field[k], D.pos_index[k]);
-        const double q = *slot + e * D.inv_mass[k] * D.p[o + k];
-        *slot = q;
-        D.q[o + k] = q;
+    if constexpr (Dense) {
+        hmc_drift_dense(D, b, e, xs);
+    } else {
+        for (int k = threadIdx.x; k < D.dim; k += blockDim.x) {
+            double* slot = hmc_state_slot(D, b, D.pos_field[k], D.pos_index[k]);
+            const double q = *slot + e * D.inv_mass[k] * D.p[o + k];
+            *slot = q;
+            D.q[o + k] = q;
+        }
     }
+}
+
+// the stand-alone drift (k_hmc_drift) under a dense metric: a workgroup per chain
+__global__ __launch_bounds__(256) void k_hmc_drift_dense(HmcDev D)
+{
+    __shared__ double xs[kHmcDenseMaxDim];
+    const int64_t b = blockIdx.x;
+    hmc_drift_dense(D, b, D.eps[b] * (D.dir ? D.dir[b] : 1.0), xs);
 }
 
 // the closing half kick together with k_hmc_collect
@@ -177,12 +211,18 @@ hipError_t launch_hmc_scatter(const HmcDev& D, hipStream_t st)
 }
 hipError_t launch_hmc_drift(const HmcDev& D, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_hmc_drift, dim3(hmc_grid(D)), dim3(256), 0, st, D);
+    if (D.metric)
+        hipLaunchKernelGGL(k_hmc_drift_dense, dim3((unsigned)D.batch), dim3(256), 0, st, D);
+    else
+        hipLaunchKernelGGL(k_hmc_drift, dim3(hmc_grid(D)), dim3(256), 0, st, D);
     return hipGetLastError();
 }
 hipError_t launch_hmc_kick_drift(const HmcDev& D, double kick, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_hmc_kick_drift, dim3((unsigned)D.batch), dim3(256), 0, st, D, kick);
+    if (D.metric)
+        hipLaunchKernelGGL(k_hmc_kick_drift<true>, dim3((unsigned)D.batch), dim3(256), 0, st, D, kick);
+    else
+        hipLaunchKernelGGL(k_hmc_kick_drift<false>, dim3((unsigned)D.batch), dim3(256), 0, st, D, kick);
     return hipGetLastError();
 }
 hipError_t launch_hmc_kick_collect(const HmcDev& D, double kick, hipStream_t st)

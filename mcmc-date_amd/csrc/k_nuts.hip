@@ -19,10 +19,17 @@
 // merge, 0x100000 + leaf number -> reservoir.  tests/test_gpu_nuts.py holds the CPU twin that follows the same streams.
 //
 // One workgroup (256 threads) per chain; coordinates strided over the threads; dot products by workgroup reductions.
+//
+// The metric: diagonal inverse masses D.inv_mass, or -- template <Dense>, chosen by the launchers when D.metric is set
+// (mcd_hmc_set_metric) -- a full inverse mass matrix C = U U^T: momenta p = U^-T z from the same normal draws z, kinetic energy
+// 1/2 p^T C p, drift q += eps (C p), U-turn (q+ - q-)^T C r >= 0 at both ends from ONE product w = C (q+ - q-).  The products are
+// metric_device.hpp's; slice, doubling, reservoir, merge, divergence test and random streams are the same code.  The diagonal
+// branches keep their expressions as they were.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
+#include "metric_device.hpp"
 #include "mh_device.hpp"
 #include "mvn_kernels.h"
 
@@ -82,13 +89,26 @@ __device__ __forceinline__ double* nuts_state_slot(const HmcDev& D, int64_t b, i
 }
 
 // (q_minus, r_minus, q_plus, r_plus) do not turn back on each other: (q+ - q-) . M^-1 r >= 0 at both ends (Algorithm 3)
-__device__ __forceinline__ bool nuts_no_u_turn(const HmcDev& D, const double* qm, const double* rm, const double* qp, const double* rp, double* red)
+template <bool Dense>
+__device__ __forceinline__ bool nuts_no_u_turn(const HmcDev& D, const double* qm, const double* rm, const double* qp, const double* rp, double* red,
+                                               double* xs)
 {
     double a = 0.0, c = 0.0;
-    for (int k = threadIdx.x; k < D.dim; k += blockDim.x) {
-        const double d = qp[k] - qm[k];
-        a += d * (rm[k] * D.inv_mass[k]);
-        c += d * (rp[k] * D.inv_mass[k]);
+    if constexpr (Dense) {
+        double w[kMetricOwned];
+        metric_apply(D.metric, D.dim, false, xs, [&](int k, int) { return qp[k] - qm[k]; }, w);
+        for (int i = 0; i < kMetricOwned; ++i) {
+            const int k = (int)threadIdx.x + 256 * i;
+            if (k >= D.dim) break;
+            a += w[i] * rm[k];
+            c += w[i] * rp[k];
+        }
+    } else {
+        for (int k = threadIdx.x; k < D.dim; k += blockDim.x) {
+            const double d = qp[k] - qm[k];
+            a += d * (rm[k] * D.inv_mass[k]);
+            c += d * (rp[k] * D.inv_mass[k]);
+        }
     }
     a = nuts_block_sum(a, red);
     c = nuts_block_sum(c, red);
@@ -96,21 +116,38 @@ __device__ __forceinline__ bool nuts_no_u_turn(const HmcDev& D, const double* qm
 }
 
 // the edge that is extended next goes to D.q / D.p / D.grad; half kick, drift, new position into the state arrays
-__device__ __forceinline__ void nuts_launch_leaf(const HmcDev& D, const NutsDev& N, int64_t b, int v)
+template <bool Dense>
+__device__ __forceinline__ void nuts_launch_leaf(const HmcDev& D, const NutsDev& N, int64_t b, int v, double* xs)
 {
     const int64_t o = b * D.dim;
     const double* eq = (v < 0 ? N.qm : N.qp) + o;
     const double* ep = (v < 0 ? N.pm : N.pp) + o;
     const double* eg = (v < 0 ? N.gm : N.gp) + o;
     const double e = D.eps[b] * (double)v;
-    for (int k = threadIdx.x; k < D.dim; k += blockDim.x) {
-        const double g = eg[k];
-        const double p = ep[k] + 0.5 * e * g;                       // p += eps / 2 grad
-        const double q = eq[k] + e * D.inv_mass[k] * p;             // q += eps M^-1 p
-        D.p[o + k] = p;
-        D.q[o + k] = q;
-        D.grad[o + k] = g;
-        *nuts_state_slot(D, b, D.pos_field[k], D.pos_index[k]) = q;
+    if constexpr (Dense) {
+        double cp[kMetricOwned];
+        metric_apply(D.metric, D.dim, false, xs, [&](int k, int) { return ep[k] + 0.5 * e * eg[k]; }, cp);
+        for (int i = 0; i < kMetricOwned; ++i) {
+            const int k = (int)threadIdx.x + 256 * i;
+            if (k >= D.dim) break;
+            const double g = eg[k];
+            const double p = ep[k] + 0.5 * e * g;                   // p += eps / 2 grad
+            const double q = eq[k] + e * cp[i];                     // q += eps (C p)
+            D.p[o + k] = p;
+            D.q[o + k] = q;
+            D.grad[o + k] = g;
+            *nuts_state_slot(D, b, D.pos_field[k], D.pos_index[k]) = q;
+        }
+    } else {
+        for (int k = threadIdx.x; k < D.dim; k += blockDim.x) {
+            const double g = eg[k];
+            const double p = ep[k] + 0.5 * e * g;                       // p += eps / 2 grad
+            const double q = eq[k] + e * D.inv_mass[k] * p;             // q += eps M^-1 p
+            D.p[o + k] = p;
+            D.q[o + k] = q;
+            D.grad[o + k] = g;
+            *nuts_state_slot(D, b, D.pos_field[k], D.pos_index[k]) = q;
+        }
     }
     if (threadIdx.x == 0) const_cast<double*>(D.dir)[b] = (double)v;
 }
@@ -124,29 +161,56 @@ __device__ __forceinline__ int nuts_direction(uint64_t seed, int64_t chain, uint
 
 // Start of a transition: momenta, slice variable, the tree = the current point, first doubling, first leaf on its way.
 // Needs D.q, D.grad, D.value of the current state (mcd_hmc_set_state / the previous transition).
+template <bool Dense>
 __global__ __launch_bounds__(256) void k_nuts_begin(HmcDev D, NutsDev N, uint64_t seed, int64_t chain0, uint64_t transition)
 {
     __shared__ double red[4];
+    __shared__ double xs[Dense ? kHmcDenseMaxDim : 1];
     const int64_t b = blockIdx.x;
     const int64_t o = b * D.dim;
     const Rng g = mh_rng(seed, chain0 + b, transition);
     double kin = 0.0;
-    for (int k = threadIdx.x; k < D.dim; k += blockDim.x) {
-        double ua, ub;
-        philox_block(g, 0x4000u + (uint32_t)(k >> 1), ua, ub);
-        const double rad = sqrt(-2.0 * log(ua)), ang = 6.28318530717958647692 * ub;
-        const double z = (k & 1) ? rad * sin(ang) : rad * cos(ang);
-        const double p = z / sqrt(D.inv_mass[k]);                   // p ~ N(0, M)
-        kin += p * p * D.inv_mass[k];
-        const double q = D.q[o + k], gr = D.grad[o + k];
-        N.qm[o + k] = q;
-        N.qp[o + k] = q;
-        N.pm[o + k] = p;
-        N.pp[o + k] = p;
-        N.gm[o + k] = gr;
-        N.gp[o + k] = gr;
-        N.qn[o + k] = q;
-        N.gn[o + k] = gr;
+    if constexpr (Dense) {
+        double p[kMetricOwned], cp[kMetricOwned];
+        metric_apply(D.metric_uinv, D.dim, true, xs, [&](int k, int) {
+            double ua, ub;
+            philox_block(g, 0x4000u + (uint32_t)(k >> 1), ua, ub);
+            const double rad = sqrt(-2.0 * log(ua)), ang = 6.28318530717958647692 * ub;
+            return (k & 1) ? rad * sin(ang) : rad * cos(ang);
+        }, p);                                                      // p = U^-T z ~ N(0, C^-1) = N(0, M)
+        metric_apply(D.metric, D.dim, false, xs, [&](int, int i) { return p[i]; }, cp);
+        for (int i = 0; i < kMetricOwned; ++i) {
+            const int k = (int)threadIdx.x + 256 * i;
+            if (k >= D.dim) break;
+            kin += p[i] * cp[i];
+            const double q = D.q[o + k], gr = D.grad[o + k];
+            N.qm[o + k] = q;
+            N.qp[o + k] = q;
+            N.pm[o + k] = p[i];
+            N.pp[o + k] = p[i];
+            N.gm[o + k] = gr;
+            N.gp[o + k] = gr;
+            N.qn[o + k] = q;
+            N.gn[o + k] = gr;
+        }
+    } else {
+        for (int k = threadIdx.x; k < D.dim; k += blockDim.x) {
+            double ua, ub;
+            philox_block(g, 0x4000u + (uint32_t)(k >> 1), ua, ub);
+            const double rad = sqrt(-2.0 * log(ua)), ang = 6.28318530717958647692 * ub;
+            const double z = (k & 1) ? rad * sin(ang) : rad * cos(ang);
+            const double p = z / sqrt(D.inv_mass[k]);                   // p ~ N(0, M)
+            kin += p * p * D.inv_mass[k];
+            const double q = D.q[o + k], gr = D.grad[o + k];
+            N.qm[o + k] = q;
+            N.qp[o + k] = q;
+            N.pm[o + k] = p;
+            N.pp[o + k] = p;
+            N.gm[o + k] = gr;
+            N.gp[o + k] = gr;
+            N.qn[o + k] = q;
+            N.gn[o + k] = gr;
+        }
     }
     kin = 0.5 * nuts_block_sum(kin, red);
     const double joint0 = D.value[b] - kin;
@@ -171,15 +235,17 @@ __global__ __launch_bounds__(256) void k_nuts_begin(HmcDev D, NutsDev N, uint64_
         N.diverged[b] = 0;
     }
     __syncthreads();
-    nuts_launch_leaf(D, N, b, v);
+    nuts_launch_leaf<Dense>(D, N, b, v, xs);
 }
 
 // One round: the gradient kernels have run at the position the drift reached.  Finish the leapfrog step (second half kick),
 // book the leaf, decide, and send the next leaf on its way -- or mark the chain done.
+template <bool Dense>
 __global__ __launch_bounds__(256) void k_nuts_step(HmcDev D, NutsDev N, uint64_t seed, int64_t chain0, uint64_t transition, int max_depth,
                                                    int* __restrict__ active)
 {
     __shared__ double red[4];
+    __shared__ double xs[Dense ? kHmcDenseMaxDim : 1];
     __shared__ int flag;
     const int64_t b = blockIdx.x;
     if (N.done[b]) return;                                          // workgroup-uniform
@@ -194,10 +260,19 @@ __global__ __launch_bounds__(256) void k_nuts_step(HmcDev D, NutsDev N, uint64_t
     for (int k = threadIdx.x; k < D.dim; k += blockDim.x) {
         const double g = nuts_grad_entry(D, b, D.pos_field[k], D.pos_index[k]);
         const double p = D.p[o + k] + 0.5 * e * g;
-        kin += p * p * D.inv_mass[k];
+        if constexpr (!Dense) kin += p * p * D.inv_mass[k];
         eq[k] = D.q[o + k];
         ep[k] = p;
         eg[k] = g;
+    }
+    if constexpr (Dense) {                                          // 1/2 p^T C p; every thread reads back the entries it has just written
+        double cp[kMetricOwned];
+        metric_apply(D.metric, D.dim, false, xs, [&](int k, int) { return ep[k]; }, cp);
+        for (int i = 0; i < kMetricOwned; ++i) {
+            const int k = (int)threadIdx.x + 256 * i;
+            if (k >= D.dim) break;
+            kin += ep[k] * cp[i];
+        }
     }
     kin = 0.5 * nuts_block_sum(kin, red);
     double lp;
@@ -246,7 +321,7 @@ __global__ __launch_bounds__(256) void k_nuts_step(HmcDev D, NutsDev N, uint64_t
         } else if (((i + 1) & (size - 1)) == 0 && s1) {
             __syncthreads();
             // in time order: going forwards the first leaf is the minus end, going backwards the plus end
-            const bool ok = v > 0 ? nuts_no_u_turn(D, lq, lr, eq, ep, red) : nuts_no_u_turn(D, eq, ep, lq, lr, red);
+            const bool ok = v > 0 ? nuts_no_u_turn<Dense>(D, lq, lr, eq, ep, red, xs) : nuts_no_u_turn<Dense>(D, eq, ep, lq, lr, red, xs);
             s1 = s1 && ok;
         }
     }
@@ -268,7 +343,7 @@ __global__ __launch_bounds__(256) void k_nuts_step(HmcDev D, NutsDev N, uint64_t
         }
         n += n1;
         __syncthreads();
-        const bool s = nuts_no_u_turn(D, N.qm + o, N.pm + o, N.qp + o, N.pp + o, red);
+        const bool s = nuts_no_u_turn<Dense>(D, N.qm + o, N.pm + o, N.qp + o, N.pp + o, red, xs);
         jn = j + 1;
         if (!s || jn >= max_depth) {
             done = 1;
@@ -293,7 +368,7 @@ __global__ __launch_bounds__(256) void k_nuts_step(HmcDev D, NutsDev N, uint64_t
         flag = done;
     }
     __syncthreads();
-    if (!flag) nuts_launch_leaf(D, N, b, vn);
+    if (!flag) nuts_launch_leaf<Dense>(D, N, b, vn, xs);
 }
 
 // End of a transition: the proposal becomes the chain's state (position, gradient and ln target with it)
@@ -312,13 +387,19 @@ __global__ __launch_bounds__(256) void k_nuts_end(HmcDev D, NutsDev N)
 
 hipError_t launch_nuts_begin(const HmcDev& D, const NutsDev& N, uint64_t seed, int64_t chain0, uint64_t transition, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_nuts_begin, dim3((unsigned)D.batch), dim3(256), 0, st, D, N, seed, chain0, transition);
+    if (D.metric)
+        hipLaunchKernelGGL(k_nuts_begin<true>, dim3((unsigned)D.batch), dim3(256), 0, st, D, N, seed, chain0, transition);
+    else
+        hipLaunchKernelGGL(k_nuts_begin<false>, dim3((unsigned)D.batch), dim3(256), 0, st, D, N, seed, chain0, transition);
     return hipGetLastError();
 }
 hipError_t launch_nuts_step(const HmcDev& D, const NutsDev& N, uint64_t seed, int64_t chain0, uint64_t transition, int max_depth, int* active,
                             hipStream_t st)
 {
-    hipLaunchKernelGGL(k_nuts_step, dim3((unsigned)D.batch), dim3(256), 0, st, D, N, seed, chain0, transition, max_depth, active);
+    if (D.metric)
+        hipLaunchKernelGGL(k_nuts_step<true>, dim3((unsigned)D.batch), dim3(256), 0, st, D, N, seed, chain0, transition, max_depth, active);
+    else
+        hipLaunchKernelGGL(k_nuts_step<false>, dim3((unsigned)D.batch), dim3(256), 0, st, D, N, seed, chain0, transition, max_depth, active);
     return hipGetLastError();
 }
 hipError_t launch_nuts_end(const HmcDev& D, const NutsDev& N, hipStream_t st)

@@ -295,7 +295,11 @@ struct HmcDev {
     double *ll, *gl_H, *gl_R, *gl_tH, *gl_rMu;   // likelihood: value and gradient
     double *q, *p, *grad, *value;           // [batch][dim] position, momentum, gradient; [batch] ln target
     const double *eps, *dir, *inv_mass;     // [batch] step sizes, [batch] +-1 or null, [dim] inverse masses
+    // a dense metric (mcd_hmc_set_metric; null = the diagonal inv_mass): C = M^-1 [dim][dim], exactly symmetric, and U^-1 of
+    // C = U U^T (lower triangular, row-major, zeros above the diagonal); dim <= kHmcDenseMaxDim
+    const double *metric, *metric_uinv;
 };
+constexpr int kHmcDenseMaxDim = 512;        // = MCD_HMC_DENSE_MAX_DIM: two coordinates per thread of a chain's workgroup, x in 4 KiB of LDS
 
 // Per-chain state of the device NUTS (k_nuts.hip); all pointers are device memory, position layout [batch][dim] unless noted.
 struct NutsDev {
@@ -322,6 +326,10 @@ hipError_t launch_hmc_record(const HmcDev& D, const NutsDev& N, const MhRec& R, 
 hipError_t launch_hmc_record_stats(const MhRecDims& S, const MhRec& R, int64_t first, int64_t count, double* stats, hipStream_t st);
 // s1[k] += sum_b q[b][k], s2[k] += sum_b q[b][k]^2 in the order b = 0, 1, ... (what mcd_hmc_nuts_run adds per transition); s1, s2 [dim]
 hipError_t launch_hmc_moments(const HmcDev& D, double* s1, double* s2, hipStream_t st);
+// The window covariance of mcd_hmc_nuts_warmup_dense (k_hmc_cov.hip): Q [n][dim] the positions a window visited, mean[k] = sum_s Q[s][k] / n,
+// cov[i][j] = sum_s (Q[s][i] - mean[i]) (Q[s][j] - mean[j]) / n, both sums in the order s = 0, 1, ...: two passes, no atomics, the same
+// bits on every call
+hipError_t launch_hmc_cov(const double* Q, int64_t n, int dim, double* mean, double* cov, hipStream_t st);
 
 // The choice of form and the public launch_logpdf / launch_grad / launch_tree_logpdf / launch_tree_grad: sweep_launch.cpp.
 int padded_blocks(int n);          // supported R for dimension n, or -1

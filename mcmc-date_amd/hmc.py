@@ -18,6 +18,7 @@ The product path is `Leapfrog.nuts` / `Leapfrog.nuts_run`: the same algorithm as
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from typing import Optional
 
@@ -29,6 +30,60 @@ from .likelihood import SparseTreeLikelihood, TreeLikelihood
 from .prior import PriorFunction
 from .recorder import DriverCalls
 from .state import StateBatch
+
+
+def _odp(a):
+    """dp of an optional array."""
+    return None if a is None else dp(a)
+
+
+# ---- the dense metric's algebra restated in numpy (what tests/test_gpu_dense_metric.py compares the device with) -------------------------
+def shrunk_covariance(Q) -> np.ndarray:
+    """The metric mcd_hmc_nuts_warmup_dense takes from the n positions Q [n, dim] of a window: n / (n + 5) Cov + 1e-3 5 / (n + 5) I,
+    Cov the centred maximum-likelihood covariance (divided by n) -- Stan's regularisation, whose diagonal is nuts_warmup's rule."""
+    Q = np.asarray(Q, np.float64)
+    n, dim = Q.shape
+    d = Q - Q.mean(axis=0)
+    return (n / (n + 5.0)) * (d.T @ d / n) + 1e-3 * (5.0 / (n + 5.0)) * np.eye(dim)
+
+
+def metric_factors(C):
+    """(U, W) of a dense metric C = M^-1: U lower triangular with U U^T = C, W = U^-T (upper triangular), so W W^T = C^-1 = M and
+    p = W z has covariance M for standard normal z."""
+    U = np.linalg.cholesky(np.asarray(C, np.float64))
+    W = np.triu(np.linalg.solve(U, np.eye(U.shape[0])).T)         # (the general solver leaves rounding dust below the diagonal)
+    return U, W
+
+
+class _Metric:
+    """M^-1 as the numpy helpers below use it: a vector (diagonal) or a symmetric matrix (dense)."""
+
+    def __init__(self, inv_mass, dim: int):
+        a = np.asarray(inv_mass, np.float64)
+        self.dense = a.ndim == 2
+        self.a = np.ascontiguousarray(a if self.dense else np.broadcast_to(a, (dim,)))
+        self.W = metric_factors(self.a)[1] if self.dense else None
+
+    def apply(self, r):
+        """M^-1 r, for r [dim] or [B, dim]."""
+        return r @ self.a if self.dense else r * self.a
+
+    def kinetic(self, r):
+        return 0.5 * np.sum(r * self.apply(r), axis=-1)
+
+    def momenta(self, z):
+        """z ~ N(0, I) [B, dim] -> p ~ N(0, M)."""
+        return z @ self.W.T if self.dense else z / np.sqrt(self.a)
+
+    def device_arg(self, lf):
+        """What Leapfrog's calls take as inv_mass: the vector, or None after making sure the handle holds this dense metric."""
+        if not self.dense:
+            return self.a
+        cur = lf.metric()
+        if cur is None or not np.array_equal(cur, 0.5 * (self.a + self.a.T)):
+            lf.set_metric(self.a)
+        return None
+
 
 class Leapfrog(DriverCalls):
     """B chains on one GPU.  `tree_lik` (a TreeLikelihood, or a SparseTreeLikelihood: the precision matrix stays sparse on the device,
@@ -49,28 +104,71 @@ class Leapfrog(DriverCalls):
         _capi.check(_capi.lib().mcd_hmc_get_position(self._h, dp(q), dp(v), dp(g)))
         return q, v, g
 
+    def _inv_mass(self, inv_mass):
+        """The vector argument of the diagonal metric, [dim] (a scalar is broadcast); None -- the handle's dense metric -- stays None."""
+        if inv_mass is None:
+            return None
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(inv_mass, np.float64), (self.dim,)))
+
+    # -- the dense metric (mcd_hmc_set_metric): the full inverse mass matrix C = M^-1 in the place of the vector inv_mass ------
+    def set_metric(self, C):
+        """C [dim, dim], symmetric positive definite, becomes the handle's metric (momenta p = U^-T z with C = U U^T, kinetic energy
+        1/2 p^T C p, drift q += eps C p, U-turn test through C); leapfrog / step_from / nuts / nuts_run then take inv_mass=None.
+        Refused (McdError, the handle untouched): a non-finite entry, an asymmetric pair, not positive definite, dim > 512."""
+        C = np.ascontiguousarray(C, dtype=np.float64)
+        if C.shape != (self.dim, self.dim):
+            raise ValueError("set_metric: C must be [dim, dim]")
+        _capi.check(_capi.lib().mcd_hmc_set_metric(self._h, dp(C)))
+
+    def clear_metric(self):
+        """Back to the diagonal metric: the handle is what it was before set_metric."""
+        _capi.check(_capi.lib().mcd_hmc_set_metric(self._h, None))
+
+    def metric(self):
+        """The stored, exactly symmetric C [dim, dim] of the dense metric, or None when the handle has none."""
+        dense = ctypes.c_int(0)
+        _capi.check(_capi.lib().mcd_hmc_get_metric(self._h, ctypes.byref(dense), None))
+        if not dense.value:
+            return None
+        C = np.empty((self.dim, self.dim))
+        _capi.check(_capi.lib().mcd_hmc_get_metric(self._h, ctypes.byref(dense), dp(C)))
+        return C
+
+    def nuts_warmup_dense(self, eps0, inv_mass0, windows: int = 3, window: int = 60, delta: float = 0.65, max_depth: int = 6, seed: int = 0,
+                          first_transition: int = 0, chain_offset: int = 0):
+        """Step sizes and the FULL mass matrix tuned in the library (mcd_hmc_nuts_warmup_dense: the schedule of nuts_warmup, after every
+        window C = shrunk_covariance of the positions it visited) from the diagonal inv_mass0.  The final metric stays set on the
+        handle.  Returns (eps [B], C [dim, dim], mean acceptance statistic of the closing window [B])."""
+        eps = np.array(np.broadcast_to(np.asarray(eps0, np.float64), (self.batch,)), dtype=np.float64, order="C")
+        im = self._inv_mass(inv_mass0)
+        ma, C = np.empty(self.batch), np.empty((self.dim, self.dim))
+        _capi.check(_capi.lib().mcd_hmc_nuts_warmup_dense(self._h, int(windows), int(window), dp(eps), dp(im), float(delta), int(max_depth), int(seed),
+                                                          int(chain_offset), int(first_transition), dp(ma), dp(C)))
+        return eps, C, ma
+
     def leapfrog(self, p, eps, inv_mass, n_steps: int, direction=None):
         """n_steps leapfrog steps from the current state with momenta p [B, dim]; returns the new momenta (the state is
-        advanced on the device; read it with position() / state())."""
+        advanced on the device; read it with position() / state()).  inv_mass=None: the handle's dense metric (set_metric)."""
         p = np.array(p, dtype=np.float64, order="C")
         eps = np.ascontiguousarray(np.broadcast_to(np.asarray(eps, np.float64), (self.batch,)))
-        inv_mass = np.ascontiguousarray(np.broadcast_to(np.asarray(inv_mass, np.float64), (self.dim,)))
+        inv_mass = self._inv_mass(inv_mass)
         d = None if direction is None else np.ascontiguousarray(direction, dtype=np.float64)
         if p.shape != (self.batch, self.dim):
             raise ValueError("leapfrog: p must be [batch, dim]")
-        _capi.check(_capi.lib().mcd_hmc_leapfrog(self._h, dp(p), dp(eps), dp(d) if d is not None else None, dp(inv_mass), int(n_steps)))
+        _capi.check(_capi.lib().mcd_hmc_leapfrog(self._h, dp(p), dp(eps), _odp(d), _odp(inv_mass),
+                                                 int(n_steps)))
         return p
 
 
     def nuts(self, eps, inv_mass, max_depth: int = 8, seed: int = 0, transition: int = 0, chain_offset: int = 0):
         """One NUTS transition of every chain ON THE DEVICE (mcd_hmc_nuts, csrc/k_nuts.hip: Hoffman & Gelman 2014, Algorithm 3
         as a per-chain state machine; counter-based random streams (seed, chain_offset + b, transition)).  Returns (mean
-        acceptance statistic [B], tree depth [B]); the chains' new states are on the device."""
+        acceptance statistic [B], tree depth [B]); the chains' new states are on the device.  inv_mass=None: the handle's dense metric."""
         eps = np.ascontiguousarray(np.broadcast_to(np.asarray(eps, np.float64), (self.batch,)))
-        inv_mass = np.ascontiguousarray(np.broadcast_to(np.asarray(inv_mass, np.float64), (self.dim,)))
+        inv_mass = self._inv_mass(inv_mass)
         alpha = np.empty(self.batch)
         depth = np.empty(self.batch, np.int32)
-        _capi.check(_capi.lib().mcd_hmc_nuts(self._h, dp(eps), dp(inv_mass), int(max_depth), int(seed), int(chain_offset), int(transition),
+        _capi.check(_capi.lib().mcd_hmc_nuts(self._h, dp(eps), _odp(inv_mass), int(max_depth), int(seed), int(chain_offset), int(transition),
                                              dp(alpha), ip(depth)))
         return alpha, depth
 
@@ -78,11 +176,12 @@ class Leapfrog(DriverCalls):
                  first_transition: int = 0, chain_offset: int = 0):
         """n transitions in the library (mcd_hmc_nuts_run); adapt: dual averaging of the step sizes (Algorithm 6).  Returns
         (eps [B] -- the averaged step sizes when adapting --, mean acceptance statistic [B], position means [dim], pooled
-        position variances [dim])."""
+        position variances [dim]).  inv_mass=None: the handle's dense metric."""
         eps = np.array(np.broadcast_to(np.asarray(eps, np.float64), (self.batch,)), dtype=np.float64, order="C")
-        inv_mass = np.ascontiguousarray(np.broadcast_to(np.asarray(inv_mass, np.float64), (self.dim,)))
+        inv_mass = self._inv_mass(inv_mass)
         ma, qm, qv = np.empty(self.batch), np.empty(self.dim), np.empty(self.dim)
-        _capi.check(_capi.lib().mcd_hmc_nuts_run(self._h, int(n_transitions), int(bool(adapt)), dp(eps), dp(inv_mass), float(delta), int(max_depth),
+        _capi.check(_capi.lib().mcd_hmc_nuts_run(self._h, int(n_transitions), int(bool(adapt)), dp(eps), _odp(inv_mass),
+                                                 float(delta), int(max_depth),
                                                  int(seed), int(chain_offset), int(first_transition), dp(ma), dp(qm), dp(qv)))
         return eps, ma, qm, qv
 
@@ -127,31 +226,32 @@ class Leapfrog(DriverCalls):
         return RecordSummary(pooled, self.topo.n_nodes, used, lag, pc, stats)
 
     def step_from(self, q, p, grad, eps, inv_mass, direction=None, have_grad=True):
-        """One leapfrog step from the given phase points (all [B, dim]); returns (q', p', grad', ln target')."""
+        """One leapfrog step from the given phase points (all [B, dim]); returns (q', p', grad', ln target').  inv_mass=None: the
+        handle's dense metric."""
         q = np.array(q, dtype=np.float64, order="C")
         p = np.array(p, dtype=np.float64, order="C")
         g = np.array(grad, dtype=np.float64, order="C")
         eps = np.ascontiguousarray(np.broadcast_to(np.asarray(eps, np.float64), (self.batch,)))
-        inv_mass = np.ascontiguousarray(np.broadcast_to(np.asarray(inv_mass, np.float64), (self.dim,)))
+        inv_mass = self._inv_mass(inv_mass)
         d = None if direction is None else np.ascontiguousarray(direction, dtype=np.float64)
         v = np.empty(self.batch)
         _capi.check(_capi.lib().mcd_hmc_step_from(self._h, dp(q), dp(p), dp(g), int(bool(have_grad)), dp(eps),
-                                                  dp(d) if d is not None else None, dp(inv_mass), dp(v)))
+                                                  _odp(d), _odp(inv_mass), dp(v)))
         return q, p, g, v
 
 
 def hmc_transition(lf: Leapfrog, rng: np.random.Generator, eps, inv_mass, n_steps: int) -> np.ndarray:
     """One fixed-length HMC transition for every chain: p ~ N(0, M), n leapfrog steps, accept with probability
     min(1, exp(H_old - H_new)), H = -ln target + 1/2 p^T M^-1 p.  Rejected chains (and chains that left the support:
-    NaN) are put back.  Returns the acceptance mask."""
-    inv_mass = np.broadcast_to(np.asarray(inv_mass, np.float64), (lf.dim,))
+    NaN) are put back.  inv_mass: [dim], or a dense metric [dim, dim] (set on the handle).  Returns the acceptance mask."""
+    met = _Metric(inv_mass, lf.dim)
     old = lf.state()
     _, v0, _ = lf.position()
-    p0 = rng.normal(size=(lf.batch, lf.dim)) / np.sqrt(inv_mass)
-    h0 = -v0 + 0.5 * np.sum(p0 * p0 * inv_mass, axis=1)
-    p1 = lf.leapfrog(p0, eps, inv_mass, n_steps)
+    p0 = met.momenta(rng.normal(size=(lf.batch, lf.dim)))
+    h0 = -v0 + met.kinetic(p0)
+    p1 = lf.leapfrog(p0, eps, met.device_arg(lf), n_steps)
     _, v1, _ = lf.position()
-    h1 = -v1 + 0.5 * np.sum(p1 * p1 * inv_mass, axis=1)
+    h1 = -v1 + met.kinetic(p1)
     with np.errstate(over="ignore", invalid="ignore"):
         accept = np.log(rng.uniform(size=lf.batch)) < (h0 - h1)
     accept &= np.isfinite(h1)
@@ -172,13 +272,20 @@ DELTA_MAX = 1000.0
 
 def _nuts_chain(q0, g0, logp0, r0, log_u, rng, inv_mass, max_depth, stats):
     """Generator of one chain's transition.  Yields leapfrog requests (q, r, grad, direction) and receives
-    (q', r', grad', ln target'); returns the selected (q, grad, ln target)."""
+    (q', r', grad', ln target'); returns the selected (q, grad, ln target).  inv_mass: [dim], or a dense metric [dim, dim]."""
+    inv_mass = np.asarray(inv_mass, np.float64)
+    dense = inv_mass.ndim == 2
 
     def kinetic(r):
+        if dense:
+            return 0.5 * float(np.dot(r, inv_mass @ r))
         return 0.5 * float(np.sum(r * r * inv_mass))
 
     def no_u_turn(qm, rm, qp, rp):
         d = qp - qm
+        if dense:
+            w = inv_mass @ d                                # one product serves both ends: the metric is symmetric
+            return float(np.dot(w, rm)) >= 0.0 and float(np.dot(w, rp)) >= 0.0
         return float(np.dot(d, rm * inv_mass)) >= 0.0 and float(np.dot(d, rp * inv_mass)) >= 0.0
 
     def build_tree(q, r, g, v, j):
@@ -227,13 +334,15 @@ def _nuts_chain(q0, g0, logp0, r0, log_u, rng, inv_mass, max_depth, stats):
 def nuts_transition(lf: Leapfrog, rng: np.random.Generator, eps, inv_mass, max_depth: int = 8):
     """One NUTS transition (Algorithm 3) for every chain of `lf`, all chains advancing their trees in lock step on the
     device.  eps: scalar or [B].  Returns (mean acceptance statistic alpha / n_alpha per chain [B], tree depth [B]);
-    the chains' new states are on the device (lf.state(), lf.position())."""
+    the chains' new states are on the device (lf.state(), lf.position()).  inv_mass: [dim], or a dense metric [dim, dim], which is
+    set on the handle."""
     B, D = lf.batch, lf.dim
-    inv_mass = np.ascontiguousarray(np.broadcast_to(np.asarray(inv_mass, np.float64), (D,)))
+    met = _Metric(inv_mass, D)
+    inv_mass, dev_mass = met.a, met.device_arg(lf)
     eps = np.ascontiguousarray(np.broadcast_to(np.asarray(eps, np.float64), (B,)))
     q0, lp0, g0 = lf.position()
-    r0 = rng.normal(size=(B, D)) / np.sqrt(inv_mass)
-    joint0 = lp0 - 0.5 * np.sum(r0 * r0 * inv_mass, axis=1)
+    r0 = met.momenta(rng.normal(size=(B, D)))
+    joint0 = lp0 - met.kinetic(r0)
     log_u = joint0 + np.log(rng.uniform(size=B))
     chain_rngs = [np.random.default_rng(rng.integers(0, 2 ** 63)) for _ in range(B)]
     stats = [{"alpha": 0.0, "n_alpha": 0, "joint0": float(joint0[b]), "depth": 0} for b in range(B)]
@@ -257,7 +366,7 @@ def nuts_transition(lf: Leapfrog, rng: np.random.Generator, eps, inv_mass, max_d
                 q_in[b], g_in[b] = result[b][0], result[b][1]
                 p_in[b] = 0.0
                 direction[b] = 1.0
-        q1, p1, g1, lp1 = lf.step_from(q_in, p_in, g_in, eps, inv_mass, direction=direction, have_grad=True)
+        q1, p1, g1, lp1 = lf.step_from(q_in, p_in, g_in, eps, dev_mass, direction=direction, have_grad=True)
         for b in range(B):
             if request[b] is None:
                 continue
@@ -268,7 +377,7 @@ def nuts_transition(lf: Leapfrog, rng: np.random.Generator, eps, inv_mass, max_d
                 result[b] = done.value
     # the selected points become the chains' states (zero-length step: the device evaluates ln target and gradient there)
     q_sel = np.array([r[0] for r in result])
-    lf.step_from(q_sel, np.zeros((B, D)), np.array([r[1] for r in result]), np.zeros(B), inv_mass, have_grad=True)
+    lf.step_from(q_sel, np.zeros((B, D)), np.array([r[1] for r in result]), np.zeros(B), dev_mass, have_grad=True)
     alpha = np.array([s["alpha"] / max(1, s["n_alpha"]) for s in stats])
     return alpha, np.array([s["depth"] for s in stats])
 
@@ -299,14 +408,17 @@ class DualAveraging:
 
 
 def nuts_warmup(lf: Leapfrog, rng: np.random.Generator, n_windows: int = 3, window: int = 60, eps0: float = 0.02, delta: float = 0.65,
-                max_depth: int = 6):
+                max_depth: int = 6, inv_mass=None):
     """Warm-up of step sizes and diagonal masses (the reference tunes both: `HTuningConf HTuneLeapfrog HTuneAllMasses`,
     app/Hamiltonian.hs:62-63; `mcmc`'s own scheme is not restated).  Windows of `window` transitions: dual averaging
     of the step sizes inside a window, then the inverse masses are set to the pooled variance of the positions visited
     in that window (over chains and transitions, shrunk towards their mean for stability).  The first window starts
-    from inverse masses (0.1 q)^2.  Returns (eps [B], inv_mass [dim])."""
+    from inverse masses (0.1 q)^2, or from `inv_mass`; a 2-D `inv_mass` asks for the dense metric: every window then ends with
+    shrunk_covariance of its later three quarters.  Returns (eps [B], inv_mass [dim] or [dim, dim])."""
     q0, _, _ = lf.position()
-    inv_mass = np.maximum((0.1 * np.abs(q0)).mean(axis=0) ** 2, 1e-12)
+    dense = inv_mass is not None and np.ndim(inv_mass) == 2
+    if inv_mass is None:
+        inv_mass = np.maximum((0.1 * np.abs(q0)).mean(axis=0) ** 2, 1e-12)
     eps = np.full(lf.batch, float(eps0))
     for w in range(n_windows):
         da = DualAveraging(eps, delta=delta)
@@ -316,6 +428,9 @@ def nuts_warmup(lf: Leapfrog, rng: np.random.Generator, n_windows: int = 3, wind
             eps = da.update(alpha)
             qs.append(lf.position()[0])
         eps = da.final()
+        if dense:
+            inv_mass = shrunk_covariance(np.concatenate(qs[window // 4:]))
+            continue
         var = np.concatenate(qs[window // 4:]).var(axis=0)
         n_eff = lf.batch * (window - window // 4)
         inv_mass = (n_eff / (n_eff + 5.0)) * var + 1e-3 * (5.0 / (n_eff + 5.0))      # Stan-style shrinkage

@@ -8,7 +8,14 @@ sizes, masses and random streams -- three ways:
                had to do before the recorder (the read-back does not depend on PERIOD: a caller cannot know the state without it).
   --name NAME            a committed input (dense likelihood), Metropolis-Hastings burn-in for the start states
   --synthetic N_LEAVES   a random tree over a banded sparse precision matrix around the states' own distances (2 N_LEAVES - 1 nodes)
-One JSON line per run; *_runs hold every repeat, the headline figures are their medians."""
+One JSON line per run; *_runs hold every repeat, the headline figures are their medians.
+
+  --metric {diag,dense}  instead of the three ways above: warm-up from the problem's crude masses with that metric -- mcd_hmc_nuts_warmup (pooled
+                         variances) or mcd_hmc_nuts_warmup_dense (the full covariance), --windows windows of --window transitions --, then
+                         --transitions recorded transitions at the tuned step sizes: microseconds per leapfrog step (a lock step of all chains:
+                         the transition's rounds are the longest tree's leaves), leapfrog steps per transition and chain, mean tree depth, the
+                         tuned step sizes, and the smallest effective sample size over the inner node ages per leapfrog step
+                         (Leapfrog.record_summary)."""
 import argparse
 import json
 import os
@@ -73,6 +80,41 @@ def synthetic_problem(n_leaves, B):
     return topo, lf, eps, inv_mass, "sparse"
 
 
+def metric_report(args, topo, lf, eps0, inv_mass0, form):
+    B, T = lf.batch, args.transitions
+    dense = args.metric == "dense"
+    kw = dict(max_depth=args.max_depth, seed=args.seed)
+    t0 = time.perf_counter()
+    if dense:
+        eps, _, alpha_w = lf.nuts_warmup_dense(eps0, inv_mass0, windows=args.windows, window=args.window, **kw)
+        inv_mass = None
+    else:
+        eps, inv_mass, alpha_w = lf.nuts_warmup(eps0, inv_mass0, windows=args.windows, window=args.window, **kw)
+    warm_s = time.perf_counter() - t0
+    first = (args.windows + 1) * args.window
+    lf.record_begin(period=1, capacity=T)
+    lf.position()
+    t0 = time.perf_counter()
+    _, alpha, _, _ = lf.nuts_run(T, eps, inv_mass, adapt=False, first_transition=first, **kw)
+    lf.position()                                                  # (waits for the handle's stream)
+    run_s = time.perf_counter() - t0
+    summ = lf.record_summary(max_lag=min(255, max(1, T // 2)))
+    nuts = lf.record_fetch()[-1]                                   # [T, B, 6] = Leapfrog.NUTS_FIELDS
+    lf.record_end()
+    steps = nuts[:, :, 1]
+    lock_steps = float(steps.max(axis=1).sum())
+    inner = np.flatnonzero(~topo.leaves)
+    ess = summ.ages[inner, 7]
+    print(json.dumps({"metric": "NUTS leapfrog steps (all chains in lock step)", "mass_matrix": args.metric,
+                      "dataset": f"synthetic {args.synthetic} leaves" if args.synthetic else args.name, "likelihood": form, "n_nodes": topo.n_nodes,
+                      "dim": lf.dim, "chains": B, "windows": args.windows, "window": args.window, "transitions": T, "max_depth": args.max_depth,
+                      "warmup_s": warm_s, "warmup_mean_alpha": float(alpha_w.mean()), "eps_mean": float(eps.mean()), "eps_min": float(eps.min()),
+                      "eps_max": float(eps.max()), "run_s": run_s, "us_per_leapfrog_step": 1e6 * run_s / max(1.0, lock_steps),
+                      "leapfrog_steps_per_transition": float(steps.mean()), "mean_depth": float(nuts[:, :, 0].mean()),
+                      "divergent": int(nuts[:, :, 3].sum()), "mean_alpha": float(alpha.mean()), "min_ess_node_ages": float(ess.min()),
+                      "min_ess_per_leapfrog_step": float(ess.min()) / max(1.0, float(steps.sum()))}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--name", default="24-leaves-braces")
@@ -83,9 +125,14 @@ def main():
     ap.add_argument("--record", type=int, default=1)
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--seed", type=int, default=5)
+    ap.add_argument("--metric", choices=("diag", "dense"), default=None)
+    ap.add_argument("--windows", type=int, default=3)
+    ap.add_argument("--window", type=int, default=60)
     args = ap.parse_args()
     B, T = args.chains, args.transitions
     topo, lf, eps, inv_mass, form = synthetic_problem(args.synthetic, B) if args.synthetic else golden_problem(args.name, B)
+    if args.metric:
+        return metric_report(args, topo, lf, eps, inv_mass, form)
     start = lf.state()
     kw = dict(max_depth=args.max_depth, seed=args.seed)
 
