@@ -97,7 +97,9 @@ const char* mcd_last_error(void);
  * mcd_mvn_logpdf_batch at up to 512 chains, where 3 selects it under any form, and is the default there for 240 < N <= 256 at 129 .. 512
  * chains under form auto; elsewhere 3 means the default),
  * "MCD_SPARSE_GRAD_CHAINS" (1 | 2: chains per workgroup of mcd_sparse_tree_grad_batch; the same bits), "MCD_STRIPE_PROLOGUE" (the inverse
- * stream's kernel: 1 = x, mu and 1/diag loaded once per workgroup, 0 = by every wave for itself; the same bits); value = a decimal integer, NULL or ""
+ * stream's kernel: 1 = x, mu and 1/diag loaded once per workgroup, 0 = by every wave for itself; the same bits), "MCD_STRIPE_SCHED" (that
+ * kernel's schedule under the shared prologue: 1 = the column broadcasts read out of LDS and the ring read one group ahead of the
+ * multiply-adds, 0 = the schedule before; the same bits); value = a decimal integer, NULL or ""
  * = back to the default.  What each knob does is said where it acts (mcd_mh_run, the forms above).  The environment variables of the same
  * names are read ONCE, when the library is loaded, as initial values -- never afterwards.  No knob changes a result beyond rounding.
  */

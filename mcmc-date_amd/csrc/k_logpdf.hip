@@ -40,7 +40,9 @@ __global__ void __launch_bounds__(64 * (CW + LW)) k_logpdf(const double* __restr
 // The inverse stream (FS = 3; R = 3, 4, up to 512 chains): S stripe waves, two chains per workgroup, every wave a share of Fw of its
 // own (stripe_device.hpp).  The same arguments, preloaded the same way.  SH: x, mu and 1/diag loaded once per workgroup and handed
 // round through LDS (the default), or by every wave for itself (mcd_set_option "MCD_STRIPE_PROLOGUE" = 0; A/B, tests: the same bits).
-template <int R, int S, bool SH>
+// SC (with SH only): the column broadcasts read out of the exchange area and the ring read one group ahead of the multiply-adds (the
+// default), or round 14's loop (mcd_set_option "MCD_STRIPE_SCHED" = 0; A/B, tests: the same bits).  Three kernels per R.
+template <int R, int S, bool SH, int SC>
 __global__ void __launch_bounds__(64 * S) k_logpdf_stripe(const double* __restrict__ Fw, const double* __restrict__ mu,
                                                           const double* __restrict__ invdiag, const double* __restrict__ X, int64_t ldx,
                                                           int64_t batch, int n, int ncols, double* __restrict__ ll, double c, double logdet)
@@ -50,20 +52,21 @@ __global__ void __launch_bounds__(64 * S) k_logpdf_stripe(const double* __restri
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     MCD_T(0);
     const MvnView M(mu, invdiag, n, c, logdet);
-    stripe_dispatch<R, S, 0, SH>(wave, Fw, ring, M, X, ldx, (int64_t)blockIdx.x * 2, batch, ncols, ll, lane);
+    stripe_dispatch<R, S, 0, SH, SC>(wave, Fw, ring, M, X, ldx, (int64_t)blockIdx.x * 2, batch, ncols, ll, lane);
 }
 
-template <int R, bool SH>
+template <int R, bool SH, int SC>
 static void launch_stripe_sh(const MvnDev& M, const double* X, int64_t ldx, int64_t batch, double* ll, hipStream_t st)
 {
-    hipLaunchKernelGGL((k_logpdf_stripe<R, kStripeWaves, SH>), dim3((unsigned)((batch + 1) / 2)), dim3(64 * kStripeWaves), 0, st, M.Fw, M.mu,
+    hipLaunchKernelGGL((k_logpdf_stripe<R, kStripeWaves, SH, SC>), dim3((unsigned)((batch + 1) / 2)), dim3(64 * kStripeWaves), 0, st, M.Fw, M.mu,
                        M.invdiag, X, ldx, batch, M.n, M.ncols, ll, M.c, M.logdet);
 }
 template <int R>
 static void launch_stripe(const MvnDev& M, const double* X, int64_t ldx, int64_t batch, double* ll, hipStream_t st)
 {
-    if (opt_or(OPT_STRIPE_PROLOGUE, kStripePrologueDefault) != 0) launch_stripe_sh<R, true>(M, X, ldx, batch, ll, st);
-    else launch_stripe_sh<R, false>(M, X, ldx, batch, ll, st);
+    if (opt_or(OPT_STRIPE_PROLOGUE, kStripePrologueDefault) == 0) launch_stripe_sh<R, false, 0>(M, X, ldx, batch, ll, st);
+    else if (opt_or(OPT_STRIPE_SCHED, kStripeSchedDefault) != 0) launch_stripe_sh<R, true, 1>(M, X, ldx, batch, ll, st);
+    else launch_stripe_sh<R, true, 0>(M, X, ldx, batch, ll, st);
 }
 
 template <int R, int BT, int CW, int LW, int FS>

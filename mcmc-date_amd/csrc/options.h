@@ -37,6 +37,8 @@ enum Option {
     OPT_SPARSE_GRAD_CHAINS, // 1 | 2: chains per workgroup of the sparse tree gradient (k_sparse_grad.hip; default: 2 from 512 chains; the same bits)
     OPT_STRIPE_PROLOGUE,    // the inverse stream's stripe kernel (stripe_device.hpp): 1 = x, mu and 1/diag loaded once per workgroup and exchanged through
                             // LDS, 0 = by every stripe wave for itself (A/B, tests; the same bits)
+    OPT_STRIPE_SCHED,       // the stripe kernel's schedule under the shared prologue: 1 = the column broadcasts read out of the exchange area and the
+                            // ring read one group ahead of the multiply-adds, 0 = the loop of round 14 (A/B, tests; the same bits)
     OPT_COUNT
 };
 constexpr int MCD_OPT_UNSET = -2147483647 - 1;

@@ -26,6 +26,17 @@
 //     it -- then every wave reads all of r and wave 0 also t.  The exchange accesses are asm like the ring reads, for the same reason.
 //   * The lookahead A (kStripeAhead <= D, -DMCD_STRIPE_AHEAD): units requested ahead of the unit being read, and the prologue's burst.
 //     Slots stay u mod D.
+//   * The schedule (SC, the default under the shared prologue; MCD_STRIPE_SCHED = 0 keeps the loop above with its v_readlane column
+//     broadcasts, and the private prologue has that loop only).  A wave alone on its SIMD is bound by its own VALU issue, and a wave
+//     body of the loop above spends 404 lane selects beside 322 multiply-adds (R = 4).  r stays in the exchange area for the whole launch, both chains
+//     of a row in one 16-byte slot, so the broadcast of column j is one ds_read_b128 of the same address in every lane -- an LDS
+//     instruction for both chains instead of four v_readlane_b32 -- and the multiply-add takes it as a vector operand: the same value.
+//     And a wave's list is a sequence of GROUPS (a chunk's diagonal part, or the wave's off-diagonal pairs of a chunk: stripe_groups):
+//     the unit reads and broadcasts of group g + 1 go into a second register set and are issued in front of the multiply-adds of group
+//     g: counted vmcnt wait for g + 1's units, the reads of g + 1, the multiply-adds of g, lgkmcnt(0), the DMAs that g + 1's slots now
+//     allow.  A group whose chunk the early stop cuts is neither waited for nor read.  Every addition keeps its operands and its place.
+//     Measured and not kept (profiles/r16_stripe_schedule_ab.txt, docs/experiments/r16_stripe_read_ahead_fill.diff): the read-ahead
+//     without the broadcasts, a fill of the ring behind the operand loads, a burst shorter than the lookahead.
 #include "mvn_device.hpp"
 #include "stripe_deal.hpp"
 
@@ -43,6 +54,7 @@ constexpr int kStripeWaves = MCD_STRIPE_WAVES;
 #endif
 constexpr int kStripeAhead = MCD_STRIPE_AHEAD;
 constexpr int kStripePrologueDefault = 1;                  // MCD_STRIPE_PROLOGUE unset: the shared prologue
+constexpr int kStripeSchedDefault = 1;                     // MCD_STRIPE_SCHED unset: the schedule
 
 template <int R, int S>
 struct Stripe {
@@ -238,6 +250,206 @@ __device__ __forceinline__ void stripe_chunks(const double* __restrict__ Fw, uns
     }
 }
 
+// The schedule's groups of wave W, in list order: a chunk's diagonal part (diag) or the wave's off-diagonal pairs of the chunk; end:
+// the list position behind the group's last unit
+struct StripeGroups {
+    int n;
+    int ci[32], diag[32], end[32];
+};
+template <int R, int S, int W>
+constexpr StripeGroups stripe_groups()
+{
+    StripeGroups q{};
+    for (int ci = 0; ci < fc_nchunk(R); ++ci) {
+        const int dpos = Stripe<R, S>::T.diag_pos[W][ci];
+        if (dpos >= 0) {
+            q.ci[q.n] = ci;
+            q.diag[q.n] = 1;
+            q.end[q.n++] = dpos + fc_diag_units(R, ci % 4);
+        }
+        int pend = -1;
+        for (int p = 0; p < 8; ++p)
+            if (Stripe<R, S>::T.pair_pos[W][ci][p] >= 0) pend = Stripe<R, S>::T.pair_pos[W][ci][p] + (R - 1 - ci / 4);
+        if (pend >= 0) {
+            q.ci[q.n] = ci;
+            q.diag[q.n] = 0;
+            q.end[q.n++] = pend;
+        }
+    }
+    return q;
+}
+// registers a group's reads fill
+template <int R, int S, int W, int GI>
+constexpr int stripe_group_regs()
+{
+    constexpr StripeGroups Q = stripe_groups<R, S, W>();
+    if constexpr (Q.diag[GI] != 0) return 8;
+    else return stripe_pairs_units<R, S, W, Q.ci[GI]>();
+}
+// the ds_reads of group GI's units (stripe_chunks' addresses and offsets)
+template <int R, int S, int W, int GI>
+__device__ __forceinline__ void stripe_group_read(d2 (&l)[8 * 3], unsigned la, unsigned za, int lane)
+{
+    constexpr StripeGroups Q = stripe_groups<R, S, W>();
+    constexpr int CI = Q.ci[GI], D = Stripe<R, S>::D, LC = CI % 4;
+    static_assert(stripe_group_regs<R, S, W, GI>() <= D, "a group within the ring");
+    if constexpr (Q.diag[GI] != 0) {
+        constexpr int dpos = Stripe<R, S>::T.diag_pos[W][CI];
+        static_assert(fc_diag_units(R, LC) <= D, "a group within the ring");
+        constexpr bool WRAP = dpos % D + fc_diag_units(R, LC) > D;
+        unsigned ad[8];
+#pragma unroll
+        for (int p = 0; p < 8; ++p) {
+            const int pl = LC * 8 + p;
+            int i = (dpos % D) * 64 + fc_diag_start(R, LC, p) - (2 * pl + 1) + lane;
+            if (WRAP) i = i >= D * 64 ? i - D * 64 : i;
+            ad[p] = lane > 2 * pl ? la - 16u * (unsigned)lane + 16u * (unsigned)i : za;
+        }
+#pragma unroll
+        for (int p = 0; p < 8; ++p) lds_read16<0>(l[p], ad[p]);
+    } else {
+        stripe_pairs_read<R, S, W, CI, 0, 0>(l, la);
+    }
+}
+// The column broadcasts of a group out of the exchange area instead of v_readlane: both chains' r of one column in one 16-byte read,
+// every lane the same address (xa: the area's LDS byte address; r of row block k, row j at xa + 1024 k + 16 j).  z[c]: the group's
+// c-th column in the order of its multiply-adds.  The values are the ones the prologue's get reads, so the multiply-adds keep their bits.
+template <int R, int S, int W, int CI, int P, int NZ>
+__device__ __forceinline__ void stripe_pairs_bcast(d2 (&z)[16], unsigned xa)
+{
+    if constexpr (P < 8) {
+        constexpr int JB = CI / 4, jj = (CI % 4) * 16 + 2 * P;
+        if constexpr (Stripe<R, S>::T.pair_pos[W][CI][P] >= 0) {
+            static_assert(NZ + 2 <= 16, "columns of a group");
+            lds_read16<(JB * 64 + jj) * 16>(z[NZ], xa);
+            lds_read16<(JB * 64 + jj + 1) * 16>(z[NZ + 1], xa);
+            stripe_pairs_bcast<R, S, W, CI, P + 1, NZ + 2>(z, xa);
+        } else {
+            stripe_pairs_bcast<R, S, W, CI, P + 1, NZ>(z, xa);
+        }
+    }
+}
+template <int R, int S, int W, int CI, int P, int NREAD, int NZ>
+__device__ __forceinline__ void stripe_pairs_apply_bcast(const d2 (&l)[8 * 3], const d2 (&z)[16], double (&a)[R][2])
+{
+    if constexpr (P < 8) {
+        constexpr int JB = CI / 4, NKO = R - 1 - JB;
+        if constexpr (Stripe<R, S>::T.pair_pos[W][CI][P] >= 0) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int k = 0; k < NKO; ++k)
+#pragma unroll
+                    for (int b = 0; b < 2; ++b)
+                        a[JB + 1 + k][b] = fma(h ? l[NREAD + k].y : l[NREAD + k].x, b ? z[NZ + h].y : z[NZ + h].x, a[JB + 1 + k][b]);
+            stripe_pairs_apply_bcast<R, S, W, CI, P + 1, NREAD + NKO, NZ + 2>(l, z, a);
+        } else {
+            stripe_pairs_apply_bcast<R, S, W, CI, P + 1, NREAD, NZ>(l, z, a);
+        }
+    }
+}
+template <int ROW, int C>
+__device__ __forceinline__ void stripe_diag_bcast(d2 (&z)[16], unsigned xa)
+{
+    if constexpr (C < 16) {
+        lds_read16<(ROW + C) * 16>(z[C], xa);
+        stripe_diag_bcast<ROW, C + 1>(z, xa);
+    }
+}
+template <int R, int S, int W, int GI>
+constexpr int stripe_group_cols()
+{
+    constexpr StripeGroups Q = stripe_groups<R, S, W>();
+    if (Q.diag[GI] != 0) return 16;
+    int n = 0;
+    for (int p = 0; p < 8; ++p)
+        if (Stripe<R, S>::T.pair_pos[W][Q.ci[GI]][p] >= 0) n += 2;
+    return n;
+}
+template <int R, int S, int W, int GI>
+__device__ __forceinline__ void stripe_group_bcast(d2 (&z)[16], unsigned xa)
+{
+    constexpr StripeGroups Q = stripe_groups<R, S, W>();
+    constexpr int CI = Q.ci[GI], JB = CI / 4, LC = CI % 4;
+    if constexpr (Q.diag[GI] != 0) {
+        stripe_diag_bcast<JB * 64 + LC * 16, 0>(z, xa);
+    } else {
+        stripe_pairs_bcast<R, S, W, CI, 0, 0>(z, xa);
+    }
+}
+template <int R, int S, int W, int GI>
+__device__ __forceinline__ void stripe_group_apply(const d2 (&l)[8 * 3], const d2 (&z)[16], double (&a)[R][2])
+{
+    constexpr StripeGroups Q = stripe_groups<R, S, W>();
+    constexpr int CI = Q.ci[GI], JB = CI / 4;
+    if constexpr (Q.diag[GI] != 0) {
+#pragma unroll
+        for (int p = 0; p < 8; ++p)
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int b = 0; b < 2; ++b) a[JB][b] = fma(h ? l[p].y : l[p].x, b ? z[2 * p + h].y : z[2 * p + h].x, a[JB][b]);
+    } else {
+        stripe_pairs_apply_bcast<R, S, W, CI, 0, 0, 0>(l, z, a);
+    }
+}
+// The schedule behind group GI: its unit reads and broadcasts have landed in L[GI & 1] and Z[GI & 1], and ISSUED DMAs are out.  If the
+// early stop does not cut group GI + 1: wait for its units, read them and its broadcasts into the other register set, multiply GI
+// meanwhile, then lgkmcnt(0) and the DMAs up to A units behind GI + 1 (everything up to GI + 1 has been read: their slots are free).
+// The waits are stripe_chunks', every one a constexpr function of ISSUED.  A group that is cut is not touched; the branch is
+// workgroup-uniform and no value in flight crosses a join.
+template <int R, int S, int W, int GI, int ISSUED>
+__device__ __forceinline__ void stripe_ahead(const double* __restrict__ Fw, unsigned my, unsigned la, unsigned za, unsigned xa, double (&a)[R][2],
+                                             d2 (&L)[2][8 * 3], d2 (&Z)[2][16], int lane, int ncols)
+{
+    using G = Stripe<R, S>;
+    constexpr StripeGroups Q = stripe_groups<R, S, W>();
+    if constexpr (GI + 1 < Q.n) {
+        if (__builtin_expect(Q.ci[GI + 1] * 16 < ncols, 1)) {   // (the cut's multiply-adds out of the straight line)
+            constexpr int NU = G::T.n[W], e1 = Q.end[GI + 1];
+            constexpr int issued0 = stripe_max(ISSUED, e1);
+            constexpr int issued1 = stripe_max(issued0, stripe_min(NU, e1 + G::A));
+            stripe_issue<R, S, W, ISSUED, issued0>(Fw, my, lane);
+            asm_wait_vmcnt<issued0 - e1>();
+            stripe_group_read<R, S, W, GI + 1>(L[(GI + 1) & 1], la, za, lane);
+            stripe_group_bcast<R, S, W, GI + 1>(Z[(GI + 1) & 1], xa);
+            MCD_SB;
+            stripe_group_apply<R, S, W, GI>(L[GI & 1], Z[GI & 1], a);
+            MCD_SB;
+            lds_landed<stripe_group_regs<R, S, W, GI + 1>()>(L[(GI + 1) & 1]);
+            lds_landed<stripe_group_cols<R, S, W, GI + 1>()>(Z[(GI + 1) & 1]);
+            stripe_issue<R, S, W, issued0, issued1>(Fw, my, lane);
+            stripe_ahead<R, S, W, GI + 1, issued1>(Fw, my, la, za, xa, a, L, Z, lane, ncols);
+            return;
+        }
+    }
+    stripe_group_apply<R, S, W, GI>(L[GI & 1], Z[GI & 1], a);
+}
+// ... and its head: the first group as stripe_chunks reads it, its broadcasts (which wait for no DMA) in front of its vmcnt wait
+template <int R, int S, int W, int ISSUED>
+__device__ __forceinline__ void stripe_sched(const double* __restrict__ Fw, unsigned my, unsigned la, unsigned za, unsigned xa, double (&a)[R][2],
+                                             int lane, int ncols)
+{
+    using G = Stripe<R, S>;
+    constexpr StripeGroups Q = stripe_groups<R, S, W>();
+    if constexpr (Q.n > 0) {
+        if (Q.ci[0] * 16 >= ncols) return;                 // workgroup-uniform: a suffix of every wave's list
+        constexpr int NU = G::T.n[W], e0 = Q.end[0];
+        constexpr int issued0 = stripe_max(ISSUED, e0);
+        constexpr int issued1 = stripe_max(issued0, stripe_min(NU, e0 + G::A));
+        d2 L[2][8 * 3], Z[2][16];
+        stripe_group_bcast<R, S, W, 0>(Z[0], xa);
+        stripe_issue<R, S, W, ISSUED, issued0>(Fw, my, lane);
+        asm_wait_vmcnt<issued0 - e0>();
+        MCD_T(2);
+        stripe_group_read<R, S, W, 0>(L[0], la, za, lane);
+        lds_landed<stripe_group_regs<R, S, W, 0>()>(L[0]);
+        lds_landed<stripe_group_cols<R, S, W, 0>()>(Z[0]);
+        stripe_issue<R, S, W, issued0, issued1>(Fw, my, lane);
+        stripe_ahead<R, S, W, 0, issued1>(Fw, my, la, za, xa, a, L, Z, lane, ncols);
+    }
+}
+
 // The private prologue: x, mu and (wave 0) 1/diag of both chains in front of the first DMA: a padded row or a chain beyond the batch
 // reads a clamped address and the value is dropped for mu (load_rawx)
 template <int R, int S, int W>
@@ -313,7 +525,8 @@ __device__ __forceinline__ void stripe_exchange_get(d2 (&e)[R], unsigned ea)
 
 // The shared prologue: the same loads, selection and operations, but only for the row blocks k = W, W + S, ... < R this wave owns
 // (four loads each); r and t = r invdiag go through the exchange area, one LDS-only barrier, every wave reads r and wave 0 t.
-template <int R, int S, int W>
+// GETR = false (the schedule, which broadcasts r out of the exchange area): r is not read back into registers.
+template <int R, int S, int W, bool GETR = true>
 __device__ __forceinline__ void stripe_prologue_shared(const double* __restrict__ Fw, unsigned mya, unsigned ea, const MvnView& M,
                                                        const double* __restrict__ X, int64_t ldx, int64_t b0, int64_t batch, double (&r)[R][2],
                                                        double (&a)[R][2], int lane)
@@ -342,37 +555,39 @@ __device__ __forceinline__ void stripe_prologue_shared(const double* __restrict_
     stripe_exchange_put<R, S, W, 0, NO>(xr, m, iv, ea, M.n, b0, batch, lane);
     lds_barrier();                                         // (lgkmcnt only: the DMAs stay in flight)
     d2 e[R], et[R];
-    stripe_exchange_get<R, 0, 0>(e, ea);
+    if constexpr (GETR) stripe_exchange_get<R, 0, 0>(e, ea);
     if constexpr (W == 0) stripe_exchange_get<R, 1, 0>(et, ea);
-    lds_landed<R>(e);
+    if constexpr (GETR) lds_landed<R>(e);
     if constexpr (W == 0) lds_landed<R>(et);
 #pragma unroll
     for (int k = 0; k < R; ++k)
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
-            r[k][c] = c ? e[k].y : e[k].x;
+            if constexpr (GETR) r[k][c] = c ? e[k].y : e[k].x;
             if constexpr (W == 0) a[k][c] = c ? et[k].y : et[k].x;
             else a[k][c] = 0.0;
         }
     MCD_T(5);
 }
 
-template <int R, int S, int W, bool SH>
+template <int R, int S, int W, bool SH, int SC>
 __device__ __forceinline__ void stripe_wave(const double* __restrict__ Fw, d2* ring, const MvnView& M, const double* __restrict__ X, int64_t ldx,
                                             int64_t b0, int64_t batch, int ncols, double* __restrict__ ll, int lane)
 {
     using G = Stripe<R, S>;
+    static_assert(SH || SC == 0, "the schedule goes with the shared prologue");
     constexpr int D = G::D, NU = G::T.n[W], PRO = stripe_min(G::A, NU);
     d2* my = ring + W * D * 64;
     d2* zu = ring + G::ZERO + W * 64;
     zu[lane] = d2{0.0, 0.0};
     const unsigned mya = lds_addr(my);
     double r[R][2], a[R][2];
-    if constexpr (SH) stripe_prologue_shared<R, S, W>(Fw, mya, lds_addr(ring + G::EXCH) + 16u * (unsigned)lane, M, X, ldx, b0, batch, r, a, lane);
+    if constexpr (SH) stripe_prologue_shared<R, S, W, SC == 0>(Fw, mya, lds_addr(ring + G::EXCH) + 16u * (unsigned)lane, M, X, ldx, b0, batch, r, a, lane);
     else stripe_prologue_private<R, S, W>(Fw, mya, M, X, ldx, b0, batch, r, a, lane);
     const unsigned la = mya + 16u * (unsigned)lane;
     const unsigned za = lds_addr(zu) + 16u * (unsigned)lane;
-    stripe_chunks<R, S, W, 0, PRO>(Fw, mya, la, za, r, a, lane, ncols);
+    if constexpr (SC != 0) stripe_sched<R, S, W, PRO>(Fw, mya, la, za, lds_addr(ring + G::EXCH), a, lane, ncols);
+    else stripe_chunks<R, S, W, 0, PRO>(Fw, mya, la, za, r, a, lane, ncols);
     MCD_T(3);
     asm_wait_vmcnt<0>();
     double* part = reinterpret_cast<double*>(my);
@@ -397,14 +612,14 @@ __device__ __forceinline__ void stripe_wave(const double* __restrict__ Fw, d2* r
     }
 }
 
-template <int R, int S, int W, bool SH>
+template <int R, int S, int W, bool SH, int SC>
 __device__ __forceinline__ void stripe_dispatch(int wave, const double* __restrict__ Fw, d2* ring, const MvnView& M, const double* __restrict__ X,
                                                 int64_t ldx, int64_t b0, int64_t batch, int ncols, double* __restrict__ ll, int lane)
 {
     if (wave == W) {
-        stripe_wave<R, S, W, SH>(Fw, ring, M, X, ldx, b0, batch, ncols, ll, lane);
+        stripe_wave<R, S, W, SH, SC>(Fw, ring, M, X, ldx, b0, batch, ncols, ll, lane);
     } else {
-        if constexpr (W + 1 < S) stripe_dispatch<R, S, W + 1, SH>(wave, Fw, ring, M, X, ldx, b0, batch, ncols, ll, lane);
+        if constexpr (W + 1 < S) stripe_dispatch<R, S, W + 1, SH, SC>(wave, Fw, ring, M, X, ldx, b0, batch, ncols, ll, lane);
     }
 }
 
