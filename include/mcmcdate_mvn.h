@@ -184,7 +184,8 @@ int mcd_tree_loglik_batch(const mcd_tree_t* t, const double* heights, const doub
  * Log-likelihood and its gradient with respect to the state, replacing the AD of
  * likelihoodFunctionG (app/Probability.hs:361-388) in htargetWith (app/Hamiltonian.hs:72-92).
  * g_heights / g_rates: [batch][ld_state] (every node; masking per app/Hamiltonian.hs:33-47 is the
- * caller's business; g_rates[.][0] = 0), g_tH / g_rMu: [batch].
+ * caller's business; g_rates[.][0] = 0), g_tH / g_rMu: [batch].  A chain whose ln likelihood is
+ * NaN has NaN in every gradient entry (g_rates[.][0] included); no other chain is touched.
  */
 int mcd_tree_grad_batch(const mcd_tree_t* t, const double* heights, const double* rates, int64_t ld_state,
                         const double* tH, const double* rMu, int64_t batch, int on_device, void* stream,

@@ -664,7 +664,6 @@ __global__ void __launch_bounds__(1024) k_split_tree_chain(int n, int NR, TreeDe
         const int rr = T.root_right;
         const double r2 = r[rr], t2 = h[0] - h[rr], g0 = -y[(n - 1) * 16], sg = s * g0;
         gR[b * lds + rr] = sg * t2;
-        gR[b * lds] = 0.0;                                 // stem rate: unused by the likelihood
         e[rr] = sg * r2;
         e[0] = 0.0;
         gd += g0 * ((t2 * r2) * s);
@@ -677,6 +676,7 @@ __global__ void __launch_bounds__(1024) k_split_tree_chain(int n, int NR, TreeDe
         for (int w = 0; w < (nt >> 6); ++w) gdot += red[w];
         gtH[b] = gdot / tH[b];
         grMu[b] = gdot / rMu[b];
+        gR[b * lds] = gdot == gdot ? 0.0 : gdot;           // stem rate: unused by the likelihood (a NaN chain: NaN, as every other entry)
     }
     if (tid < T.n_nodes) {
         double acc = (tid == 0) ? 0.0 : -e[tid];

@@ -71,7 +71,7 @@ __global__ void __launch_bounds__(64 * (CW + LW)) k_tree_grad(MvnDev M, TreeDev 
     }
     const double gdot = wave_sum(gd);
     if (lane == 0) {
-        gR[b * lds] = 0.0;                 // stem rate: unused by the likelihood
+        gR[b * lds] = gdot == gdot ? 0.0 : gdot;   // stem rate: unused by the likelihood (a NaN chain: NaN, as every other entry)
         gtH[b] = gdot / tH[b];
         grMu[b] = gdot / rMu[b];
     }

@@ -157,10 +157,7 @@ __global__ void __launch_bounds__(64 * WD_WAVES) k_wide_grad(MvnDev M, WideSrc A
             const double sg = scs[tid] * g0;
             e_rr = sg * r2;
             gd_rr = g0 * ((t2 * r2) * scs[tid]);
-            if (b0 + tid < batch) {
-                O.gR[b * A.lds + rr] = sg * t2;
-                O.gR[b * A.lds] = 0.0;                                           // stem rate: unused by the likelihood
-            }
+            if (b0 + tid < batch) O.gR[b * A.lds + rr] = sg * t2;
         }
         WD_T(6);
         // g . d: the 64 columns of this wave (all chain rows at once, so the exchanges overlap), then the four waves of a
@@ -188,6 +185,7 @@ __global__ void __launch_bounds__(64 * WD_WAVES) k_wide_grad(MvnDev M, WideSrc A
             const double gdot = (((gpart[tid * 4] + gpart[tid * 4 + 1]) + gpart[tid * 4 + 2]) + gpart[tid * 4 + 3]) + gpart[CT * 16 * 4 + tid];
             O.gtH[b0 + tid] = gdot / A.tH[b0 + tid];
             O.grMu[b0 + tid] = gdot / A.rMu[b0 + tid];
+            O.gR[(b0 + tid) * A.lds] = gdot == gdot ? 0.0 : gdot;                // stem rate: unused by the likelihood (a NaN chain: NaN, as every other entry)
         }
         WD_T(8);
         // d ll / d h_v = sum_children e_c - e_v, one node per thread column (n_nodes <= 258: columns 0 .. 255 and a tail of 2)

@@ -193,7 +193,6 @@ __global__ void __launch_bounds__(64 * WD_WAVES) k_wide_grad_mc(MvnDev M, WideSr
                 e_rr = sg * r2;
                 gd_rr = g0 * ((t2 * r2) * scs[c0 + tid]);
                 O.gR[b * A.lds + rr] = sg * t2;
-                O.gR[b * A.lds] = 0.0;                     // stem rate: unused by the likelihood
                 eb[tid * WD_EL + rr] = e_rr;
                 eb[tid * WD_EL] = 0.0;
             }
@@ -209,6 +208,7 @@ __global__ void __launch_bounds__(64 * WD_WAVES) k_wide_grad_mc(MvnDev M, WideSr
                 for (int w = 0; w < WD_WAVES; ++w) gdot += gpart[w * SBC + tid];
                 O.gtH[b0 + c0 + tid] = gdot / A.tH[b0 + c0 + tid];
                 O.grMu[b0 + c0 + tid] = gdot / A.rMu[b0 + c0 + tid];
+                O.gR[(b0 + c0 + tid) * A.lds] = gdot == gdot ? 0.0 : gdot;       // stem rate: unused by the likelihood (a NaN chain: NaN, as every other entry)
             }
             for (int v = tid; v < n_nodes; v += 64 * WD_WAVES) {
                 const int p0 = A.T.child_ptr[v], p1 = A.T.child_ptr[v + 1];
