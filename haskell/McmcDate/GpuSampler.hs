@@ -51,6 +51,9 @@ module McmcDate.GpuSampler
     c_hmc_record_end,
     c_hmc_record_quantities,
     c_hmc_record_summary,
+    -- the form of the NUTS driver's dense metric, raw
+    c_hmc_set_metric_form,
+    c_hmc_get_metric_form,
   )
 where
 
@@ -184,6 +187,14 @@ foreign import ccall unsafe "mcd_hmc_record_quantities"
 -- (safe: several passes over the whole ring)
 foreign import ccall safe "mcd_hmc_record_summary"
   c_hmc_record_summary :: Ptr McdHmc -> Int64 -> Int64 -> Int32 -> Ptr Int64 -> Ptr CDouble -> Ptr CDouble -> Ptr CDouble -> IO CInt
+
+-- the form of the dense metric's products (@HTuneAllMasses@ beyond 512 coordinates): 0 = one workgroup's sum per chain (the default),
+-- 1 = one matrix product across the lock-step chains, every dim; to be chosen before @mcd_hmc_set_metric@ / @mcd_hmc_nuts_warmup_dense@
+foreign import ccall unsafe "mcd_hmc_set_metric_form"
+  c_hmc_set_metric_form :: Ptr McdHmc -> CInt -> IO CInt
+
+foreign import ccall unsafe "mcd_hmc_get_metric_form"
+  c_hmc_get_metric_form :: Ptr McdHmc -> Ptr CInt -> IO CInt
 
 check :: String -> CInt -> IO ()
 check _ 0 = pure ()

@@ -301,9 +301,18 @@ int mcd_hmc_nuts_warmup(mcd_hmc_t* m, int windows, int window, double* eps, doub
  *   mcd_hmc_set_metric   inv_mass_dense = C [dim][dim] row-major (host); NULL clears the dense metric, and the handle is again what it
  *                        was before.  Refused with MCD_ERR_INVALID_ARG, the handle untouched, the message naming the first offender:
  *                        a non-finite entry; |C_ij - C_ji| > 1e-10 sqrt(C_ii C_jj); not positive definite (the pivot).  Refused with
- *                        MCD_ERR_UNSUPPORTED: dim > MCD_HMC_DENSE_MAX_DIM (C is read once per product and chain out of the L2; beyond,
- *                        the right form is one multiply across the lock-step chains, which is not built).  The handle keeps
+ *                        MCD_ERR_UNSUPPORTED: dim > MCD_HMC_DENSE_MAX_DIM in the default form (C is read once per product and chain
+ *                        out of the L2; beyond, the right form is one multiply across the lock-step chains: mcd_hmc_set_metric_form),
+ *                        dim > MCD_HMC_DENSE_ACROSS_MAX_DIM -- more than any handle has -- in the across-chains form.  The handle keeps
  *                        (C + C^T) / 2, exactly symmetric, and U^-1 on its device.
+ *   mcd_hmc_set_metric_form   how the products with C and U^-1 are taken.  MCD_HMC_METRIC_PER_CHAIN (the default): one workgroup's sum
+ *                        per chain, dim <= MCD_HMC_DENSE_MAX_DIM.  MCD_HMC_METRIC_ACROSS_CHAINS: the chains of a transition are in lock
+ *                        step, so the products of a round are rows of ONE matrix product on the fp64 matrix cores (k_metric_gemm.hip);
+ *                        every dim, the same definitions, draws and order of decisions; a chain's bits still depend on nothing but the
+ *                        chain (the order of every sum is a function of dim alone), but they are not the per-chain form's bits.
+ *                        Allowed only while no dense metric is set (else MCD_ERR_INVALID_ARG, the handle untouched; a value that is
+ *                        neither form likewise); the form survives mcd_hmc_set_metric(NULL) and is followed by
+ *                        mcd_hmc_nuts_warmup_dense.  mcd_hmc_get_metric_form: *form = the handle's form.
  *   mcd_hmc_get_metric   *is_dense = 0 / 1; inv_mass_dense (may be NULL) receives the stored symmetrised C when dense.
  * While a dense metric is set, mcd_hmc_leapfrog, mcd_hmc_step_from, mcd_hmc_nuts and mcd_hmc_nuts_run require inv_mass == NULL
  * (a vector is MCD_ERR_INVALID_ARG: no caller silently runs the other metric); with none set, NULL stays the error it was.
@@ -317,7 +326,12 @@ int mcd_hmc_nuts_warmup(mcd_hmc_t* m, int windows, int window, double* eps, doub
  *                        (windows + 1) window - 1; the recorder's room is checked up front for all of them.
  */
 #define MCD_HMC_DENSE_MAX_DIM 512
+#define MCD_HMC_METRIC_PER_CHAIN 0
+#define MCD_HMC_METRIC_ACROSS_CHAINS 1
+#define MCD_HMC_DENSE_ACROSS_MAX_DIM 4098 /* 2 * 2048 + 2: every dim an mcd_hmc_t can have */
 int mcd_hmc_set_metric(mcd_hmc_t* m, const double* inv_mass_dense);
+int mcd_hmc_set_metric_form(mcd_hmc_t* m, int form);
+int mcd_hmc_get_metric_form(const mcd_hmc_t* m, int* form);
 int mcd_hmc_get_metric(const mcd_hmc_t* m, int* is_dense, double* inv_mass_dense);
 int mcd_hmc_nuts_warmup_dense(mcd_hmc_t* m, int windows, int window, double* eps, const double* inv_mass0, double delta, int max_depth,
                               uint64_t seed, int64_t chain_offset, uint64_t first_transition, double* mean_alpha, double* inv_mass_dense_out);

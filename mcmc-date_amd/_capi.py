@@ -25,6 +25,9 @@ MCD_ML_COLS = 5
 MCD_GLASSO_INFO_LEN = 8
 MCD_GLASSO_MAX_DIM = 2048
 MCD_HMC_DENSE_MAX_DIM = 512
+MCD_HMC_METRIC_PER_CHAIN = 0
+MCD_HMC_METRIC_ACROSS_CHAINS = 1
+MCD_HMC_DENSE_ACROSS_MAX_DIM = 4098
 MCD_MAT_SIGMA = 0
 MCD_MAT_SIGMA_INV = 1
 
@@ -96,6 +99,8 @@ SYMBOLS = {
     "mcd_hmc_nuts_warmup": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_double, C.c_int, C.c_uint64, C.c_int64, C.c_uint64, _dp]),
     "mcd_hmc_set_metric": (C.c_int, [_vp, _dp]),
     "mcd_hmc_get_metric": (C.c_int, [_vp, C.POINTER(C.c_int), _dp]),
+    "mcd_hmc_set_metric_form": (C.c_int, [_vp, C.c_int]),
+    "mcd_hmc_get_metric_form": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "mcd_hmc_nuts_warmup_dense": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_double, C.c_int, C.c_uint64, C.c_int64, C.c_uint64, _dp, _dp]),
     "mcd_mh_create": (C.c_int, [C.POINTER(_vp), _vp, _vp, C.c_int, _ip, _ip, _ip, _ip, _ip, _ip, _dp, _dp, C.c_int64, C.c_uint64]),
     "mcd_mh_create_sparse": (C.c_int, [C.POINTER(_vp), _vp, _vp, C.c_int, _ip, _ip, _ip, _ip, _ip, _ip, _dp, _dp, C.c_int64, C.c_uint64]),

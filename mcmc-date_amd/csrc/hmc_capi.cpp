@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -13,6 +14,7 @@
 #include "../../include/mcmcdate_mvn.h"
 #include "host_factor.h"
 #include "mvn_kernels.h"
+#include "nuts_rhs_plan.hpp"
 #include "recorder.hpp"
 #include "summary_device.hpp"
 
@@ -51,11 +53,18 @@ struct mcd_hmc {
     double *d_eps = nullptr, *d_dir = nullptr, *d_inv_mass = nullptr;
     mcd::NutsDev nuts{};           // allocated by the first NUTS transition (mcd_hmc_nuts)
     int* d_active = nullptr;
+    int* d_list = nullptr;         // [batch] the chains still building their trees (across-chains form of a dense metric), with the workspace
     double *d_s1 = nullptr, *d_s2 = nullptr;   // [dim] position moments of one mcd_hmc_nuts_run (k_hmc_moments)
     // the dense metric (mcd_hmc_set_metric): [dim][dim] device buffers behind dev.metric / dev.metric_uinv, allocated by the first
     // metric set; h_metric is the host copy of the stored symmetrised C.  dev.metric == nullptr: the diagonal metric.
     double *d_metric = nullptr, *d_uinv = nullptr;
     std::vector<double> h_metric;
+    // the form of the dense metric's products (mcd_hmc_set_metric_form) and, for MCD_HMC_METRIC_ACROSS_CHAINS, the workspace of
+    // k_metric_gemm.hip's right-hand sides and products: wx_slots x [batch][dim] each, allocated by the first call that needs them
+    int form = MCD_HMC_METRIC_PER_CHAIN;
+    mcd::MetricAcross wx{};
+    int wx_slots = 0;
+    double warmup_phase[4] = {0, 0, 0, 0};     // seconds of the last mcd_hmc_nuts_warmup_dense: factorisations, covariance, window buffer, transitions
     bool have_state = false;
     hipStream_t stream = nullptr;
     std::vector<void*> allocs;
@@ -97,6 +106,43 @@ int eval_gradients(mcd_hmc* m)
                                        m->stream));
     return MCD_OK;
 }
+
+// the dense metric's products are taken across the chains (k_metric_gemm.hip)
+bool across(const mcd_hmc* m) { return m->dev.metric && m->form == MCD_HMC_METRIC_ACROSS_CHAINS; }
+
+// the across-chains workspace holds `slots` right-hand sides per chain (1: leapfrog steps; kNutsRhsMaxSlots: NUTS).  Called by the entry
+// points before their first launch, never inside a round.
+int across_alloc(mcd_hmc* m, int slots)
+{
+    if (m->wx_slots >= slots) return MCD_OK;
+    HHIP_TRY(hipStreamSynchronize(m->stream));
+    for (double* old : {m->wx.X, m->wx.Y})
+        if (old) {
+            m->allocs.erase(std::find(m->allocs.begin(), m->allocs.end(), (void*)old));
+            (void)hipFree(old);
+        }
+    m->wx = mcd::MetricAcross{};
+    m->wx_slots = 0;
+    const size_t count = (size_t)slots * (size_t)m->dev.batch * (size_t)m->dev.dim;
+    if (int rc = halloc(m, &m->wx.X, count)) return rc;
+    if (int rc = halloc(m, &m->wx.Y, count)) return rc;
+    if (!m->d_list)
+        if (int rc = halloc(m, &m->d_list, (size_t)m->dev.batch)) return rc;
+    m->wx_slots = slots;
+    return MCD_OK;
+}
+
+// the drift of one leapfrog step under the across-chains form: Y = P C over all chains, then q += eps Y
+int drift_across(mcd_hmc* m)
+{
+    const mcd::HmcDev& D = m->dev;
+    HHIP_TRY(mcd::launch_metric_gemm(D.p, D.metric, m->wx.Y, D.batch, D.dim, false, m->stream));
+    HHIP_TRY(mcd::launch_hmc_drift_across(D, m->wx.Y, m->stream));
+    return MCD_OK;
+}
+
+// the largest position a dense metric serves on this handle: the form decides
+int dense_max_dim(const mcd_hmc* m) { return m->form == MCD_HMC_METRIC_ACROSS_CHAINS ? MCD_HMC_DENSE_ACROSS_MAX_DIM : MCD_HMC_DENSE_MAX_DIM; }
 
 // The metric argument of an entry point: positive inverse masses [dim] -- or NULL while a dense metric is set on the handle, so that
 // no caller runs another metric than the one it names.
@@ -344,6 +390,8 @@ int mcd_hmc_leapfrog(mcd_hmc_t* m, double* p, const double* eps, const double* d
     const size_t B = (size_t)D.batch, BD = B * (size_t)D.dim;
     if (int rc = check_inv_mass(m, "mcd_hmc_leapfrog", inv_mass)) return rc;
     HHIP_TRY(hipSetDevice(m->device));
+    if (across(m))
+        if (int rc = across_alloc(m, 1)) return rc;
     HHIP_TRY(hipMemcpyAsync(D.p, p, sizeof(double) * BD, hipMemcpyHostToDevice, m->stream));
     HHIP_TRY(hipMemcpyAsync(m->d_eps, eps, sizeof(double) * B, hipMemcpyHostToDevice, m->stream));
     if (int rc = upload_inv_mass(m, inv_mass)) return rc;
@@ -355,8 +403,14 @@ int mcd_hmc_leapfrog(mcd_hmc_t* m, double* p, const double* eps, const double* d
     }
     // p += eps/2 g;  [ q += eps Minv p;  g = grad(q);  p += eps g ] x (n - 1);  q += eps Minv p;  g = grad(q);  p += eps/2 g
     // three launches per step (kick + drift fused, prior gradient, likelihood gradient), the closing half kick with the collect
+    // (across-chains form of a dense metric: the kick, the product over all chains, the drift)
     for (int s = 0; s < n_steps; ++s) {
-        HHIP_TRY(mcd::launch_hmc_kick_drift(D, (s == 0) ? 0.5 : 1.0, m->stream));
+        if (across(m)) {
+            HHIP_TRY(mcd::launch_hmc_kick(D, (s == 0) ? 0.5 : 1.0, 0, m->stream));
+            if (int rc = drift_across(m)) return rc;
+        } else {
+            HHIP_TRY(mcd::launch_hmc_kick_drift(D, (s == 0) ? 0.5 : 1.0, m->stream));
+        }
         if (int rc = eval_gradients(m)) return rc;
     }
     if (n_steps > 0)
@@ -377,6 +431,8 @@ int mcd_hmc_step_from(mcd_hmc_t* m, double* q, double* p, double* grad, int have
     const size_t B = (size_t)D.batch, BD = B * (size_t)D.dim;
     if (int rc = check_inv_mass(m, "mcd_hmc_step_from", inv_mass)) return rc;
     HHIP_TRY(hipSetDevice(m->device));
+    if (across(m))
+        if (int rc = across_alloc(m, 1)) return rc;
     HHIP_TRY(hipMemcpyAsync(D.q, q, sizeof(double) * BD, hipMemcpyHostToDevice, m->stream));
     HHIP_TRY(hipMemcpyAsync(D.p, p, sizeof(double) * BD, hipMemcpyHostToDevice, m->stream));
     HHIP_TRY(hipMemcpyAsync(m->d_eps, eps, sizeof(double) * B, hipMemcpyHostToDevice, m->stream));
@@ -394,7 +450,11 @@ int mcd_hmc_step_from(mcd_hmc_t* m, double* q, double* p, double* grad, int have
         if (int rc = eval_gradients(m)) return rc;
     }
     HHIP_TRY(mcd::launch_hmc_kick(D, 0.5, have_grad ? 1 : 0, m->stream));
-    HHIP_TRY(mcd::launch_hmc_drift(D, m->stream));
+    if (across(m)) {
+        if (int rc = drift_across(m)) return rc;
+    } else {
+        HHIP_TRY(mcd::launch_hmc_drift(D, m->stream));
+    }
     if (int rc = eval_gradients(m)) return rc;
     HHIP_TRY(mcd::launch_hmc_kick(D, 0.5, 0, m->stream));
     HHIP_TRY(mcd::launch_hmc_collect(D, m->stream));
@@ -413,6 +473,8 @@ namespace {
 
 constexpr int kNutsMaxDepth = 12;
 static_assert(mcd::kHmcDenseMaxDim == MCD_HMC_DENSE_MAX_DIM, "the kernels' bound is the header's");
+static_assert(mcd::kNutsMaxDepthLevels == kNutsMaxDepth, "the right-hand-side plan's depth is the driver's");
+static_assert(MCD_HMC_DENSE_ACROSS_MAX_DIM >= 2 * mcd::kSparseGradMaxNodes + 2, "every dim a handle can have");
 
 int nuts_alloc(mcd_hmc* m)
 {
@@ -436,11 +498,49 @@ int nuts_alloc(mcd_hmc* m)
     return halloc(m, &m->d_active, 1);
 }
 
-// one transition for every chain; eps and inv_mass already on the device
-int nuts_transition(mcd_hmc* m, int max_depth, uint64_t seed, int64_t chain0, uint64_t transition)
+// The tree building of one transition under the across-chains form of a dense metric (k_nuts_across.hip has the sequence): the chains are
+// in lock step, so round r is leaf i of doubling j for every chain still building (nuts_round_position) and the number of products it
+// needs is known here (nuts_rhs_plan).  The counter the host polls after every round is the number of chains that go on, and the kernel
+// that counts them lists them: the products multiply the listed chains' rows only.
+int nuts_build_across(mcd_hmc* m, int max_depth, uint64_t seed, int64_t chain0, uint64_t transition)
 {
-    mcd::HmcDev& D = m->dev;
-    D.dir = m->d_dir;
+    const mcd::HmcDev& D = m->dev;
+    const mcd::MetricAcross& W = m->wx;
+    const int64_t B = D.batch;
+    HHIP_TRY(mcd::launch_nutsx_draw(D, W.X, seed, chain0, transition, m->stream));
+    HHIP_TRY(mcd::launch_metric_gemm(W.X, D.metric_uinv, W.Y, B, D.dim, true, m->stream));        // P = U^-T z
+    HHIP_TRY(mcd::launch_metric_gemm(W.Y, D.metric, W.X, B, D.dim, false, m->stream));            // CP
+    HHIP_TRY(mcd::launch_nutsx_begin(D, m->nuts, W.Y, W.X, seed, chain0, transition, m->stream));
+    HHIP_TRY(mcd::launch_metric_gemm(D.p, D.metric, W.Y, B, D.dim, false, m->stream));
+    HHIP_TRY(mcd::launch_nutsx_drift(D, m->nuts, W.Y, m->stream));
+    const int64_t max_rounds = (int64_t)1 << max_depth;
+    const int* list = nullptr;                                        // every chain in round 0
+    int n = (int)B;
+    for (int64_t r = 0; r < max_rounds; ++r) {
+        int j = 0, i = 0;
+        mcd::nuts_round_position(r, &j, &i);
+        const mcd::NutsRhsPlan plan = mcd::nuts_rhs_plan(j, i);
+        if (int rc = eval_gradients(m)) return rc;
+        HHIP_TRY(mcd::launch_nutsx_leaf(D, m->nuts, W.X, m->stream));                                          // (a)
+        HHIP_TRY(mcd::launch_metric_gemm_rows(W.X, D.metric, W.Y, (int64_t)plan.count * n, D.dim, false, list, n, B, m->stream));   // (b)
+        HHIP_TRY(hipMemsetAsync(m->d_active, 0, sizeof(int), m->stream));
+        HHIP_TRY(mcd::launch_nutsx_book(D, m->nuts, W.Y, seed, chain0, transition, max_depth, m->d_active, m->d_list, m->stream));   // (c)
+        int active = 0;
+        HHIP_TRY(hipMemcpyAsync(&active, m->d_active, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+        HHIP_TRY(hipStreamSynchronize(m->stream));
+        if (active == 0) break;
+        list = m->d_list;
+        n = active;
+        HHIP_TRY(mcd::launch_metric_gemm_rows(D.p, D.metric, W.Y, n, D.dim, false, list, n, B, m->stream));    // (d)
+        HHIP_TRY(mcd::launch_nutsx_drift(D, m->nuts, W.Y, m->stream));                                          // (e)
+    }
+    return MCD_OK;
+}
+
+// the per-chain kernels: diagonal metric, or a dense one in the per-chain form
+int nuts_build(mcd_hmc* m, int max_depth, uint64_t seed, int64_t chain0, uint64_t transition)
+{
+    const mcd::HmcDev& D = m->dev;
     HHIP_TRY(mcd::launch_nuts_begin(D, m->nuts, seed, chain0, transition, m->stream));
     const int64_t max_rounds = (int64_t)1 << max_depth;               // 2^max_depth - 1 leaves at most
     for (int64_t r = 0; r < max_rounds; ++r) {
@@ -452,6 +552,15 @@ int nuts_transition(mcd_hmc* m, int max_depth, uint64_t seed, int64_t chain0, ui
         HHIP_TRY(hipStreamSynchronize(m->stream));
         if (active == 0) break;
     }
+    return MCD_OK;
+}
+
+// one transition for every chain; eps and inv_mass already on the device
+int nuts_transition(mcd_hmc* m, int max_depth, uint64_t seed, int64_t chain0, uint64_t transition)
+{
+    mcd::HmcDev& D = m->dev;
+    D.dir = m->d_dir;
+    if (int rc = across(m) ? nuts_build_across(m, max_depth, seed, chain0, transition) : nuts_build(m, max_depth, seed, chain0, transition)) return rc;
     HHIP_TRY(mcd::launch_nuts_end(D, m->nuts, m->stream));
     // k_nuts_end put the accepted point into D.q / D.grad / D.value and the state arrays, but the raw outputs of the gradient
     // kernels still belong to the LAST LEAF evaluated (another point, possibly outside the support).  mcd_hmc_leapfrog's first
@@ -481,6 +590,8 @@ int mcd_hmc_nuts(mcd_hmc_t* m, const double* eps, const double* inv_mass, int ma
     if (int rc = m->rec.room("mcd_hmc_nuts", 1)) return rc;
     HHIP_TRY(hipSetDevice(m->device));
     if (int rc = nuts_alloc(m)) return rc;
+    if (across(m))
+        if (int rc = across_alloc(m, mcd::kNutsRhsMaxSlots)) return rc;
     HHIP_TRY(hipMemcpyAsync(m->d_eps, eps, sizeof(double) * B, hipMemcpyHostToDevice, m->stream));
     if (int rc = upload_inv_mass(m, inv_mass)) return rc;
     if (int rc = nuts_transition(m, max_depth, seed, chain_offset, transition)) return rc;
@@ -583,13 +694,31 @@ int mcd_hmc_set_metric(mcd_hmc_t* m, const double* inv_mass_dense)
         metric_clear(m);
         return MCD_OK;
     }
-    if (m->dev.dim > MCD_HMC_DENSE_MAX_DIM)
-        return hfail(MCD_ERR_UNSUPPORTED, "mcd_hmc_set_metric: dim = %d, a dense metric serves positions of up to MCD_HMC_DENSE_MAX_DIM = %d coordinates",
-                     m->dev.dim, MCD_HMC_DENSE_MAX_DIM);
+    if (m->dev.dim > dense_max_dim(m))
+        return hfail(MCD_ERR_UNSUPPORTED, "mcd_hmc_set_metric: dim = %d, a dense metric serves positions of up to %s = %d coordinates", m->dev.dim,
+                     m->form == MCD_HMC_METRIC_ACROSS_CHAINS ? "MCD_HMC_DENSE_ACROSS_MAX_DIM" : "MCD_HMC_DENSE_MAX_DIM", dense_max_dim(m));
     std::vector<double> sym, uinv;
     char why[256];
     if (!metric_factors(m->dev.dim, inv_mass_dense, sym, uinv, why, sizeof why)) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_set_metric: %s", why);
     return metric_install(m, sym, uinv);
+}
+
+int mcd_hmc_set_metric_form(mcd_hmc_t* m, int form)
+{
+    if (!m) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_set_metric_form: NULL handle");
+    if (form != MCD_HMC_METRIC_PER_CHAIN && form != MCD_HMC_METRIC_ACROSS_CHAINS)
+        return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_set_metric_form: form = %d is neither MCD_HMC_METRIC_PER_CHAIN nor MCD_HMC_METRIC_ACROSS_CHAINS", form);
+    if (m->dev.metric)
+        return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_set_metric_form: a dense metric is set on this handle: clear it first (mcd_hmc_set_metric(NULL))");
+    m->form = form;
+    return MCD_OK;
+}
+
+int mcd_hmc_get_metric_form(const mcd_hmc_t* m, int* form)
+{
+    if (!m || !form) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_get_metric_form: NULL argument");
+    *form = m->form;
+    return MCD_OK;
 }
 
 int mcd_hmc_get_metric(const mcd_hmc_t* m, int* is_dense, double* inv_mass_dense)
@@ -608,18 +737,25 @@ int mcd_hmc_nuts_warmup_dense(mcd_hmc_t* m, int windows, int window, double* eps
     if (!m || !eps || !inv_mass0) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_warmup_dense: NULL argument");
     if (windows < 1 || window < 1) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_warmup_dense: need windows >= 1 and window >= 1");
     const size_t B = (size_t)m->dev.batch, dim = (size_t)m->dev.dim;
-    if (m->dev.dim > MCD_HMC_DENSE_MAX_DIM)
-        return hfail(MCD_ERR_UNSUPPORTED, "mcd_hmc_nuts_warmup_dense: dim = %d, a dense metric serves positions of up to MCD_HMC_DENSE_MAX_DIM = %d coordinates",
-                     m->dev.dim, MCD_HMC_DENSE_MAX_DIM);
+    if (m->dev.dim > dense_max_dim(m))
+        return hfail(MCD_ERR_UNSUPPORTED, "mcd_hmc_nuts_warmup_dense: dim = %d, a dense metric serves positions of up to %s = %d coordinates", m->dev.dim,
+                     m->form == MCD_HMC_METRIC_ACROSS_CHAINS ? "MCD_HMC_DENSE_ACROSS_MAX_DIM" : "MCD_HMC_DENSE_MAX_DIM", dense_max_dim(m));
     for (size_t k = 0; k < dim; ++k)
         if (!(inv_mass0[k] > 0) || !std::isfinite(inv_mass0[k])) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_warmup_dense: inverse masses must be positive");
     if (int rc = m->rec.room("mcd_hmc_nuts_warmup_dense", ((int64_t)windows + 1) * (int64_t)window)) return rc;
     metric_clear(m);
     HHIP_TRY(hipSetDevice(m->device));
+    // where the call's time goes (mcd_hmc_warmup_phases_): 0 factorisations (host) + upload, 1 covariance, 2 window buffer, 3 transitions
+    using clk = std::chrono::steady_clock;
+    double* phase = m->warmup_phase;
+    std::fill(phase, phase + 4, 0.0);
+    auto since = [](clk::time_point t0) { return std::chrono::duration<double>(clk::now() - t0).count(); };
+    clk::time_point t0 = clk::now();
     const size_t n = B * (size_t)window;
     Scratch Q, mom;                                                   // [window][batch][dim] positions; [dim] means + [dim][dim] covariance
     HHIP_TRY(hipMalloc((void**)&Q.p, sizeof(double) * n * dim));
     HHIP_TRY(hipMalloc((void**)&mom.p, sizeof(double) * (dim + dim * dim)));
+    phase[2] += since(t0);
     std::vector<double> alpha(B), cov(dim * dim), sym, uinv;
     char why[256];
     uint64_t t = first_transition;
@@ -627,27 +763,87 @@ int mcd_hmc_nuts_warmup_dense(mcd_hmc_t* m, int windows, int window, double* eps
         if (int rc = nuts_run(m, window, 1, eps, m->dev.metric ? nullptr : inv_mass0, delta, max_depth, seed, chain_offset, t, alpha.data(), nullptr,
                               nullptr, Q.p))
             return rc;
+        HHIP_TRY(hipStreamSynchronize(m->stream));
+        phase[3] += since(t0);
+        t0 = clk::now();
         t += (uint64_t)window;
         HHIP_TRY(mcd::launch_hmc_cov(Q.p, (int64_t)n, (int)dim, mom.p, mom.p + dim, m->stream));
         HHIP_TRY(hipMemcpyAsync(cov.data(), mom.p + dim, sizeof(double) * dim * dim, hipMemcpyDeviceToHost, m->stream));
         HHIP_TRY(hipStreamSynchronize(m->stream));
+        phase[1] += since(t0);
+        t0 = clk::now();
         const double n_eff = (double)n, keep = n_eff / (n_eff + 5.0), floor_ = 1e-3 * (5.0 / (n_eff + 5.0));
         for (size_t i = 0; i < dim; ++i)
             for (size_t j = 0; j < dim; ++j) cov[i * dim + j] = keep * cov[i * dim + j] + (i == j ? floor_ : 0.0);
         // a chain outside the support leaves NaN positions, a degenerate window no factor: keep the metric
         if (metric_factors((int)dim, cov.data(), sym, uinv, why, sizeof why))
             if (int rc = metric_install(m, sym, uinv)) return rc;
+        phase[0] += since(t0);
+        t0 = clk::now();
     }
     if (!m->dev.metric) {                                             // no window could be used: the starting masses as the dense metric
         std::fill(cov.begin(), cov.end(), 0.0);
         for (size_t k = 0; k < dim; ++k) cov[k * dim + k] = inv_mass0[k];
         if (!metric_factors((int)dim, cov.data(), sym, uinv, why, sizeof why)) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_warmup_dense: %s", why);
         if (int rc = metric_install(m, sym, uinv)) return rc;
+        phase[0] += since(t0);
+        t0 = clk::now();
     }
     if (int rc = nuts_run(m, window, 1, eps, nullptr, delta, max_depth, seed, chain_offset, t, alpha.data(), nullptr, nullptr, nullptr)) return rc;
+    HHIP_TRY(hipStreamSynchronize(m->stream));
+    phase[3] += since(t0);
     if (mean_alpha) std::copy(alpha.begin(), alpha.end(), mean_alpha);
     if (inv_mass_dense_out) std::copy(m->h_metric.begin(), m->h_metric.end(), inv_mass_dense_out);
     return MCD_OK;
+}
+
+// seconds the last mcd_hmc_nuts_warmup_dense of this handle spent in its four phases: host factorisations and their upload, the window
+// covariance (kernel + copy), the window buffer's allocation, the transitions (tools/bench_nuts.py; not part of the public header)
+int mcd_hmc_warmup_phases_(const mcd_hmc_t* m, double* seconds)
+{
+    if (!m || !seconds) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_warmup_phases_: NULL argument");
+    std::copy(m->warmup_phase, m->warmup_phase + 4, seconds);
+    return MCD_OK;
+}
+
+// Host-only self test of the right-hand-side plan of the across-chains NUTS (nuts_rhs_plan.hpp; tests/test_nuts_rhs_plan_host.py, no GPU):
+// walks every leaf of every doubling j < depth as k_nuts_step does -- level k closes at leaf i when (i + 1) % 2^k == 0 and i % 2^k != 0,
+// the whole tree's test follows leaf 2^j - 1 -- and compares count, slots and the round's (j, i) with the plan.  Returns the number of
+// rounds checked (2^depth - 1), < 0 for the first kind of disagreement.  out[0 .. 2]: rounds, the largest count, the sum of all counts.
+int mcd_nuts_rhs_plan_selftest_(int depth, int64_t* out)
+{
+    if (depth < 1 || depth > mcd::kNutsMaxDepthLevels) return -1;
+    int64_t r = 0, total = 0;
+    int largest = 0;
+    for (int j = 0; j < depth; ++j)
+        for (int i = 0; i < (1 << j); ++i, ++r) {
+            int jr = -1, ir = -1;
+            mcd::nuts_round_position(r, &jr, &ir);
+            if (jr != j || ir != i) return -2;
+            const mcd::NutsRhsPlan p = mcd::nuts_rhs_plan(j, i);
+            int closes = 0;
+            for (int k = 1; k <= j; ++k) {
+                const int size = 1 << k;
+                const bool opens = i % size == 0, closing = (i + 1) % size == 0;
+                if (opens && closing) return -3;
+                if (closing) {
+                    if (k != closes + 1) return -4;               // the closed levels are 1 .. closes, in the order of the slots
+                    ++closes;
+                }
+            }
+            const int whole = (i + 1 == (1 << j)) ? 1 : 0;
+            if (p.closes != closes || p.whole != whole || p.count != 1 + closes + whole) return -5;
+            if (p.count < 1 || p.count > mcd::kNutsRhsMaxSlots) return -6;
+            largest = std::max(largest, p.count);
+            total += p.count;
+        }
+    if (r != ((int64_t)1 << depth) - 1) return -7;
+    if (out) {
+        out[0] = r;
+        out[1] = largest;
+        out[2] = total;
+    }
+    return (int)r;
 }
 
 // Step sizes AND masses: the reference tunes both (`HTuningConf HTuneLeapfrog HTuneAllMasses`, app/Hamiltonian.hs:62-63; the

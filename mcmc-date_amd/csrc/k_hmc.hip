@@ -175,6 +175,20 @@ __global__ __launch_bounds__(256) void k_hmc_drift_dense(HmcDev D)
     hmc_drift_dense(D, b, D.eps[b] * (D.dir ? D.dir[b] : 1.0), xs);
 }
 
+// the drift under a dense metric in the across-chains form: Y = P C is k_metric_gemm.hip's product over all chains, q += e Y elementwise
+__global__ __launch_bounds__(256) void k_hmc_drift_across(HmcDev D, const double* __restrict__ Y)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= D.batch * D.dim) return;
+    const int64_t b = i / D.dim;
+    const int k = (int)(i - b * D.dim);
+    const double e = D.eps[b] * (D.dir ? D.dir[b] : 1.0);
+    double* slot = hmc_state_slot(D, b, D.pos_field[k], D.pos_index[k]);
+    const double q = *slot + e * Y[i];
+    *slot = q;
+    D.q[i] = q;
+}
+
 // the closing half kick together with k_hmc_collect
 __global__ __launch_bounds__(256) void k_hmc_kick_collect(HmcDev D, double kick)
 {
@@ -215,6 +229,11 @@ hipError_t launch_hmc_drift(const HmcDev& D, hipStream_t st)
         hipLaunchKernelGGL(k_hmc_drift_dense, dim3((unsigned)D.batch), dim3(256), 0, st, D);
     else
         hipLaunchKernelGGL(k_hmc_drift, dim3(hmc_grid(D)), dim3(256), 0, st, D);
+    return hipGetLastError();
+}
+hipError_t launch_hmc_drift_across(const HmcDev& D, const double* Y, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_hmc_drift_across, dim3(hmc_grid(D)), dim3(256), 0, st, D, Y);
     return hipGetLastError();
 }
 hipError_t launch_hmc_kick_drift(const HmcDev& D, double kick, hipStream_t st)

@@ -24,7 +24,8 @@
 // (mcd_hmc_set_metric) -- a full inverse mass matrix C = U U^T: momenta p = U^-T z from the same normal draws z, kinetic energy
 // 1/2 p^T C p, drift q += eps (C p), U-turn (q+ - q-)^T C r >= 0 at both ends from ONE product w = C (q+ - q-).  The products are
 // metric_device.hpp's; slice, doubling, reservoir, merge, divergence test and random streams are the same code.  The diagonal
-// branches keep their expressions as they were.
+// branches keep their expressions as they were.  The dense metric's other form (mcd_hmc_set_metric_form: the products of all chains as one
+// matrix product, any dim) is k_nuts_across.hip; the helpers both files use are nuts_device.hpp's.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -32,61 +33,9 @@
 #include "metric_device.hpp"
 #include "mh_device.hpp"
 #include "mvn_kernels.h"
+#include "nuts_device.hpp"
 
 namespace mcd {
-
-constexpr double NUTS_DELTA_MAX = 1000.0;
-
-__device__ __forceinline__ double nuts_block_sum(double v, double* red)
-{
-    v = mh_wave_sum(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
-// the entries of k_hmc.hip's hmc_grad_entry / hmc_state_slot, needed here as well
-__device__ __forceinline__ double nuts_grad_entry(const HmcDev& D, int64_t b, int field, int v)
-{
-    const int64_t B = D.batch;
-    const double* H = D.H + b * D.ld;
-    const double* R = D.R + b * D.ld;
-    const int l = 1, r = D.root_right;
-    switch (field) {
-        case 0: return D.gp_sc[0 * B + b];
-        case 1: return D.gp_sc[1 * B + b];
-        case 2: return D.gp_sc[2 * B + b] + D.gl_tH[b] - 1.0 / D.sc[2 * B + b];
-        case 4: return D.gp_sc[3 * B + b] + D.gl_rMu[b] - 1.0 / D.sc[3 * B + b];
-        case 5: return D.gp_sc[4 * B + b];
-        default: break;
-    }
-    const double S = (H[0] - H[l]) * R[l] + (H[0] - H[r]) * R[r];
-    if (field == 3) {
-        double j = 0.0;
-        if (v == l || v == r) j = R[v] / S;
-        if (v == 0) j = -(R[l] + R[r]) / S;
-        return D.gp_H[b * D.ld + v] + D.gl_H[b * D.ld + v] + j;
-    }
-    double j = 0.0;
-    if (v == l || v == r) j = -(H[0] - H[v]) / S;
-    return D.gp_R[b * D.ld + v] + D.gl_R[b * D.ld + v] + j;
-}
-
-__device__ __forceinline__ double* nuts_state_slot(const HmcDev& D, int64_t b, int field, int v)
-{
-    const int64_t B = D.batch;
-    switch (field) {
-        case 0: return D.sc + 0 * B + b;
-        case 1: return D.sc + 1 * B + b;
-        case 2: return D.sc + 2 * B + b;
-        case 4: return D.sc + 3 * B + b;
-        case 5: return D.sc + 4 * B + b;
-        case 3: return D.H + b * D.ld + v;
-        default: return D.R + b * D.ld + v;
-    }
-}
 
 // (q_minus, r_minus, q_plus, r_plus) do not turn back on each other: (q+ - q-) . M^-1 r >= 0 at both ends (Algorithm 3)
 template <bool Dense>
@@ -150,13 +99,6 @@ __device__ __forceinline__ void nuts_launch_leaf(const HmcDev& D, const NutsDev&
         }
     }
     if (threadIdx.x == 0) const_cast<double*>(D.dir)[b] = (double)v;
-}
-
-__device__ __forceinline__ int nuts_direction(uint64_t seed, int64_t chain, uint64_t transition, int j)
-{
-    double ua, ub;
-    philox_block(mh_rng(seed, chain, transition), 0x10u + 2u * (uint32_t)j, ua, ub);
-    return ua < 0.5 ? -1 : 1;
 }
 
 // Start of a transition: momenta, slice variable, the tree = the current point, first doubling, first leaf on its way.

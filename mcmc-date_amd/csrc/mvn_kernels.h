@@ -316,6 +316,29 @@ hipError_t launch_nuts_begin(const HmcDev& D, const NutsDev& N, uint64_t seed, i
 hipError_t launch_nuts_step(const HmcDev& D, const NutsDev& N, uint64_t seed, int64_t chain0, uint64_t transition, int max_depth, int* active,
                             hipStream_t st);
 hipError_t launch_nuts_end(const HmcDev& D, const NutsDev& N, hipStream_t st);
+// The dense metric's second form (mcd_hmc_set_metric_form, MCD_HMC_METRIC_ACROSS_CHAINS): the products with C and U^-1 are rows of one
+// matrix product over the lock-step chains (k_metric_gemm.hip) instead of one workgroup's matvec per chain (metric_device.hpp), so no
+// bound on dim comes from a workgroup's registers and LDS.  Y[r][k] = sum_j X[r][j] A[j dim + k], X and Y [rows][dim], A [dim][dim];
+// lower: A is lower triangular (U^-1: the rows of Y are U^-T x).  A row of Y depends on that row of X and on dim only.
+hipError_t launch_metric_gemm(const double* X, const double* A, double* Y, int64_t rows, int dim, bool lower, hipStream_t st);
+// the same for the rows (r / n_list) stride + list[r % n_list], r < rows, of X and Y only: list [n_list] on the device holds the chains
+// still building their trees, stride = batch; the other rows are neither read nor written
+hipError_t launch_metric_gemm_rows(const double* X, const double* A, double* Y, int64_t rows, int dim, bool lower, const int* list, int n_list,
+                                   int64_t stride, hipStream_t st);
+// The workspace of that form, the handle's: right-hand sides and products, slot s of chain b = row s batch + b (nuts_rhs_plan.hpp);
+// [kNutsRhsMaxSlots][batch][dim] each.  Passed to the across-chains kernels only: HmcDev and the per-chain kernels stay as they are.
+struct MetricAcross {
+    double *X, *Y;
+};
+hipError_t launch_hmc_drift_across(const HmcDev& D, const double* Y, hipStream_t st);   // q += eps dir Y, scattered into the state (Y = P C)
+// k_nuts_across.hip: k_nuts_begin and k_nuts_step split at the products (the launch sequence: hmc_capi.cpp, nuts_transition_across)
+hipError_t launch_nutsx_draw(const HmcDev& D, double* Z, uint64_t seed, int64_t chain0, uint64_t transition, hipStream_t st);
+hipError_t launch_nutsx_begin(const HmcDev& D, const NutsDev& N, const double* P, const double* CP, uint64_t seed, int64_t chain0, uint64_t transition,
+                              hipStream_t st);
+hipError_t launch_nutsx_drift(const HmcDev& D, const NutsDev& N, const double* Y, hipStream_t st);
+hipError_t launch_nutsx_leaf(const HmcDev& D, const NutsDev& N, double* X, hipStream_t st);
+hipError_t launch_nutsx_book(const HmcDev& D, const NutsDev& N, const double* Y, uint64_t seed, int64_t chain0, uint64_t transition, int max_depth,
+                             int* active, int* list, hipStream_t st);
 // The NUTS driver's sample recorder (k_hmc_record.hip; mcd_hmc_record_*): the state the handle holds after a transition as sample number
 // `sample` (1, 2, ...) of the ring R -- the MhRec slot layout, slot (sample - 1) % capacity, beta = 1; the seven doubles that are padding in
 // a Metropolis-Hastings record carry the transition's diagnostics: tree depth, leapfrog steps, acceptance statistic alpha / max(n_alpha, 1),

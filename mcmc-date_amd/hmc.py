@@ -114,11 +114,29 @@ class Leapfrog(DriverCalls):
     def set_metric(self, C):
         """C [dim, dim], symmetric positive definite, becomes the handle's metric (momenta p = U^-T z with C = U U^T, kinetic energy
         1/2 p^T C p, drift q += eps C p, U-turn test through C); leapfrog / step_from / nuts / nuts_run then take inv_mass=None.
-        Refused (McdError, the handle untouched): a non-finite entry, an asymmetric pair, not positive definite, dim > 512."""
+        Refused (McdError, the handle untouched): a non-finite entry, an asymmetric pair, not positive definite, dim > 512 in the
+        default per-chain form (set_metric_form("across_chains") serves every dim)."""
         C = np.ascontiguousarray(C, dtype=np.float64)
         if C.shape != (self.dim, self.dim):
             raise ValueError("set_metric: C must be [dim, dim]")
         _capi.check(_capi.lib().mcd_hmc_set_metric(self._h, dp(C)))
+
+    _METRIC_FORMS = {"per_chain": _capi.MCD_HMC_METRIC_PER_CHAIN, "across_chains": _capi.MCD_HMC_METRIC_ACROSS_CHAINS}
+
+    def set_metric_form(self, form: str):
+        """How the dense metric's products are taken (mcd_hmc_set_metric_form): "per_chain" (the default: one workgroup's sum per chain,
+        dim <= 512) or "across_chains" (the lock-step chains' products as one matrix product on the matrix cores, every dim).  Allowed
+        only while no dense metric is set (McdError otherwise, the handle untouched); survives clear_metric."""
+        if form not in self._METRIC_FORMS:
+            raise ValueError(f"set_metric_form: {form!r} is none of {sorted(self._METRIC_FORMS)}")
+        _capi.check(_capi.lib().mcd_hmc_set_metric_form(self._h, self._METRIC_FORMS[form]))
+
+    @property
+    def metric_form(self) -> str:
+        """"per_chain" or "across_chains": the handle's form of the dense metric's products."""
+        form = ctypes.c_int(-1)
+        _capi.check(_capi.lib().mcd_hmc_get_metric_form(self._h, ctypes.byref(form)))
+        return next(name for name, value in self._METRIC_FORMS.items() if value == form.value)
 
     def clear_metric(self):
         """Back to the diagonal metric: the handle is what it was before set_metric."""

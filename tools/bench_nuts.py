@@ -15,8 +15,12 @@ One JSON line per run; *_runs hold every repeat, the headline figures are their 
                          --transitions recorded transitions at the tuned step sizes: microseconds per leapfrog step (a lock step of all chains:
                          the transition's rounds are the longest tree's leaves), leapfrog steps per transition and chain, mean tree depth, the
                          tuned step sizes, and the smallest effective sample size over the inner node ages per leapfrog step
-                         (Leapfrog.record_summary)."""
+                         (Leapfrog.record_summary).
+  --metric-form {per_chain,across_chains}   with --metric dense: how the dense metric's products are taken (Leapfrog.set_metric_form); the
+                         line then carries the seconds the warm-up call spent in its four phases (host factorisations, window covariance,
+                         window buffer, transitions)."""
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -86,11 +90,19 @@ def metric_report(args, topo, lf, eps0, inv_mass0, form):
     kw = dict(max_depth=args.max_depth, seed=args.seed)
     t0 = time.perf_counter()
     if dense:
+        lf.set_metric_form(args.metric_form)
         eps, _, alpha_w = lf.nuts_warmup_dense(eps0, inv_mass0, windows=args.windows, window=args.window, **kw)
         inv_mass = None
     else:
         eps, inv_mass, alpha_w = lf.nuts_warmup(eps0, inv_mass0, windows=args.windows, window=args.window, **kw)
     warm_s = time.perf_counter() - t0
+    phases = None
+    if dense:                                                      # the library's own clock over the call's four phases (hmc_capi.cpp)
+        buf = (ctypes.c_double * 4)()
+        hook = ctypes.CDLL(M._capi.LIB_PATH).mcd_hmc_warmup_phases_
+        hook.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+        M._capi.check(hook(lf._h, buf))
+        phases = dict(zip(("factorisations_s", "covariance_s", "window_buffer_s", "transitions_s"), buf))
     first = (args.windows + 1) * args.window
     lf.record_begin(period=1, capacity=T)
     lf.position()
@@ -106,6 +118,7 @@ def metric_report(args, topo, lf, eps0, inv_mass0, form):
     inner = np.flatnonzero(~topo.leaves)
     ess = summ.ages[inner, 7]
     print(json.dumps({"metric": "NUTS leapfrog steps (all chains in lock step)", "mass_matrix": args.metric,
+                      "metric_form": args.metric_form if dense else None, "warmup_phases": phases,
                       "dataset": f"synthetic {args.synthetic} leaves" if args.synthetic else args.name, "likelihood": form, "n_nodes": topo.n_nodes,
                       "dim": lf.dim, "chains": B, "windows": args.windows, "window": args.window, "transitions": T, "max_depth": args.max_depth,
                       "warmup_s": warm_s, "warmup_mean_alpha": float(alpha_w.mean()), "eps_mean": float(eps.mean()), "eps_min": float(eps.min()),
@@ -126,9 +139,12 @@ def main():
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--seed", type=int, default=5)
     ap.add_argument("--metric", choices=("diag", "dense"), default=None)
+    ap.add_argument("--metric-form", choices=("per_chain", "across_chains"), default="per_chain")
     ap.add_argument("--windows", type=int, default=3)
     ap.add_argument("--window", type=int, default=60)
     args = ap.parse_args()
+    if args.metric_form != "per_chain" and args.metric != "dense":
+        ap.error("--metric-form is valid with --metric dense")
     B, T = args.chains, args.transitions
     topo, lf, eps, inv_mass, form = synthetic_problem(args.synthetic, B) if args.synthetic else golden_problem(args.name, B)
     if args.metric:
