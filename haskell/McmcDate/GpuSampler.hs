@@ -24,6 +24,9 @@
 --     fetched samples, one @mcd_mh_record_fetch@ per chunk instead of one @mcd_mh_get_state@ per two iterations;
 --   * 'recordSummary' asks the device for the node-age summary, split R-hat and effective sample size of the samples the recorder
 --     holds (@mcd_mh_record_summary@) instead of fetching them;
+--   * 'withHamiltonian' is @--hamiltonian@ ('maybeHamiltonianProposal', app/Definitions.hs:272-278): for the duration of an action a
+--     leapfrog handle is attached to the driver (@mcd_mh_attach_hamiltonian@) and every iteration of the loops above begins with one NUTS
+--     transition of every chain, the chains moving between the two drivers on the device;
 --   * 'runMc3Gpu' is @mc3 (MC3Settings (NChains 4) (SwapPeriod 2) (NSwaps 3))@ (app/Main.hs:476-478): @mcd_mh_mc3_init@, per swap
 --     period @mcd_mh_run@ + @mcd_mh_mc3_swap@, the monitors read the chains whose temperature rank is 0 (@mcd_mh_mc3_get@).
 --
@@ -44,6 +47,10 @@ module McmcDate.GpuSampler
     recordSummary,
     runMc3Gpu,
     nodeAgeSummary,
+    -- the Hamiltonian proposal in the cycle (@--hamiltonian@)
+    withHamiltonian,
+    c_hmc_take_state,
+    c_mh_take_state,
     -- the NUTS driver's recorder, raw (the handle comes from 'McmcDate.Gpu')
     c_hmc_record_begin,
     c_hmc_record_count,
@@ -195,6 +202,23 @@ foreign import ccall unsafe "mcd_hmc_set_metric_form"
 
 foreign import ccall unsafe "mcd_hmc_get_metric_form"
   c_hmc_get_metric_form :: Ptr McdHmc -> Ptr CInt -> IO CInt
+
+-- the Hamiltonian proposal in the cycle (@--hamiltonian@: 'maybeHamiltonianProposal', app/Definitions.hs:272-278): the chains move between
+-- the two drivers on the device, and an attached @mcd_hmc_t@ makes one NUTS transition in front of every iteration of @mcd_mh_run@
+foreign import ccall unsafe "mcd_hmc_take_state"
+  c_hmc_take_state :: Ptr McdHmc -> Ptr McdMh -> IO CInt
+
+foreign import ccall unsafe "mcd_mh_take_state"
+  c_mh_take_state :: Ptr McdMh -> Ptr McdHmc -> IO CInt
+
+foreign import ccall unsafe "mcd_mh_attach_hamiltonian"
+  c_mh_attach_hamiltonian :: Ptr McdMh -> Ptr McdHmc -> Ptr CDouble -> Ptr CDouble -> CInt -> Word64 -> Word64 -> IO CInt
+
+foreign import ccall unsafe "mcd_mh_detach_hamiltonian"
+  c_mh_detach_hamiltonian :: Ptr McdMh -> IO CInt
+
+foreign import ccall unsafe "mcd_mh_hamiltonian_stats"
+  c_mh_hamiltonian_stats :: Ptr McdMh -> Ptr Int64 -> Ptr CDouble -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> CInt -> IO CInt
 
 check :: String -> CInt -> IO ()
 check _ 0 = pure ()
@@ -424,6 +448,40 @@ pourState s at hs rs =
     relabel t ls = case T.setBranches ls t of
       Just t' -> t'
       Nothing -> error "pourState: wrong number of branch labels."
+
+-- | @--hamiltonian@ ('maybeHamiltonianProposal', app/Definitions.hs:272-278; 'nutsWith', app/Hamiltonian.hs:95-105): for the duration
+-- of the action every iteration of every loop of this module ('runMetropolisHastingsGreenGpu', 'runRecorded', ...) begins with one NUTS
+-- transition of every chain on the leapfrog handle @hmc@ (made by "McmcDate.Gpu" over the same likelihood and prior, as many chains),
+-- and the shuffled cycle follows.  The reference shuffles the proposal into the cycle; here it is the first position, so the monitors
+-- and the recorder see complete iterations.
+--   eps       step sizes, one per chain (tuned beforehand: @mcd_hmc_take_state@ + @mcd_hmc_nuts_warmup@ / @_warmup_dense@ on @hmc@)
+--   invMass   @Just@ the diagonal inverse masses (length @mcd_hmc_dim@), or @Nothing@: the dense metric set on @hmc@
+--   seed      the sampler's seed xor a constant of the host's, so that the NUTS streams stay apart from the proposals' streams
+-- Returns the action's result and the mean acceptance statistic, mean tree depth and number of divergent transitions per chain.
+withHamiltonian :: GpuSampler -> Ptr McdHmc -> [Double] -> Maybe [Double] -> Int -> Word64 -> IO a -> IO (a, [(Double, Double, Int)])
+withHamiltonian s hmc eps invMass maxDepth seed act =
+  VS.unsafeWith (VS.fromList (map realToFrac eps)) $ \pe ->
+    withMass $ \pm -> do
+      check "mcd_mh_attach_hamiltonian" =<< c_mh_attach_hamiltonian (gsHandle s) hmc pe pm (fromIntegral maxDepth) seed 0
+      r <- act
+      let b = gsChains s
+      al <- VSM.new b
+      dp <- VSM.new b
+      dv <- VSM.new b
+      n <- alloca $ \pn -> do
+        VSM.unsafeWith al $ \pa -> VSM.unsafeWith dp $ \pd -> VSM.unsafeWith dv $ \pv ->
+          check "mcd_mh_hamiltonian_stats" =<< c_mh_hamiltonian_stats (gsHandle s) pn pa pd nullPtr pv 0
+        peek pn
+      check "mcd_mh_detach_hamiltonian" =<< c_mh_detach_hamiltonian (gsHandle s)
+      av <- VS.freeze al
+      dpv <- VS.freeze dp
+      dvv <- VS.freeze dv
+      let k = fromIntegral (max 1 n) :: Double
+      pure (r, [(realToFrac (av VS.! i) / k, fromIntegral (dpv VS.! i) / k, fromIntegral (dvv VS.! i)) | i <- [0 .. b - 1]])
+  where
+    withMass k = case invMass of
+      Nothing -> k nullPtr
+      Just ms -> VS.unsafeWith (VS.fromList (map realToFrac ms)) k
 
 -- one block of iterations through the shuffled cycle; accumulate: add the node ages to the running sums after every iteration
 runBlock :: StatefulGen g IO => GpuSampler -> g -> Int -> Bool -> IO ()

@@ -387,7 +387,8 @@ int mcd_hmc_step_from(mcd_hmc_t* m, double* q, double* p, double* grad, int have
  * time, each with its own random numbers, tuning parameter and accept/reject decision.  The state never leaves
  * the device between calls.  A proposal is a row of the table below; the caller builds the table and the
  * per-iteration order (the reference: app/Definitions.hs:127-278 `proposals`, weights replicated and shuffled by
- * `mcmc`).  Every proposal of the reference cycle is a kind below; NUTS (app/Hamiltonian.hs, row f3) is not built.
+ * `mcmc`).  Every proposal of the reference cycle is a kind below; the Hamiltonian proposal of `--hamiltonian` (NUTS,
+ * app/Hamiltonian.hs, row f3) is no kind of the table: it is an mcd_hmc_t attached to the driver (mcd_mh_attach_hamiltonian, below).
  * ---------------------------------------------------------------------------------------------- */
 #define MCD_PROP_SCALE_SCALAR 0        /* scaleUnbiased k [mcmc]: node = 0 birth, 1 death, 2 tH, 3 rMu, 4 rVar; p0 = k          */
 #define MCD_PROP_SLIDE_NODE 1          /* slideNodeAtUltrametric (Ultrametric.hs:50-59): node; p0 = sd                          */
@@ -534,6 +535,61 @@ int mcd_mh_mc3_get(const mcd_mh_t* m, int32_t* rank, int64_t* tried, int64_t* ac
 /* age_sum / age_sq: [batch][n_nodes] running sums over *n_samples accumulated iterations; reset with the call below. */
 int mcd_mh_get_age_sums(const mcd_mh_t* m, double* age_sum, double* age_sq, int64_t* n_samples);
 int mcd_mh_reset_age_sums(mcd_mh_t* m);
+/*
+ * The chains of one driver become the chains of the other ON THE DEVICE (k_handover.hip): what a host that runs the reference's
+ * `--hamiltonian` mode (`maybeHamiltonianProposal`, app/Definitions.hs:272-278; target `getHTarget`, app/Main.hs:349-368; `nutsWith`,
+ * app/Hamiltonian.hs:95-105) needs between the Metropolis-Hastings cycle and the NUTS transition, without seven arrays crossing the bus
+ * twice per iteration.
+ *   mcd_hmc_take_state   h := the current states of m.  Leaves h exactly as mcd_hmc_set_state would after mcd_mh_get_state of the same
+ *                        chains: state arrays, position, ln target and gradient (the gradient kernels run at the new point).
+ *   mcd_mh_take_state    m := the states h holds.  Leaves m exactly as mcd_mh_set_state would after mcd_hmc_get_state: the state arrays
+ *                        and ln prior, ln likelihood, ln jacobianRootBranch from the launches mcd_mh_set_state uses (not h's values, which
+ *                        come out of the gradient kernels and are other bits); whatever a later mcd_mh_run derives when it starts -- prior
+ *                        blocks, kept summands, the incremental z / q -- is derived from the new states.  Step counter, tuning parameters,
+ *                        counters, age sums, recorder and temperatures of m are untouched.
+ * One launch each way copies the scalars [5][batch] and the first n_nodes entries of every row of heights and rates (the two handles may
+ * have different leading dimensions), lanes over the node index.  The handles own different streams: the taking handle's stream waits for
+ * an event of the other's, nothing waits for the whole device, and the host waits where the set_state calls wait (once, at the end).
+ * Refused with MCD_ERR_INVALID_ARG, the message naming the mismatch, both handles untouched: different devices, different numbers of
+ * nodes or parent arrays, different batches, no state on the source.
+ */
+int mcd_hmc_take_state(mcd_hmc_t* h, const mcd_mh_t* m);
+int mcd_mh_take_state(mcd_mh_t* m, const mcd_hmc_t* h);
+/*
+ * The Hamiltonian proposal in the cycle: `maybeHamiltonianProposal` (app/Definitions.hs:272-278) adds one NUTS proposal of weight 1
+ * (`nutsWith`, app/Hamiltonian.hs:95-105) on the target of `getHTarget` (app/Main.hs:349-368) to the Metropolis-Hastings cycle.
+ *   mcd_mh_attach_hamiltonian   from now on every iteration of mcd_mh_run BEGINS with one NUTS transition of every chain on h, and the
+ *                        steps_per_iter scheduled proposals follow.  DEVIATION: the reference shuffles the proposal into the cycle anew
+ *                        at every iteration, so its position is random there; here it is the first.  What the kernels do at the end of
+ *                        an iteration -- recorder store, accumulate, age sums -- therefore sees the complete iteration, and the recorder
+ *                        and the summaries work unchanged.  DEFINITION: mcd_mh_run(m, schedule, n_iter, S, ...) gives the bits of, for
+ *                        it = 0 .. n_iter - 1: mcd_hmc_take_state(h, m); mcd_hmc_nuts(h, eps, inv_mass, max_depth, seed, the chain
+ *                        offset of m, first_transition + done + it, ...); mcd_mh_take_state(m, h); mcd_mh_run(m, schedule + it S, 1, S,
+ *                        ...) without an attachment -- `done` the attached transitions since this call, so consecutive runs continue the
+ *                        stream.  eps[batch] and inv_mass[dim] are copied to the device once, here; inv_mass == NULL: the dense metric
+ *                        set on h (mcd_hmc_set_metric), in whichever form h has.  seed: the caller's (a host that runs both drivers on
+ *                        one seed passes seed ^ constant, see mcd_hmc_nuts); the chain offset is m's (mcd_mh_set_chain_offset), so the
+ *                        shards of a sharded run keep disjoint streams.  trace_alpha / trace_accept keep their shape and hold the
+ *                        scheduled proposals only; mcd_mh_last_path reports the path of the Metropolis-Hastings stretches; the
+ *                        recorder's room is one check for the whole call, before anything is launched.  No kernel of either driver
+ *                        changes: per iteration the cost beside the transition is two copy launches, one posterior evaluation, and the
+ *                        launch boundaries of a run of one iteration.  h must outlive the attachment; mcd_mh_destroy does not destroy it.
+ *                        MCD_ERR_UNSUPPORTED, the handles untouched: MC3 initialised on m, m in power-posterior mode, any temperature of
+ *                        m other than 1 (a tempered Hamiltonian target is not built) -- and while attached the same from
+ *                        mcd_mh_mc3_init, mcd_mh_set_power and mcd_mh_set_temperatures (other than 1).  MCD_ERR_INVALID_ARG: the
+ *                        mismatches of mcd_hmc_take_state; an eps that is not positive and finite; max_depth outside what mcd_hmc_nuts
+ *                        accepts; an inv_mass that does not fit h's metric (a vector while h has a dense metric, NULL while it has none);
+ *                        an active recorder on h; a second attach without detach.  The last three are checked again when a run starts.
+ *   mcd_mh_detach_hamiltonian   ends the attachment; the handle then runs what a handle that never had one runs, to the bit.
+ *   mcd_mh_hamiltonian_stats    *transitions made since the attach call (or the last reset) and per chain the sums over them of the
+ *                        acceptance statistic (the alpha of mcd_hmc_nuts), tree depth, leapfrog steps and divergent transitions,
+ *                        added on the device after every transition (no host copy per iteration); any may be NULL; reset != 0 clears them.
+ */
+int mcd_mh_attach_hamiltonian(mcd_mh_t* m, mcd_hmc_t* h, const double* eps, const double* inv_mass, int max_depth, uint64_t seed,
+                              uint64_t first_transition);
+int mcd_mh_detach_hamiltonian(mcd_mh_t* m);
+int mcd_mh_hamiltonian_stats(const mcd_mh_t* m, int64_t* transitions, double* alpha_sum, int64_t* depth_sum, int64_t* leapfrog_steps,
+                             int64_t* divergent, int reset);
 /*
  * The sample recorder: thinned samples of every chain kept ON THE DEVICE while mcd_mh_run runs.  Replaces: the `monitor` of
  * app/Definitions.hs:288-417 (`mcmc`'s MonitorFile with period 2 everywhere) as the source of the states that the monitor files and

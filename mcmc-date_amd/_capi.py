@@ -123,6 +123,11 @@ SYMBOLS = {
     "mcd_mh_mc3_get": (C.c_int, [_vp, _ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _dp]),
     "mcd_mh_get_age_sums": (C.c_int, [_vp, _dp, _dp, C.POINTER(C.c_int64)]),
     "mcd_mh_reset_age_sums": (C.c_int, [_vp]),
+    "mcd_hmc_take_state": (C.c_int, [_vp, _vp]),
+    "mcd_mh_take_state": (C.c_int, [_vp, _vp]),
+    "mcd_mh_attach_hamiltonian": (C.c_int, [_vp, _vp, _dp, _dp, C.c_int, C.c_uint64, C.c_uint64]),
+    "mcd_mh_detach_hamiltonian": (C.c_int, [_vp]),
+    "mcd_mh_hamiltonian_stats": (C.c_int, [_vp, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]),
     "mcd_mh_record_begin": (C.c_int, [_vp, C.c_int32, C.c_int64]),
     "mcd_mh_record_count": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "mcd_mh_record_fetch": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _dp, _dp, _dp, _dp, _dp]),

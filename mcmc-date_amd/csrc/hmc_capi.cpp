@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/mcmcdate_mvn.h"
+#include "handover_device.hpp"
 #include "host_factor.h"
 #include "mvn_kernels.h"
 #include "nuts_rhs_plan.hpp"
@@ -67,6 +68,8 @@ struct mcd_hmc {
     double warmup_phase[4] = {0, 0, 0, 0};     // seconds of the last mcd_hmc_nuts_warmup_dense: factorisations, covariance, window buffer, transitions
     bool have_state = false;
     hipStream_t stream = nullptr;
+    const int32_t* host_parent = nullptr;      // [n_nodes] the likelihood handle's host copy of the topology (hand-overs compare it)
+    mutable hipEvent_t mark = nullptr;         // what another handle's stream waits for (mcd_hmc_chains_), created on first use
     std::vector<void*> allocs;
     mcd::Recorder rec{"mcd_hmc_record"};       // the sample recorder (mcd_hmc_record_*, recorder.cpp): it counts transitions
     mcd::RecOn rec_on() const { return {device, stream, mcd::MhRecDims{dev.batch, dev.ld, dev.n_nodes}}; }
@@ -75,6 +78,7 @@ struct mcd_hmc {
     {
         (void)hipSetDevice(device);
         for (void* p : allocs) (void)hipFree(p);
+        if (mark) (void)hipEventDestroy(mark);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -254,6 +258,7 @@ int hmc_build(std::unique_ptr<mcd_hmc>& m, int n, int root_right, const int32_t*
     HHIP_TRY(hipSetDevice(m->device));
     HHIP_TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
     mcd::HmcDev& D = m->dev;
+    m->host_parent = parent;
     D.n_nodes = n;
     D.dim = dim;
     D.root_right = root_right;
@@ -605,6 +610,91 @@ int mcd_hmc_nuts(mcd_hmc_t* m, const double* eps, const double* inv_mass, int ma
         if (alpha) alpha[b] = a[b] / (double)(na[b] > 0 ? na[b] : 1);
         if (depth) depth[b] = dp[b];
     }
+    return MCD_OK;
+}
+
+}  // extern "C"
+
+// ---- the chains of a Metropolis-Hastings handle become this handle's, on the device (handover_device.hpp, k_handover.hip) -----------
+namespace {
+
+mcd::ChainArrays arrays_of(const mcd_hmc* h) { return {h->dev.sc, h->dev.H, h->dev.R, h->dev.ld}; }
+
+// h := the chains at src once `ready` has passed on the source's stream: what mcd_hmc_set_state does behind its copies.  No host wait.
+int take_chains(mcd_hmc* h, const mcd::ChainArrays& src, hipEvent_t ready)
+{
+    const mcd::HmcDev& D = h->dev;
+    if (ready) HHIP_TRY(hipStreamWaitEvent(h->stream, ready, 0));
+    HHIP_TRY(mcd::launch_handover(arrays_of(h), src, D.batch, D.n_nodes, h->stream));
+    if (int rc = eval_gradients(h)) return rc;
+    HHIP_TRY(mcd::launch_hmc_collect(D, h->stream));
+    h->have_state = true;
+    return MCD_OK;
+}
+
+}  // namespace
+
+int mcd_hmc_chains_(const mcd_hmc* h, mcd::ChainsView* v, hipEvent_t* mark)
+{
+    if (!h || !v) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_chains_: NULL argument");
+    *v = mcd::ChainsView{h->device, h->stream, h->dev.n_nodes, h->dev.batch, h->host_parent, h->have_state, arrays_of(h)};
+    if (mark) {
+        HHIP_TRY(hipSetDevice(h->device));
+        if (!h->mark) HHIP_TRY(hipEventCreateWithFlags(&h->mark, hipEventDisableTiming));
+        HHIP_TRY(hipEventRecord(h->mark, h->stream));
+        *mark = h->mark;
+    }
+    return MCD_OK;
+}
+
+int mcd_hmc_cycle_ready_(mcd_hmc* h, const char* who, bool dense)
+{
+    if (h->rec.active())
+        return hfail(MCD_ERR_INVALID_ARG, "%s: the attached mcd_hmc_t has an active recorder (mcd_hmc_record_end first): the cycle's samples are the mcd_mh_t's", who);
+    if (dense && !h->dev.metric)
+        return hfail(MCD_ERR_INVALID_ARG, "%s: the attachment names the dense metric of the mcd_hmc_t (inv_mass == NULL), which has none set (mcd_hmc_set_metric)", who);
+    if (!dense && h->dev.metric)
+        return hfail(MCD_ERR_INVALID_ARG, "%s: a dense metric is set on the attached mcd_hmc_t (mcd_hmc_set_metric): the attachment's inv_mass must be NULL", who);
+    HHIP_TRY(hipSetDevice(h->device));
+    if (int rc = nuts_alloc(h)) return rc;
+    if (across(h))
+        if (int rc = across_alloc(h, mcd::kNutsRhsMaxSlots)) return rc;
+    return MCD_OK;
+}
+
+int mcd_hmc_cycle_transition_(mcd_hmc* h, const mcd::ChainArrays& src, hipEvent_t ready, const double* d_eps, const double* d_inv_mass, int max_depth,
+                              uint64_t seed, int64_t chain0, uint64_t transition, const mcd::HamSums& sums, hipEvent_t* done)
+{
+    // the kernels read step sizes and inverse masses through HmcDev: for this transition the attachment's arrays, then the handle's own again
+    mcd::HmcDev& D = h->dev;
+    D.eps = d_eps;
+    if (d_inv_mass) D.inv_mass = d_inv_mass;
+    int rc = take_chains(h, src, ready);
+    if (!rc) rc = nuts_transition(h, max_depth, seed, chain0, transition);
+    if (!rc && mcd::launch_ham_stats(h->nuts, sums, D.batch, h->stream) != hipSuccess) rc = hfail(MCD_ERR_HIP, "mcd_mh_run: the attached transition's diagnostics could not be launched");
+    D.eps = h->d_eps;
+    D.inv_mass = h->d_inv_mass;
+    if (rc) return rc;
+    mcd::ChainsView v;
+    return mcd_hmc_chains_(h, &v, done);
+}
+
+extern "C" {
+
+// h := the current states of m (include/mcmcdate_mvn.h): mcd_hmc_set_state after mcd_mh_get_state, without the host in between
+int mcd_hmc_take_state(mcd_hmc_t* h, const mcd_mh_t* m)
+{
+    if (!h || !m) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_take_state: NULL handle");
+    mcd::ChainsView dst, src;
+    if (int rc = mcd_hmc_chains_(h, &dst, nullptr)) return rc;
+    if (int rc = mcd_mh_chains_(m, &src, nullptr)) return rc;
+    char why[256];
+    if (!mcd::handover_allowed(dst, src, why, sizeof why)) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_take_state: %s", why);
+    hipEvent_t ready = nullptr;
+    if (int rc = mcd_mh_chains_(m, &src, &ready)) return rc;
+    HHIP_TRY(hipSetDevice(h->device));
+    if (int rc = take_chains(h, src.a, ready)) return rc;
+    HHIP_TRY(hipStreamSynchronize(h->stream));
     return MCD_OK;
 }
 

@@ -13,7 +13,9 @@
 #include <vector>
 
 #include "../../include/mcmcdate_mvn.h"
+#include "handover_device.hpp"
 #include "mvn_kernels.h"
+#include "nuts_rhs_plan.hpp"
 #include "options.h"
 #include "recorder.hpp"
 #include "summary_device.hpp"
@@ -88,11 +90,32 @@ struct mcd_mh {
     mcd::Mc3Dev mc3{};
     uint64_t mc3_seed = 0, mc3_phase = 0;
     mcd::Recorder rec{"mcd_mh_record"};       // the sample recorder (mcd_mh_record_*, recorder.cpp): it counts iterations
+    const int32_t* host_parent = nullptr;     // [n_nodes] the likelihood handle's host copy of the topology (hand-overs compare it)
+    mutable hipEvent_t mark = nullptr;        // what another handle's stream waits for (mcd_mh_chains_), created on first use
+    // the Hamiltonian proposal attached to this handle (mcd_mh_attach_hamiltonian): h null = none.  The step sizes, the inverse masses
+    // (null: h's dense metric) and the sums of the transitions' diagnostics live on the device and belong to the attachment.
+    struct Hamiltonian {
+        mcd_hmc* h = nullptr;
+        double *d_eps = nullptr, *d_inv_mass = nullptr;
+        int max_depth = 0;
+        uint64_t seed = 0, first = 0, done = 0;   // the next transition's number is first + done
+        int64_t counted = 0;                      // transitions in the sums
+        void* d_sums = nullptr;                   // one block behind `sums`
+        mcd::HamSums sums{};
+        void release()
+        {
+            for (void* p : {(void*)d_eps, (void*)d_inv_mass, d_sums})
+                if (p) (void)hipFree(p);
+            *this = Hamiltonian{};
+        }
+    } ham;
     mcd::RecOn rec_on() const { return {device, stream, mcd::MhRecDims{dev.batch, dev.ld, dev.n_nodes}}; }
 
     ~mcd_mh()
     {
         (void)hipSetDevice(device);
+        ham.release();
+        if (mark) (void)hipEventDestroy(mark);
         for (void* p : allocs) (void)hipFree(p);
         if (d_sched) (void)hipFree(d_sched);
         if (d_trace_alpha) (void)hipFree(d_trace_alpha);
@@ -102,6 +125,10 @@ struct mcd_mh {
 };
 
 namespace {
+
+// why a tempered target and an attached Hamiltonian proposal exclude each other, whichever comes second
+const char* const kHamTempered = "a Hamiltonian proposal is attached to this handle (mcd_mh_attach_hamiltonian) and its target is prior x likelihood x "
+                                 "jacobianRootBranch at temperature 1: no MC3, no power posterior, no temperature other than 1";
 
 template <class T>
 int dev_alloc(mcd_mh* m, T** p, size_t count, bool zero)
@@ -310,6 +337,7 @@ int mh_create_impl(mcd_mh_t** out, std::unique_ptr<mcd_mh>& m, const mcd_prior_t
     m->sparse_rows = moves_few(t, inc_slots, m->list_all, n_prop, kind, node);
     m->device = dev_t;
     m->seed = seed;
+    m->host_parent = parent;
     for (int i = 0; i < n_prop; ++i) m->rows.push_back(mcd::MhRow{kind[i], node[i], n1[i], n2[i], jac_root[i], p0[i], p1[i]});
     MHIP_TRY(hipSetDevice(m->device));
     MHIP_TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
@@ -483,6 +511,7 @@ int64_t mcd_mh_last_dynamic_lds(const mcd_mh_t* m) { return m ? (int64_t)m->last
 int mcd_mh_mc3_init(mcd_mh_t* m, int n_chains, const double* betas, int64_t total_chains, uint64_t seed)
 {
     if (!m || !betas) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_mc3_init: NULL argument");
+    if (m->ham.h) return mfail(MCD_ERR_UNSUPPORTED, "mcd_mh_mc3_init: %s", kHamTempered);
     const mcd::MhDev& D = m->dev;
     if (n_chains < 2 || n_chains > 16) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_mc3_init: n_chains must be 2 .. 16");
     if (total_chains <= 0 || total_chains % n_chains != 0)
@@ -559,6 +588,143 @@ int mcd_mh_mc3_get(const mcd_mh_t* cm, int32_t* rank, int64_t* tried, int64_t* a
     if (tried) MHIP_TRY(hipMemcpy(tried, C.tried, sizeof(int64_t) * (size_t)(C.n_chains - 1), hipMemcpyDeviceToHost));
     if (accepted) MHIP_TRY(hipMemcpy(accepted, C.accepted, sizeof(int64_t) * (size_t)(C.n_chains - 1), hipMemcpyDeviceToHost));
     if (beta) MHIP_TRY(hipMemcpy(beta, cm->dev.beta, sizeof(double) * (size_t)cm->dev.batch, hipMemcpyDeviceToHost));
+    return MCD_OK;
+}
+
+}  // extern "C"
+
+// ---- the chains of a leapfrog / NUTS handle become this handle's, on the device, and the Hamiltonian proposal in the cycle ----------
+// (`maybeHamiltonianProposal`, app/Definitions.hs:272-278; handover_device.hpp, k_handover.hip)
+namespace {
+
+mcd::ChainArrays arrays_of(const mcd_mh* m) { return {m->dev.sc, m->dev.H, m->dev.R, m->dev.ld}; }
+
+// m := the chains at src once `ready` has passed on the source's stream: what mcd_mh_set_state does behind its copies -- the same
+// eval_posterior launches, so post and the prior blocks are those of the new states, and a run derives the rest when it starts.  No host wait.
+int take_chains(mcd_mh* m, const mcd::ChainArrays& src, hipEvent_t ready)
+{
+    const mcd::MhDev& D = m->dev;
+    if (ready) MHIP_TRY(hipStreamWaitEvent(m->stream, ready, 0));
+    MHIP_TRY(mcd::launch_handover(arrays_of(m), src, D.batch, D.n_nodes, m->stream));
+    if (int rc = eval_posterior(m, D.sc, D.H, D.R, D.post)) return rc;
+    m->have_state = true;
+    return MCD_OK;
+}
+
+}  // namespace
+
+int mcd_mh_chains_(const mcd_mh* m, mcd::ChainsView* v, hipEvent_t* mark)
+{
+    if (!m || !v) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_chains_: NULL argument");
+    *v = mcd::ChainsView{m->device, m->stream, m->dev.n_nodes, m->dev.batch, m->host_parent, m->have_state, arrays_of(m)};
+    if (mark) {
+        MHIP_TRY(hipSetDevice(m->device));
+        if (!m->mark) MHIP_TRY(hipEventCreateWithFlags(&m->mark, hipEventDisableTiming));
+        MHIP_TRY(hipEventRecord(m->mark, m->stream));
+        *mark = m->mark;
+    }
+    return MCD_OK;
+}
+
+extern "C" {
+
+// m := the states h holds (include/mcmcdate_mvn.h): mcd_mh_set_state after mcd_hmc_get_state, without the host in between
+int mcd_mh_take_state(mcd_mh_t* m, const mcd_hmc_t* h)
+{
+    if (!m || !h) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_take_state: NULL handle");
+    mcd::ChainsView dst, src;
+    if (int rc = mcd_mh_chains_(m, &dst, nullptr)) return rc;
+    if (int rc = mcd_hmc_chains_(h, &src, nullptr)) return rc;
+    char why[256];
+    if (!mcd::handover_allowed(dst, src, why, sizeof why)) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_take_state: %s", why);
+    hipEvent_t ready = nullptr;
+    if (int rc = mcd_hmc_chains_(h, &src, &ready)) return rc;
+    MHIP_TRY(hipSetDevice(m->device));
+    if (int rc = take_chains(m, src.a, ready)) return rc;
+    MHIP_TRY(hipStreamSynchronize(m->stream));
+    return MCD_OK;
+}
+
+int mcd_mh_attach_hamiltonian(mcd_mh_t* m, mcd_hmc_t* h, const double* eps, const double* inv_mass, int max_depth, uint64_t seed, uint64_t first_transition)
+{
+    const char* who = "mcd_mh_attach_hamiltonian";
+    if (!m || !h || !eps) return mfail(MCD_ERR_INVALID_ARG, "%s: NULL argument", who);
+    if (m->ham.h) return mfail(MCD_ERR_INVALID_ARG, "%s: a Hamiltonian proposal is attached to this handle already (mcd_mh_detach_hamiltonian first)", who);
+    mcd::ChainsView mine, theirs;
+    if (int rc = mcd_mh_chains_(m, &mine, nullptr)) return rc;
+    if (int rc = mcd_hmc_chains_(h, &theirs, nullptr)) return rc;
+    theirs.have_state = mine.have_state = true;                   // (neither needs a state yet: every transition starts with a hand-over)
+    char why[256];
+    if (!mcd::handover_allowed(theirs, mine, why, sizeof why)) return mfail(MCD_ERR_INVALID_ARG, "%s: %s", who, why);
+    const mcd::MhDev& D = m->dev;
+    const size_t B = (size_t)D.batch;
+    for (size_t b = 0; b < B; ++b)
+        if (!(eps[b] > 0) || !std::isfinite(eps[b])) return mfail(MCD_ERR_INVALID_ARG, "%s: step sizes must be positive and finite (chain %zu: %g)", who, b, eps[b]);
+    if (max_depth < 1 || max_depth > mcd::kNutsMaxDepthLevels)
+        return mfail(MCD_ERR_INVALID_ARG, "%s: max_depth must be 1 .. %d", who, mcd::kNutsMaxDepthLevels);
+    const int dim = mcd_hmc_dim(h);
+    for (int k = 0; k < dim && inv_mass; ++k)
+        if (!(inv_mass[k] > 0) || !std::isfinite(inv_mass[k])) return mfail(MCD_ERR_INVALID_ARG, "%s: inverse masses must be positive", who);
+    if (m->mc3.n_chains != 0) return mfail(MCD_ERR_UNSUPPORTED, "%s: Metropolis-coupled MCMC is initialised on this handle: a tempered Hamiltonian target is not built", who);
+    if (D.lik_only) return mfail(MCD_ERR_UNSUPPORTED, "%s: the handle is in power-posterior mode (mcd_mh_set_power): a tempered Hamiltonian target is not built", who);
+    MHIP_TRY(hipSetDevice(m->device));
+    MHIP_TRY(hipStreamSynchronize(m->stream));
+    std::vector<double> beta(B);
+    MHIP_TRY(hipMemcpy(beta.data(), D.beta, sizeof(double) * B, hipMemcpyDeviceToHost));
+    for (size_t b = 0; b < B; ++b)
+        if (beta[b] != 1.0)
+            return mfail(MCD_ERR_UNSUPPORTED, "%s: chain %zu has the reciprocal temperature %g: a tempered Hamiltonian target is not built", who, b, beta[b]);
+    if (int rc = mcd_hmc_cycle_ready_(h, who, inv_mass == nullptr)) return rc;
+    // step sizes, inverse masses and the sums stay on the device for as long as the attachment lasts
+    mcd_mh::Hamiltonian A;
+    hipError_t e = hipMalloc((void**)&A.d_eps, sizeof(double) * B);
+    if (e == hipSuccess && inv_mass) e = hipMalloc((void**)&A.d_inv_mass, sizeof(double) * (size_t)dim);
+    if (e == hipSuccess) e = hipMalloc(&A.d_sums, 4 * 8 * B);
+    if (e == hipSuccess) e = hipMemcpy(A.d_eps, eps, sizeof(double) * B, hipMemcpyHostToDevice);
+    if (e == hipSuccess && inv_mass) e = hipMemcpy(A.d_inv_mass, inv_mass, sizeof(double) * (size_t)dim, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(A.d_sums, 0, 4 * 8 * B);
+    if (e != hipSuccess) {
+        A.release();
+        return mfail(MCD_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+    static_assert(sizeof(double) == 8 && sizeof(int64_t) == 8, "");
+    A.sums = mcd::HamSums{(double*)A.d_sums, (int64_t*)A.d_sums + B, (int64_t*)A.d_sums + 2 * B, (int64_t*)A.d_sums + 3 * B};
+    A.h = h;
+    A.max_depth = max_depth;
+    A.seed = seed;
+    A.first = first_transition;
+    m->ham = A;
+    return MCD_OK;
+}
+
+int mcd_mh_detach_hamiltonian(mcd_mh_t* m)
+{
+    if (!m) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_detach_hamiltonian: NULL handle");
+    if (!m->ham.h) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_detach_hamiltonian: no Hamiltonian proposal is attached to this handle");
+    MHIP_TRY(hipSetDevice(m->device));
+    MHIP_TRY(hipStreamSynchronize(m->stream));                    // (every run ends with this wait: nothing of the attachment is in flight)
+    m->ham.release();
+    return MCD_OK;
+}
+
+int mcd_mh_hamiltonian_stats(const mcd_mh_t* cm, int64_t* transitions, double* alpha_sum, int64_t* depth_sum, int64_t* leapfrog_steps, int64_t* divergent,
+                             int reset)
+{
+    if (!cm) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_hamiltonian_stats: NULL handle");
+    const mcd_mh::Hamiltonian& A = cm->ham;
+    if (!A.h) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_hamiltonian_stats: no Hamiltonian proposal is attached to this handle");
+    const size_t B = (size_t)cm->dev.batch;
+    MHIP_TRY(hipSetDevice(cm->device));
+    MHIP_TRY(hipStreamSynchronize(cm->stream));
+    if (transitions) *transitions = A.counted;
+    if (alpha_sum) MHIP_TRY(hipMemcpy(alpha_sum, A.sums.alpha, 8 * B, hipMemcpyDeviceToHost));
+    if (depth_sum) MHIP_TRY(hipMemcpy(depth_sum, A.sums.depth, 8 * B, hipMemcpyDeviceToHost));
+    if (leapfrog_steps) MHIP_TRY(hipMemcpy(leapfrog_steps, A.sums.leaves, 8 * B, hipMemcpyDeviceToHost));
+    if (divergent) MHIP_TRY(hipMemcpy(divergent, A.sums.diverged, 8 * B, hipMemcpyDeviceToHost));
+    if (reset) {
+        MHIP_TRY(hipMemset(A.d_sums, 0, 4 * 8 * B));
+        const_cast<mcd_mh*>(cm)->ham.counted = 0;                 // (the sums are the attachment's, not the chains': reading them may clear them)
+    }
     return MCD_OK;
 }
 
@@ -722,7 +888,8 @@ const mcd::MhRow kNoRow{0, 0, 0, 0, 0, 1.0, 0.0};
 struct MhRun {
     mcd_mh* m;
     const MhPlan& p;
-    const int32_t* schedule;
+    const int32_t* schedule;         // (host) position 0 of this run
+    int64_t off;                     // where that position lies in the call's device schedule and traces (m->d_sched, m->d_trace_*)
     int64_t total;                   // steps
     int32_t S;
     int accumulate;
@@ -736,8 +903,8 @@ struct MhRun {
     int dense_mode;                  // where the z' (q') of a dense proposal is afterwards: zprop (1) or the z tiles (2)
     mcd::MhRec rec;                  // the sample recorder as it stands when the call starts (base null: off)
 
-    MhRun(mcd_mh* m_, const MhPlan& p_, const int32_t* schedule_, int64_t total_, int32_t S_, int accumulate_, bool trace_)
-        : m(m_), p(p_), schedule(schedule_), total(total_), S(S_), accumulate(accumulate_), trace(trace_), step_base(m_->step),
+    MhRun(mcd_mh* m_, const MhPlan& p_, const int32_t* schedule_, int64_t off_, int64_t total_, int32_t S_, int accumulate_, bool trace_)
+        : m(m_), p(p_), schedule(schedule_), off(off_), total(total_), S(S_), accumulate(accumulate_), trace(trace_), step_base(m_->step),
           n_dim(m_->mvn ? m_->mvn->n : m_->sp->n), prior_inline(p_.beside ? 0 : 1), Tx(p_.use_x ? m_->tree : nullptr), X1(p_.use_x ? m_->d_X1 : nullptr),
           inc(p_.inc_dense || p_.inc_sparse), dense_mode((p_.chunked || p_.inc_sparse) ? 1 : 2),
           rec(m_->rec.view(m_->rec.counts().iter)) {}
@@ -754,10 +921,10 @@ struct MhRun {
         if (gs < 0 || (gs + 1) % S != 0) m->dev.rec.base = nullptr;
         else m->dev.rec.iter0 += (gs + 1) / S;
     }
-    double* alpha(int64_t gs) const { return trace ? m->d_trace_alpha + gs * m->dev.batch : nullptr; }
-    int8_t* accept(int64_t gs) const { return trace ? m->d_trace_accept + gs * m->dev.batch : nullptr; }
+    double* alpha(int64_t gs) const { return trace ? m->d_trace_alpha + (off + gs) * m->dev.batch : nullptr; }
+    int8_t* accept(int64_t gs) const { return trace ? m->d_trace_accept + (off + gs) * m->dev.batch : nullptr; }
     // the schedule positions [first, first + count) as one launch of a persistent kernel takes them
-    mcd::MhSpan span(int64_t first, int64_t n) const { return {m->d_sched + first, n, S, accumulate ? 1 : 0, step_base + (uint64_t)first, m->seed, alpha(first), accept(first)}; }
+    mcd::MhSpan span(int64_t first, int64_t n) const { return {m->d_sched + off + first, n, S, accumulate ? 1 : 0, step_base + (uint64_t)first, m->seed, alpha(first), accept(first)}; }
     // the step launch that only proposes schedule position gs (nothing is pending, so no uniform is drawn from the step number; init: MhDev::psum
     // does not hold the current states' summands yet), and the one that decides position gs and proposes row pn (< 0: none) for position gs + 1
     mcd::MhStep propose(int64_t gs, bool init) const { return {-1, 0, schedule[gs], m->rows[(size_t)schedule[gs]], (int)(gs & 63), m->step, 0, nullptr, nullptr, init ? 1 : 0}; }
@@ -772,7 +939,7 @@ struct MhRun {
     {
         if ((idx & 63) == 0) {
             const int count = (int)((total - idx < 64) ? total - idx : 64);
-            MHIP_TRY(mcd::launch_mh_draws(m->dev, m->d_sched, idx, count, step_base + (uint64_t)idx, m->seed, m->stream));
+            MHIP_TRY(mcd::launch_mh_draws(m->dev, m->d_sched + off, idx, count, step_base + (uint64_t)idx, m->seed, m->stream));
         }
         return MCD_OK;
     }
@@ -1011,6 +1178,8 @@ int mcd_mh_run(mcd_mh_t* m, const int32_t* schedule, int64_t n_iter, int32_t S, 
     for (size_t i = 0; i < steps; ++i)
         if (schedule[i] < 0 || schedule[i] >= D.n_prop) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_run: schedule[%zu] = %d is not a proposal row", i, schedule[i]);
     if (int rc = m->rec.room("mcd_mh_run", n_iter)) return rc;   // an active recorder: the samples of this call must fit, or nothing is launched
+    if (m->ham.h)                                                // an attachment: may its handle make the transitions, or nothing is launched
+        if (int rc = mcd_hmc_cycle_ready_(m->ham.h, "mcd_mh_run", m->ham.d_inv_mass == nullptr)) return rc;
     MHIP_TRY(hipSetDevice(m->device));
     if (steps > m->sched_cap) {
         if (m->d_sched) (void)hipFree(m->d_sched);
@@ -1037,11 +1206,36 @@ int mcd_mh_run(mcd_mh_t* m, const int32_t* schedule, int64_t n_iter, int32_t S, 
     if (p.path != MCD_MH_PATH_CHAIN_LDS && p.path != MCD_MH_PATH_CHAIN_STREAMED)
         if (int rc = plan_buffers(m, p)) return rc;
     m->last_path = p.path;
-    const MhRun r(m, p, schedule, (int64_t)steps, S, accumulate, trace);
-    const int rc = p.path == MCD_MH_PATH_CHAIN_LDS ? run_chain(r) : p.path == MCD_MH_PATH_CHAIN_STREAMED ? run_streamed(r) : p.segments ? run_segments(r) : run_steps(r);
-    m->dev.rec = mcd::MhRec{};
-    if (rc) return rc;
-    m->rec.advance(n_iter);
+    // the iterations [first, first + count) of the call as one run of the plan
+    auto stretch = [&](int64_t first, int64_t count) -> int {
+        const MhRun r(m, p, schedule + first * S, first * S, count * S, S, accumulate, trace);
+        const int rc = p.path == MCD_MH_PATH_CHAIN_LDS ? run_chain(r) : p.path == MCD_MH_PATH_CHAIN_STREAMED ? run_streamed(r) : p.segments ? run_segments(r) : run_steps(r);
+        m->dev.rec = mcd::MhRec{};
+        if (rc) return rc;
+        m->rec.advance(count);
+        return MCD_OK;
+    };
+    if (!m->ham.h) {
+        if (int rc = stretch(0, n_iter)) return rc;
+    } else {
+        // Every iteration begins with one NUTS transition of every chain on the attached handle, and the scheduled proposals follow as a
+        // run of their own: mcd_hmc_take_state, mcd_hmc_nuts, mcd_mh_take_state, mcd_mh_run of one iteration, to the bit.  The two
+        // streams are ordered by the handles' events; the host waits only where mcd_hmc_nuts waits.
+        mcd_mh::Hamiltonian& A = m->ham;
+        for (int64_t it = 0; it < n_iter; ++it) {
+            mcd::ChainsView me;
+            hipEvent_t mine = nullptr, theirs = nullptr;
+            if (int rc = mcd_mh_chains_(m, &me, &mine)) return rc;
+            if (int rc = mcd_hmc_cycle_transition_(A.h, me.a, mine, A.d_eps, A.d_inv_mass, A.max_depth, A.seed, D.chain0, A.first + A.done, A.sums, &theirs))
+                return rc;
+            A.done += 1;
+            A.counted += 1;
+            mcd::ChainsView other;
+            if (int rc = mcd_hmc_chains_(A.h, &other, nullptr)) return rc;
+            if (int rc = take_chains(m, other.a, theirs)) return rc;
+            if (int rc = stretch(it, 1)) return rc;
+        }
+    }
     m->last_lds = mcd::last_dynamic_lds();
     if (trace_alpha) MHIP_TRY(hipMemcpyAsync(trace_alpha, m->d_trace_alpha, sizeof(double) * steps * B, hipMemcpyDeviceToHost, m->stream));
     if (trace_accept) MHIP_TRY(hipMemcpyAsync(trace_accept, m->d_trace_accept, steps * B, hipMemcpyDeviceToHost, m->stream));
@@ -1090,6 +1284,8 @@ int mcd_mh_set_temperatures(mcd_mh_t* m, const double* beta)
     const mcd::MhDev& D = m->dev;
     for (int64_t b = 0; b < D.batch; ++b)
         if (!(beta[b] > 0) || !(beta[b] <= 1.0)) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_set_temperatures: reciprocal temperatures must be in (0, 1]");
+    for (int64_t b = 0; b < D.batch && m->ham.h; ++b)
+        if (beta[b] != 1.0) return mfail(MCD_ERR_UNSUPPORTED, "mcd_mh_set_temperatures: chain %lld at %g: %s", (long long)b, beta[b], kHamTempered);
     MHIP_TRY(hipSetDevice(m->device));
     MHIP_TRY(hipStreamSynchronize(m->stream));
     MHIP_TRY(hipMemcpy(D.beta, beta, sizeof(double) * (size_t)D.batch, hipMemcpyHostToDevice));
@@ -1101,6 +1297,7 @@ int mcd_mh_set_temperatures(mcd_mh_t* m, const double* beta)
 int mcd_mh_set_power(mcd_mh_t* m, const double* beta)
 {
     if (!m || !beta) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_set_power: NULL argument");
+    if (m->ham.h) return mfail(MCD_ERR_UNSUPPORTED, "mcd_mh_set_power: %s", kHamTempered);
     const mcd::MhDev& D = m->dev;
     if (m->mc3.n_chains != 0)
         return mfail(MCD_ERR_UNSUPPORTED, "mcd_mh_set_power: Metropolis-coupled MCMC is initialised on this handle: its swaps exchange temperatures of (prior x likelihood)^beta");

@@ -97,6 +97,11 @@ class Leapfrog(DriverCalls):
         self._create(tree_lik, prior._p, int(bool(calibrations_available)), self.batch)
         self.dim = int(_capi.lib().mcd_hmc_dim(self._h))
 
+    def take_state(self, sampler):
+        """The current states of the sampler.Sampler become this handle's, on the device (mcd_hmc_take_state): set_state(sampler.state())
+        to the bit -- state, position, ln target and gradient -- without the host in between."""
+        _capi.check(_capi.lib().mcd_hmc_take_state(self._h, sampler._h))
+
     def position(self):
         """(q [B, dim], ln target [B], gradient [B, dim]) of the current state."""
         q, g = np.empty((self.batch, self.dim)), np.empty((self.batch, self.dim))

@@ -8,7 +8,8 @@ helper lists :145-253), the burn-in schedule with auto tuning (`burnIn`, :420-42
 own random numbers, tuning parameter and accept/reject decision.  There is no CPU path.
 
 Built: every proposal of the reference's Metropolis-Hastings cycle (`proposals bs calibrationsAvailable x Nothing`).
-NUTS (`Just htarget`, app/Hamiltonian.hs) is not; `proposals()` returns the names of what it
+NUTS (`Just htarget`, app/Hamiltonian.hs) is no row of the table: `Sampler.attach_hamiltonian` puts one
+transition of an `hmc.Leapfrog` in front of every iteration (mcd_mh_attach_hamiltonian).  `proposals()` returns the names of what it
 leaves out (an empty list for the default cycle) so that nothing is skipped silently.
 """
 from __future__ import annotations
@@ -306,6 +307,46 @@ class Sampler(DriverCalls):
         if beta.shape != (self.batch,):
             raise ValueError("set_power: expected [batch]")
         _capi.check(_capi.lib().mcd_mh_set_power(self._h, dp(beta)))
+
+    # -- the Hamiltonian proposal in the cycle (mcd_mh_attach_hamiltonian; `--hamiltonian`, app/Definitions.hs:272-278) --------------------
+    def take_state(self, lf):
+        """The states the hmc.Leapfrog `lf` holds become this sampler's, on the device (mcd_mh_take_state): set_state(lf.state()) to the
+        bit, without the host in between."""
+        _capi.check(_capi.lib().mcd_mh_take_state(self._h, lf._h))
+
+    def attach_hamiltonian(self, lf, eps, inv_mass, max_depth: int = 6, seed: Optional[int] = None, first_transition: int = 0):
+        """From now on every iteration of run / run_schedule / burn_in (and so of record_* and monitor.record) begins with one NUTS
+        transition of every chain on the hmc.Leapfrog `lf` and the scheduled proposals follow (mcd_mh_attach_hamiltonian: the bits of
+        lf.take_state(self); lf.nuts(eps, inv_mass, max_depth, seed, transition, chain_offset=self.first_chain); self.take_state(lf);
+        one iteration of an unattached sampler).  eps: scalar or [B]; inv_mass: [dim] (a scalar is broadcast), or None: the dense metric
+        set on `lf`.  seed defaults to this sampler's ^ hmc.NUTS_STREAM_DOMAIN, as hmc.run_cycle_with_nuts passes it.  `lf` must outlive
+        the attachment.  Refused (McdError): an MC3 or power-posterior sampler, temperatures other than 1, mismatching handles."""
+        from .hmc import NUTS_STREAM_DOMAIN
+
+        eps = np.ascontiguousarray(np.broadcast_to(np.asarray(eps, np.float64), (self.batch,)))
+        im = lf._inv_mass(inv_mass)
+        seed = (self.seed ^ NUTS_STREAM_DOMAIN) if seed is None else int(seed)
+        _capi.check(_capi.lib().mcd_mh_attach_hamiltonian(self._h, lf._h, dp(eps), None if im is None else dp(im), int(max_depth),
+                                                          C.c_uint64(seed), C.c_uint64(int(first_transition))))
+        self._hamiltonian = lf                                         # (kept alive for as long as the library uses it)
+
+    def detach_hamiltonian(self):
+        """Ends the attachment (mcd_mh_detach_hamiltonian): the sampler runs what a sampler that never had one runs, to the bit."""
+        _capi.check(_capi.lib().mcd_mh_detach_hamiltonian(self._h))
+        self._hamiltonian = None
+
+    def hamiltonian_stats(self, reset: bool = False) -> dict:
+        """What the attached transitions did since attach_hamiltonian (or the last reset), summed on the device (mcd_mh_hamiltonian_stats):
+        {"transitions": n, "alpha_sum" [B], "depth_sum" [B], "leapfrog_steps" [B], "divergent" [B]} -- alpha_sum / n is the mean
+        acceptance statistic of a chain, depth_sum / n its mean tree depth."""
+        B = self.batch
+        n = C.c_int64(0)
+        a = np.empty(B)
+        d, l, v = np.empty(B, np.int64), np.empty(B, np.int64), np.empty(B, np.int64)
+        lp = C.POINTER(C.c_int64)
+        _capi.check(_capi.lib().mcd_mh_hamiltonian_stats(self._h, C.byref(n), dp(a), d.ctypes.data_as(lp), l.ctypes.data_as(lp),
+                                                         v.ctypes.data_as(lp), int(bool(reset))))
+        return {"transitions": int(n.value), "alpha_sum": a, "depth_sum": d, "leapfrog_steps": l, "divergent": v}
 
     def age_sums(self):
         """(sum, sum of squares [B, n_nodes], n): running sums of the absolute node ages tH * h_v."""

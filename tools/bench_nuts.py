@@ -18,11 +18,19 @@ One JSON line per run; *_runs hold every repeat, the headline figures are their 
                          (Leapfrog.record_summary).
   --metric-form {per_chain,across_chains}   with --metric dense: how the dense metric's products are taken (Leapfrog.set_metric_form); the
                          line then carries the seconds the warm-up call spent in its four phases (host factorisations, window covariance,
-                         window buffer, transitions)."""
+                         window buffer, transitions).
+
+  --cycle {host,library}  instead: --transitions iterations of the reference's `--hamiltonian` mode (the Metropolis-Hastings cycle plus one
+                         NUTS transition per iteration) on --name x --chains, from the same start states, step sizes and masses:
+                         host      hmc.run_cycle_with_nuts -- the states cross the host twice per iteration between the two handles;
+                         library   Sampler.attach_hamiltonian + Sampler.run -- mcd_mh_run with the attached handle, hand-overs on the device.
+                         Milliseconds per iteration (median, every repeat, maximum - minimum of the repeats), mean tree depth and leapfrog
+                         steps per transition.  The measurement runs in a child process under --limit seconds."""
 import argparse
 import ctypes
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -37,6 +45,11 @@ from mcmc_date_amd import monitor  # noqa: E402
 
 
 def golden_problem(name, B):
+    topo, _, lf, eps, inv_mass = golden_setup(name, B)
+    return topo, lf, eps, inv_mass, "dense"
+
+
+def golden_setup(name, B):
     fx = dict(np.load(os.path.join(ROOT, "tests", "golden", name + ".npz")))
     topo = M.Topology(fx["parent"])
     cal = [M.Calibration(f"c{i}", int(r[0]), r[2] if r[1] else None, r[3], r[5] if r[4] else None, r[6]) for i, r in enumerate(fx["cal"])]
@@ -57,7 +70,51 @@ def golden_problem(name, B):
     q0 = lf.position()[0]
     inv_mass = np.maximum((0.1 * np.abs(q0)).mean(axis=0) ** 2, 1e-12)
     eps, _, _, _ = lf.nuts_run(40, 0.05, inv_mass, adapt=True, max_depth=5, seed=1)
-    return topo, lf, eps, inv_mass, "dense"
+    return topo, smp, lf, eps, inv_mass
+
+
+def cycle_report(args):
+    """--cycle: the same iterations through the host round trip or through the attached handle."""
+    B, T = args.chains, args.transitions
+    topo, smp, lf, eps, inv_mass = golden_setup(args.name, B)
+    start = smp.state()
+    library = args.cycle == "library"
+    if library:
+        smp.attach_hamiltonian(lf, eps, inv_mass, max_depth=args.max_depth)
+
+    def go(n, first):
+        if library:
+            smp.run(n)
+        else:
+            M.run_cycle_with_nuts(smp, lf, None, n, eps, inv_mass, max_depth=args.max_depth, first_transition=first)
+        smp.posterior()                                                # (waits for the sampler's stream)
+
+    smp.set_state(start)
+    go(2, 0)                                                           # (code objects, allocations)
+    if library:
+        smp.hamiltonian_stats(reset=True)
+    runs = []
+    for r in range(max(1, args.repeat)):
+        smp.set_state(start)
+        t0 = time.perf_counter()
+        go(T, 1000 * (r + 1))
+        runs.append(1e3 * (time.perf_counter() - t0) / T)
+    if library:
+        st = smp.hamiltonian_stats()
+        n = max(1, st["transitions"])
+        depth, leaves, divergent = float(st["depth_sum"].mean()) / n, float(st["leapfrog_steps"].mean()) / n, int(st["divergent"].sum())
+    else:                                                              # one more pass, untimed, with the NUTS driver's recorder on
+        smp.set_state(start)
+        lf.record_begin(period=1, capacity=T)
+        go(T, 1000)
+        nuts = lf.record_fetch()[-1]
+        lf.record_end()
+        depth, leaves, divergent = float(nuts[:, :, 0].mean()), float(nuts[:, :, 1].mean()), int(nuts[:, :, 3].sum())
+    print(json.dumps({"metric": "Metropolis-Hastings cycle + one NUTS transition per iteration", "cycle": args.cycle, "dataset": args.name,
+                      "n_nodes": topo.n_nodes, "chains": B, "iterations": T, "steps_per_iteration": int(sum(p.weight for p in smp.table)),
+                      "max_depth": args.max_depth, "path": smp.last_path(), "ms_per_iteration": float(np.median(runs)), "ms_per_iteration_runs": runs,
+                      "spread_ms": max(runs) - min(runs), "mean_depth": depth, "leapfrog_steps_per_transition": leaves, "divergent": divergent}),
+          flush=True)
 
 
 def synthetic_problem(n_leaves, B):
@@ -142,7 +199,20 @@ def main():
     ap.add_argument("--metric-form", choices=("per_chain", "across_chains"), default="per_chain")
     ap.add_argument("--windows", type=int, default=3)
     ap.add_argument("--window", type=int, default=60)
+    ap.add_argument("--cycle", choices=("host", "library"), default=None)
+    ap.add_argument("--limit", type=int, default=300, help="seconds the child process of --cycle may take")
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.cycle and not args.child:                                   # the measurement in a child of its own, under its own time limit
+        if args.synthetic:
+            ap.error("--cycle runs on a committed input (--name)")
+        try:
+            return subprocess.run([sys.executable, os.path.abspath(__file__), "--child"] + sys.argv[1:], timeout=args.limit).returncode
+        except subprocess.TimeoutExpired:
+            print(json.dumps({"cycle": args.cycle, "error": f"time limit of {args.limit} s"}), flush=True)
+            return 124
+    if args.cycle:
+        return cycle_report(args)
     if args.metric_form != "per_chain" and args.metric != "dense":
         ap.error("--metric-form is valid with --metric dense")
     B, T = args.chains, args.transitions
@@ -185,4 +255,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())
