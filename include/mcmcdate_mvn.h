@@ -99,7 +99,8 @@ const char* mcd_last_error(void);
  * "MCD_SPARSE_GRAD_CHAINS" (1 | 2: chains per workgroup of mcd_sparse_tree_grad_batch; the same bits), "MCD_STRIPE_PROLOGUE" (the inverse
  * stream's kernel: 1 = x, mu and 1/diag loaded once per workgroup, 0 = by every wave for itself; the same bits), "MCD_STRIPE_SCHED" (that
  * kernel's schedule under the shared prologue: 1 = the column broadcasts read out of LDS and the ring read one group ahead of the
- * multiply-adds, 0 = the schedule before; the same bits); value = a decimal integer, NULL or ""
+ * multiply-adds, 2 (the default) = that with the off-diagonal units loaded straight into registers where the sweep does not stop
+ * early, 0 = the schedule before; the same bits); value = a decimal integer, NULL or ""
  * = back to the default.  What each knob does is said where it acts (mcd_mh_run, the forms above).  The environment variables of the same
  * names are read ONCE, when the library is loaded, as initial values -- never afterwards.  No knob changes a result beyond rounding.
  */

@@ -41,7 +41,8 @@ __global__ void __launch_bounds__(64 * (CW + LW)) k_logpdf(const double* __restr
 // own (stripe_device.hpp).  The same arguments, preloaded the same way.  SH: x, mu and 1/diag loaded once per workgroup and handed
 // round through LDS (the default), or by every wave for itself (mcd_set_option "MCD_STRIPE_PROLOGUE" = 0; A/B, tests: the same bits).
 // SC (with SH only): the column broadcasts read out of the exchange area and the ring read one group ahead of the multiply-adds (the
-// default), or round 14's loop (mcd_set_option "MCD_STRIPE_SCHED" = 0; A/B, tests: the same bits).  Three kernels per R.
+// schedule of "MCD_STRIPE_SCHED" = 1), that schedule with the off-diagonal units loaded straight into registers (2, the default; whole
+// sweeps only, a sweep that stops early runs schedule 1), or round 14's loop (0).  A/B, tests: the same bits.  Four kernels per R.
 template <int R, int S, bool SH, int SC>
 __global__ void __launch_bounds__(64 * S) k_logpdf_stripe(const double* __restrict__ Fw, const double* __restrict__ mu,
                                                           const double* __restrict__ invdiag, const double* __restrict__ X, int64_t ldx,
@@ -64,8 +65,10 @@ static void launch_stripe_sh(const MvnDev& M, const double* X, int64_t ldx, int6
 template <int R>
 static void launch_stripe(const MvnDev& M, const double* X, int64_t ldx, int64_t batch, double* ll, hipStream_t st)
 {
-    if (opt_or(OPT_STRIPE_PROLOGUE, kStripePrologueDefault) == 0) launch_stripe_sh<R, false, 0>(M, X, ldx, batch, ll, st);
-    else if (opt_or(OPT_STRIPE_SCHED, kStripeSchedDefault) != 0) launch_stripe_sh<R, true, 1>(M, X, ldx, batch, ll, st);
+    const int sc = stripe_schedule(opt_or(OPT_STRIPE_PROLOGUE, kStripePrologueDefault), opt_or(OPT_STRIPE_SCHED, kStripeSchedDefault), R, M.ncols);
+    if (sc < 0) launch_stripe_sh<R, false, 0>(M, X, ldx, batch, ll, st);
+    else if (sc == 2) launch_stripe_sh<R, true, 2>(M, X, ldx, batch, ll, st);
+    else if (sc == 1) launch_stripe_sh<R, true, 1>(M, X, ldx, batch, ll, st);
     else launch_stripe_sh<R, true, 0>(M, X, ldx, batch, ll, st);
 }
 

@@ -38,7 +38,8 @@ enum Option {
     OPT_STRIPE_PROLOGUE,    // the inverse stream's stripe kernel (stripe_device.hpp): 1 = x, mu and 1/diag loaded once per workgroup and exchanged through
                             // LDS, 0 = by every stripe wave for itself (A/B, tests; the same bits)
     OPT_STRIPE_SCHED,       // the stripe kernel's schedule under the shared prologue: 1 = the column broadcasts read out of the exchange area and the
-                            // ring read one group ahead of the multiply-adds, 0 = the loop of round 14 (A/B, tests; the same bits)
+                            // ring read one group ahead of the multiply-adds, 2 = that schedule with the off-diagonal units loaded straight into
+                            // registers (stripe_plan.hpp), 0 = the loop of round 14 (A/B, tests; the same bits)
     OPT_COUNT
 };
 constexpr int MCD_OPT_UNSET = -2147483647 - 1;

@@ -37,8 +37,16 @@
 //     allow.  A group whose chunk the early stop cuts is neither waited for nor read.  Every addition keeps its operands and its place.
 //     Measured and not kept (profiles/r16_stripe_schedule_ab.txt, docs/experiments/r16_stripe_read_ahead_fill.diff): the read-ahead
 //     without the broadcasts, a fill of the ring behind the operand loads, a burst shorter than the lookahead.
+//   * Schedule 2 (the default for sweeps that do not stop early; MCD_STRIPE_SCHED = 1 keeps the schedule above): since the private
+//     stripes every unit has one reader, the wave that requested it, and an off-diagonal unit needs no lane shift -- lane l's 16 bytes
+//     are the two entries of row l that lane l multiplies.  Those units (three quarters of the stream at R = 4) skip LDS: one
+//     global_load_dwordx4 with a scalar base, 16 l as the vector offset and an immediate brings the unit into a register ring, with no
+//     vector address arithmetic, no M0 write, no ds_read and no lgkmcnt wait.  The diagonal parts keep their LDS-DMAs and ring slots.
+//     Both kinds count on vmcnt in issue order; one constexpr plan per wave (stripe_plan.hpp) holds every position's kind, slot, base
+//     and immediate and every group's wait, and is proved at compile time.  Same operands, same order of additions, same bits.
 #include "mvn_device.hpp"
 #include "stripe_deal.hpp"
+#include "stripe_plan.hpp"
 
 namespace mcd {
 
@@ -53,8 +61,6 @@ constexpr int kStripeWaves = MCD_STRIPE_WAVES;
 #define MCD_STRIPE_AHEAD 12
 #endif
 constexpr int kStripeAhead = MCD_STRIPE_AHEAD;
-constexpr int kStripePrologueDefault = 1;                  // MCD_STRIPE_PROLOGUE unset: the shared prologue
-constexpr int kStripeSchedDefault = 1;                     // MCD_STRIPE_SCHED unset: the schedule
 
 template <int R, int S>
 struct Stripe {
@@ -450,6 +456,175 @@ __device__ __forceinline__ void stripe_sched(const double* __restrict__ Fw, unsi
     }
 }
 
+// ---- SC = 2: the off-diagonal units by register load (stripe_plan.hpp) ----
+// The wave's plan, proved at compile time
+template <int R, int S, int W>
+struct StripePlanOf {
+    static constexpr StripePlan P = stripe_plan(R, S, W, Stripe<R, S>::A);
+    static_assert(stripe_plan_check(P, R, S, W) == 0, "stripe plan: waits, outstanding operations, slot reuse, immediates");
+    static_assert(P.D == Stripe<R, S>::D && P.pro == stripe_min(Stripe<R, S>::A, Stripe<R, S>::T.n[W]), "stripe plan: the ring and the burst");
+};
+// One unit into a register slot: lane l's 16 bytes at base + 16 l + IMM.  Outside the compiler's bookkeeping like asm_load8: the
+// covering vmcnt wait and stripe_regs_pin() before the first use.
+template <int IMM>
+__device__ __forceinline__ void stripe_load_reg(d2& v, unsigned voff, const char* base /* wave-uniform */)
+{
+    static_assert(IMM >= -4096 && IMM <= 4095, "global offset");
+    asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=&v"(v) : "v"(voff), "s"(base), "n"(IMM) : "memory");
+}
+// list positions [U0, U1) of the plan, each by its kind; voff = 16 lane
+template <int R, int S, int W, int U0, int U1>
+__device__ __forceinline__ void stripe_issue_plan(const double* __restrict__ Fw, unsigned my, int lane, unsigned voff, d2 (&RR)[kStripeRegSlots])
+{
+    if constexpr (U0 < U1) {
+        constexpr const StripePlan& P = StripePlanOf<R, S, W>::P;
+        if constexpr (P.kind[U0] == 0) stripe_issue<R, S, W, U0, U0 + 1>(Fw, my, lane);
+        else {
+            constexpr int slot = P.slot[U0], base = P.base[U0];
+            stripe_load_reg<P.imm[U0]>(RR[slot], voff, reinterpret_cast<const char*>(Fw) + base);
+        }
+        stripe_issue_plan<R, S, W, U0 + 1, U1>(Fw, my, lane, voff, RR);
+    }
+}
+// behind the covering wait: the registers of positions [U0, U1) are the loaded values from here on
+template <int R, int S, int W, int U0, int U1>
+__device__ __forceinline__ void stripe_regs_pin(d2 (&RR)[kStripeRegSlots])
+{
+    if constexpr (U0 < U1) {
+        constexpr int slot = StripePlanOf<R, S, W>::P.slot[U0];
+        asm volatile("" : "+v"(RR[slot]));
+        stripe_regs_pin<R, S, W, U0 + 1, U1>(RR);
+    }
+}
+// the ds_reads of a diagonal part (stripe_group_read's addresses)
+template <int R, int S, int W, int GI>
+__device__ __forceinline__ void stripe_diag_read(d2 (&l)[8], unsigned la, unsigned za, int lane)
+{
+    constexpr const StripePlan& P = StripePlanOf<R, S, W>::P;
+    constexpr int D = Stripe<R, S>::D, LC = P.gci[GI] % 4, dpos = P.gbeg[GI];
+    static_assert(dpos == Stripe<R, S>::T.diag_pos[W][P.gci[GI]] && fc_diag_units(R, LC) <= D, "a group within the ring");
+    constexpr bool WRAP = dpos % D + fc_diag_units(R, LC) > D;
+    unsigned ad[8];
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {
+        const int pl = LC * 8 + p;
+        int i = (dpos % D) * 64 + fc_diag_start(R, LC, p) - (2 * pl + 1) + lane;
+        if (WRAP) i = i >= D * 64 ? i - D * 64 : i;
+        ad[p] = lane > 2 * pl ? la - 16u * (unsigned)lane + 16u * (unsigned)i : za;
+        asm volatile("" : "+v"(ad[p]));                    // (formed here: hoisted to the kernel's top the 32 addresses of a wave cost it its registers)
+    }
+#pragma unroll
+    for (int p = 0; p < 8; ++p) lds_read16<0>(l[p], ad[p]);
+}
+// the multiply-adds of stripe_pairs_apply_bcast, the units out of their register slots
+template <int R, int S, int W, int CI, int P, int NZ>
+__device__ __forceinline__ void stripe_pairs_apply_reg(const d2 (&RR)[kStripeRegSlots], const d2 (&z)[16], double (&a)[R][2])
+{
+    if constexpr (P < 8) {
+        constexpr int JB = CI / 4, NKO = R - 1 - JB, pos = Stripe<R, S>::T.pair_pos[W][CI][P];
+        if constexpr (pos >= 0) {
+            constexpr int s0 = StripePlanOf<R, S, W>::P.slot[pos];   // (a group's register slots follow each other round the ring)
+            static_assert(StripePlanOf<R, S, W>::P.slot[pos + NKO - 1] == (s0 + NKO - 1) % kStripeRegSlots, "a pair's slots");
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int k = 0; k < NKO; ++k) {
+                    const d2& l = RR[(s0 + k) % kStripeRegSlots];
+#pragma unroll
+                    for (int b = 0; b < 2; ++b) a[JB + 1 + k][b] = fma(h ? l.y : l.x, b ? z[NZ + h].y : z[NZ + h].x, a[JB + 1 + k][b]);
+                }
+            stripe_pairs_apply_reg<R, S, W, CI, P + 1, NZ + 2>(RR, z, a);
+        } else {
+            stripe_pairs_apply_reg<R, S, W, CI, P + 1, NZ>(RR, z, a);
+        }
+    }
+}
+template <int R, int S, int W, int GI>
+__device__ __forceinline__ void stripe_plan_apply(const d2 (&RR)[kStripeRegSlots], const d2 (&l)[8], const d2 (&z)[16], double (&a)[R][2])
+{
+    constexpr const StripePlan& P = StripePlanOf<R, S, W>::P;
+    constexpr int CI = P.gci[GI], JB = CI / 4;
+    if constexpr (P.gdiag[GI] != 0) {
+#pragma unroll
+        for (int p = 0; p < 8; ++p)
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int b = 0; b < 2; ++b) a[JB][b] = fma(h ? l[p].y : l[p].x, b ? z[2 * p + h].y : z[2 * p + h].x, a[JB][b]);
+    } else {
+        stripe_pairs_apply_reg<R, S, W, CI, 0, 0>(RR, z, a);
+    }
+}
+// The schedule behind group GI (stripe_ahead's, every count out of the plan): group GI's units are in L[GI & 1] (a diagonal part) or
+// in their register slots, its broadcasts in Z[GI & 1].  Then group GI + 1's broadcasts; a diagonal part's wait and LDS reads; the
+// multiply-adds of GI; a register group's wait, which needs no instruction in front of the multiply-adds; lgkmcnt(0); the requests up
+// to A units behind GI + 1, into the slots GI and the groups before it have left.
+// There is no early stop: this schedule runs whole sweeps only (stripe_plan.hpp: stripe_schedule; the others run schedule 1).
+// With the stop's branches every cut leaves register loads in flight into registers the compiler holds dead, and the generated code
+// kept ring registers alive across the cuts' tails until it spilled them, loads in flight included.
+template <int R, int S, int W, int GI>
+__device__ __forceinline__ void stripe_plan_ahead(const double* __restrict__ Fw, unsigned my, unsigned xa, unsigned voff, double (&a)[R][2],
+                                                  d2 (&RR)[kStripeRegSlots], d2 (&L)[2][8], d2 (&Z)[2][16], unsigned la, unsigned za, int lane)
+{
+    constexpr const StripePlan& P = StripePlanOf<R, S, W>::P;   // (its members in constant expressions only: read at run time they are loads)
+    constexpr StripeGroups Q = stripe_groups<R, S, W>();
+    static_assert(Q.n == P.ng && Q.ci[GI] == P.gci[GI] && Q.diag[GI] == P.gdiag[GI] && Q.end[GI] == P.gend[GI], "the plan's groups are the schedule's");
+    if constexpr (GI + 1 < P.ng) {
+        constexpr int N = GI + 1;
+        stripe_group_bcast<R, S, W, N>(Z[N & 1], xa);
+        if constexpr (P.gdiag[N] != 0) {
+            stripe_issue_plan<R, S, W, P.gpost[GI], P.gpre[N]>(Fw, my, lane, voff, RR);
+            asm_wait_vmcnt<P.gwait[N]>();
+            stripe_diag_read<R, S, W, N>(L[N & 1], la, za, lane);
+        }
+        MCD_SB;
+        stripe_plan_apply<R, S, W, GI>(RR, L[GI & 1], Z[GI & 1], a);
+        MCD_SB;
+        if constexpr (P.gdiag[N] != 0) {
+            lds_landed<8>(L[N & 1]);
+        } else {
+            stripe_issue_plan<R, S, W, P.gpost[GI], P.gpre[N]>(Fw, my, lane, voff, RR);
+            asm_wait_vmcnt<P.gwait[N]>();
+            stripe_regs_pin<R, S, W, P.gbeg[N], P.gend[N]>(RR);
+        }
+        lds_landed<stripe_group_cols<R, S, W, N>()>(Z[N & 1]);
+        stripe_issue_plan<R, S, W, P.gpre[N], P.gpost[N]>(Fw, my, lane, voff, RR);
+        stripe_plan_ahead<R, S, W, N>(Fw, my, xa, voff, a, RR, L, Z, la, za, lane);
+    } else {
+        stripe_plan_apply<R, S, W, GI>(RR, L[GI & 1], Z[GI & 1], a);
+    }
+}
+// ... and its head
+template <int R, int S, int W>
+__device__ __forceinline__ void stripe_plan_sched(const double* __restrict__ Fw, unsigned my, unsigned xa, unsigned voff, double (&a)[R][2],
+                                                  d2 (&RR)[kStripeRegSlots], unsigned la, unsigned za, int lane, int ncols)
+{
+    constexpr const StripePlan& P = StripePlanOf<R, S, W>::P;
+    // Never taken (stripe_sched_whole).  The branch ends the prologue's basic block: as one block with the sweep, the compiler's
+    // scheduling ran the kernel out of its 256 registers and copied ring registers with loads in flight (tools/stripe_inflight_audit.py).
+    // The prologue's register loads are out here and nothing on this path reads them, so they are waited for before the path joins
+    // the wave's end, where the compiler places address arithmetic in front of the written vmcnt(0).
+    if (ncols <= 0) {
+        MCD_SB;
+        asm_wait_vmcnt<0>();
+        MCD_SB;
+        return;
+    }
+    d2 L[2][8], Z[2][16];
+    stripe_group_bcast<R, S, W, 0>(Z[0], xa);
+    stripe_issue_plan<R, S, W, P.pro, P.gpre[0]>(Fw, my, lane, voff, RR);
+    asm_wait_vmcnt<P.gwait[0]>();
+    MCD_T(2);
+    if constexpr (P.gdiag[0] != 0) {
+        stripe_diag_read<R, S, W, 0>(L[0], la, za, lane);
+        lds_landed<8>(L[0]);
+    } else {
+        stripe_regs_pin<R, S, W, P.gbeg[0], P.gend[0]>(RR);
+    }
+    lds_landed<stripe_group_cols<R, S, W, 0>()>(Z[0]);
+    stripe_issue_plan<R, S, W, P.gpre[0], P.gpost[0]>(Fw, my, lane, voff, RR);
+    stripe_plan_ahead<R, S, W, 0>(Fw, my, xa, voff, a, RR, L, Z, la, za, lane);
+}
 // The private prologue: x, mu and (wave 0) 1/diag of both chains in front of the first DMA: a padded row or a chain beyond the batch
 // reads a clamped address and the value is dropped for mu (load_rawx)
 template <int R, int S, int W>
@@ -526,10 +701,10 @@ __device__ __forceinline__ void stripe_exchange_get(d2 (&e)[R], unsigned ea)
 // The shared prologue: the same loads, selection and operations, but only for the row blocks k = W, W + S, ... < R this wave owns
 // (four loads each); r and t = r invdiag go through the exchange area, one LDS-only barrier, every wave reads r and wave 0 t.
 // GETR = false (the schedule, which broadcasts r out of the exchange area): r is not read back into registers.
-template <int R, int S, int W, bool GETR = true>
-__device__ __forceinline__ void stripe_prologue_shared(const double* __restrict__ Fw, unsigned mya, unsigned ea, const MvnView& M,
-                                                       const double* __restrict__ X, int64_t ldx, int64_t b0, int64_t batch, double (&r)[R][2],
-                                                       double (&a)[R][2], int lane)
+// burst(): the wave's first PRO requests (and whatever else the schedule wants done while the loads are out).
+template <int R, int S, int W, bool GETR = true, class Burst>
+__device__ __forceinline__ void stripe_prologue_shared(unsigned ea, const MvnView& M, const double* __restrict__ X, int64_t ldx, int64_t b0,
+                                                       int64_t batch, double (&r)[R][2], double (&a)[R][2], int lane, Burst burst)
 {
     using G = Stripe<R, S>;
     constexpr int PRO = stripe_min(G::A, G::T.n[W]);
@@ -547,7 +722,7 @@ __device__ __forceinline__ void stripe_prologue_shared(const double* __restrict_
             asm_load8(xr[i][c], X + bc * ldx + rc);
         }
     }
-    stripe_issue<R, S, W, 0, PRO>(Fw, mya, lane);
+    burst();
     asm_wait_vmcnt<PRO>();                                 // the loads in front of the DMAs have returned
 #pragma unroll
     for (int i = 0; i < NO; ++i) asm volatile("" : "+v"(m[i]), "+v"(iv[i]), "+v"(xr[i][0]), "+v"(xr[i][1]));
@@ -576,20 +751,33 @@ __device__ __forceinline__ void stripe_wave(const double* __restrict__ Fw, d2* r
 {
     using G = Stripe<R, S>;
     static_assert(SH || SC == 0, "the schedule goes with the shared prologue");
+    static_assert(SC >= 0 && SC <= 2, "MCD_STRIPE_SCHED");
     constexpr int D = G::D, NU = G::T.n[W], PRO = stripe_min(G::A, NU);
     d2* my = ring + W * D * 64;
     d2* zu = ring + G::ZERO + W * 64;
     zu[lane] = d2{0.0, 0.0};
     const unsigned mya = lds_addr(my);
     double r[R][2], a[R][2];
-    if constexpr (SH) stripe_prologue_shared<R, S, W, SC == 0>(Fw, mya, lds_addr(ring + G::EXCH) + 16u * (unsigned)lane, M, X, ldx, b0, batch, r, a, lane);
-    else stripe_prologue_private<R, S, W>(Fw, mya, M, X, ldx, b0, batch, r, a, lane);
-    const unsigned la = mya + 16u * (unsigned)lane;
-    const unsigned za = lds_addr(zu) + 16u * (unsigned)lane;
-    if constexpr (SC != 0) stripe_sched<R, S, W, PRO>(Fw, mya, la, za, lds_addr(ring + G::EXCH), a, lane, ncols);
-    else stripe_chunks<R, S, W, 0, PRO>(Fw, mya, la, za, r, a, lane, ncols);
+    if constexpr (SC == 2) {
+        const unsigned voff = 16u * (unsigned)lane, la = mya + voff, za = lds_addr(zu) + voff;
+        d2 RR[kStripeRegSlots];
+        stripe_prologue_shared<R, S, W, false>(lds_addr(ring + G::EXCH) + voff, M, X, ldx, b0, batch, r, a, lane,
+                                               [&]() __attribute__((always_inline)) { stripe_issue_plan<R, S, W, 0, PRO>(Fw, mya, lane, voff, RR); });
+        stripe_plan_sched<R, S, W>(Fw, mya, lds_addr(ring + G::EXCH), voff, a, RR, la, za, lane, ncols);
+    } else {
+        if constexpr (SH)
+            stripe_prologue_shared<R, S, W, SC == 0>(lds_addr(ring + G::EXCH) + 16u * (unsigned)lane, M, X, ldx, b0, batch, r, a, lane,
+                                                     [&]() __attribute__((always_inline)) { stripe_issue<R, S, W, 0, PRO>(Fw, mya, lane); });
+        else stripe_prologue_private<R, S, W>(Fw, mya, M, X, ldx, b0, batch, r, a, lane);
+        const unsigned la = mya + 16u * (unsigned)lane;
+        const unsigned za = lds_addr(zu) + 16u * (unsigned)lane;
+        if constexpr (SC != 0) stripe_sched<R, S, W, PRO>(Fw, mya, la, za, lds_addr(ring + G::EXCH), a, lane, ncols);
+        else stripe_chunks<R, S, W, 0, PRO>(Fw, mya, la, za, r, a, lane, ncols);
+    }
     MCD_T(3);
-    asm_wait_vmcnt<0>();
+    if constexpr (SC == 2) MCD_SB;                         // (nothing of the hand-over moves in front of the wait: the path that skips the
+    asm_wait_vmcnt<0>();                                   //  sweep joins here, and the audit of the generated code follows every path)
+    if constexpr (SC == 2) MCD_SB;
     double* part = reinterpret_cast<double*>(my);
     if constexpr (W > 0) {
 #pragma unroll

@@ -4,6 +4,7 @@
 // (sweep_groups.hpp).
 #include "sweep_groups.hpp"
 #include "stripe_deal.hpp"
+#include "stripe_plan.hpp"
 #include <stdlib.h>
 #include <atomic>
 
@@ -302,4 +303,35 @@ extern "C" int mcd_stripe_deal_selftest_(int R, int S, int w, int ncols, int* pi
             if (d.pair_pos[w][ci][p] >= 0) put(ci, p, d.pair_pos[w][ci][p], R - 1 - ci / mcd::fc_cpb(R));
     }
     return np <= cap ? np : -2;
+}
+
+// Test hook (tests/test_stripe_plan_host.py; no device): the kernel a launch of the stripe kernel takes for R row blocks and a sweep over
+// ncols columns under the options as they stand (stripe_plan.hpp: stripe_schedule, the function launch_stripe calls)
+extern "C" int mcd_stripe_schedule_selftest_(int R, int ncols)
+{
+    if (R != 3 && R != 4) return -2;
+    return mcd::stripe_schedule(mcd::opt_or(mcd::OPT_STRIPE_PROLOGUE, mcd::kStripePrologueDefault),
+                                mcd::opt_or(mcd::OPT_STRIPE_SCHED, mcd::kStripeSchedDefault), R, ncols);
+}
+
+// Test hook (tests/test_stripe_plan_host.py; no device): the issue plan of stripe wave w under the register-load schedule with lookahead A
+// (stripe_plan.hpp).  head = {units, groups, leading loads, burst, ring units, register slots}; pos[u] = {kind, slot, base, immediate,
+// unit in Fw, group}; grp[g] = {chunk, diagonal, first position, end, issued at the wait, vmcnt of the wait, issued behind the reads}.
+// Returns stripe_plan_check's verdict (0: every claim holds), -1 for a plan that does not exist, -2 if the arrays are too small.
+extern "C" int mcd_stripe_plan_selftest_(int R, int S, int w, int A, int* head, int* pos, int cap_pos, int* grp, int cap_grp)
+{
+    if ((R != 3 && R != 4) || (S != 4 && S != 8) || w < 0 || w >= S || A < 1) return -1;
+    const mcd::StripePlan p = mcd::stripe_plan(R, S, w, A);
+    const mcd::StripeDeal d = mcd::stripe_deal(R, S);
+    if (p.n > cap_pos || p.ng > cap_grp) return -2;
+    head[0] = p.n, head[1] = p.ng, head[2] = p.lead, head[3] = p.pro, head[4] = p.D, head[5] = mcd::kStripeRegSlots;
+    for (int u = 0; u < p.n; ++u) {
+        int* q = pos + 6 * u;
+        q[0] = p.kind[u], q[1] = p.slot[u], q[2] = p.base[u], q[3] = p.imm[u], q[4] = d.unit[w][u], q[5] = p.group[u];
+    }
+    for (int g = 0; g < p.ng; ++g) {
+        int* q = grp + 7 * g;
+        q[0] = p.gci[g], q[1] = p.gdiag[g], q[2] = p.gbeg[g], q[3] = p.gend[g], q[4] = p.gpre[g], q[5] = p.gwait[g], q[6] = p.gpost[g];
+    }
+    return mcd::stripe_plan_check(p, R, S, w);
 }
