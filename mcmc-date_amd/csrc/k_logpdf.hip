@@ -42,7 +42,7 @@ __global__ void __launch_bounds__(64 * (CW + LW)) k_logpdf(const double* __restr
 // round through LDS (the default), or by every wave for itself (mcd_set_option "MCD_STRIPE_PROLOGUE" = 0; A/B, tests: the same bits).
 // SC (with SH only): the column broadcasts read out of the exchange area and the ring read one group ahead of the multiply-adds (the
 // schedule of "MCD_STRIPE_SCHED" = 1), that schedule with the off-diagonal units loaded straight into registers (2, the default; whole
-// sweeps only, a sweep that stops early runs schedule 1), or round 14's loop (0).  A/B, tests: the same bits.  Four kernels per R.
+// sweeps only, a sweep that stops early runs schedule 1), or round 14's loop (0).  A/B, tests: the same bits.  Four kernels per R, and k_logpdf_stripe_fin below.
 template <int R, int S, bool SH, int SC>
 __global__ void __launch_bounds__(64 * S) k_logpdf_stripe(const double* __restrict__ Fw, const double* __restrict__ mu,
                                                           const double* __restrict__ invdiag, const double* __restrict__ X, int64_t ldx,
@@ -56,6 +56,24 @@ __global__ void __launch_bounds__(64 * S) k_logpdf_stripe(const double* __restri
     stripe_dispatch<R, S, 0, SH, SC>(wave, Fw, ring, M, X, ldx, (int64_t)blockIdx.x * 2, batch, ncols, ll, lane);
 }
 
+// Schedule 2 under the shared prologue with a finishing wave per chain (stripe_device.hpp: stripe_wave_fin; "MCD_STRIPE_FINISH" = 0
+// keeps k_logpdf_stripe<R, S, true, 2>; the same bits).  A kernel of its own name: the audit of the generated code finds each by its
+// prefix.  c and logdet are not read here -- the finishing waves fetch them from their place in the arguments (kStripeArgC), which
+// this list fixes: eight 8-byte arguments (n and ncols share one), then ll, c, logdet.
+template <int R, int S>
+__global__ void __launch_bounds__(64 * S) k_logpdf_stripe_fin(const double* __restrict__ Fw, const double* __restrict__ mu,
+                                                              const double* __restrict__ invdiag, const double* __restrict__ X, int64_t ldx,
+                                                              int64_t batch, int n, int ncols, double* __restrict__ ll, double c, double logdet)
+{
+    static_assert(kStripeArgC == 8 * 8, "c follows Fw, mu, invdiag, X, ldx, batch, {n, ncols} and ll");
+    __shared__ d2 ring[Stripe<R, S>::D3];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    MCD_T(0);
+    const MvnView M(mu, invdiag, n, 0.0, 0.0);
+    stripe_dispatch_fin<R, S, 0>(wave, Fw, ring, M, X, ldx, (int64_t)blockIdx.x * 2, batch, ncols, ll, lane);
+}
+
 template <int R, bool SH, int SC>
 static void launch_stripe_sh(const MvnDev& M, const double* X, int64_t ldx, int64_t batch, double* ll, hipStream_t st)
 {
@@ -65,8 +83,12 @@ static void launch_stripe_sh(const MvnDev& M, const double* X, int64_t ldx, int6
 template <int R>
 static void launch_stripe(const MvnDev& M, const double* X, int64_t ldx, int64_t batch, double* ll, hipStream_t st)
 {
-    const int sc = stripe_schedule(opt_or(OPT_STRIPE_PROLOGUE, kStripePrologueDefault), opt_or(OPT_STRIPE_SCHED, kStripeSchedDefault), R, M.ncols);
+    const int pro = opt_or(OPT_STRIPE_PROLOGUE, kStripePrologueDefault), sched = opt_or(OPT_STRIPE_SCHED, kStripeSchedDefault);
+    const int sc = stripe_schedule(pro, sched, R, M.ncols);
     if (sc < 0) launch_stripe_sh<R, false, 0>(M, X, ldx, batch, ll, st);
+    else if (stripe_finish(pro, sched, opt_or(OPT_STRIPE_FINISH, kStripeFinishDefault), R, M.ncols) != 0)
+        hipLaunchKernelGGL((k_logpdf_stripe_fin<R, kStripeWaves>), dim3((unsigned)((batch + 1) / 2)), dim3(64 * kStripeWaves), 0, st, M.Fw, M.mu,
+                           M.invdiag, X, ldx, batch, M.n, M.ncols, ll, M.c, M.logdet);
     else if (sc == 2) launch_stripe_sh<R, true, 2>(M, X, ldx, batch, ll, st);
     else if (sc == 1) launch_stripe_sh<R, true, 1>(M, X, ldx, batch, ll, st);
     else launch_stripe_sh<R, true, 0>(M, X, ldx, batch, ll, st);

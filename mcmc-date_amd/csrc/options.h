@@ -40,6 +40,8 @@ enum Option {
     OPT_STRIPE_SCHED,       // the stripe kernel's schedule under the shared prologue: 1 = the column broadcasts read out of the exchange area and the
                             // ring read one group ahead of the multiply-adds, 2 = that schedule with the off-diagonal units loaded straight into
                             // registers (stripe_plan.hpp), 0 = the loop of round 14 (A/B, tests; the same bits)
+    OPT_STRIPE_FINISH,      // schedule 2's kernel only: 1 = each of the workgroup's two chains finished by a wave of its own, c and logdet fetched at
+                            // entry; 0 = wave 0 finishes both (round 18's kernel) (A/B, tests; the same bits)
     OPT_COUNT
 };
 constexpr int MCD_OPT_UNSET = -2147483647 - 1;

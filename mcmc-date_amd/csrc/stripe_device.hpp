@@ -44,6 +44,7 @@
 //     vector address arithmetic, no M0 write, no ds_read and no lgkmcnt wait.  The diagonal parts keep their LDS-DMAs and ring slots.
 //     Both kinds count on vmcnt in issue order; one constexpr plan per wave (stripe_plan.hpp) holds every position's kind, slot, base
 //     and immediate and every group's wait, and is proved at compile time.  Same operands, same order of additions, same bits.
+//   * The finish per chain (schedule 2 only, the default there; MCD_STRIPE_FINISH = 0 keeps wave 0 finishing both): see stripe_wave_fin.
 #include "mvn_device.hpp"
 #include "stripe_deal.hpp"
 #include "stripe_plan.hpp"
@@ -797,6 +798,134 @@ __device__ __forceinline__ void stripe_wave(const double* __restrict__ Fw, d2* r
         }
         finish_ll<R, 2>(a, M, b0, batch, ll, lane);
         MCD_T(4);
+    }
+}
+
+// ---- the per-chain finish (MCD_STRIPE_FINISH = 1, the default; schedule 2 with the shared prologue only: k_logpdf_stripe_fin) ----
+// Behind the hand-over barrier wave 0 used to form z for both chains and run finish_ll<R, 2>, chain 0 to its store before chain 1's
+// reduction began, while three waves idled.  Here wave kStripeFinishWave + c finishes chain c: z_k = ((a0_k + a1_k) + a2_k) + a3_k in
+// wave order, its own partial out of its registers; s = fma(z_k, z_k, s), k ascending; wave_sum; ll = c + (-0.5)(logdet + q) -- the
+// operations of finish_ll for that chain in its order, so the bits are the old finish's.  One barrier as before, reached by every
+// wave on every path.
+//   * The hand-over keeps the 8-byte layout [w][k][c][lane] in the waves' ring regions.  A finishing wave wants one chain only: a
+//     ds_read_b64 at 8 lane + const covers all 64 banks once per 32 lanes (2 LDS cycles, no conflict).  With {c0, c1} in 16-byte slots
+//     it would read twice the bytes into twice the registers (ds_read_b128: 4 cycles) to drop half, and one ds_write_b128 moves its
+//     operands no faster than the two ds_write_b64 it replaces (13 cycles against 2 x 6).
+//   * A wave stores only what another wave reads: both chains, or the chain it does not finish.
+//   * The reads are asm (the compiler put a wait of its own behind every few of them): all issued, one lgkmcnt(0).
+//   * c and logdet: kernel arguments 10 and 11 lie behind the preloaded dwords.  The finishing waves fetch them at entry, by an asm
+//     scalar load the compiler cannot sink in front of the barrier, and wait for them behind the wave sum.  (Any lgkmcnt(0) covers
+//     the load, and every LDS wait of this kernel is one; the exchange barrier's is the first.)
+//   * Waves 0 and 1 finish: they are the last at the barrier, and so store one chain's partials in front of it, not two.  Measured
+//     (profiles/r19_stripe_finish_ab.txt): waves 2 and 3 (-DMCD_STRIPE_FINISH_WAVE=2) 4.509 us per launch against 4.472.
+//   * Measured and not kept (docs/experiments/r19_stripe_x_first_late_t.diff): x loaded in front of mu and 1/diag (+0.04 us), and
+//     wave 0's t left in flight until the first group's wait (level).
+#ifndef MCD_STRIPE_FINISH_WAVE
+#define MCD_STRIPE_FINISH_WAVE 0
+#endif
+constexpr int kStripeFinishWave = MCD_STRIPE_FINISH_WAVE;  // chain c of the workgroup is finished by wave kStripeFinishWave + c
+constexpr int kStripeArgC = 0x40;                          // byte offset of c (logdet: + 8) in the kernel's arguments (k_logpdf.hip)
+typedef unsigned stripe_u4 __attribute__((ext_vector_type(4)));
+// c and logdet into four SGPRs, outside the compiler's bookkeeping like asm_load8: stripe_args_landed() before the first use
+__device__ __forceinline__ void stripe_args_load(stripe_u4& v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("s_load_dwordx4 %0, %1, %2" : "=&s"(v) : "s"(__builtin_amdgcn_kernarg_segment_ptr()), "n"(kStripeArgC) : "memory");
+#endif
+}
+__device__ __forceinline__ void stripe_args_landed(stripe_u4& v)
+{
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(v)::"memory");
+}
+template <int OFF>
+__device__ __forceinline__ void lds_read8(double& v, unsigned addr)
+{
+    static_assert(OFF >= 0 && OFF < 65536, "ds offset");
+    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
+}
+template <int R, int S, int W, int C, int I>
+__device__ __forceinline__ void stripe_finish_get(double (&p)[S][R], unsigned pa)
+{
+    if constexpr (I < S * R) {
+        constexpr int w = I / R, k = I % R;
+        if constexpr (w != W) lds_read8<(k * 2 + C) * 512>(p[w][k], pa + (unsigned)(w * Stripe<R, S>::D * 1024));   // (a region is 32 KiB: past the offset field)
+        stripe_finish_get<R, S, W, C, I + 1>(p, pa);
+    }
+}
+// chain C of the workgroup, by wave W: pa = the ring's LDS byte address + 8 lane; cl = c and logdet in flight
+template <int R, int S, int W, int C>
+__device__ __forceinline__ void stripe_finish_chain(const double (&a)[R][2], unsigned pa, stripe_u4& cl, int64_t b0, int64_t batch,
+                                                    double* __restrict__ ll, int lane)
+{
+    double p[S][R];
+    stripe_finish_get<R, S, W, C, 0>(p, pa);               // every other wave's partials of chain C, one wait
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int w = 0; w < S; ++w)
+#pragma unroll
+        for (int k = 0; k < R; ++k)
+            if (w != W) asm volatile("" : "+v"(p[w][k]));
+    MCD_T(7);
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+        double z = W == 0 ? a[k][C] : p[0][k];
+#pragma unroll
+        for (int w = 1; w < S; ++w) z = z + (w == W ? a[k][C] : p[w][k]);
+        s = fma(z, z, s);
+    }
+    const double q = wave_sum(s);
+    stripe_args_landed(cl);
+    const double c = __hiloint2double((int)cl.y, (int)cl.x), logdet = __hiloint2double((int)cl.w, (int)cl.z);
+    if (lane == 0 && b0 + C < batch) ll[b0 + C] = c + (-0.5) * (logdet + q);   // (finish_ll's line)
+}
+
+template <int R, int S, int W>
+__device__ __forceinline__ void stripe_wave_fin(const double* __restrict__ Fw, d2* ring, const MvnView& M, const double* __restrict__ X, int64_t ldx,
+                                                int64_t b0, int64_t batch, int ncols, double* __restrict__ ll, int lane)
+{
+    using G = Stripe<R, S>;
+    static_assert(kStripeFinishWave >= 0 && kStripeFinishWave + 2 <= S, "MCD_STRIPE_FINISH_WAVE");
+    constexpr int D = G::D, NU = G::T.n[W], PRO = stripe_min(G::A, NU);
+    constexpr int C = W - kStripeFinishWave;               // the chain this wave finishes, if 0 or 1
+    constexpr bool FIN = C == 0 || C == 1;
+    stripe_u4 cl;
+    if constexpr (FIN) stripe_args_load(cl);
+    d2* my = ring + W * D * 64;
+    d2* zu = ring + G::ZERO + W * 64;
+    zu[lane] = d2{0.0, 0.0};
+    const unsigned mya = lds_addr(my);
+    double r[R][2], a[R][2];
+    const unsigned voff = 16u * (unsigned)lane, la = mya + voff, za = lds_addr(zu) + voff;
+    d2 RR[kStripeRegSlots];
+    stripe_prologue_shared<R, S, W, false>(lds_addr(ring + G::EXCH) + voff, M, X, ldx, b0, batch, r, a, lane,
+                                           [&]() __attribute__((always_inline)) { stripe_issue_plan<R, S, W, 0, PRO>(Fw, mya, lane, voff, RR); });
+    stripe_plan_sched<R, S, W>(Fw, mya, lds_addr(ring + G::EXCH), voff, a, RR, la, za, lane, ncols);
+    MCD_T(3);
+    MCD_SB;                                                // (as in stripe_wave: the path that skips the sweep joins here)
+    asm_wait_vmcnt<0>();
+    MCD_SB;
+    double* part = reinterpret_cast<double*>(my);
+#pragma unroll
+    for (int k = 0; k < R; ++k)
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+            if (c != C) part[(k * 2 + c) * 64 + lane] = a[k][c];
+    lds_barrier();
+    if constexpr (FIN) {
+        MCD_T(6);
+        stripe_finish_chain<R, S, W, C>(a, lds_addr(ring) + 8u * (unsigned)lane, cl, b0, batch, ll, lane);
+        MCD_T(4);
+    }
+}
+template <int R, int S, int W>
+__device__ __forceinline__ void stripe_dispatch_fin(int wave, const double* __restrict__ Fw, d2* ring, const MvnView& M, const double* __restrict__ X,
+                                                    int64_t ldx, int64_t b0, int64_t batch, int ncols, double* __restrict__ ll, int lane)
+{
+    if (wave == W) {
+        stripe_wave_fin<R, S, W>(Fw, ring, M, X, ldx, b0, batch, ncols, ll, lane);
+    } else {
+        if constexpr (W + 1 < S) stripe_dispatch_fin<R, S, W + 1>(wave, Fw, ring, M, X, ldx, b0, batch, ncols, ll, lane);
     }
 }
 

@@ -51,6 +51,14 @@ constexpr int stripe_schedule(int prologue, int sched, int R, int ncols)
     if (sched == 2) return stripe_sched_whole(R, ncols) ? 2 : 1;
     return sched != 0 ? 1 : 0;
 }
+// Which finish a launch takes (mcd_stripe_finish_selftest_): finish is the value of MCD_STRIPE_FINISH or its default.  1: each chain of
+// the workgroup finished by a wave of its own (k_logpdf_stripe_fin); 0: wave 0 finishes both (k_logpdf_stripe).  Only
+// schedule 2's kernel has the per-chain finish; everywhere else the option has no effect.
+constexpr int kStripeFinishDefault = 1;                    // MCD_STRIPE_FINISH unset: a finishing wave per chain
+constexpr int stripe_finish(int prologue, int sched, int finish, int R, int ncols)
+{
+    return stripe_schedule(prologue, sched, R, ncols) == 2 && finish != 0 ? 1 : 0;
+}
 
 constexpr int stripe_plan_min(int a, int b) { return a < b ? a : b; }
 constexpr int stripe_plan_max(int a, int b) { return a > b ? a : b; }

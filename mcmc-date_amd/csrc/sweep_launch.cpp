@@ -314,6 +314,16 @@ extern "C" int mcd_stripe_schedule_selftest_(int R, int ncols)
                                 mcd::opt_or(mcd::OPT_STRIPE_SCHED, mcd::kStripeSchedDefault), R, ncols);
 }
 
+// Test hook (tests/test_stripe_finish_codegen_host.py, tests/test_gpu_stripe_finish.py; no device): the finish such a launch takes under the
+// options as they stand (stripe_plan.hpp: stripe_finish, the function launch_stripe calls): 1 a finishing wave per chain, 0 wave 0 alone
+extern "C" int mcd_stripe_finish_selftest_(int R, int ncols)
+{
+    if (R != 3 && R != 4) return -2;
+    return mcd::stripe_finish(mcd::opt_or(mcd::OPT_STRIPE_PROLOGUE, mcd::kStripePrologueDefault),
+                              mcd::opt_or(mcd::OPT_STRIPE_SCHED, mcd::kStripeSchedDefault),
+                              mcd::opt_or(mcd::OPT_STRIPE_FINISH, mcd::kStripeFinishDefault), R, ncols);
+}
+
 // Test hook (tests/test_stripe_plan_host.py; no device): the issue plan of stripe wave w under the register-load schedule with lookahead A
 // (stripe_plan.hpp).  head = {units, groups, leading loads, burst, ring units, register slots}; pos[u] = {kind, slot, base, immediate,
 // unit in Fw, group}; grp[g] = {chunk, diagonal, first position, end, issued at the wait, vmcnt of the wait, issued behind the reads}.

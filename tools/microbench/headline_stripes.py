@@ -4,7 +4,9 @@ tools/microbench/libheadlinestamp.so; STAMPLIB names another file beside it, suc
 The harness is headline_phases.py's: graphs of 100 launches alternating two input batches, replayed back to back; the last 64
 launches are kept.  Milestones of a wave: 0 entry, 1 its loads of x / mu / 1/diag landed (behind the issue of the prologue's LDS-DMAs),
 5 exchange barrier passed and r read (the shared prologue only; MCD_STRIPE_PROLOGUE=0 in the environment: the private one), 2 first
-unit landed, 3 last unit applied, and on wave 0: 4 ll stored.  A wave's stream rate is its units x 1024 bytes over 2 -> 3; the CU's is the
+unit landed, 3 last unit applied, and on wave 0: 4 ll stored.  Under the per-chain finish (MCD_STRIPE_FINISH unset or 1) both
+finishing waves stamp 6 hand-over barrier passed, 7 hand-over read and 4 ll stored; a stamp the second finishing wave takes after wave 0
+has closed the launch's slot lands in the next slot and is dropped here (counted in "of").  A wave's stream rate is its units x 1024 bytes over 2 -> 3; the CU's is the
 whole stream over (first wave's 2) -> (last wave's 3), and over entry -> (last wave's 3).
 
 usage: python tools/microbench/headline_stripes.py [N [chains [waves]]]"""
@@ -61,6 +63,13 @@ for w in range(NW):
         return f"{np.median(t[:, w, i]):6.0f} ({t[:, w, i].min():6d} .. {t[:, w, i].max():6d})"
     print(f"  wave {w}: entry {m(0)}  loads landed {m(1)}  " + (f"barrier passed, r read {m(5)}  " if shared else "") +
           f"first unit landed {m(2)}  last unit applied {m(3)}  first -> last {np.median(t[:, w, 3] - t[:, w, 2]):6.0f}")
+for w in range(NW):                                                            # the finishing waves (milestone 6: the per-chain finish only)
+    good = (t[:, w, 6] > t[:, w, 3]) & (t[:, w, 7] >= t[:, w, 6]) & (t[:, w, 4] >= t[:, w, 7]) & (t[:, w, 4] < 100000)
+    if good.any():
+        f = t[good]
+        print(f"  wave {w} finishes ({good.sum()} of {len(t)}): barrier passed {np.median(f[:, w, 6]):6.0f}  hand-over read {np.median(f[:, w, 7]):6.0f}  "
+              f"ll stored {np.median(f[:, w, 4]):6.0f}  last unit applied -> ll stored {np.median(f[:, w, 4] - f[:, w, 3]):6.0f}  "
+              f"workgroup's last unit -> ll stored {np.median(f[:, w, 4] - f[:, :, 3].max(axis=1)):6.0f}")
 first, last = t[:, :, 2].min(axis=1), t[:, :, 3].max(axis=1)
 print(f"  workgroup: first unit landed {np.median(first):6.0f}, last unit applied {np.median(last):6.0f}, ll stored {np.median(t[:, 0, 4]):6.0f}")
 print(f"  stream: {total} units; {total * 1024 / np.median(last - first):5.1f} B/clk first landed -> last applied, "

@@ -27,6 +27,7 @@ import tempfile
 LLVM = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin")
 LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mcmc-date_amd", "libmcmcdate_mvn.so")
 STRIPE = "_ZN3mcd15k_logpdf_stripeILi%dELi4ELb1ELi%dE"        # k_logpdf_stripe<R, 4, true, SC>
+STRIPE_FIN = "_ZN3mcd19k_logpdf_stripe_finILi%dELi4EE"        # k_logpdf_stripe_fin<R, 4>
 
 
 def regs(text):
