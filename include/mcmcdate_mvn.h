@@ -101,7 +101,10 @@ const char* mcd_last_error(void);
  * kernel's schedule under the shared prologue: 1 = the column broadcasts read out of LDS and the ring read one group ahead of the
  * multiply-adds, 2 (the default) = that with the off-diagonal units loaded straight into registers where the sweep does not stop
  * early, 0 = the schedule before; the same bits), "MCD_STRIPE_FINISH" (where schedule 2 runs: 1 (the default) = each of a workgroup's two
- * chains is finished by a wave of its own, 0 = one wave finishes both; no effect elsewhere; the same bits); value = a decimal integer, NULL or ""
+ * chains is finished by a wave of its own, 0 = one wave finishes both; no effect elsewhere; the same bits), "MCD_STRIPE_DIAG" (where that finish runs: 1 = the diagonal parts of the
+ * stream by register load like every other unit, no LDS ring, 0 = through the ring; unset = 1 for batches of 385 chains and more, where it is the faster one, else 0; no effect elsewhere;
+ * the same bits);
+ * value = a decimal integer, NULL or ""
  * = back to the default.  What each knob does is said where it acts (mcd_mh_run, the forms above).  The environment variables of the same
  * names are read ONCE, when the library is loaded, as initial values -- never afterwards.  No knob changes a result beyond rounding.
  */

@@ -74,6 +74,22 @@ __global__ void __launch_bounds__(64 * S) k_logpdf_stripe_fin(const double* __re
     stripe_dispatch_fin<R, S, 0>(wave, Fw, ring, M, X, ldx, (int64_t)blockIdx.x * 2, batch, ncols, ll, lane);
 }
 
+// The per-chain-finish kernel with the diagonal parts by register load too ("MCD_STRIPE_DIAG" = 1; stripe_device.hpp: stripe_wave_reg; the
+// same bits).  No ring: LDS is the exchange area and the hand-over of the partial sums.  The same arguments in the same places.
+template <int R, int S>
+__global__ void __launch_bounds__(64 * S) k_logpdf_stripe_reg(const double* __restrict__ Fw, const double* __restrict__ mu,
+                                                              const double* __restrict__ invdiag, const double* __restrict__ X, int64_t ldx,
+                                                              int64_t batch, int n, int ncols, double* __restrict__ ll, double c, double logdet)
+{
+    static_assert(kStripeArgC == 8 * 8, "c follows Fw, mu, invdiag, X, ldx, batch, {n, ncols} and ll");
+    __shared__ d2 lds[StripeReg<R, S>::D2];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    MCD_T(0);
+    const MvnView M(mu, invdiag, n, 0.0, 0.0);
+    stripe_dispatch_reg<R, S, 0>(wave, Fw, lds, M, X, ldx, (int64_t)blockIdx.x * 2, batch, ncols, ll, lane);
+}
+
 template <int R, bool SH, int SC>
 static void launch_stripe_sh(const MvnDev& M, const double* X, int64_t ldx, int64_t batch, double* ll, hipStream_t st)
 {
@@ -84,9 +100,12 @@ template <int R>
 static void launch_stripe(const MvnDev& M, const double* X, int64_t ldx, int64_t batch, double* ll, hipStream_t st)
 {
     const int pro = opt_or(OPT_STRIPE_PROLOGUE, kStripePrologueDefault), sched = opt_or(OPT_STRIPE_SCHED, kStripeSchedDefault);
-    const int sc = stripe_schedule(pro, sched, R, M.ncols);
+    const int sc = stripe_schedule(pro, sched, R, M.ncols), fin = opt_or(OPT_STRIPE_FINISH, kStripeFinishDefault);
     if (sc < 0) launch_stripe_sh<R, false, 0>(M, X, ldx, batch, ll, st);
-    else if (stripe_finish(pro, sched, opt_or(OPT_STRIPE_FINISH, kStripeFinishDefault), R, M.ncols) != 0)
+    else if (stripe_diag(pro, sched, fin, opt_or(OPT_STRIPE_DIAG, stripe_diag_default(batch)), R, M.ncols) != 0)
+        hipLaunchKernelGGL((k_logpdf_stripe_reg<R, kStripeWaves>), dim3((unsigned)((batch + 1) / 2)), dim3(64 * kStripeWaves), 0, st, M.Fw, M.mu,
+                           M.invdiag, X, ldx, batch, M.n, M.ncols, ll, M.c, M.logdet);
+    else if (stripe_finish(pro, sched, fin, R, M.ncols) != 0)
         hipLaunchKernelGGL((k_logpdf_stripe_fin<R, kStripeWaves>), dim3((unsigned)((batch + 1) / 2)), dim3(64 * kStripeWaves), 0, st, M.Fw, M.mu,
                            M.invdiag, X, ldx, batch, M.n, M.ncols, ll, M.c, M.logdet);
     else if (sc == 2) launch_stripe_sh<R, true, 2>(M, X, ldx, batch, ll, st);

@@ -276,8 +276,12 @@ int mcd_mvn_create(mcd_mvn_t** out, int n, const double* mu, const double* mat, 
         HIP_TRY(hipMemcpy(h->d_Fc, Fc.data(), Fc.size() * sizeof(double), hipMemcpyHostToDevice));
         std::vector<double> Fw;            // ... and W = L^-1 in the same layout: the inverse stream of k_logpdf (FS = 3)
         mcd::pack_inverse_forward(n, h->R, W, Fw);
-        HIP_TRY(hipMalloc((void**)&h->d_Fw, Fw.size() * sizeof(double)));
-        HIP_TRY(hipMemcpy(h->d_Fw, Fw.data(), Fw.size() * sizeof(double), hipMemcpyHostToDevice));
+        // On the device one 1-KiB unit of zeros stands behind the stream: the lanes of a diagonal pair whose entries the stream does not
+        // store read it (k_logpdf_stripe_reg; stripe_plan.hpp: stripe_reg_zero)
+        const size_t zero_at = Fw.size();  // = fc_total_units(R) x 128 doubles
+        HIP_TRY(hipMalloc((void**)&h->d_Fw, (zero_at + 128) * sizeof(double)));
+        HIP_TRY(hipMemcpy(h->d_Fw, Fw.data(), zero_at * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(h->d_Fw + zero_at, 0, 128 * sizeof(double)));
     }
 
     const int ch = mcd::sweep_chunk_columns(h->R);

@@ -703,12 +703,12 @@ __device__ __forceinline__ void stripe_exchange_get(d2 (&e)[R], unsigned ea)
 // (four loads each); r and t = r invdiag go through the exchange area, one LDS-only barrier, every wave reads r and wave 0 t.
 // GETR = false (the schedule, which broadcasts r out of the exchange area): r is not read back into registers.
 // burst(): the wave's first PRO requests (and whatever else the schedule wants done while the loads are out).
-template <int R, int S, int W, bool GETR = true, class Burst>
+template <int R, int S, int W, bool GETR = true, int BURST = -1, class Burst>
 __device__ __forceinline__ void stripe_prologue_shared(unsigned ea, const MvnView& M, const double* __restrict__ X, int64_t ldx, int64_t b0,
                                                        int64_t batch, double (&r)[R][2], double (&a)[R][2], int lane, Burst burst)
 {
     using G = Stripe<R, S>;
-    constexpr int PRO = stripe_min(G::A, G::T.n[W]);
+    constexpr int PRO = BURST >= 0 ? BURST : stripe_min(G::A, G::T.n[W]);   // (BURST: a kernel whose burst is not the ring plan's)
     constexpr int NO = W < R ? (R - W + S - 1) / S : 0;    // row blocks owned
     double xr[NO + 1][2], m[NO + 1], iv[NO + 1];
 #pragma unroll
@@ -843,22 +843,23 @@ __device__ __forceinline__ void lds_read8(double& v, unsigned addr)
     static_assert(OFF >= 0 && OFF < 65536, "ds offset");
     asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
 }
-template <int R, int S, int W, int C, int I>
+// REGION: bytes from one wave's partials to the next wave's
+template <int R, int S, int W, int C, int I, int REGION = Stripe<R, S>::D * 1024>
 __device__ __forceinline__ void stripe_finish_get(double (&p)[S][R], unsigned pa)
 {
     if constexpr (I < S * R) {
         constexpr int w = I / R, k = I % R;
-        if constexpr (w != W) lds_read8<(k * 2 + C) * 512>(p[w][k], pa + (unsigned)(w * Stripe<R, S>::D * 1024));   // (a region is 32 KiB: past the offset field)
-        stripe_finish_get<R, S, W, C, I + 1>(p, pa);
+        if constexpr (w != W) lds_read8<(k * 2 + C) * 512>(p[w][k], pa + (unsigned)(w * REGION));   // (a region is 32 KiB: past the offset field)
+        stripe_finish_get<R, S, W, C, I + 1, REGION>(p, pa);
     }
 }
 // chain C of the workgroup, by wave W: pa = the ring's LDS byte address + 8 lane; cl = c and logdet in flight
-template <int R, int S, int W, int C>
+template <int R, int S, int W, int C, int REGION = Stripe<R, S>::D * 1024>
 __device__ __forceinline__ void stripe_finish_chain(const double (&a)[R][2], unsigned pa, stripe_u4& cl, int64_t b0, int64_t batch,
                                                     double* __restrict__ ll, int lane)
 {
     double p[S][R];
-    stripe_finish_get<R, S, W, C, 0>(p, pa);               // every other wave's partials of chain C, one wait
+    stripe_finish_get<R, S, W, C, 0, REGION>(p, pa);       // every other wave's partials of chain C, one wait
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
     for (int w = 0; w < S; ++w)
@@ -937,6 +938,195 @@ __device__ __forceinline__ void stripe_dispatch(int wave, const double* __restri
         stripe_wave<R, S, W, SH, SC>(Fw, ring, M, X, ldx, b0, batch, ncols, ll, lane);
     } else {
         if constexpr (W + 1 < S) stripe_dispatch<R, S, W + 1, SH, SC>(wave, Fw, ring, M, X, ldx, b0, batch, ncols, ll, lane);
+    }
+}
+
+// ---- every unit by register load (MCD_STRIPE_DIAG = 1: k_logpdf_stripe_reg; the shared prologue, schedule 2's groups, the per-chain finish) ----
+// Under schedule 2 a diagonal part still went global -> LDS -> register, only to be shifted by a lane offset: per part 7, 5, 3 or 1
+// LDS-DMAs (each with a vector address add, an M0 write and a literal move), eight ds_read_b128 whose addresses take three VALU
+// instructions each, and an lgkmcnt(0) in front of the group's multiply-adds.  A per-lane load address says the same shift: pair pl of
+// a part is one global_load_dwordx4 whose lanes l > 2 pl read base + imm + 16 l (stripe_plan.hpp: stripe_reg_plan, proved against
+// fc_diag_start at compile time), and whose lanes l <= 2 pl -- zeros the stream does not store -- read a unit of zeros behind the stream
+// (mvn_capi.cpp).  They are not skipped: the multiply-adds stay the same operations on every lane, so 0 x inf is still NaN.  One
+// v_cmp and one v_cndmask per pair choose between 16 l and the pair's constant offset to the zero unit.
+// Every group is a register group: broadcasts of g + 1, the multiply-adds of g out of the register ring, the requests g + 1 still
+// lacks, its counted wait, the requests up to the lookahead behind it.  No ring, no zero units in LDS, no L[2][8]: LDS holds the
+// exchange area and, behind it, the hand-over of the partial sums ([w][k][c][lane], 8 bytes, as under the ring).
+// Same operands, same order of additions, same bits.
+template <int R, int S>
+struct StripeReg {
+    static constexpr int EXCH = 0;                        // the exchange area [r | t][R][64] (d2 index)
+    static constexpr int HAND = 2 * R * 64;               // the hand-over: R x 64 d2 (= [R][2][64] doubles) per wave
+    static constexpr int REGION = R * 1024;               // ... in bytes
+    static constexpr int D2 = HAND + S * R * 64;          // 24 KiB at R = 4, S = 4
+    static_assert(stripe_reg_plans_cover(R, S, kStripeRegAhead), "stripe register plan: every off-diagonal unit and every (part, pair) once");
+};
+template <int R, int S, int W>
+struct StripeRegPlanOf {
+    static constexpr StripeRegPlan P = stripe_reg_plan(R, S, W, kStripeRegAhead);
+    static_assert(stripe_reg_plan_check(P, R, S, W) == 0, "stripe register plan: waits, outstanding operations, slot reuse, immediates, lane addresses");
+};
+// requests [U0, U1) of the plan; voff = 16 lane
+template <int R, int S, int W, int U0, int U1>
+__device__ __forceinline__ void stripe_reg_issue(const double* __restrict__ Fw, int lane, unsigned voff, d2 (&RR)[kStripeRegRing])
+{
+    if constexpr (U0 < U1) {
+        constexpr const StripeRegPlan& P = StripeRegPlanOf<R, S, W>::P;
+        constexpr int slot = P.slot[U0], base = P.base[U0];
+        if constexpr (P.thr[U0] < 0) {
+            stripe_load_reg<P.imm[U0]>(RR[slot], voff, reinterpret_cast<const char*>(Fw) + base);
+        } else {
+            constexpr int thr = P.thr[U0];
+            constexpr unsigned zoff = (unsigned)P.zoff[U0];
+            unsigned v = lane > thr ? voff : zoff;         // (stripe_plan.hpp: stripe_reg_lane_voff, which the plan's check evaluates)
+            asm volatile("" : "+v"(v));                    // (formed here, like stripe_diag_read's addresses)
+            stripe_load_reg<P.imm[U0]>(RR[slot], v, reinterpret_cast<const char*>(Fw) + base);
+        }
+        stripe_reg_issue<R, S, W, U0 + 1, U1>(Fw, lane, voff, RR);
+    }
+}
+template <int R, int S, int W, int U0, int U1>
+__device__ __forceinline__ void stripe_reg_pin(d2 (&RR)[kStripeRegRing])
+{
+    if constexpr (U0 < U1) {
+        constexpr int slot = StripeRegPlanOf<R, S, W>::P.slot[U0];
+        asm volatile("" : "+v"(RR[slot]));
+        stripe_reg_pin<R, S, W, U0 + 1, U1>(RR);
+    }
+}
+// the multiply-adds of stripe_pairs_apply_reg: group GI's requests follow each other round the ring, pair after pair, row blocks ascending
+template <int R, int S, int W, int GI, int P_, int NREAD, int NZ>
+__device__ __forceinline__ void stripe_reg_pairs_apply(const d2 (&RR)[kStripeRegRing], const d2 (&z)[16], double (&a)[R][2])
+{
+    if constexpr (P_ < 8) {
+        constexpr const StripeRegPlan& P = StripeRegPlanOf<R, S, W>::P;
+        constexpr int CI = P.gci[GI], JB = CI / 4, NKO = R - 1 - JB, pos = Stripe<R, S>::T.pair_pos[W][CI][P_];
+        if constexpr (pos >= 0) {
+            constexpr int u0 = P.gbeg[GI] + NREAD, s0 = P.slot[u0];   // (the plan's members in constant expressions only)
+            static_assert(u0 + NKO <= P.gend[GI] && P.unit[u0] == Stripe<R, S>::T.unit[W][pos] && P.thr[u0] < 0, "a pair's requests");
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int k = 0; k < NKO; ++k) {
+                    const d2& l = RR[(s0 + k) % kStripeRegRing];
+#pragma unroll
+                    for (int b = 0; b < 2; ++b) a[JB + 1 + k][b] = fma(h ? l.y : l.x, b ? z[NZ + h].y : z[NZ + h].x, a[JB + 1 + k][b]);
+                }
+            stripe_reg_pairs_apply<R, S, W, GI, P_ + 1, NREAD + NKO, NZ + 2>(RR, z, a);
+        } else {
+            stripe_reg_pairs_apply<R, S, W, GI, P_ + 1, NREAD, NZ>(RR, z, a);
+        }
+    }
+}
+// ... and of stripe_plan_apply: a part's pair p out of the slot of its request
+template <int R, int S, int W, int GI>
+__device__ __forceinline__ void stripe_reg_apply(const d2 (&RR)[kStripeRegRing], const d2 (&z)[16], double (&a)[R][2])
+{
+    constexpr const StripeRegPlan& P = StripeRegPlanOf<R, S, W>::P;
+    constexpr int JB = P.gci[GI] / 4;
+    if constexpr (P.gdiag[GI] != 0) {
+        static_assert(P.gend[GI] - P.gbeg[GI] == 8 && P.pair[P.gbeg[GI]] == 0, "a part's requests");
+        constexpr int s0 = P.slot[P.gbeg[GI]];
+#pragma unroll
+        for (int p = 0; p < 8; ++p) {
+            const d2& l = RR[(s0 + p) % kStripeRegRing];
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int b = 0; b < 2; ++b) a[JB][b] = fma(h ? l.y : l.x, b ? z[2 * p + h].y : z[2 * p + h].x, a[JB][b]);
+        }
+    } else {
+        stripe_reg_pairs_apply<R, S, W, GI, 0, 0, 0>(RR, z, a);
+    }
+}
+// The schedule behind group GI (stripe_plan_ahead's register branch, for every group): GI's requests have landed in their slots, its
+// broadcasts in Z[GI & 1].  Whole sweeps only, like schedule 2.
+template <int R, int S, int W, int GI>
+__device__ __forceinline__ void stripe_reg_ahead(const double* __restrict__ Fw, unsigned xa, unsigned voff, double (&a)[R][2],
+                                                 d2 (&RR)[kStripeRegRing], d2 (&Z)[2][16], int lane)
+{
+    constexpr const StripeRegPlan& P = StripeRegPlanOf<R, S, W>::P;
+    constexpr StripeGroups Q = stripe_groups<R, S, W>();
+    static_assert(Q.n == P.ng && Q.ci[GI] == P.gci[GI] && Q.diag[GI] == P.gdiag[GI], "the plan's groups are the schedule's");
+    if constexpr (GI + 1 < P.ng) {
+        constexpr int N = GI + 1;
+        stripe_group_bcast<R, S, W, N>(Z[N & 1], xa);
+        MCD_SB;
+        stripe_reg_apply<R, S, W, GI>(RR, Z[GI & 1], a);
+        MCD_SB;
+        stripe_reg_issue<R, S, W, P.gpost[GI], P.gpre[N]>(Fw, lane, voff, RR);
+        asm_wait_vmcnt<P.gwait[N]>();
+        stripe_reg_pin<R, S, W, P.gbeg[N], P.gend[N]>(RR);
+        lds_landed<stripe_group_cols<R, S, W, N>()>(Z[N & 1]);
+        stripe_reg_issue<R, S, W, P.gpre[N], P.gpost[N]>(Fw, lane, voff, RR);
+        stripe_reg_ahead<R, S, W, N>(Fw, xa, voff, a, RR, Z, lane);
+    } else {
+        stripe_reg_apply<R, S, W, GI>(RR, Z[GI & 1], a);
+    }
+}
+template <int R, int S, int W>
+__device__ __forceinline__ void stripe_reg_sched(const double* __restrict__ Fw, unsigned xa, unsigned voff, double (&a)[R][2],
+                                                 d2 (&RR)[kStripeRegRing], int lane, int ncols)
+{
+    constexpr const StripeRegPlan& P = StripeRegPlanOf<R, S, W>::P;
+    if (ncols <= 0) {                                      // never taken: it ends the prologue's basic block (stripe_plan_sched)
+        MCD_SB;
+        asm_wait_vmcnt<0>();
+        MCD_SB;
+        return;
+    }
+    d2 Z[2][16];
+    stripe_group_bcast<R, S, W, 0>(Z[0], xa);
+    stripe_reg_issue<R, S, W, P.pro, P.gpre[0]>(Fw, lane, voff, RR);
+    asm_wait_vmcnt<P.gwait[0]>();
+    MCD_T(2);
+    stripe_reg_pin<R, S, W, P.gbeg[0], P.gend[0]>(RR);
+    lds_landed<stripe_group_cols<R, S, W, 0>()>(Z[0]);
+    stripe_reg_issue<R, S, W, P.gpre[0], P.gpost[0]>(Fw, lane, voff, RR);
+    stripe_reg_ahead<R, S, W, 0>(Fw, xa, voff, a, RR, Z, lane);
+}
+template <int R, int S, int W>
+__device__ __forceinline__ void stripe_wave_reg(const double* __restrict__ Fw, d2* lds, const MvnView& M, const double* __restrict__ X, int64_t ldx,
+                                                int64_t b0, int64_t batch, int ncols, double* __restrict__ ll, int lane)
+{
+    using G = StripeReg<R, S>;
+    constexpr const StripeRegPlan& P = StripeRegPlanOf<R, S, W>::P;
+    static_assert(kStripeFinishWave >= 0 && kStripeFinishWave + 2 <= S, "MCD_STRIPE_FINISH_WAVE");
+    constexpr int C = W - kStripeFinishWave;               // the chain this wave finishes, if 0 or 1
+    constexpr bool FIN = C == 0 || C == 1;
+    stripe_u4 cl;
+    if constexpr (FIN) stripe_args_load(cl);
+    double r[R][2], a[R][2];
+    const unsigned voff = 16u * (unsigned)lane, xa = lds_addr(lds + G::EXCH);
+    d2 RR[kStripeRegRing];
+    stripe_prologue_shared<R, S, W, false, P.pro>(xa + voff, M, X, ldx, b0, batch, r, a, lane,
+                                                  [&]() __attribute__((always_inline)) { stripe_reg_issue<R, S, W, 0, P.pro>(Fw, lane, voff, RR); });
+    stripe_reg_sched<R, S, W>(Fw, xa, voff, a, RR, lane, ncols);
+    MCD_T(3);
+    MCD_SB;                                                // (as in stripe_wave: the path that skips the sweep joins here)
+    asm_wait_vmcnt<0>();
+    MCD_SB;
+    double* part = reinterpret_cast<double*>(lds + G::HAND + W * R * 64);
+#pragma unroll
+    for (int k = 0; k < R; ++k)
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+            if (c != C) part[(k * 2 + c) * 64 + lane] = a[k][c];
+    lds_barrier();
+    if constexpr (FIN) {
+        MCD_T(6);
+        stripe_finish_chain<R, S, W, C, G::REGION>(a, lds_addr(lds + G::HAND) + 8u * (unsigned)lane, cl, b0, batch, ll, lane);
+        MCD_T(4);
+    }
+}
+template <int R, int S, int W>
+__device__ __forceinline__ void stripe_dispatch_reg(int wave, const double* __restrict__ Fw, d2* lds, const MvnView& M, const double* __restrict__ X,
+                                                    int64_t ldx, int64_t b0, int64_t batch, int ncols, double* __restrict__ ll, int lane)
+{
+    if (wave == W) {
+        stripe_wave_reg<R, S, W>(Fw, lds, M, X, ldx, b0, batch, ncols, ll, lane);
+    } else {
+        if constexpr (W + 1 < S) stripe_dispatch_reg<R, S, W + 1>(wave, Fw, lds, M, X, ldx, b0, batch, ncols, ll, lane);
     }
 }
 

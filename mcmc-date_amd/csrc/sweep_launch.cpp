@@ -324,6 +324,43 @@ extern "C" int mcd_stripe_finish_selftest_(int R, int ncols)
                               mcd::opt_or(mcd::OPT_STRIPE_FINISH, mcd::kStripeFinishDefault), R, ncols);
 }
 
+// Test hook (tests/test_stripe_regdiag_plan_host.py, tests/test_gpu_stripe_regdiag.py; no device): where such a launch over `batch` chains
+// takes the diagonal parts of the stream from under the options as they stand (stripe_plan.hpp: stripe_diag and stripe_diag_default, the
+// functions launch_stripe calls): 1 register loads (k_logpdf_stripe_reg), 0 the LDS ring.  With MCD_STRIPE_DIAG unset the batch decides.
+extern "C" int mcd_stripe_diag_batch_selftest_(int R, int ncols, long long batch)
+{
+    if (R != 3 && R != 4) return -2;
+    return mcd::stripe_diag(mcd::opt_or(mcd::OPT_STRIPE_PROLOGUE, mcd::kStripePrologueDefault),
+                            mcd::opt_or(mcd::OPT_STRIPE_SCHED, mcd::kStripeSchedDefault),
+                            mcd::opt_or(mcd::OPT_STRIPE_FINISH, mcd::kStripeFinishDefault),
+                            mcd::opt_or(mcd::OPT_STRIPE_DIAG, mcd::stripe_diag_default(batch)), R, ncols);
+}
+// ... and for the headline batch, 512 chains, the largest the stripe kernel takes
+extern "C" int mcd_stripe_diag_selftest_(int R, int ncols) { return mcd_stripe_diag_batch_selftest_(R, ncols, 512); }
+
+// Test hook (tests/test_stripe_regdiag_plan_host.py; no device): the plan of stripe wave w of k_logpdf_stripe_reg with lookahead A
+// (stripe_plan.hpp: stripe_reg_plan; A = 0: the lookahead the library is built with).  head = {requests, groups, leading loads, burst,
+// register slots, lookahead, the zero unit's byte offset}; pos[u] = {slot, base, immediate, lane threshold, zero offset, unit in Fw, pair,
+// group}; lanes (NULL or [requests][64]): every lane's vector offset; grp[g] as mcd_stripe_plan_selftest_.  Returns stripe_reg_plan_check's verdict,
+// -1 for a plan that does not exist, -2 if the arrays are too small.
+extern "C" int mcd_stripe_regplan_selftest_(int R, int S, int w, int A, int* head, int* pos, int cap_pos, int* grp, int cap_grp, unsigned* lanes)
+{
+    if ((R != 3 && R != 4) || (S != 4 && S != 8) || w < 0 || w >= S || A < 0) return -1;
+    const mcd::StripeRegPlan p = mcd::stripe_reg_plan(R, S, w, A ? A : mcd::kStripeRegAhead);
+    if (p.n > cap_pos || p.ng > cap_grp) return -2;
+    head[0] = p.n, head[1] = p.ng, head[2] = p.lead, head[3] = p.pro, head[4] = p.NS, head[5] = p.A, head[6] = mcd::stripe_reg_zero(R);
+    for (int u = 0; u < p.n; ++u) {
+        int* q = pos + 8 * u;
+        q[0] = p.slot[u], q[1] = p.base[u], q[2] = p.imm[u], q[3] = p.thr[u], q[4] = p.zoff[u], q[5] = p.unit[u], q[6] = p.pair[u], q[7] = p.group[u];
+        for (int l = 0; lanes && l < 64; ++l) lanes[64 * u + l] = mcd::stripe_reg_lane_voff(p, u, l);
+    }
+    for (int g = 0; g < p.ng; ++g) {
+        int* q = grp + 7 * g;
+        q[0] = p.gci[g], q[1] = p.gdiag[g], q[2] = p.gbeg[g], q[3] = p.gend[g], q[4] = p.gpre[g], q[5] = p.gwait[g], q[6] = p.gpost[g];
+    }
+    return mcd::stripe_reg_plan_check(p, R, S, w);
+}
+
 // Test hook (tests/test_stripe_plan_host.py; no device): the issue plan of stripe wave w under the register-load schedule with lookahead A
 // (stripe_plan.hpp).  head = {units, groups, leading loads, burst, ring units, register slots}; pos[u] = {kind, slot, base, immediate,
 // unit in Fw, group}; grp[g] = {chunk, diagonal, first position, end, issued at the wait, vmcnt of the wait, issued behind the reads}.

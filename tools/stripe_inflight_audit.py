@@ -28,6 +28,7 @@ LLVM = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin")
 LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mcmc-date_amd", "libmcmcdate_mvn.so")
 STRIPE = "_ZN3mcd15k_logpdf_stripeILi%dELi4ELb1ELi%dE"        # k_logpdf_stripe<R, 4, true, SC>
 STRIPE_FIN = "_ZN3mcd19k_logpdf_stripe_finILi%dELi4EE"        # k_logpdf_stripe_fin<R, 4>
+STRIPE_REG = "_ZN3mcd19k_logpdf_stripe_regILi%dELi4EE"        # k_logpdf_stripe_reg<R, 4>
 
 
 def regs(text):
@@ -139,7 +140,9 @@ def audit(ins, verbose=True):
 def report(lib, prefix, work, verbose=True):
     obj, symbol = code_object(lib, prefix, work)
     out = metadata(obj, symbol)
-    out.update(audit(disassemble(obj, symbol), verbose))
+    ins = disassemble(obj, symbol)
+    out.update(audit(ins, verbose))
+    out["lds_dmas"] = sum(op.startswith("global_load_lds") for _, op, _, _ in ins)   # LDS-DMA instructions in the kernel's text
     out["symbol"] = symbol
     return out
 
