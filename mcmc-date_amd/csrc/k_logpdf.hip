@@ -38,11 +38,9 @@ __global__ void __launch_bounds__(64 * (CW + LW)) k_logpdf(const double* __restr
 }
 
 // The inverse stream (FS = 3; R = 3, 4, up to 512 chains): S stripe waves, two chains per workgroup, every wave a share of Fw of its
-// own (stripe_device.hpp).  The same arguments, preloaded the same way.  SH: x, mu and 1/diag loaded once per workgroup and handed
-// round through LDS (the default), or by every wave for itself (mcd_set_option "MCD_STRIPE_PROLOGUE" = 0; A/B, tests: the same bits).
-// SC (with SH only): the column broadcasts read out of the exchange area and the ring read one group ahead of the multiply-adds (the
-// schedule of "MCD_STRIPE_SCHED" = 1), that schedule with the off-diagonal units loaded straight into registers (2, the default; whole
-// sweeps only, a sweep that stops early runs schedule 1), or round 14's loop (0).  A/B, tests: the same bits.  Four kernels per R, and k_logpdf_stripe_fin below.
+// own (stripe_device.hpp, which describes the forms; stripe_plan.hpp: stripe_form chooses).  The same arguments, preloaded the same way.
+// SH: the shared prologue (the default) or the private one ("MCD_STRIPE_PROLOGUE" = 0); SC (with SH only): schedule 0, 1 or 2
+// ("MCD_STRIPE_SCHED"; 2 is the default, whole sweeps only).  Wave 0 finishes both chains.  A/B, tests: the same bits.  Four kernels per R.
 template <int R, int S, bool SH, int SC>
 __global__ void __launch_bounds__(64 * S) k_logpdf_stripe(const double* __restrict__ Fw, const double* __restrict__ mu,
                                                           const double* __restrict__ invdiag, const double* __restrict__ X, int64_t ldx,
@@ -53,64 +51,65 @@ __global__ void __launch_bounds__(64 * S) k_logpdf_stripe(const double* __restri
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     MCD_T(0);
     const MvnView M(mu, invdiag, n, c, logdet);
-    stripe_dispatch<R, S, 0, SH, SC>(wave, Fw, ring, M, X, ldx, (int64_t)blockIdx.x * 2, batch, ncols, ll, lane);
+    stripe_dispatch<StripeWaveOf<R, S, SH, SC>>(wave, Fw, ring, M, X, ldx, (int64_t)blockIdx.x * 2, batch, ncols, ll, lane);
 }
 
-// Schedule 2 under the shared prologue with a finishing wave per chain (stripe_device.hpp: stripe_wave_fin; "MCD_STRIPE_FINISH" = 0
-// keeps k_logpdf_stripe<R, S, true, 2>; the same bits).  A kernel of its own name: the audit of the generated code finds each by its
-// prefix.  c and logdet are not read here -- the finishing waves fetch them from their place in the arguments (kStripeArgC), which
-// this list fixes: eight 8-byte arguments (n and ncols share one), then ll, c, logdet.
+// Schedule 2 under the shared prologue with a finishing wave per chain, over the form F (stripe_device.hpp: StripeWavePlan): the body
+// of the two kernels below.  c and logdet are not read here -- the finishing waves fetch them from their place in the arguments
+// (kStripeArgC), which the kernels' list fixes: eight 8-byte arguments (n and ncols share one), then ll, c, logdet.
+template <class F>
+__device__ __forceinline__ void stripe_kernel_per_chain(d2* lds, const double* __restrict__ Fw, const double* __restrict__ mu,
+                                                        const double* __restrict__ invdiag, const double* __restrict__ X, int64_t ldx, int64_t batch,
+                                                        int n, int ncols, double* __restrict__ ll)
+{
+    static_assert(kStripeArgC == 8 * 8, "c follows Fw, mu, invdiag, X, ldx, batch, {n, ncols} and ll");
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    MCD_T(0);
+    const MvnView M(mu, invdiag, n, 0.0, 0.0);
+    stripe_dispatch<StripeWavePlan<F, true>>(wave, Fw, lds, M, X, ldx, (int64_t)blockIdx.x * 2, batch, ncols, ll, lane);
+}
+// The diagonal parts through the LDS ring ("MCD_STRIPE_FINISH" = 0 keeps k_logpdf_stripe<R, S, true, 2>; the same bits).  Kernels of
+// their own names: the audit of the generated code finds each by its prefix.
 template <int R, int S>
 __global__ void __launch_bounds__(64 * S) k_logpdf_stripe_fin(const double* __restrict__ Fw, const double* __restrict__ mu,
                                                               const double* __restrict__ invdiag, const double* __restrict__ X, int64_t ldx,
                                                               int64_t batch, int n, int ncols, double* __restrict__ ll, double c, double logdet)
 {
-    static_assert(kStripeArgC == 8 * 8, "c follows Fw, mu, invdiag, X, ldx, batch, {n, ncols} and ll");
-    __shared__ d2 ring[Stripe<R, S>::D3];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    MCD_T(0);
-    const MvnView M(mu, invdiag, n, 0.0, 0.0);
-    stripe_dispatch_fin<R, S, 0>(wave, Fw, ring, M, X, ldx, (int64_t)blockIdx.x * 2, batch, ncols, ll, lane);
+    __shared__ d2 ring[Stripe<R, S>::LDS];
+    stripe_kernel_per_chain<Stripe<R, S>>(ring, Fw, mu, invdiag, X, ldx, batch, n, ncols, ll);
 }
-
-// The per-chain-finish kernel with the diagonal parts by register load too ("MCD_STRIPE_DIAG" = 1; stripe_device.hpp: stripe_wave_reg; the
-// same bits).  No ring: LDS is the exchange area and the hand-over of the partial sums.  The same arguments in the same places.
+// The diagonal parts by register load too ("MCD_STRIPE_DIAG" = 1; the same bits).  No ring: LDS is the exchange area and the hand-over
+// of the partial sums.  The same arguments in the same places.
 template <int R, int S>
 __global__ void __launch_bounds__(64 * S) k_logpdf_stripe_reg(const double* __restrict__ Fw, const double* __restrict__ mu,
                                                               const double* __restrict__ invdiag, const double* __restrict__ X, int64_t ldx,
                                                               int64_t batch, int n, int ncols, double* __restrict__ ll, double c, double logdet)
 {
-    static_assert(kStripeArgC == 8 * 8, "c follows Fw, mu, invdiag, X, ldx, batch, {n, ncols} and ll");
-    __shared__ d2 lds[StripeReg<R, S>::D2];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    MCD_T(0);
-    const MvnView M(mu, invdiag, n, 0.0, 0.0);
-    stripe_dispatch_reg<R, S, 0>(wave, Fw, lds, M, X, ldx, (int64_t)blockIdx.x * 2, batch, ncols, ll, lane);
+    __shared__ d2 lds[StripeReg<R, S>::LDS];
+    stripe_kernel_per_chain<StripeReg<R, S>>(lds, Fw, mu, invdiag, X, ldx, batch, n, ncols, ll);
 }
 
-template <int R, bool SH, int SC>
-static void launch_stripe_sh(const MvnDev& M, const double* X, int64_t ldx, int64_t batch, double* ll, hipStream_t st)
+template <class K>
+static void launch_stripe_kernel(K kernel, const MvnDev& M, const double* X, int64_t ldx, int64_t batch, double* ll, hipStream_t st)
 {
-    hipLaunchKernelGGL((k_logpdf_stripe<R, kStripeWaves, SH, SC>), dim3((unsigned)((batch + 1) / 2)), dim3(64 * kStripeWaves), 0, st, M.Fw, M.mu,
-                       M.invdiag, X, ldx, batch, M.n, M.ncols, ll, M.c, M.logdet);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((batch + 1) / 2)), dim3(64 * kStripeWaves), 0, st, M.Fw, M.mu, M.invdiag, X, ldx, batch, M.n,
+                       M.ncols, ll, M.c, M.logdet);
 }
 template <int R>
 static void launch_stripe(const MvnDev& M, const double* X, int64_t ldx, int64_t batch, double* ll, hipStream_t st)
 {
-    const int pro = opt_or(OPT_STRIPE_PROLOGUE, kStripePrologueDefault), sched = opt_or(OPT_STRIPE_SCHED, kStripeSchedDefault);
-    const int sc = stripe_schedule(pro, sched, R, M.ncols), fin = opt_or(OPT_STRIPE_FINISH, kStripeFinishDefault);
-    if (sc < 0) launch_stripe_sh<R, false, 0>(M, X, ldx, batch, ll, st);
-    else if (stripe_diag(pro, sched, fin, opt_or(OPT_STRIPE_DIAG, stripe_diag_default(batch)), R, M.ncols) != 0)
-        hipLaunchKernelGGL((k_logpdf_stripe_reg<R, kStripeWaves>), dim3((unsigned)((batch + 1) / 2)), dim3(64 * kStripeWaves), 0, st, M.Fw, M.mu,
-                           M.invdiag, X, ldx, batch, M.n, M.ncols, ll, M.c, M.logdet);
-    else if (stripe_finish(pro, sched, fin, R, M.ncols) != 0)
-        hipLaunchKernelGGL((k_logpdf_stripe_fin<R, kStripeWaves>), dim3((unsigned)((batch + 1) / 2)), dim3(64 * kStripeWaves), 0, st, M.Fw, M.mu,
-                           M.invdiag, X, ldx, batch, M.n, M.ncols, ll, M.c, M.logdet);
-    else if (sc == 2) launch_stripe_sh<R, true, 2>(M, X, ldx, batch, ll, st);
-    else if (sc == 1) launch_stripe_sh<R, true, 1>(M, X, ldx, batch, ll, st);
-    else launch_stripe_sh<R, true, 0>(M, X, ldx, batch, ll, st);
+    static_assert(kStripeUnset == MCD_OPT_UNSET, "stripe_form's unset option");
+    constexpr int S = kStripeWaves;
+    switch (stripe_form(opt_get(OPT_STRIPE_PROLOGUE), opt_get(OPT_STRIPE_SCHED), opt_get(OPT_STRIPE_FINISH), opt_get(OPT_STRIPE_DIAG), batch, R,
+                        M.ncols)) {
+    case kStripePrivate0: return launch_stripe_kernel(k_logpdf_stripe<R, S, false, 0>, M, X, ldx, batch, ll, st);
+    case kStripeShared0: return launch_stripe_kernel(k_logpdf_stripe<R, S, true, 0>, M, X, ldx, batch, ll, st);
+    case kStripeShared1: return launch_stripe_kernel(k_logpdf_stripe<R, S, true, 1>, M, X, ldx, batch, ll, st);
+    case kStripeShared2: return launch_stripe_kernel(k_logpdf_stripe<R, S, true, 2>, M, X, ldx, batch, ll, st);
+    case kStripeFin: return launch_stripe_kernel(k_logpdf_stripe_fin<R, S>, M, X, ldx, batch, ll, st);
+    case kStripeReg: return launch_stripe_kernel(k_logpdf_stripe_reg<R, S>, M, X, ldx, batch, ll, st);
+    }
 }
 
 template <int R, int BT, int CW, int LW, int FS>

@@ -277,7 +277,7 @@ int mcd_mvn_create(mcd_mvn_t** out, int n, const double* mu, const double* mat, 
         std::vector<double> Fw;            // ... and W = L^-1 in the same layout: the inverse stream of k_logpdf (FS = 3)
         mcd::pack_inverse_forward(n, h->R, W, Fw);
         // On the device one 1-KiB unit of zeros stands behind the stream: the lanes of a diagonal pair whose entries the stream does not
-        // store read it (k_logpdf_stripe_reg; stripe_plan.hpp: stripe_reg_zero)
+        // store read it (k_logpdf_stripe_reg; stripe_plan.hpp: stripe_zero)
         const size_t zero_at = Fw.size();  // = fc_total_units(R) x 128 doubles
         HIP_TRY(hipMalloc((void**)&h->d_Fw, (zero_at + 128) * sizeof(double)));
         HIP_TRY(hipMemcpy(h->d_Fw, Fw.data(), zero_at * sizeof(double), hipMemcpyHostToDevice));

@@ -43,7 +43,7 @@ enum Option {
     OPT_STRIPE_FINISH,      // schedule 2's kernel only: 1 = each of the workgroup's two chains finished by a wave of its own, c and logdet fetched at
                             // entry; 0 = wave 0 finishes both (round 18's kernel) (A/B, tests; the same bits)
     OPT_STRIPE_DIAG,        // the per-chain-finish kernel only: 1 = the diagonal parts by register load too, no LDS ring (k_logpdf_stripe_reg,
-                            // stripe_plan.hpp: stripe_reg_plan); 0 = through the ring (round 19's kernel); unset = 1 from kStripeDiagFrom chains
+                            // stripe_plan.hpp: stripe_plan); 0 = through the ring (round 19's kernel); unset = 1 from kStripeDiagFrom chains
                             // on, else 0 (A/B, tests; the same bits)
     OPT_COUNT
 };

@@ -2,49 +2,59 @@
 // stripe_device.hpp -- the inverse stream (FS = 3) of the raw-x log-density at R = 3, 4 and up to 512 chains: z = W (x - mu) with
 // W = L^-1 read from Fw (fc_layout.hpp) by S "stripe" waves, no loader waves and no barrier inside the sweep.
 //
-//   * One workgroup serves 2 chains; every stripe wave holds both (r[R][2] and the accumulators a[R][2]) and multiplies only the units
-//     dealt to it (stripe_deal.hpp).  Nothing forces two waves to read the same bytes, so each wave loads its own units by LDS-DMA
-//     into a ring of D units that only it reads: the u-th unit of its list lives at slot u mod D.
-//   * Ordering inside a wave is the wave's own counters.  A wave's LDS-DMAs land in issue order, so once vmcnt is down to the number
-//     of DMAs issued behind unit u, unit u is in LDS; the DMA of unit u + A (A <= D) is issued once the ds_reads of unit u have returned.
-//     The compiler does not know which DMA a ds_read depends on and would wait for all of them, so the ring is read by ds_read_b128
-//     in asm statements, with the waits written out; for the same reason the loads of x, mu and 1/diag, issued before the first
-//     DMA, are asm loads waited for by count.
+// What every form shares
+//   * One workgroup serves 2 chains; every stripe wave holds both (the accumulators a[R][2]) and multiplies only the units dealt to it
+//     (stripe_deal.hpp).  Nothing forces two waves to read the same bytes, so each wave loads its own units, and ordering inside a
+//     wave is the wave's own counters: a wave's loads land in issue order, so once vmcnt is down to the number of loads issued behind
+//     unit u, unit u is there.  The compiler does not know which load a read depends on and would wait for all of them, so the loads
+//     and the reads behind them are asm statements, with the waits written out; for the same reason the loads of x, mu and 1/diag,
+//     issued before the first unit, are asm loads waited for by count.
 //   * Order of additions, fixed: within a wave a row's additions follow the wave's list (chunk after chunk; a chunk's diagonal part
 //     pair by pair, then its off-diagonal pairs, per pair column 2p before 2p + 1, row blocks ascending).  Wave 0's accumulators
-//     start at r_i invdiag_i, the others at 0.  After its last unit each wave w > 0 stores a into its own ring region; one barrier;
-//     wave 0 forms z_i = ((a0 + a1) + a2) + ... in wave order and runs finish_ll.  The bits belong to the S the library is built with
-//     (kStripeWaves): another S deals the units differently.
-//   * Every wave's code is its own instantiation (W is a template parameter): list positions, ring slots, wait counts and the
-//     v_readlane lane selects of the column broadcasts are immediates.
-//   * The waves end on vmcnt(0): nothing of one launch is in flight into LDS when the next one starts.  A sweep that stops early
-//     (ncols < 64 R) has requested up to A units behind the cut; they land in the wave's own ring and are never read.
-//   * The prologue (SH, the default; MCD_STRIPE_PROLOGUE = 0 keeps every wave loading everything for itself): row block k belongs to
-//     wave k mod S, which loads mu_k, 1/diag_k and both chains' x_k in front of its first DMA, forms r = x - mu and t = r invdiag with
-//     the operations of the private prologue and stores both into an exchange area behind the zero units ([r | t][R][64 lanes][2
-//     chains], one 16-byte access per lane for both chains).  One barrier that waits for LDS only -- the DMAs stay in flight across
-//     it -- then every wave reads all of r and wave 0 also t.  The exchange accesses are asm like the ring reads, for the same reason.
-//   * The lookahead A (kStripeAhead <= D, -DMCD_STRIPE_AHEAD): units requested ahead of the unit being read, and the prologue's burst.
-//     Slots stay u mod D.
-//   * The schedule (SC, the default under the shared prologue; MCD_STRIPE_SCHED = 0 keeps the loop above with its v_readlane column
-//     broadcasts, and the private prologue has that loop only).  A wave alone on its SIMD is bound by its own VALU issue, and a wave
-//     body of the loop above spends 404 lane selects beside 322 multiply-adds (R = 4).  r stays in the exchange area for the whole launch, both chains
-//     of a row in one 16-byte slot, so the broadcast of column j is one ds_read_b128 of the same address in every lane -- an LDS
-//     instruction for both chains instead of four v_readlane_b32 -- and the multiply-add takes it as a vector operand: the same value.
-//     And a wave's list is a sequence of GROUPS (a chunk's diagonal part, or the wave's off-diagonal pairs of a chunk: stripe_groups):
-//     the unit reads and broadcasts of group g + 1 go into a second register set and are issued in front of the multiply-adds of group
-//     g: counted vmcnt wait for g + 1's units, the reads of g + 1, the multiply-adds of g, lgkmcnt(0), the DMAs that g + 1's slots now
-//     allow.  A group whose chunk the early stop cuts is neither waited for nor read.  Every addition keeps its operands and its place.
-//     Measured and not kept (profiles/r16_stripe_schedule_ab.txt, docs/experiments/r16_stripe_read_ahead_fill.diff): the read-ahead
-//     without the broadcasts, a fill of the ring behind the operand loads, a burst shorter than the lookahead.
-//   * Schedule 2 (the default for sweeps that do not stop early; MCD_STRIPE_SCHED = 1 keeps the schedule above): since the private
-//     stripes every unit has one reader, the wave that requested it, and an off-diagonal unit needs no lane shift -- lane l's 16 bytes
-//     are the two entries of row l that lane l multiplies.  Those units (three quarters of the stream at R = 4) skip LDS: one
-//     global_load_dwordx4 with a scalar base, 16 l as the vector offset and an immediate brings the unit into a register ring, with no
-//     vector address arithmetic, no M0 write, no ds_read and no lgkmcnt wait.  The diagonal parts keep their LDS-DMAs and ring slots.
-//     Both kinds count on vmcnt in issue order; one constexpr plan per wave (stripe_plan.hpp) holds every position's kind, slot, base
-//     and immediate and every group's wait, and is proved at compile time.  Same operands, same order of additions, same bits.
-//   * The finish per chain (schedule 2 only, the default there; MCD_STRIPE_FINISH = 0 keeps wave 0 finishing both): see stripe_wave_fin.
+//     start at r_i invdiag_i, the others at 0.  After its last unit the waves hand their partial sums over through LDS; one barrier;
+//     z_i = ((a0 + a1) + a2) + ... in wave order, then finish_ll's operations.  Every form below keeps operands and order, so all give
+//     the same bits.  The bits belong to the S the library is built with (kStripeWaves): another S deals the units differently.
+//   * Every wave's code is its own instantiation (W is a template parameter): list positions, slots, wait counts and lane selects
+//     are immediates.  stripe_dispatch sends a wave to its body.
+//   * The waves end on vmcnt(0): nothing of one launch is in flight when the next one starts.
+//   * The lookahead A (kStripeAhead, -DMCD_STRIPE_AHEAD; kStripeRegAhead, -DMCD_STRIPE_REG_AHEAD for the form without a ring): units
+//     requested ahead of the unit being read, and the prologue's burst.
+// The forms (stripe_plan.hpp: stripe_form chooses one per launch from the options and the launch's shape; k_logpdf.hip: launch_stripe)
+//   * The LDS ring (Stripe<R, S>): each wave loads its units by LDS-DMA into a ring of D units that only it reads, the u-th unit of its
+//     list at slot u mod D, and reads them by ds_read_b128; the DMA of unit u + A (A <= D) is issued once the reads of unit u have
+//     returned.  A sweep that stops early (ncols < 64 R) has requested up to A units behind the cut; they land in the wave's own ring
+//     and are never read.
+//   * The prologue.  Private (MCD_STRIPE_PROLOGUE = 0; stripe_prologue_private): every wave loads x, mu and 1/diag for itself.  Shared
+//     (the default; stripe_prologue_shared): row block k belongs to wave k mod S, which loads mu_k, 1/diag_k and both chains' x_k in
+//     front of its first unit, forms r = x - mu and t = r invdiag with the operations of the private prologue and stores both into an
+//     exchange area ([r | t][R][64 lanes][2 chains], one 16-byte access per lane for both chains).  One barrier that waits for LDS only
+//     -- the loads stay in flight across it -- then every wave reads what it needs of r and wave 0 also t.
+//   * Schedule 0 (MCD_STRIPE_SCHED = 0, and the private prologue's only one; stripe_chunks): chunk after chunk, wait, read, request,
+//     multiply, the column broadcasts by v_readlane.
+//   * Schedule 1 (MCD_STRIPE_SCHED = 1, and every sweep that stops early; stripe_sched, stripe_ahead).  A wave alone on its SIMD is
+//     bound by its own VALU issue, and a wave body of schedule 0 spends 404 lane selects beside 322 multiply-adds (R = 4).  r stays in
+//     the exchange area for the whole launch, both chains of a row in one 16-byte slot, so the broadcast of column j is one
+//     ds_read_b128 of the same address in every lane and the multiply-add takes it as a vector operand: the same value.  And the unit
+//     reads and broadcasts of group g + 1 (stripe_plan.hpp: stripe_groups) go into a second register set and are issued in front of the
+//     multiply-adds of group g.  A group whose chunk the early stop cuts is neither waited for nor read.
+//   * Schedule 2 (the default; whole sweeps only; StripeWavePlan over stripe_plan_sched, stripe_plan_ahead).  Every unit has one
+//     reader, the wave that requested it, and an off-diagonal unit needs no lane shift -- lane l's 16 bytes are the two entries of row
+//     l that lane l multiplies.  Those units (three quarters of the stream at R = 4) skip LDS: one global_load_dwordx4 with a scalar
+//     base, 16 l as the vector offset and an immediate brings the unit into a register ring, with no vector address arithmetic, no M0
+//     write, no ds_read and no lgkmcnt wait.  Both kinds of request count on vmcnt in issue order; one constexpr plan per wave
+//     (stripe_plan.hpp) holds every request's kind, slot, base and immediate and every group's wait, and is proved at compile time.
+//     The wave body is written once over a FORM, which supplies the plan and the LDS layout:
+//       - Stripe<R, S>: the diagonal parts keep their LDS-DMAs, ring slots and lane-shifted reads (k_logpdf_stripe<R, S, true, 2>,
+//         k_logpdf_stripe_fin);
+//       - StripeReg<R, S> (MCD_STRIPE_DIAG = 1, the default from kStripeDiagFrom chains on; k_logpdf_stripe_reg): the diagonal parts by
+//         register load too, see there.
+//   * The finish.  Wave 0 finishes both chains (MCD_STRIPE_FINISH = 0, and every form but schedule 2's), or each chain is finished by
+//     a wave of its own (schedule 2's default; stripe_finish_chain).  Wave 0's finish stands in both wave bodies, StripeWavePlan and
+//     StripeWaveLoop, word for word: as a function of its own it changed the generated code of the eight k_logpdf_stripe kernels.
+// Measured and not kept (profiles/r16_stripe_schedule_ab.txt, docs/experiments/r16_stripe_read_ahead_fill.diff): the read-ahead
+// without the broadcasts, a fill of the ring behind the operand loads, a burst shorter than the lookahead.
+#include <type_traits>
+
 #include "mvn_device.hpp"
 #include "stripe_deal.hpp"
 #include "stripe_plan.hpp"
@@ -63,8 +73,10 @@ constexpr int kStripeWaves = MCD_STRIPE_WAVES;
 #endif
 constexpr int kStripeAhead = MCD_STRIPE_AHEAD;
 
-template <int R, int S>
+// The ring's layout, and as a form of schedule 2's wave body: the diagonal parts through the ring
+template <int R_, int S_>
 struct Stripe {
+    static constexpr int R = R_, S = S_;
     static_assert((R == 3 || R == 4) && (S == 4 || S == 8), "stripe kernel: R = 3, 4; S = 4, 8");
     // ring units per wave: S D KiB + the waves' zero units within 160 KiB, and x loads + D DMAs within the 6 bits of vmcnt
     static constexpr int D = 128 / S;
@@ -78,6 +90,10 @@ struct Stripe {
     // leading loads in front of the DMAs: 4 R (private prologue, wave 0), 4 per row block owned (shared)
     static_assert(4 * R + D < 64, "vmcnt");
     static constexpr StripeDeal T = stripe_deal(R, S);
+    static constexpr bool RING = true;                    // the form: an LDS ring and zero units; the plan's lookahead and register slots;
+    static constexpr int AHEAD = A, NS = kStripeRegSlots;
+    static constexpr int HAND = 0, REGION = D * 1024;     // the hand-over of the partial sums in the waves' ring regions (d2 index; bytes)
+    static constexpr int LDS = D3;
 };
 
 // LDS byte address of a pointer into the ring
@@ -120,24 +136,86 @@ __device__ __forceinline__ void asm_load8(double& v, const double* p)
     asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(v) : "v"(p) : "memory");
 }
 
-// the DMAs of list positions [U0, U1); my: the LDS byte address of the wave's ring (an integer: a pointer converted back from the
-// generic address space would carry a null check into every M0 write)
+// the DMA of unit UNIT of Fw into slot SLOT of the wave's ring; my: the ring's LDS byte address (an integer: a pointer converted back
+// from the generic address space would carry a null check into every M0 write)
+template <int UNIT, int SLOT>
+__device__ __forceinline__ void stripe_dma(const double* __restrict__ Fw, unsigned my, int lane)
+{
+#if defined(__HIP_DEVICE_COMPILE__)                       // (an LDS pointer is 32 bits wide on the device only)
+    const __attribute__((address_space(1))) d2* src =
+        (const __attribute__((address_space(1))) d2*)reinterpret_cast<const d2*>(Fw) + ((size_t)UNIT * 64 + lane);
+    __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)(my + SLOT * 1024u), 16, 0, 0);
+#endif
+}
+// ... of list positions [U0, U1)
 template <int R, int S, int W, int U0, int U1>
 __device__ __forceinline__ void stripe_issue(const double* __restrict__ Fw, unsigned my, int lane)
 {
     if constexpr (U0 < U1) {
-#if defined(__HIP_DEVICE_COMPILE__)                       // (an LDS pointer is 32 bits wide on the device only)
-        constexpr int g = Stripe<R, S>::T.unit[W][U0];
-        const __attribute__((address_space(1))) d2* src =
-            (const __attribute__((address_space(1))) d2*)reinterpret_cast<const d2*>(Fw) + ((size_t)g * 64 + lane);
-        __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)(my + (U0 % Stripe<R, S>::D) * 1024u), 16, 0, 0);
-#endif
+        stripe_dma<Stripe<R, S>::T.unit[W][U0], U0 % Stripe<R, S>::D>(Fw, my, lane);
         stripe_issue<R, S, W, U0 + 1, U1>(Fw, my, lane);
     }
 }
 
-constexpr int stripe_min(int a, int b) { return a < b ? a : b; }
-constexpr int stripe_max(int a, int b) { return a > b ? a : b; }
+// The groups of wave W (stripe_plan.hpp), the group of its off-diagonal pairs of chunk CI (-1: none), the list position behind the last
+// of those pairs (-1) and their units
+template <int R, int S, int W>
+constexpr StripeGroups stripe_groups()
+{
+    return stripe_groups(Stripe<R, S>::T, R, W);
+}
+template <int R, int S, int W, int CI>
+constexpr int stripe_pairs_group()
+{
+    constexpr StripeGroups Q = stripe_groups<R, S, W>();
+    for (int g = 0; g < Q.n; ++g)
+        if (Q.ci[g] == CI && Q.diag[g] == 0) return g;
+    return -1;
+}
+template <int R, int S, int W, int CI>
+constexpr int stripe_pairs_end()
+{
+    constexpr int g = stripe_pairs_group<R, S, W, CI>();
+    return g < 0 ? -1 : stripe_groups<R, S, W>().end[g < 0 ? 0 : g];
+}
+template <int R, int S, int W, int CI>
+constexpr int stripe_pairs_units()
+{
+    constexpr int g = stripe_pairs_group<R, S, W, CI>();
+    return g < 0 ? 0 : stripe_groups<R, S, W>().end[g < 0 ? 0 : g] - stripe_groups<R, S, W>().beg[g < 0 ? 0 : g];
+}
+// registers a group's reads fill, and the columns it multiplies (two per pair)
+template <int R, int S, int W, int GI>
+constexpr int stripe_group_regs()
+{
+    constexpr StripeGroups Q = stripe_groups<R, S, W>();
+    return Q.diag[GI] != 0 ? 8 : Q.end[GI] - Q.beg[GI];
+}
+template <int R, int S, int W, int GI>
+constexpr int stripe_group_cols()
+{
+    constexpr StripeGroups Q = stripe_groups<R, S, W>();
+    return Q.diag[GI] != 0 ? 16 : 2 * (Q.end[GI] - Q.beg[GI]) / (R - 1 - Q.ci[GI] / 4);
+}
+
+// The LDS addresses of the eight column pairs of a diagonal part in the ring, chunk LC of its block, the part's first unit at list
+// position DPOS: pair p's lanes 2 pl + 1 .. 63 lie back to back in the part, the others read the wave's zero unit.  la, za: the ring's
+// and the zero unit's LDS byte address + 16 lane.  PIN: every address is formed where this stands.
+template <int R, int S, int LC, int DPOS, bool PIN>
+__device__ __forceinline__ void stripe_diag_addrs(unsigned (&ad)[8], unsigned la, unsigned za, int lane)
+{
+    constexpr int D = Stripe<R, S>::D;
+    static_assert(fc_diag_units(R, LC) <= D, "a group within the ring");
+    constexpr bool WRAP = DPOS % D + fc_diag_units(R, LC) > D;
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {
+        const int pl = LC * 8 + p;
+        int i = (DPOS % D) * 64 + fc_diag_start(R, LC, p) - (2 * pl + 1) + lane;
+        if (WRAP) i = i >= D * 64 ? i - D * 64 : i;
+        ad[p] = lane > 2 * pl ? la - 16u * (unsigned)lane + 16u * (unsigned)i : za;
+        if constexpr (PIN) asm volatile("" : "+v"(ad[p]));   // (formed here: hoisted to the kernel's top the 32 addresses of a wave cost it its registers)
+    }
+}
 
 // off-diagonal pairs P .. 7 of chunk CI that wave W owns: reads of all of them first, then the multiply-adds
 template <int R, int S, int W, int CI, int P, int NREAD>
@@ -178,27 +256,11 @@ __device__ __forceinline__ void stripe_pairs_apply(const d2 (&l)[8 * 3], const d
         }
     }
 }
-// the list position behind the last of wave W's off-diagonal pairs of chunk CI (-1: none), and their units
-template <int R, int S, int W, int CI>
-constexpr int stripe_pairs_end()
-{
-    int e = -1;
-    for (int p = 0; p < 8; ++p)
-        if (Stripe<R, S>::T.pair_pos[W][CI][p] >= 0) e = Stripe<R, S>::T.pair_pos[W][CI][p] + (R - 1 - CI / 4);
-    return e;
-}
-template <int R, int S, int W, int CI>
-constexpr int stripe_pairs_units()
-{
-    int n = 0;
-    for (int p = 0; p < 8; ++p)
-        if (Stripe<R, S>::T.pair_pos[W][CI][p] >= 0) n += R - 1 - CI / 4;
-    return n;
-}
 
-// Chunk CI and the ones behind it.  ISSUED: DMAs issued so far (list positions 0 .. ISSUED - 1); every wait leaves the DMAs behind the
-// last unit it needs in flight, and every group of reads is followed by the DMAs up to A units behind it.  (A lookahead shorter than
-// a group: the rest of the group is requested in front of its wait; everything before the group has been read, so its slots are free.)
+// Schedule 0.  Chunk CI and the ones behind it.  ISSUED: DMAs issued so far (list positions 0 .. ISSUED - 1); every wait leaves the DMAs
+// behind the last unit it needs in flight, and every group of reads is followed by the DMAs up to A units behind it.  (A lookahead
+// shorter than a group: the rest of the group is requested in front of its wait; everything before the group has been read, so its
+// slots are free.)
 template <int R, int S, int W, int CI, int ISSUED>
 __device__ __forceinline__ void stripe_chunks(const double* __restrict__ Fw, unsigned my, unsigned la, unsigned za, const double (&r)[R][2],
                                               double (&a)[R][2], int lane, int ncols)
@@ -212,18 +274,9 @@ __device__ __forceinline__ void stripe_chunks(const double* __restrict__ Fw, uns
         constexpr int issued0 = stripe_max(ISSUED, dend);
         constexpr int issued1 = dpos >= 0 ? stripe_max(issued0, stripe_min(NU, dend + A)) : ISSUED;
         if constexpr (dpos >= 0) {
-            static_assert(fc_diag_units(R, LC) <= D, "a group within the ring");
-            // the diagonal part: pair p's lanes 2 pl + 1 .. 63 lie back to back in the part, the others read the wave's zero unit
-            constexpr bool WRAP = dpos % D + fc_diag_units(R, LC) > D;
             d2 l[8];
             unsigned ad[8];
-#pragma unroll
-            for (int p = 0; p < 8; ++p) {
-                const int pl = LC * 8 + p;
-                int i = (dpos % D) * 64 + fc_diag_start(R, LC, p) - (2 * pl + 1) + lane;
-                if (WRAP) i = i >= D * 64 ? i - D * 64 : i;
-                ad[p] = lane > 2 * pl ? la - 16u * (unsigned)lane + 16u * (unsigned)i : za;
-            }
+            stripe_diag_addrs<R, S, LC, dpos, false>(ad, la, za, lane);
             stripe_issue<R, S, W, ISSUED, issued0>(Fw, my, lane);
             asm_wait_vmcnt<issued0 - dend>();
             if constexpr (CI == 0) MCD_T(2);
@@ -257,65 +310,19 @@ __device__ __forceinline__ void stripe_chunks(const double* __restrict__ Fw, uns
     }
 }
 
-// The schedule's groups of wave W, in list order: a chunk's diagonal part (diag) or the wave's off-diagonal pairs of the chunk; end:
-// the list position behind the group's last unit
-struct StripeGroups {
-    int n;
-    int ci[32], diag[32], end[32];
-};
-template <int R, int S, int W>
-constexpr StripeGroups stripe_groups()
-{
-    StripeGroups q{};
-    for (int ci = 0; ci < fc_nchunk(R); ++ci) {
-        const int dpos = Stripe<R, S>::T.diag_pos[W][ci];
-        if (dpos >= 0) {
-            q.ci[q.n] = ci;
-            q.diag[q.n] = 1;
-            q.end[q.n++] = dpos + fc_diag_units(R, ci % 4);
-        }
-        int pend = -1;
-        for (int p = 0; p < 8; ++p)
-            if (Stripe<R, S>::T.pair_pos[W][ci][p] >= 0) pend = Stripe<R, S>::T.pair_pos[W][ci][p] + (R - 1 - ci / 4);
-        if (pend >= 0) {
-            q.ci[q.n] = ci;
-            q.diag[q.n] = 0;
-            q.end[q.n++] = pend;
-        }
-    }
-    return q;
-}
-// registers a group's reads fill
-template <int R, int S, int W, int GI>
-constexpr int stripe_group_regs()
-{
-    constexpr StripeGroups Q = stripe_groups<R, S, W>();
-    if constexpr (Q.diag[GI] != 0) return 8;
-    else return stripe_pairs_units<R, S, W, Q.ci[GI]>();
-}
-// the ds_reads of group GI's units (stripe_chunks' addresses and offsets)
+// Schedule 1.  The ds_reads of group GI's units (stripe_chunks' addresses and offsets)
 template <int R, int S, int W, int GI>
 __device__ __forceinline__ void stripe_group_read(d2 (&l)[8 * 3], unsigned la, unsigned za, int lane)
 {
     constexpr StripeGroups Q = stripe_groups<R, S, W>();
-    constexpr int CI = Q.ci[GI], D = Stripe<R, S>::D, LC = CI % 4;
-    static_assert(stripe_group_regs<R, S, W, GI>() <= D, "a group within the ring");
+    static_assert(stripe_group_regs<R, S, W, GI>() <= Stripe<R, S>::D, "a group within the ring");
     if constexpr (Q.diag[GI] != 0) {
-        constexpr int dpos = Stripe<R, S>::T.diag_pos[W][CI];
-        static_assert(fc_diag_units(R, LC) <= D, "a group within the ring");
-        constexpr bool WRAP = dpos % D + fc_diag_units(R, LC) > D;
         unsigned ad[8];
-#pragma unroll
-        for (int p = 0; p < 8; ++p) {
-            const int pl = LC * 8 + p;
-            int i = (dpos % D) * 64 + fc_diag_start(R, LC, p) - (2 * pl + 1) + lane;
-            if (WRAP) i = i >= D * 64 ? i - D * 64 : i;
-            ad[p] = lane > 2 * pl ? la - 16u * (unsigned)lane + 16u * (unsigned)i : za;
-        }
+        stripe_diag_addrs<R, S, Q.ci[GI] % 4, Q.beg[GI], false>(ad, la, za, lane);
 #pragma unroll
         for (int p = 0; p < 8; ++p) lds_read16<0>(l[p], ad[p]);
     } else {
-        stripe_pairs_read<R, S, W, CI, 0, 0>(l, la);
+        stripe_pairs_read<R, S, W, Q.ci[GI], 0, 0>(l, la);
     }
 }
 // The column broadcasts of a group out of the exchange area instead of v_readlane: both chains' r of one column in one 16-byte read,
@@ -362,16 +369,6 @@ __device__ __forceinline__ void stripe_diag_bcast(d2 (&z)[16], unsigned xa)
         lds_read16<(ROW + C) * 16>(z[C], xa);
         stripe_diag_bcast<ROW, C + 1>(z, xa);
     }
-}
-template <int R, int S, int W, int GI>
-constexpr int stripe_group_cols()
-{
-    constexpr StripeGroups Q = stripe_groups<R, S, W>();
-    if (Q.diag[GI] != 0) return 16;
-    int n = 0;
-    for (int p = 0; p < 8; ++p)
-        if (Stripe<R, S>::T.pair_pos[W][Q.ci[GI]][p] >= 0) n += 2;
-    return n;
 }
 template <int R, int S, int W, int GI>
 __device__ __forceinline__ void stripe_group_bcast(d2 (&z)[16], unsigned xa)
@@ -457,15 +454,35 @@ __device__ __forceinline__ void stripe_sched(const double* __restrict__ Fw, unsi
     }
 }
 
-// ---- SC = 2: the off-diagonal units by register load (stripe_plan.hpp) ----
-// The wave's plan, proved at compile time
-template <int R, int S, int W>
-struct StripePlanOf {
-    static constexpr StripePlan P = stripe_plan(R, S, W, Stripe<R, S>::A);
-    static_assert(stripe_plan_check(P, R, S, W) == 0, "stripe plan: waits, outstanding operations, slot reuse, immediates");
-    static_assert(P.D == Stripe<R, S>::D && P.pro == stripe_min(Stripe<R, S>::A, Stripe<R, S>::T.n[W]), "stripe plan: the ring and the burst");
+// ---- schedule 2: the wave body over a form F (Stripe<R, S> above, StripeReg<R, S> below) and the plan the form asks for ----
+// StripeReg: every unit by register load (MCD_STRIPE_DIAG = 1: k_logpdf_stripe_reg).  Through the ring a diagonal part goes global -> LDS
+// -> register, only to be shifted by a lane offset: per part 7, 5, 3 or 1 LDS-DMAs (each with a vector address add, an M0 write and a
+// literal move), eight ds_read_b128 whose addresses take three VALU instructions each, and an lgkmcnt(0) in front of the group's
+// multiply-adds.  A per-lane load address says the same shift: pair pl of a part is one global_load_dwordx4 whose lanes l > 2 pl read
+// base + imm + 16 l (stripe_plan.hpp, proved against fc_diag_start at compile time), and whose lanes l <= 2 pl -- zeros the stream does
+// not store -- read a unit of zeros behind the stream (mvn_capi.cpp).  They are not skipped: the multiply-adds stay the same operations
+// on every lane, so 0 x inf is still NaN.  One v_cmp and one v_cndmask per pair choose between 16 l and the pair's constant offset to the
+// zero unit.  Every group is a register group.  No ring, no zero units in LDS: LDS holds the exchange area and, behind it, the
+// hand-over of the partial sums ([w][k][c][lane], 8 bytes, as under the ring).
+template <int R_, int S_>
+struct StripeReg {
+    static constexpr int R = R_, S = S_;
+    static constexpr bool RING = false;
+    static constexpr int AHEAD = kStripeRegAhead, NS = kStripeRegRing;
+    static constexpr int EXCH = 0;                        // the exchange area [r | t][R][64] (d2 index)
+    static constexpr int HAND = 2 * R * 64;               // the hand-over: R x 64 d2 (= [R][2][64] doubles) per wave
+    static constexpr int REGION = R * 1024;               // ... in bytes
+    static constexpr int LDS = HAND + S * R * 64;         // 24 KiB at R = 4, S = 4
+    static_assert(stripe_plans_cover(R, S, kStripeRegAhead, true), "stripe register plan: every off-diagonal unit and every (part, pair) once");
 };
-// One unit into a register slot: lane l's 16 bytes at base + 16 l + IMM.  Outside the compiler's bookkeeping like asm_load8: the
+// The wave's plan, proved at compile time
+template <class F, int W>
+struct StripePlanOf {
+    static constexpr StripePlan P = stripe_plan(F::R, F::S, W, F::AHEAD, !F::RING);
+    static_assert(stripe_plan_check(P, F::R, F::S, W) == 0, "stripe plan: waits, outstanding operations, slot reuse, immediates, lane addresses");
+    static_assert(P.NS == F::NS && (F::RING ? P.D == Stripe<F::R, F::S>::D && P.n == Stripe<F::R, F::S>::T.n[W] : P.D == 0), "stripe plan: the rings");
+};
+// One request into a register slot: lane l's 16 bytes at base + voff + IMM.  Outside the compiler's bookkeeping like asm_load8: the
 // covering vmcnt wait and stripe_regs_pin() before the first use.
 template <int IMM>
 __device__ __forceinline__ void stripe_load_reg(d2& v, unsigned voff, const char* base /* wave-uniform */)
@@ -473,134 +490,142 @@ __device__ __forceinline__ void stripe_load_reg(d2& v, unsigned voff, const char
     static_assert(IMM >= -4096 && IMM <= 4095, "global offset");
     asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=&v"(v) : "v"(voff), "s"(base), "n"(IMM) : "memory");
 }
-// list positions [U0, U1) of the plan, each by its kind; voff = 16 lane
-template <int R, int S, int W, int U0, int U1>
-__device__ __forceinline__ void stripe_issue_plan(const double* __restrict__ Fw, unsigned my, int lane, unsigned voff, d2 (&RR)[kStripeRegSlots])
+// requests [U0, U1) of the plan, each by its kind; voff = 16 lane
+template <class F, int W, int U0, int U1>
+__device__ __forceinline__ void stripe_issue_plan(const double* __restrict__ Fw, unsigned my, int lane, unsigned voff, d2 (&RR)[F::NS])
 {
     if constexpr (U0 < U1) {
-        constexpr const StripePlan& P = StripePlanOf<R, S, W>::P;
-        if constexpr (P.kind[U0] == 0) stripe_issue<R, S, W, U0, U0 + 1>(Fw, my, lane);
-        else {
-            constexpr int slot = P.slot[U0], base = P.base[U0];
+        constexpr const StripePlan& P = StripePlanOf<F, W>::P;
+        constexpr int slot = P.slot[U0], base = P.base[U0];
+        if constexpr (P.kind[U0] == 0) {
+            stripe_dma<P.unit[U0], slot>(Fw, my, lane);
+        } else if constexpr (P.thr[U0] < 0) {
             stripe_load_reg<P.imm[U0]>(RR[slot], voff, reinterpret_cast<const char*>(Fw) + base);
+        } else {
+            constexpr int thr = P.thr[U0];
+            constexpr unsigned zoff = (unsigned)P.zoff[U0];
+            unsigned v = lane > thr ? voff : zoff;         // (stripe_plan.hpp: stripe_lane_voff, which the plan's check evaluates)
+            asm volatile("" : "+v"(v));                    // (formed here, like stripe_diag_addrs' addresses)
+            stripe_load_reg<P.imm[U0]>(RR[slot], v, reinterpret_cast<const char*>(Fw) + base);
         }
-        stripe_issue_plan<R, S, W, U0 + 1, U1>(Fw, my, lane, voff, RR);
+        stripe_issue_plan<F, W, U0 + 1, U1>(Fw, my, lane, voff, RR);
     }
 }
-// behind the covering wait: the registers of positions [U0, U1) are the loaded values from here on
-template <int R, int S, int W, int U0, int U1>
-__device__ __forceinline__ void stripe_regs_pin(d2 (&RR)[kStripeRegSlots])
+// behind the covering wait: the registers of requests [U0, U1) are the loaded values from here on
+template <class F, int W, int U0, int U1>
+__device__ __forceinline__ void stripe_regs_pin(d2 (&RR)[F::NS])
 {
     if constexpr (U0 < U1) {
-        constexpr int slot = StripePlanOf<R, S, W>::P.slot[U0];
+        constexpr int slot = StripePlanOf<F, W>::P.slot[U0];
         asm volatile("" : "+v"(RR[slot]));
-        stripe_regs_pin<R, S, W, U0 + 1, U1>(RR);
+        stripe_regs_pin<F, W, U0 + 1, U1>(RR);
     }
 }
-// the ds_reads of a diagonal part (stripe_group_read's addresses)
-template <int R, int S, int W, int GI>
+// the ds_reads of a diagonal part that came through the ring (stripe_group_read's addresses)
+template <class F, int W, int GI>
 __device__ __forceinline__ void stripe_diag_read(d2 (&l)[8], unsigned la, unsigned za, int lane)
 {
-    constexpr const StripePlan& P = StripePlanOf<R, S, W>::P;
-    constexpr int D = Stripe<R, S>::D, LC = P.gci[GI] % 4, dpos = P.gbeg[GI];
-    static_assert(dpos == Stripe<R, S>::T.diag_pos[W][P.gci[GI]] && fc_diag_units(R, LC) <= D, "a group within the ring");
-    constexpr bool WRAP = dpos % D + fc_diag_units(R, LC) > D;
+    constexpr const StripePlan& P = StripePlanOf<F, W>::P;
+    constexpr int dpos = Stripe<F::R, F::S>::T.diag_pos[W][P.gci[GI]];
+    static_assert(dpos >= 0 && P.slot[P.gbeg[GI]] == dpos % Stripe<F::R, F::S>::D, "the part's ring slots");
     unsigned ad[8];
-#pragma unroll
-    for (int p = 0; p < 8; ++p) {
-        const int pl = LC * 8 + p;
-        int i = (dpos % D) * 64 + fc_diag_start(R, LC, p) - (2 * pl + 1) + lane;
-        if (WRAP) i = i >= D * 64 ? i - D * 64 : i;
-        ad[p] = lane > 2 * pl ? la - 16u * (unsigned)lane + 16u * (unsigned)i : za;
-        asm volatile("" : "+v"(ad[p]));                    // (formed here: hoisted to the kernel's top the 32 addresses of a wave cost it its registers)
-    }
+    stripe_diag_addrs<F::R, F::S, P.gci[GI] % 4, dpos, true>(ad, la, za, lane);
 #pragma unroll
     for (int p = 0; p < 8; ++p) lds_read16<0>(l[p], ad[p]);
 }
-// the multiply-adds of stripe_pairs_apply_bcast, the units out of their register slots
-template <int R, int S, int W, int CI, int P, int NZ>
-__device__ __forceinline__ void stripe_pairs_apply_reg(const d2 (&RR)[kStripeRegSlots], const d2 (&z)[16], double (&a)[R][2])
+// the multiply-adds of stripe_pairs_apply_bcast, the units out of their register slots: group GI's requests follow each other round the
+// register ring, pair after pair, row blocks ascending
+template <class F, int W, int GI, int P_, int NREAD, int NZ>
+__device__ __forceinline__ void stripe_pairs_apply_reg(const d2 (&RR)[F::NS], const d2 (&z)[16], double (&a)[F::R][2])
 {
-    if constexpr (P < 8) {
-        constexpr int JB = CI / 4, NKO = R - 1 - JB, pos = Stripe<R, S>::T.pair_pos[W][CI][P];
+    if constexpr (P_ < 8) {
+        constexpr const StripePlan& P = StripePlanOf<F, W>::P;
+        constexpr int CI = P.gci[GI], JB = CI / 4, NKO = F::R - 1 - JB, pos = Stripe<F::R, F::S>::T.pair_pos[W][CI][P_];
         if constexpr (pos >= 0) {
-            constexpr int s0 = StripePlanOf<R, S, W>::P.slot[pos];   // (a group's register slots follow each other round the ring)
-            static_assert(StripePlanOf<R, S, W>::P.slot[pos + NKO - 1] == (s0 + NKO - 1) % kStripeRegSlots, "a pair's slots");
+            constexpr int u0 = P.gbeg[GI] + NREAD, s0 = P.slot[u0];   // (the plan's members in constant expressions only)
+            static_assert(u0 + NKO <= P.gend[GI] && P.unit[u0] == Stripe<F::R, F::S>::T.unit[W][pos] && P.thr[u0] < 0, "a pair's requests");
+            static_assert(P.slot[u0 + NKO - 1] == (s0 + NKO - 1) % F::NS, "a pair's slots");
 #pragma unroll
             for (int h = 0; h < 2; ++h)
 #pragma unroll
                 for (int k = 0; k < NKO; ++k) {
-                    const d2& l = RR[(s0 + k) % kStripeRegSlots];
+                    const d2& l = RR[(s0 + k) % F::NS];
 #pragma unroll
                     for (int b = 0; b < 2; ++b) a[JB + 1 + k][b] = fma(h ? l.y : l.x, b ? z[NZ + h].y : z[NZ + h].x, a[JB + 1 + k][b]);
                 }
-            stripe_pairs_apply_reg<R, S, W, CI, P + 1, NZ + 2>(RR, z, a);
+            stripe_pairs_apply_reg<F, W, GI, P_ + 1, NREAD + NKO, NZ + 2>(RR, z, a);
         } else {
-            stripe_pairs_apply_reg<R, S, W, CI, P + 1, NZ>(RR, z, a);
+            stripe_pairs_apply_reg<F, W, GI, P_ + 1, NREAD, NZ>(RR, z, a);
         }
     }
 }
-template <int R, int S, int W, int GI>
-__device__ __forceinline__ void stripe_plan_apply(const d2 (&RR)[kStripeRegSlots], const d2 (&l)[8], const d2 (&z)[16], double (&a)[R][2])
+// ... and of stripe_group_apply: a part's pair p out of l (the ring) or out of the slot of its request
+template <class F, int W, int GI>
+__device__ __forceinline__ void stripe_plan_apply(const d2 (&RR)[F::NS], const d2 (&l)[8], const d2 (&z)[16], double (&a)[F::R][2])
 {
-    constexpr const StripePlan& P = StripePlanOf<R, S, W>::P;
-    constexpr int CI = P.gci[GI], JB = CI / 4;
+    constexpr const StripePlan& P = StripePlanOf<F, W>::P;
+    constexpr int JB = P.gci[GI] / 4, s0 = P.slot[P.gbeg[GI]];
     if constexpr (P.gdiag[GI] != 0) {
+        constexpr bool DMA = P.kind[P.gbeg[GI]] == 0;
+        static_assert(DMA || (P.gend[GI] - P.gbeg[GI] == 8 && P.pair[P.gbeg[GI]] == 0), "a part's requests");
 #pragma unroll
-        for (int p = 0; p < 8; ++p)
+        for (int p = 0; p < 8; ++p) {
+            const d2& v = DMA ? l[p] : RR[(s0 + p) % F::NS];
 #pragma unroll
             for (int h = 0; h < 2; ++h)
 #pragma unroll
-                for (int b = 0; b < 2; ++b) a[JB][b] = fma(h ? l[p].y : l[p].x, b ? z[2 * p + h].y : z[2 * p + h].x, a[JB][b]);
+                for (int b = 0; b < 2; ++b) a[JB][b] = fma(h ? v.y : v.x, b ? z[2 * p + h].y : z[2 * p + h].x, a[JB][b]);
+        }
     } else {
-        stripe_pairs_apply_reg<R, S, W, CI, 0, 0>(RR, z, a);
+        stripe_pairs_apply_reg<F, W, GI, 0, 0, 0>(RR, z, a);
     }
 }
-// The schedule behind group GI (stripe_ahead's, every count out of the plan): group GI's units are in L[GI & 1] (a diagonal part) or
-// in their register slots, its broadcasts in Z[GI & 1].  Then group GI + 1's broadcasts; a diagonal part's wait and LDS reads; the
+// The schedule behind group GI (stripe_ahead's, every count out of the plan): group GI's units are in L[GI & 1] (a part out of the ring) or
+// in their register slots, its broadcasts in Z[GI & 1].  Then group GI + 1's broadcasts; an LDS-DMA group's wait and LDS reads; the
 // multiply-adds of GI; a register group's wait, which needs no instruction in front of the multiply-adds; lgkmcnt(0); the requests up
-// to A units behind GI + 1, into the slots GI and the groups before it have left.
-// There is no early stop: this schedule runs whole sweeps only (stripe_plan.hpp: stripe_schedule; the others run schedule 1).
+// to A behind GI + 1, into the slots GI and the groups before it have left.  (A plan without LDS-DMA groups has no L.)
+// There is no early stop: this schedule runs whole sweeps only (stripe_plan.hpp: stripe_form; the others run schedule 1).
 // With the stop's branches every cut leaves register loads in flight into registers the compiler holds dead, and the generated code
 // kept ring registers alive across the cuts' tails until it spilled them, loads in flight included.
-template <int R, int S, int W, int GI>
-__device__ __forceinline__ void stripe_plan_ahead(const double* __restrict__ Fw, unsigned my, unsigned xa, unsigned voff, double (&a)[R][2],
-                                                  d2 (&RR)[kStripeRegSlots], d2 (&L)[2][8], d2 (&Z)[2][16], unsigned la, unsigned za, int lane)
+template <class F, int W, int GI>
+__device__ __forceinline__ void stripe_plan_ahead(const double* __restrict__ Fw, unsigned my, unsigned xa, unsigned voff, double (&a)[F::R][2],
+                                                  d2 (&RR)[F::NS], d2 (&L)[2][8], d2 (&Z)[2][16], unsigned la, unsigned za, int lane)
 {
-    constexpr const StripePlan& P = StripePlanOf<R, S, W>::P;   // (its members in constant expressions only: read at run time they are loads)
-    constexpr StripeGroups Q = stripe_groups<R, S, W>();
-    static_assert(Q.n == P.ng && Q.ci[GI] == P.gci[GI] && Q.diag[GI] == P.gdiag[GI] && Q.end[GI] == P.gend[GI], "the plan's groups are the schedule's");
+    constexpr int R = F::R, S = F::S;
+    constexpr const StripePlan& P = StripePlanOf<F, W>::P;   // (its members in constant expressions only: read at run time they are loads)
     if constexpr (GI + 1 < P.ng) {
         constexpr int N = GI + 1;
+        constexpr bool DMA = P.kind[P.gbeg[N]] == 0;
         stripe_group_bcast<R, S, W, N>(Z[N & 1], xa);
-        if constexpr (P.gdiag[N] != 0) {
-            stripe_issue_plan<R, S, W, P.gpost[GI], P.gpre[N]>(Fw, my, lane, voff, RR);
+        if constexpr (DMA) {
+            stripe_issue_plan<F, W, P.gpost[GI], P.gpre[N]>(Fw, my, lane, voff, RR);
             asm_wait_vmcnt<P.gwait[N]>();
-            stripe_diag_read<R, S, W, N>(L[N & 1], la, za, lane);
+            stripe_diag_read<F, W, N>(L[N & 1], la, za, lane);
         }
         MCD_SB;
-        stripe_plan_apply<R, S, W, GI>(RR, L[GI & 1], Z[GI & 1], a);
+        stripe_plan_apply<F, W, GI>(RR, L[GI & 1], Z[GI & 1], a);
         MCD_SB;
-        if constexpr (P.gdiag[N] != 0) {
+        if constexpr (DMA) {
             lds_landed<8>(L[N & 1]);
         } else {
-            stripe_issue_plan<R, S, W, P.gpost[GI], P.gpre[N]>(Fw, my, lane, voff, RR);
+            stripe_issue_plan<F, W, P.gpost[GI], P.gpre[N]>(Fw, my, lane, voff, RR);
             asm_wait_vmcnt<P.gwait[N]>();
-            stripe_regs_pin<R, S, W, P.gbeg[N], P.gend[N]>(RR);
+            stripe_regs_pin<F, W, P.gbeg[N], P.gend[N]>(RR);
         }
         lds_landed<stripe_group_cols<R, S, W, N>()>(Z[N & 1]);
-        stripe_issue_plan<R, S, W, P.gpre[N], P.gpost[N]>(Fw, my, lane, voff, RR);
-        stripe_plan_ahead<R, S, W, N>(Fw, my, xa, voff, a, RR, L, Z, la, za, lane);
+        stripe_issue_plan<F, W, P.gpre[N], P.gpost[N]>(Fw, my, lane, voff, RR);
+        stripe_plan_ahead<F, W, N>(Fw, my, xa, voff, a, RR, L, Z, la, za, lane);
     } else {
-        stripe_plan_apply<R, S, W, GI>(RR, L[GI & 1], Z[GI & 1], a);
+        stripe_plan_apply<F, W, GI>(RR, L[GI & 1], Z[GI & 1], a);
     }
 }
 // ... and its head
-template <int R, int S, int W>
-__device__ __forceinline__ void stripe_plan_sched(const double* __restrict__ Fw, unsigned my, unsigned xa, unsigned voff, double (&a)[R][2],
-                                                  d2 (&RR)[kStripeRegSlots], unsigned la, unsigned za, int lane, int ncols)
+template <class F, int W>
+__device__ __forceinline__ void stripe_plan_sched(const double* __restrict__ Fw, unsigned my, unsigned xa, unsigned voff, double (&a)[F::R][2],
+                                                  d2 (&RR)[F::NS], unsigned la, unsigned za, int lane, int ncols)
 {
-    constexpr const StripePlan& P = StripePlanOf<R, S, W>::P;
+    constexpr int R = F::R, S = F::S;
+    constexpr const StripePlan& P = StripePlanOf<F, W>::P;
     // Never taken (stripe_sched_whole).  The branch ends the prologue's basic block: as one block with the sweep, the compiler's
     // scheduling ran the kernel out of its 256 registers and copied ring registers with loads in flight (tools/stripe_inflight_audit.py).
     // The prologue's register loads are out here and nothing on this path reads them, so they are waited for before the path joins
@@ -613,19 +638,20 @@ __device__ __forceinline__ void stripe_plan_sched(const double* __restrict__ Fw,
     }
     d2 L[2][8], Z[2][16];
     stripe_group_bcast<R, S, W, 0>(Z[0], xa);
-    stripe_issue_plan<R, S, W, P.pro, P.gpre[0]>(Fw, my, lane, voff, RR);
+    stripe_issue_plan<F, W, P.pro, P.gpre[0]>(Fw, my, lane, voff, RR);
     asm_wait_vmcnt<P.gwait[0]>();
     MCD_T(2);
-    if constexpr (P.gdiag[0] != 0) {
-        stripe_diag_read<R, S, W, 0>(L[0], la, za, lane);
+    if constexpr (P.kind[P.gbeg[0]] == 0) {
+        stripe_diag_read<F, W, 0>(L[0], la, za, lane);
         lds_landed<8>(L[0]);
     } else {
-        stripe_regs_pin<R, S, W, P.gbeg[0], P.gend[0]>(RR);
+        stripe_regs_pin<F, W, P.gbeg[0], P.gend[0]>(RR);
     }
     lds_landed<stripe_group_cols<R, S, W, 0>()>(Z[0]);
-    stripe_issue_plan<R, S, W, P.gpre[0], P.gpost[0]>(Fw, my, lane, voff, RR);
-    stripe_plan_ahead<R, S, W, 0>(Fw, my, xa, voff, a, RR, L, Z, la, za, lane);
+    stripe_issue_plan<F, W, P.gpre[0], P.gpost[0]>(Fw, my, lane, voff, RR);
+    stripe_plan_ahead<F, W, 0>(Fw, my, xa, voff, a, RR, L, Z, la, za, lane);
 }
+
 // The private prologue: x, mu and (wave 0) 1/diag of both chains in front of the first DMA: a padded row or a chain beyond the batch
 // reads a clamped address and the value is dropped for mu (load_rawx)
 template <int R, int S, int W>
@@ -701,14 +727,12 @@ __device__ __forceinline__ void stripe_exchange_get(d2 (&e)[R], unsigned ea)
 
 // The shared prologue: the same loads, selection and operations, but only for the row blocks k = W, W + S, ... < R this wave owns
 // (four loads each); r and t = r invdiag go through the exchange area, one LDS-only barrier, every wave reads r and wave 0 t.
-// GETR = false (the schedule, which broadcasts r out of the exchange area): r is not read back into registers.
+// GETR = false (schedules 1 and 2, which broadcast r out of the exchange area): r is not read back into registers.
 // burst(): the wave's first PRO requests (and whatever else the schedule wants done while the loads are out).
-template <int R, int S, int W, bool GETR = true, int BURST = -1, class Burst>
+template <int R, int S, int W, bool GETR, int PRO, class Burst>
 __device__ __forceinline__ void stripe_prologue_shared(unsigned ea, const MvnView& M, const double* __restrict__ X, int64_t ldx, int64_t b0,
                                                        int64_t batch, double (&r)[R][2], double (&a)[R][2], int lane, Burst burst)
 {
-    using G = Stripe<R, S>;
-    constexpr int PRO = BURST >= 0 ? BURST : stripe_min(G::A, G::T.n[W]);   // (BURST: a kernel whose burst is not the ring plan's)
     constexpr int NO = W < R ? (R - W + S - 1) / S : 0;    // row blocks owned
     double xr[NO + 1][2], m[NO + 1], iv[NO + 1];
 #pragma unroll
@@ -724,12 +748,12 @@ __device__ __forceinline__ void stripe_prologue_shared(unsigned ea, const MvnVie
         }
     }
     burst();
-    asm_wait_vmcnt<PRO>();                                 // the loads in front of the DMAs have returned
+    asm_wait_vmcnt<PRO>();                                 // the loads in front of the burst have returned
 #pragma unroll
     for (int i = 0; i < NO; ++i) asm volatile("" : "+v"(m[i]), "+v"(iv[i]), "+v"(xr[i][0]), "+v"(xr[i][1]));
     MCD_T(1);
     stripe_exchange_put<R, S, W, 0, NO>(xr, m, iv, ea, M.n, b0, batch, lane);
-    lds_barrier();                                         // (lgkmcnt only: the DMAs stay in flight)
+    lds_barrier();                                         // (lgkmcnt only: the loads stay in flight)
     d2 e[R], et[R];
     if constexpr (GETR) stripe_exchange_get<R, 0, 0>(e, ea);
     if constexpr (W == 0) stripe_exchange_get<R, 1, 0>(et, ea);
@@ -746,68 +770,13 @@ __device__ __forceinline__ void stripe_prologue_shared(unsigned ea, const MvnVie
     MCD_T(5);
 }
 
-template <int R, int S, int W, bool SH, int SC>
-__device__ __forceinline__ void stripe_wave(const double* __restrict__ Fw, d2* ring, const MvnView& M, const double* __restrict__ X, int64_t ldx,
-                                            int64_t b0, int64_t batch, int ncols, double* __restrict__ ll, int lane)
-{
-    using G = Stripe<R, S>;
-    static_assert(SH || SC == 0, "the schedule goes with the shared prologue");
-    static_assert(SC >= 0 && SC <= 2, "MCD_STRIPE_SCHED");
-    constexpr int D = G::D, NU = G::T.n[W], PRO = stripe_min(G::A, NU);
-    d2* my = ring + W * D * 64;
-    d2* zu = ring + G::ZERO + W * 64;
-    zu[lane] = d2{0.0, 0.0};
-    const unsigned mya = lds_addr(my);
-    double r[R][2], a[R][2];
-    if constexpr (SC == 2) {
-        const unsigned voff = 16u * (unsigned)lane, la = mya + voff, za = lds_addr(zu) + voff;
-        d2 RR[kStripeRegSlots];
-        stripe_prologue_shared<R, S, W, false>(lds_addr(ring + G::EXCH) + voff, M, X, ldx, b0, batch, r, a, lane,
-                                               [&]() __attribute__((always_inline)) { stripe_issue_plan<R, S, W, 0, PRO>(Fw, mya, lane, voff, RR); });
-        stripe_plan_sched<R, S, W>(Fw, mya, lds_addr(ring + G::EXCH), voff, a, RR, la, za, lane, ncols);
-    } else {
-        if constexpr (SH)
-            stripe_prologue_shared<R, S, W, SC == 0>(lds_addr(ring + G::EXCH) + 16u * (unsigned)lane, M, X, ldx, b0, batch, r, a, lane,
-                                                     [&]() __attribute__((always_inline)) { stripe_issue<R, S, W, 0, PRO>(Fw, mya, lane); });
-        else stripe_prologue_private<R, S, W>(Fw, mya, M, X, ldx, b0, batch, r, a, lane);
-        const unsigned la = mya + 16u * (unsigned)lane;
-        const unsigned za = lds_addr(zu) + 16u * (unsigned)lane;
-        if constexpr (SC != 0) stripe_sched<R, S, W, PRO>(Fw, mya, la, za, lds_addr(ring + G::EXCH), a, lane, ncols);
-        else stripe_chunks<R, S, W, 0, PRO>(Fw, mya, la, za, r, a, lane, ncols);
-    }
-    MCD_T(3);
-    if constexpr (SC == 2) MCD_SB;                         // (nothing of the hand-over moves in front of the wait: the path that skips the
-    asm_wait_vmcnt<0>();                                   //  sweep joins here, and the audit of the generated code follows every path)
-    if constexpr (SC == 2) MCD_SB;
-    double* part = reinterpret_cast<double*>(my);
-    if constexpr (W > 0) {
-#pragma unroll
-        for (int k = 0; k < R; ++k)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) part[(k * 2 + c) * 64 + lane] = a[k][c];
-    }
-    lds_barrier();
-    if constexpr (W == 0) {
-#pragma unroll
-        for (int w = 1; w < S; ++w) {
-            const double* pw = reinterpret_cast<const double*>(ring + w * D * 64);
-#pragma unroll
-            for (int k = 0; k < R; ++k)
-#pragma unroll
-                for (int c = 0; c < 2; ++c) a[k][c] = a[k][c] + pw[(k * 2 + c) * 64 + lane];
-        }
-        finish_ll<R, 2>(a, M, b0, batch, ll, lane);
-        MCD_T(4);
-    }
-}
-
-// ---- the per-chain finish (MCD_STRIPE_FINISH = 1, the default; schedule 2 with the shared prologue only: k_logpdf_stripe_fin) ----
-// Behind the hand-over barrier wave 0 used to form z for both chains and run finish_ll<R, 2>, chain 0 to its store before chain 1's
-// reduction began, while three waves idled.  Here wave kStripeFinishWave + c finishes chain c: z_k = ((a0_k + a1_k) + a2_k) + a3_k in
+// ---- the finish per chain (MCD_STRIPE_FINISH = 1, the default; schedule 2 only: k_logpdf_stripe_fin, k_logpdf_stripe_reg) ----
+// Behind the hand-over barrier wave 0 alone forms z for both chains and runs finish_ll<R, 2>, chain 0 to its store before chain 1's
+// reduction begins, while three waves idle.  Here wave kStripeFinishWave + c finishes chain c: z_k = ((a0_k + a1_k) + a2_k) + a3_k in
 // wave order, its own partial out of its registers; s = fma(z_k, z_k, s), k ascending; wave_sum; ll = c + (-0.5)(logdet + q) -- the
-// operations of finish_ll for that chain in its order, so the bits are the old finish's.  One barrier as before, reached by every
+// operations of finish_ll for that chain in its order, so the bits are that finish's.  One barrier as there, reached by every
 // wave on every path.
-//   * The hand-over keeps the 8-byte layout [w][k][c][lane] in the waves' ring regions.  A finishing wave wants one chain only: a
+//   * The hand-over keeps the 8-byte layout [w][k][c][lane] in the waves' regions.  A finishing wave wants one chain only: a
 //     ds_read_b64 at 8 lane + const covers all 64 banks once per 32 lanes (2 LDS cycles, no conflict).  With {c0, c1} in 16-byte slots
 //     it would read twice the bytes into twice the registers (ds_read_b128: 4 cycles) to drop half, and one ds_write_b128 moves its
 //     operands no faster than the two ds_write_b64 it replaces (13 cycles against 2 x 6).
@@ -844,17 +813,17 @@ __device__ __forceinline__ void lds_read8(double& v, unsigned addr)
     asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
 }
 // REGION: bytes from one wave's partials to the next wave's
-template <int R, int S, int W, int C, int I, int REGION = Stripe<R, S>::D * 1024>
+template <int R, int S, int W, int C, int I, int REGION>
 __device__ __forceinline__ void stripe_finish_get(double (&p)[S][R], unsigned pa)
 {
     if constexpr (I < S * R) {
         constexpr int w = I / R, k = I % R;
-        if constexpr (w != W) lds_read8<(k * 2 + C) * 512>(p[w][k], pa + (unsigned)(w * REGION));   // (a region is 32 KiB: past the offset field)
+        if constexpr (w != W) lds_read8<(k * 2 + C) * 512>(p[w][k], pa + (unsigned)(w * REGION));   // (a region may be 32 KiB: past the offset field)
         stripe_finish_get<R, S, W, C, I + 1, REGION>(p, pa);
     }
 }
-// chain C of the workgroup, by wave W: pa = the ring's LDS byte address + 8 lane; cl = c and logdet in flight
-template <int R, int S, int W, int C, int REGION = Stripe<R, S>::D * 1024>
+// chain C of the workgroup, by wave W: pa = the hand-over's LDS byte address + 8 lane; cl = c and logdet in flight
+template <int R, int S, int W, int C, int REGION>
 __device__ __forceinline__ void stripe_finish_chain(const double (&a)[R][2], unsigned pa, stripe_u4& cl, int64_t b0, int64_t batch,
                                                     double* __restrict__ ll, int lane)
 {
@@ -881,252 +850,139 @@ __device__ __forceinline__ void stripe_finish_chain(const double (&a)[R][2], uns
     if (lane == 0 && b0 + C < batch) ll[b0 + C] = c + (-0.5) * (logdet + q);   // (finish_ll's line)
 }
 
-template <int R, int S, int W>
-__device__ __forceinline__ void stripe_wave_fin(const double* __restrict__ Fw, d2* ring, const MvnView& M, const double* __restrict__ X, int64_t ldx,
-                                                int64_t b0, int64_t batch, int ncols, double* __restrict__ ll, int lane)
+// The wave bodies, as types for stripe_dispatch: wave W of the workgroup runs Body::run<W>.
+// Schedule 2's wave over the form F.  PER_CHAIN: wave kStripeFinishWave + c finishes chain c; otherwise wave 0 finishes both.
+// lds: the kernel's LDS, F::LDS d2.  The wave's hand-over region is, under the ring form, its ring.
+template <class F, bool PER_CHAIN>
+struct StripeWavePlan {
+static constexpr int S = F::S;
+template <int W>
+static __device__ __forceinline__ void run(const double* __restrict__ Fw, d2* lds, const MvnView& M, const double* __restrict__ X, int64_t ldx,
+                                           int64_t b0, int64_t batch, int ncols, double* __restrict__ ll, int lane)
 {
-    using G = Stripe<R, S>;
+    constexpr int R = F::R;
+    constexpr const StripePlan& P = StripePlanOf<F, W>::P;
     static_assert(kStripeFinishWave >= 0 && kStripeFinishWave + 2 <= S, "MCD_STRIPE_FINISH_WAVE");
-    constexpr int D = G::D, NU = G::T.n[W], PRO = stripe_min(G::A, NU);
-    constexpr int C = W - kStripeFinishWave;               // the chain this wave finishes, if 0 or 1
+    constexpr int C = PER_CHAIN ? W - kStripeFinishWave : -1;   // the chain this wave finishes, if 0 or 1
     constexpr bool FIN = C == 0 || C == 1;
     stripe_u4 cl;
     if constexpr (FIN) stripe_args_load(cl);
-    d2* my = ring + W * D * 64;
-    d2* zu = ring + G::ZERO + W * 64;
-    zu[lane] = d2{0.0, 0.0};
-    const unsigned mya = lds_addr(my);
+    d2* my = lds + F::HAND + W * (F::REGION / 16);
+    const unsigned voff = 16u * (unsigned)lane, xa = lds_addr(lds + F::EXCH);
+    unsigned mya = 0, la = 0, za = 0;
+    if constexpr (F::RING) {
+        d2* zu = lds + F::ZERO + W * 64;
+        zu[lane] = d2{0.0, 0.0};
+        mya = lds_addr(my), la = mya + voff, za = lds_addr(zu) + voff;
+    }
     double r[R][2], a[R][2];
-    const unsigned voff = 16u * (unsigned)lane, la = mya + voff, za = lds_addr(zu) + voff;
-    d2 RR[kStripeRegSlots];
-    stripe_prologue_shared<R, S, W, false>(lds_addr(ring + G::EXCH) + voff, M, X, ldx, b0, batch, r, a, lane,
-                                           [&]() __attribute__((always_inline)) { stripe_issue_plan<R, S, W, 0, PRO>(Fw, mya, lane, voff, RR); });
-    stripe_plan_sched<R, S, W>(Fw, mya, lds_addr(ring + G::EXCH), voff, a, RR, la, za, lane, ncols);
+    d2 RR[F::NS];
+    stripe_prologue_shared<R, S, W, false, P.pro>(xa + voff, M, X, ldx, b0, batch, r, a, lane,
+                                                  [&]() __attribute__((always_inline)) { stripe_issue_plan<F, W, 0, P.pro>(Fw, mya, lane, voff, RR); });
+    stripe_plan_sched<F, W>(Fw, mya, xa, voff, a, RR, la, za, lane, ncols);
     MCD_T(3);
-    MCD_SB;                                                // (as in stripe_wave: the path that skips the sweep joins here)
-    asm_wait_vmcnt<0>();
+    MCD_SB;                                                // (nothing of the hand-over moves in front of the wait: the path that skips the
+    asm_wait_vmcnt<0>();                                   //  sweep joins here, and the audit of the generated code follows every path)
     MCD_SB;
     double* part = reinterpret_cast<double*>(my);
+    if constexpr (PER_CHAIN) {
 #pragma unroll
-    for (int k = 0; k < R; ++k)
+        for (int k = 0; k < R; ++k)
 #pragma unroll
-        for (int c = 0; c < 2; ++c)
-            if (c != C) part[(k * 2 + c) * 64 + lane] = a[k][c];
-    lds_barrier();
-    if constexpr (FIN) {
-        MCD_T(6);
-        stripe_finish_chain<R, S, W, C>(a, lds_addr(ring) + 8u * (unsigned)lane, cl, b0, batch, ll, lane);
-        MCD_T(4);
+            for (int c = 0; c < 2; ++c)
+                if (c != C) part[(k * 2 + c) * 64 + lane] = a[k][c];
+        lds_barrier();
+        if constexpr (FIN) {
+            MCD_T(6);
+            stripe_finish_chain<R, S, W, C, F::REGION>(a, lds_addr(lds + F::HAND) + 8u * (unsigned)lane, cl, b0, batch, ll, lane);
+            MCD_T(4);
+        }
+    } else {
+        if constexpr (W > 0) {
+#pragma unroll
+            for (int k = 0; k < R; ++k)
+#pragma unroll
+                for (int c = 0; c < 2; ++c) part[(k * 2 + c) * 64 + lane] = a[k][c];
+        }
+        lds_barrier();
+        if constexpr (W == 0) {
+#pragma unroll
+            for (int w = 1; w < S; ++w) {
+                const double* pw = reinterpret_cast<const double*>(lds + w * Stripe<R, S>::D * 64);
+#pragma unroll
+                for (int k = 0; k < R; ++k)
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) a[k][c] = a[k][c] + pw[(k * 2 + c) * 64 + lane];
+            }
+            finish_ll<R, 2>(a, M, b0, batch, ll, lane);
+            MCD_T(4);
+        }
     }
 }
-template <int R, int S, int W>
-__device__ __forceinline__ void stripe_dispatch_fin(int wave, const double* __restrict__ Fw, d2* ring, const MvnView& M, const double* __restrict__ X,
-                                                    int64_t ldx, int64_t b0, int64_t batch, int ncols, double* __restrict__ ll, int lane)
+};
+// Schedules 0 and 1, under the private (SH = false, schedule 0 only) or the shared prologue
+template <int R, int S_, bool SH, int SC>
+struct StripeWaveLoop {
+static constexpr int S = S_;
+static_assert(SH || SC == 0, "the schedule goes with the shared prologue");
+static_assert(SC == 0 || SC == 1, "MCD_STRIPE_SCHED");
+template <int W>
+static __device__ __forceinline__ void run(const double* __restrict__ Fw, d2* ring, const MvnView& M, const double* __restrict__ X, int64_t ldx,
+                                           int64_t b0, int64_t batch, int ncols, double* __restrict__ ll, int lane)
 {
-    if (wave == W) {
-        stripe_wave_fin<R, S, W>(Fw, ring, M, X, ldx, b0, batch, ncols, ll, lane);
-    } else {
-        if constexpr (W + 1 < S) stripe_dispatch_fin<R, S, W + 1>(wave, Fw, ring, M, X, ldx, b0, batch, ncols, ll, lane);
+    using G = Stripe<R, S>;
+    {
+        constexpr int D = G::D, NU = G::T.n[W], PRO = stripe_min(G::A, NU);
+        d2* my = ring + W * D * 64;
+        d2* zu = ring + G::ZERO + W * 64;
+        zu[lane] = d2{0.0, 0.0};
+        const unsigned mya = lds_addr(my);
+        double r[R][2], a[R][2];
+        if constexpr (SH)
+            stripe_prologue_shared<R, S, W, SC == 0, PRO>(lds_addr(ring + G::EXCH) + 16u * (unsigned)lane, M, X, ldx, b0, batch, r, a, lane,
+                                                          [&]() __attribute__((always_inline)) { stripe_issue<R, S, W, 0, PRO>(Fw, mya, lane); });
+        else stripe_prologue_private<R, S, W>(Fw, mya, M, X, ldx, b0, batch, r, a, lane);
+        const unsigned la = mya + 16u * (unsigned)lane;
+        const unsigned za = lds_addr(zu) + 16u * (unsigned)lane;
+        if constexpr (SC != 0) stripe_sched<R, S, W, PRO>(Fw, mya, la, za, lds_addr(ring + G::EXCH), a, lane, ncols);
+        else stripe_chunks<R, S, W, 0, PRO>(Fw, mya, la, za, r, a, lane, ncols);
+        MCD_T(3);
+        asm_wait_vmcnt<0>();
+        double* part = reinterpret_cast<double*>(my);
+        if constexpr (W > 0) {
+#pragma unroll
+            for (int k = 0; k < R; ++k)
+#pragma unroll
+                for (int c = 0; c < 2; ++c) part[(k * 2 + c) * 64 + lane] = a[k][c];
+        }
+        lds_barrier();
+        if constexpr (W == 0) {
+#pragma unroll
+            for (int w = 1; w < S; ++w) {
+                const double* pw = reinterpret_cast<const double*>(ring + w * Stripe<R, S>::D * 64);
+#pragma unroll
+                for (int k = 0; k < R; ++k)
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) a[k][c] = a[k][c] + pw[(k * 2 + c) * 64 + lane];
+            }
+            finish_ll<R, 2>(a, M, b0, batch, ll, lane);
+            MCD_T(4);
+        }
     }
 }
 
-template <int R, int S, int W, bool SH, int SC>
-__device__ __forceinline__ void stripe_dispatch(int wave, const double* __restrict__ Fw, d2* ring, const MvnView& M, const double* __restrict__ X,
+};
+// the wave body of k_logpdf_stripe<R, S, SH, SC>
+template <int R, int S, bool SH, int SC>
+using StripeWaveOf = std::conditional_t<SC == 2, StripeWavePlan<Stripe<R, S>, false>, StripeWaveLoop<R, S, SH, SC>>;
+template <class Body, int W = 0>
+__device__ __forceinline__ void stripe_dispatch(int wave, const double* __restrict__ Fw, d2* lds, const MvnView& M, const double* __restrict__ X,
                                                 int64_t ldx, int64_t b0, int64_t batch, int ncols, double* __restrict__ ll, int lane)
 {
     if (wave == W) {
-        stripe_wave<R, S, W, SH, SC>(Fw, ring, M, X, ldx, b0, batch, ncols, ll, lane);
+        Body::template run<W>(Fw, lds, M, X, ldx, b0, batch, ncols, ll, lane);
     } else {
-        if constexpr (W + 1 < S) stripe_dispatch<R, S, W + 1, SH, SC>(wave, Fw, ring, M, X, ldx, b0, batch, ncols, ll, lane);
-    }
-}
-
-// ---- every unit by register load (MCD_STRIPE_DIAG = 1: k_logpdf_stripe_reg; the shared prologue, schedule 2's groups, the per-chain finish) ----
-// Under schedule 2 a diagonal part still went global -> LDS -> register, only to be shifted by a lane offset: per part 7, 5, 3 or 1
-// LDS-DMAs (each with a vector address add, an M0 write and a literal move), eight ds_read_b128 whose addresses take three VALU
-// instructions each, and an lgkmcnt(0) in front of the group's multiply-adds.  A per-lane load address says the same shift: pair pl of
-// a part is one global_load_dwordx4 whose lanes l > 2 pl read base + imm + 16 l (stripe_plan.hpp: stripe_reg_plan, proved against
-// fc_diag_start at compile time), and whose lanes l <= 2 pl -- zeros the stream does not store -- read a unit of zeros behind the stream
-// (mvn_capi.cpp).  They are not skipped: the multiply-adds stay the same operations on every lane, so 0 x inf is still NaN.  One
-// v_cmp and one v_cndmask per pair choose between 16 l and the pair's constant offset to the zero unit.
-// Every group is a register group: broadcasts of g + 1, the multiply-adds of g out of the register ring, the requests g + 1 still
-// lacks, its counted wait, the requests up to the lookahead behind it.  No ring, no zero units in LDS, no L[2][8]: LDS holds the
-// exchange area and, behind it, the hand-over of the partial sums ([w][k][c][lane], 8 bytes, as under the ring).
-// Same operands, same order of additions, same bits.
-template <int R, int S>
-struct StripeReg {
-    static constexpr int EXCH = 0;                        // the exchange area [r | t][R][64] (d2 index)
-    static constexpr int HAND = 2 * R * 64;               // the hand-over: R x 64 d2 (= [R][2][64] doubles) per wave
-    static constexpr int REGION = R * 1024;               // ... in bytes
-    static constexpr int D2 = HAND + S * R * 64;          // 24 KiB at R = 4, S = 4
-    static_assert(stripe_reg_plans_cover(R, S, kStripeRegAhead), "stripe register plan: every off-diagonal unit and every (part, pair) once");
-};
-template <int R, int S, int W>
-struct StripeRegPlanOf {
-    static constexpr StripeRegPlan P = stripe_reg_plan(R, S, W, kStripeRegAhead);
-    static_assert(stripe_reg_plan_check(P, R, S, W) == 0, "stripe register plan: waits, outstanding operations, slot reuse, immediates, lane addresses");
-};
-// requests [U0, U1) of the plan; voff = 16 lane
-template <int R, int S, int W, int U0, int U1>
-__device__ __forceinline__ void stripe_reg_issue(const double* __restrict__ Fw, int lane, unsigned voff, d2 (&RR)[kStripeRegRing])
-{
-    if constexpr (U0 < U1) {
-        constexpr const StripeRegPlan& P = StripeRegPlanOf<R, S, W>::P;
-        constexpr int slot = P.slot[U0], base = P.base[U0];
-        if constexpr (P.thr[U0] < 0) {
-            stripe_load_reg<P.imm[U0]>(RR[slot], voff, reinterpret_cast<const char*>(Fw) + base);
-        } else {
-            constexpr int thr = P.thr[U0];
-            constexpr unsigned zoff = (unsigned)P.zoff[U0];
-            unsigned v = lane > thr ? voff : zoff;         // (stripe_plan.hpp: stripe_reg_lane_voff, which the plan's check evaluates)
-            asm volatile("" : "+v"(v));                    // (formed here, like stripe_diag_read's addresses)
-            stripe_load_reg<P.imm[U0]>(RR[slot], v, reinterpret_cast<const char*>(Fw) + base);
-        }
-        stripe_reg_issue<R, S, W, U0 + 1, U1>(Fw, lane, voff, RR);
-    }
-}
-template <int R, int S, int W, int U0, int U1>
-__device__ __forceinline__ void stripe_reg_pin(d2 (&RR)[kStripeRegRing])
-{
-    if constexpr (U0 < U1) {
-        constexpr int slot = StripeRegPlanOf<R, S, W>::P.slot[U0];
-        asm volatile("" : "+v"(RR[slot]));
-        stripe_reg_pin<R, S, W, U0 + 1, U1>(RR);
-    }
-}
-// the multiply-adds of stripe_pairs_apply_reg: group GI's requests follow each other round the ring, pair after pair, row blocks ascending
-template <int R, int S, int W, int GI, int P_, int NREAD, int NZ>
-__device__ __forceinline__ void stripe_reg_pairs_apply(const d2 (&RR)[kStripeRegRing], const d2 (&z)[16], double (&a)[R][2])
-{
-    if constexpr (P_ < 8) {
-        constexpr const StripeRegPlan& P = StripeRegPlanOf<R, S, W>::P;
-        constexpr int CI = P.gci[GI], JB = CI / 4, NKO = R - 1 - JB, pos = Stripe<R, S>::T.pair_pos[W][CI][P_];
-        if constexpr (pos >= 0) {
-            constexpr int u0 = P.gbeg[GI] + NREAD, s0 = P.slot[u0];   // (the plan's members in constant expressions only)
-            static_assert(u0 + NKO <= P.gend[GI] && P.unit[u0] == Stripe<R, S>::T.unit[W][pos] && P.thr[u0] < 0, "a pair's requests");
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int k = 0; k < NKO; ++k) {
-                    const d2& l = RR[(s0 + k) % kStripeRegRing];
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) a[JB + 1 + k][b] = fma(h ? l.y : l.x, b ? z[NZ + h].y : z[NZ + h].x, a[JB + 1 + k][b]);
-                }
-            stripe_reg_pairs_apply<R, S, W, GI, P_ + 1, NREAD + NKO, NZ + 2>(RR, z, a);
-        } else {
-            stripe_reg_pairs_apply<R, S, W, GI, P_ + 1, NREAD, NZ>(RR, z, a);
-        }
-    }
-}
-// ... and of stripe_plan_apply: a part's pair p out of the slot of its request
-template <int R, int S, int W, int GI>
-__device__ __forceinline__ void stripe_reg_apply(const d2 (&RR)[kStripeRegRing], const d2 (&z)[16], double (&a)[R][2])
-{
-    constexpr const StripeRegPlan& P = StripeRegPlanOf<R, S, W>::P;
-    constexpr int JB = P.gci[GI] / 4;
-    if constexpr (P.gdiag[GI] != 0) {
-        static_assert(P.gend[GI] - P.gbeg[GI] == 8 && P.pair[P.gbeg[GI]] == 0, "a part's requests");
-        constexpr int s0 = P.slot[P.gbeg[GI]];
-#pragma unroll
-        for (int p = 0; p < 8; ++p) {
-            const d2& l = RR[(s0 + p) % kStripeRegRing];
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int b = 0; b < 2; ++b) a[JB][b] = fma(h ? l.y : l.x, b ? z[2 * p + h].y : z[2 * p + h].x, a[JB][b]);
-        }
-    } else {
-        stripe_reg_pairs_apply<R, S, W, GI, 0, 0, 0>(RR, z, a);
-    }
-}
-// The schedule behind group GI (stripe_plan_ahead's register branch, for every group): GI's requests have landed in their slots, its
-// broadcasts in Z[GI & 1].  Whole sweeps only, like schedule 2.
-template <int R, int S, int W, int GI>
-__device__ __forceinline__ void stripe_reg_ahead(const double* __restrict__ Fw, unsigned xa, unsigned voff, double (&a)[R][2],
-                                                 d2 (&RR)[kStripeRegRing], d2 (&Z)[2][16], int lane)
-{
-    constexpr const StripeRegPlan& P = StripeRegPlanOf<R, S, W>::P;
-    constexpr StripeGroups Q = stripe_groups<R, S, W>();
-    static_assert(Q.n == P.ng && Q.ci[GI] == P.gci[GI] && Q.diag[GI] == P.gdiag[GI], "the plan's groups are the schedule's");
-    if constexpr (GI + 1 < P.ng) {
-        constexpr int N = GI + 1;
-        stripe_group_bcast<R, S, W, N>(Z[N & 1], xa);
-        MCD_SB;
-        stripe_reg_apply<R, S, W, GI>(RR, Z[GI & 1], a);
-        MCD_SB;
-        stripe_reg_issue<R, S, W, P.gpost[GI], P.gpre[N]>(Fw, lane, voff, RR);
-        asm_wait_vmcnt<P.gwait[N]>();
-        stripe_reg_pin<R, S, W, P.gbeg[N], P.gend[N]>(RR);
-        lds_landed<stripe_group_cols<R, S, W, N>()>(Z[N & 1]);
-        stripe_reg_issue<R, S, W, P.gpre[N], P.gpost[N]>(Fw, lane, voff, RR);
-        stripe_reg_ahead<R, S, W, N>(Fw, xa, voff, a, RR, Z, lane);
-    } else {
-        stripe_reg_apply<R, S, W, GI>(RR, Z[GI & 1], a);
-    }
-}
-template <int R, int S, int W>
-__device__ __forceinline__ void stripe_reg_sched(const double* __restrict__ Fw, unsigned xa, unsigned voff, double (&a)[R][2],
-                                                 d2 (&RR)[kStripeRegRing], int lane, int ncols)
-{
-    constexpr const StripeRegPlan& P = StripeRegPlanOf<R, S, W>::P;
-    if (ncols <= 0) {                                      // never taken: it ends the prologue's basic block (stripe_plan_sched)
-        MCD_SB;
-        asm_wait_vmcnt<0>();
-        MCD_SB;
-        return;
-    }
-    d2 Z[2][16];
-    stripe_group_bcast<R, S, W, 0>(Z[0], xa);
-    stripe_reg_issue<R, S, W, P.pro, P.gpre[0]>(Fw, lane, voff, RR);
-    asm_wait_vmcnt<P.gwait[0]>();
-    MCD_T(2);
-    stripe_reg_pin<R, S, W, P.gbeg[0], P.gend[0]>(RR);
-    lds_landed<stripe_group_cols<R, S, W, 0>()>(Z[0]);
-    stripe_reg_issue<R, S, W, P.gpre[0], P.gpost[0]>(Fw, lane, voff, RR);
-    stripe_reg_ahead<R, S, W, 0>(Fw, xa, voff, a, RR, Z, lane);
-}
-template <int R, int S, int W>
-__device__ __forceinline__ void stripe_wave_reg(const double* __restrict__ Fw, d2* lds, const MvnView& M, const double* __restrict__ X, int64_t ldx,
-                                                int64_t b0, int64_t batch, int ncols, double* __restrict__ ll, int lane)
-{
-    using G = StripeReg<R, S>;
-    constexpr const StripeRegPlan& P = StripeRegPlanOf<R, S, W>::P;
-    static_assert(kStripeFinishWave >= 0 && kStripeFinishWave + 2 <= S, "MCD_STRIPE_FINISH_WAVE");
-    constexpr int C = W - kStripeFinishWave;               // the chain this wave finishes, if 0 or 1
-    constexpr bool FIN = C == 0 || C == 1;
-    stripe_u4 cl;
-    if constexpr (FIN) stripe_args_load(cl);
-    double r[R][2], a[R][2];
-    const unsigned voff = 16u * (unsigned)lane, xa = lds_addr(lds + G::EXCH);
-    d2 RR[kStripeRegRing];
-    stripe_prologue_shared<R, S, W, false, P.pro>(xa + voff, M, X, ldx, b0, batch, r, a, lane,
-                                                  [&]() __attribute__((always_inline)) { stripe_reg_issue<R, S, W, 0, P.pro>(Fw, lane, voff, RR); });
-    stripe_reg_sched<R, S, W>(Fw, xa, voff, a, RR, lane, ncols);
-    MCD_T(3);
-    MCD_SB;                                                // (as in stripe_wave: the path that skips the sweep joins here)
-    asm_wait_vmcnt<0>();
-    MCD_SB;
-    double* part = reinterpret_cast<double*>(lds + G::HAND + W * R * 64);
-#pragma unroll
-    for (int k = 0; k < R; ++k)
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-            if (c != C) part[(k * 2 + c) * 64 + lane] = a[k][c];
-    lds_barrier();
-    if constexpr (FIN) {
-        MCD_T(6);
-        stripe_finish_chain<R, S, W, C, G::REGION>(a, lds_addr(lds + G::HAND) + 8u * (unsigned)lane, cl, b0, batch, ll, lane);
-        MCD_T(4);
-    }
-}
-template <int R, int S, int W>
-__device__ __forceinline__ void stripe_dispatch_reg(int wave, const double* __restrict__ Fw, d2* lds, const MvnView& M, const double* __restrict__ X,
-                                                    int64_t ldx, int64_t b0, int64_t batch, int ncols, double* __restrict__ ll, int lane)
-{
-    if (wave == W) {
-        stripe_wave_reg<R, S, W>(Fw, lds, M, X, ldx, b0, batch, ncols, ll, lane);
-    } else {
-        if constexpr (W + 1 < S) stripe_dispatch_reg<R, S, W + 1>(wave, Fw, lds, M, X, ldx, b0, batch, ncols, ll, lane);
+        if constexpr (W + 1 < Body::S) stripe_dispatch<Body, W + 1>(wave, Fw, lds, M, X, ldx, b0, batch, ncols, ll, lane);
     }
 }
 

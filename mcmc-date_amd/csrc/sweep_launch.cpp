@@ -305,80 +305,78 @@ extern "C" int mcd_stripe_deal_selftest_(int R, int S, int w, int ncols, int* pi
     return np <= cap ? np : -2;
 }
 
-// Test hook (tests/test_stripe_plan_host.py; no device): the kernel a launch of the stripe kernel takes for R row blocks and a sweep over
-// ncols columns under the options as they stand (stripe_plan.hpp: stripe_schedule, the function launch_stripe calls)
+// Test hooks (no device): the form a launch of the stripe kernel takes for R row blocks, a sweep over ncols columns and `batch` chains
+// under the options as they stand (stripe_plan.hpp: stripe_form, the function launch_stripe calls), seen three ways.
+static int stripe_form_now(int R, int ncols, long long batch)
+{
+    static_assert(mcd::kStripeUnset == mcd::MCD_OPT_UNSET, "stripe_form's unset option");
+    if (R != 3 && R != 4) return -2;
+    return mcd::stripe_form(mcd::opt_get(mcd::OPT_STRIPE_PROLOGUE), mcd::opt_get(mcd::OPT_STRIPE_SCHED), mcd::opt_get(mcd::OPT_STRIPE_FINISH),
+                            mcd::opt_get(mcd::OPT_STRIPE_DIAG), batch, R, ncols);
+}
+// (tests/test_stripe_plan_host.py) -1: the private prologue; 0, 1, 2: the shared prologue with that schedule
 extern "C" int mcd_stripe_schedule_selftest_(int R, int ncols)
 {
-    if (R != 3 && R != 4) return -2;
-    return mcd::stripe_schedule(mcd::opt_or(mcd::OPT_STRIPE_PROLOGUE, mcd::kStripePrologueDefault),
-                                mcd::opt_or(mcd::OPT_STRIPE_SCHED, mcd::kStripeSchedDefault), R, ncols);
+    const int f = stripe_form_now(R, ncols, 512);
+    return f < 0 ? f : f == mcd::kStripePrivate0 ? -1 : f == mcd::kStripeShared0 ? 0 : f == mcd::kStripeShared1 ? 1 : 2;
 }
-
-// Test hook (tests/test_stripe_finish_codegen_host.py, tests/test_gpu_stripe_finish.py; no device): the finish such a launch takes under the
-// options as they stand (stripe_plan.hpp: stripe_finish, the function launch_stripe calls): 1 a finishing wave per chain, 0 wave 0 alone
+// (tests/test_stripe_finish_codegen_host.py, tests/test_gpu_stripe_finish.py) 1: a finishing wave per chain, 0: wave 0 alone
 extern "C" int mcd_stripe_finish_selftest_(int R, int ncols)
 {
-    if (R != 3 && R != 4) return -2;
-    return mcd::stripe_finish(mcd::opt_or(mcd::OPT_STRIPE_PROLOGUE, mcd::kStripePrologueDefault),
-                              mcd::opt_or(mcd::OPT_STRIPE_SCHED, mcd::kStripeSchedDefault),
-                              mcd::opt_or(mcd::OPT_STRIPE_FINISH, mcd::kStripeFinishDefault), R, ncols);
+    const int f = stripe_form_now(R, ncols, 512);
+    return f < 0 ? f : f >= mcd::kStripeFin ? 1 : 0;
 }
-
-// Test hook (tests/test_stripe_regdiag_plan_host.py, tests/test_gpu_stripe_regdiag.py; no device): where such a launch over `batch` chains
-// takes the diagonal parts of the stream from under the options as they stand (stripe_plan.hpp: stripe_diag and stripe_diag_default, the
-// functions launch_stripe calls): 1 register loads (k_logpdf_stripe_reg), 0 the LDS ring.  With MCD_STRIPE_DIAG unset the batch decides.
+// (tests/test_stripe_regdiag_plan_host.py, tests/test_gpu_stripe_regdiag.py) where the diagonal parts of the stream come from: 1 register
+// loads (k_logpdf_stripe_reg), 0 the LDS ring.  With MCD_STRIPE_DIAG unset the batch decides.
 extern "C" int mcd_stripe_diag_batch_selftest_(int R, int ncols, long long batch)
 {
-    if (R != 3 && R != 4) return -2;
-    return mcd::stripe_diag(mcd::opt_or(mcd::OPT_STRIPE_PROLOGUE, mcd::kStripePrologueDefault),
-                            mcd::opt_or(mcd::OPT_STRIPE_SCHED, mcd::kStripeSchedDefault),
-                            mcd::opt_or(mcd::OPT_STRIPE_FINISH, mcd::kStripeFinishDefault),
-                            mcd::opt_or(mcd::OPT_STRIPE_DIAG, mcd::stripe_diag_default(batch)), R, ncols);
+    const int f = stripe_form_now(R, ncols, batch);
+    return f < 0 ? f : f == mcd::kStripeReg ? 1 : 0;
 }
 // ... and for the headline batch, 512 chains, the largest the stripe kernel takes
 extern "C" int mcd_stripe_diag_selftest_(int R, int ncols) { return mcd_stripe_diag_batch_selftest_(R, ncols, 512); }
 
-// Test hook (tests/test_stripe_regdiag_plan_host.py; no device): the plan of stripe wave w of k_logpdf_stripe_reg with lookahead A
-// (stripe_plan.hpp: stripe_reg_plan; A = 0: the lookahead the library is built with).  head = {requests, groups, leading loads, burst,
-// register slots, lookahead, the zero unit's byte offset}; pos[u] = {slot, base, immediate, lane threshold, zero offset, unit in Fw, pair,
-// group}; lanes (NULL or [requests][64]): every lane's vector offset; grp[g] as mcd_stripe_plan_selftest_.  Returns stripe_reg_plan_check's verdict,
-// -1 for a plan that does not exist, -2 if the arrays are too small.
-extern "C" int mcd_stripe_regplan_selftest_(int R, int S, int w, int A, int* head, int* pos, int cap_pos, int* grp, int cap_grp, unsigned* lanes)
+// Test hooks (tests/test_stripe_regdiag_plan_host.py, tests/test_stripe_plan_host.py; no device): the plan of stripe wave w with lookahead A
+// (stripe_plan.hpp: stripe_plan) and stripe_plan_check's verdict on it (0: every claim holds); -1 for a plan that does not exist, -2 if the
+// arrays are too small.  grp[g] = {chunk, diagonal, first request, end, issued at the wait, vmcnt of the wait, issued behind the wait}.
+static int stripe_plan_out(const mcd::StripePlan& p, int R, int S, int w, int cap_pos, int* grp, int cap_grp)
 {
-    if ((R != 3 && R != 4) || (S != 4 && S != 8) || w < 0 || w >= S || A < 0) return -1;
-    const mcd::StripeRegPlan p = mcd::stripe_reg_plan(R, S, w, A ? A : mcd::kStripeRegAhead);
     if (p.n > cap_pos || p.ng > cap_grp) return -2;
-    head[0] = p.n, head[1] = p.ng, head[2] = p.lead, head[3] = p.pro, head[4] = p.NS, head[5] = p.A, head[6] = mcd::stripe_reg_zero(R);
-    for (int u = 0; u < p.n; ++u) {
-        int* q = pos + 8 * u;
-        q[0] = p.slot[u], q[1] = p.base[u], q[2] = p.imm[u], q[3] = p.thr[u], q[4] = p.zoff[u], q[5] = p.unit[u], q[6] = p.pair[u], q[7] = p.group[u];
-        for (int l = 0; lanes && l < 64; ++l) lanes[64 * u + l] = mcd::stripe_reg_lane_voff(p, u, l);
-    }
-    for (int g = 0; g < p.ng; ++g) {
-        int* q = grp + 7 * g;
-        q[0] = p.gci[g], q[1] = p.gdiag[g], q[2] = p.gbeg[g], q[3] = p.gend[g], q[4] = p.gpre[g], q[5] = p.gwait[g], q[6] = p.gpost[g];
-    }
-    return mcd::stripe_reg_plan_check(p, R, S, w);
-}
-
-// Test hook (tests/test_stripe_plan_host.py; no device): the issue plan of stripe wave w under the register-load schedule with lookahead A
-// (stripe_plan.hpp).  head = {units, groups, leading loads, burst, ring units, register slots}; pos[u] = {kind, slot, base, immediate,
-// unit in Fw, group}; grp[g] = {chunk, diagonal, first position, end, issued at the wait, vmcnt of the wait, issued behind the reads}.
-// Returns stripe_plan_check's verdict (0: every claim holds), -1 for a plan that does not exist, -2 if the arrays are too small.
-extern "C" int mcd_stripe_plan_selftest_(int R, int S, int w, int A, int* head, int* pos, int cap_pos, int* grp, int cap_grp)
-{
-    if ((R != 3 && R != 4) || (S != 4 && S != 8) || w < 0 || w >= S || A < 1) return -1;
-    const mcd::StripePlan p = mcd::stripe_plan(R, S, w, A);
-    const mcd::StripeDeal d = mcd::stripe_deal(R, S);
-    if (p.n > cap_pos || p.ng > cap_grp) return -2;
-    head[0] = p.n, head[1] = p.ng, head[2] = p.lead, head[3] = p.pro, head[4] = p.D, head[5] = mcd::kStripeRegSlots;
-    for (int u = 0; u < p.n; ++u) {
-        int* q = pos + 6 * u;
-        q[0] = p.kind[u], q[1] = p.slot[u], q[2] = p.base[u], q[3] = p.imm[u], q[4] = d.unit[w][u], q[5] = p.group[u];
-    }
     for (int g = 0; g < p.ng; ++g) {
         int* q = grp + 7 * g;
         q[0] = p.gci[g], q[1] = p.gdiag[g], q[2] = p.gbeg[g], q[3] = p.gend[g], q[4] = p.gpre[g], q[5] = p.gwait[g], q[6] = p.gpost[g];
     }
     return mcd::stripe_plan_check(p, R, S, w);
+}
+// k_logpdf_stripe_reg's plan, the diagonal parts by register load (A = 0: the lookahead the library is built with).  head = {requests,
+// groups, leading loads, burst, register slots, lookahead, the zero unit's byte offset}; pos[u] = {slot, base, immediate, lane threshold,
+// zero offset, unit in Fw, pair, group}; lanes (NULL or [requests][64]): every lane's vector offset.
+extern "C" int mcd_stripe_regplan_selftest_(int R, int S, int w, int A, int* head, int* pos, int cap_pos, int* grp, int cap_grp, unsigned* lanes)
+{
+    if ((R != 3 && R != 4) || (S != 4 && S != 8) || w < 0 || w >= S || A < 0) return -1;
+    const mcd::StripePlan p = mcd::stripe_plan(R, S, w, A ? A : mcd::kStripeRegAhead, true);
+    const int verdict = stripe_plan_out(p, R, S, w, cap_pos, grp, cap_grp);
+    if (verdict == -2) return -2;
+    head[0] = p.n, head[1] = p.ng, head[2] = p.lead, head[3] = p.pro, head[4] = p.NS, head[5] = p.A, head[6] = mcd::stripe_zero(R);
+    for (int u = 0; u < p.n; ++u) {
+        int* q = pos + 8 * u;
+        q[0] = p.slot[u], q[1] = p.base[u], q[2] = p.imm[u], q[3] = p.thr[u], q[4] = p.zoff[u], q[5] = p.unit[u], q[6] = p.pair[u], q[7] = p.group[u];
+        for (int l = 0; lanes && l < 64; ++l) lanes[64 * u + l] = mcd::stripe_lane_voff(p, u, l);
+    }
+    return verdict;
+}
+// The plan with the diagonal parts through the LDS ring.  head = {units, groups, leading loads, burst, ring units, register slots};
+// pos[u] = {kind, slot, base, immediate, unit in Fw, group}.
+extern "C" int mcd_stripe_plan_selftest_(int R, int S, int w, int A, int* head, int* pos, int cap_pos, int* grp, int cap_grp)
+{
+    if ((R != 3 && R != 4) || (S != 4 && S != 8) || w < 0 || w >= S || A < 1) return -1;
+    const mcd::StripePlan p = mcd::stripe_plan(R, S, w, A);
+    const int verdict = stripe_plan_out(p, R, S, w, cap_pos, grp, cap_grp);
+    if (verdict == -2) return -2;
+    head[0] = p.n, head[1] = p.ng, head[2] = p.lead, head[3] = p.pro, head[4] = p.D, head[5] = p.NS;
+    for (int u = 0; u < p.n; ++u) {
+        int* q = pos + 6 * u;
+        q[0] = p.kind[u], q[1] = p.slot[u], q[2] = p.base[u], q[3] = p.imm[u], q[4] = p.unit[u], q[5] = p.group[u];
+    }
+    return verdict;
 }

@@ -9,10 +9,10 @@
 
 #include "../../mcmc-date_amd/csrc/stripe_plan.hpp"
 
-static_assert(mcd::stripe_reg_plans_cover(4, 4, mcd::kStripeRegAhead) && mcd::stripe_reg_plans_cover(3, 4, mcd::kStripeRegAhead), "the shipped plans");
+static_assert(mcd::stripe_plans_cover(4, 4, mcd::kStripeRegAhead, true) && mcd::stripe_plans_cover(3, 4, mcd::kStripeRegAhead, true), "the shipped plans");
 
 // the queue of one wave: -1 a leading load, otherwise the request; vmcnt(n) retires from the front until n are left
-static int replay(const mcd::StripeRegPlan& p)
+static int replay(const mcd::StripePlan& p)
 {
     std::deque<int> q;
     std::vector<char> landed(p.n, 0), applied_g(p.ng, 0);
@@ -57,14 +57,14 @@ static int replay(const mcd::StripeRegPlan& p)
 }
 
 // the bytes of Fw every lane of every request reads, against the layout and the deal: 0, or the request that is wrong + 1
-static int addresses(const mcd::StripeRegPlan& p, int R, int S, int w, std::vector<int>& units, std::vector<int>& pairs)
+static int addresses(const mcd::StripePlan& p, int R, int S, int w, std::vector<int>& units, std::vector<int>& pairs)
 {
     const mcd::StripeDeal d = mcd::stripe_deal(R, S);
     const long long zero = 1024LL * mcd::fc_total_units(R);
     for (int u = 0; u < p.n; ++u) {
         const int ci = p.gci[p.group[u]], lc = ci % mcd::fc_cpb(R);
         for (int l = 0; l < 64; ++l) {
-            const long long at = (long long)p.base[u] + p.imm[u] + (long long)mcd::stripe_reg_lane_voff(p, u, l);
+            const long long at = (long long)p.base[u] + p.imm[u] + (long long)mcd::stripe_lane_voff(p, u, l);
             if (!p.gdiag[p.group[u]]) {
                 if (at != 1024LL * p.unit[u] + 16 * l) return u + 1;
                 continue;
@@ -90,38 +90,38 @@ int main()
 {
     int plans = 0;
     {   // a lookahead the register ring cannot hold: both replays say so
-        const mcd::StripeRegPlan p = mcd::stripe_reg_plan(4, 4, 0, 28);
-        if (mcd::stripe_reg_plan_check(p, 4, 4, 0) != 6 || replay(p) != 6) return std::printf("A = 28 passes\n"), 1;
+        const mcd::StripePlan p = mcd::stripe_plan(4, 4, 0, 28, true);
+        if (mcd::stripe_plan_check(p, 4, 4, 0) != 6 || replay(p) != 6) return std::printf("A = 28 passes\n"), 1;
     }
     for (int R = 3; R <= 4; ++R)
         for (int S = 4; S <= 8; S += 4)
             for (int A : {1, 7, 10, 11, 12, 13, 14, 15, 16}) {
                 std::vector<int> units(mcd::fc_total_units(R), 0), pairs(mcd::fc_nchunk(R) * 8, 0);
                 for (int w = 0; w < S; ++w, ++plans) {
-                    const mcd::StripeRegPlan p = mcd::stripe_reg_plan(R, S, w, A);
-                    const int c = mcd::stripe_reg_plan_check(p, R, S, w), r = replay(p), a = addresses(p, R, S, w, units, pairs);
+                    const mcd::StripePlan p = mcd::stripe_plan(R, S, w, A, true);
+                    const int c = mcd::stripe_plan_check(p, R, S, w), r = replay(p), a = addresses(p, R, S, w, units, pairs);
                     if (c != 0 || r != 0 || a != 0) return std::printf("R %d S %d A %d wave %d: check %d, replay %d, addresses %d\n", R, S, A, w, c, r, a), 1;
                     // damaged plans: a wait one short, a slot taken a ring too early, a wide immediate, a pair one lane off, a zero
                     // offset that misses the zero unit
-                    mcd::StripeRegPlan bad = p;
+                    mcd::StripePlan bad = p;
                     bad.gwait[p.ng / 2] += 1;
-                    if (mcd::stripe_reg_plan_check(bad, R, S, w) != 2) return std::printf("R %d S %d A %d wave %d: a short wait passes\n", R, S, A, w), 1;
+                    if (mcd::stripe_plan_check(bad, R, S, w) != 2) return std::printf("R %d S %d A %d wave %d: a short wait passes\n", R, S, A, w), 1;
                     bad = p;
                     if (p.pro < p.n) {
                         bad.slot[p.pro] = p.slot[p.pro - 1];
-                        if (mcd::stripe_reg_plan_check(bad, R, S, w) != 6) return std::printf("R %d S %d A %d wave %d: a live slot is reused\n", R, S, A, w), 1;
+                        if (mcd::stripe_plan_check(bad, R, S, w) != 6) return std::printf("R %d S %d A %d wave %d: a live slot is reused\n", R, S, A, w), 1;
                     }
                     bad = p;
                     bad.base[0] -= 8192, bad.imm[0] += 8192;
-                    if (mcd::stripe_reg_plan_check(bad, R, S, w) != 5) return std::printf("R %d S %d A %d wave %d: a wide immediate passes\n", R, S, A, w), 1;
+                    if (mcd::stripe_plan_check(bad, R, S, w) != 5) return std::printf("R %d S %d A %d wave %d: a wide immediate passes\n", R, S, A, w), 1;
                     for (int u = 0; u < p.n; ++u)
                         if (p.thr[u] >= 0) {
                             bad = p;
                             bad.imm[u] += 16, bad.zoff[u] -= 16;
-                            if (mcd::stripe_reg_plan_check(bad, R, S, w) != 9) return std::printf("R %d S %d A %d wave %d: a shifted pair passes\n", R, S, A, w), 1;
+                            if (mcd::stripe_plan_check(bad, R, S, w) != 9) return std::printf("R %d S %d A %d wave %d: a shifted pair passes\n", R, S, A, w), 1;
                             bad = p;
                             bad.zoff[u] += 16;
-                            if (mcd::stripe_reg_plan_check(bad, R, S, w) != 9) return std::printf("R %d S %d A %d wave %d: a missed zero unit passes\n", R, S, A, w), 1;
+                            if (mcd::stripe_plan_check(bad, R, S, w) != 9) return std::printf("R %d S %d A %d wave %d: a missed zero unit passes\n", R, S, A, w), 1;
                             break;
                         }
                 }
@@ -132,7 +132,7 @@ int main()
                     for (int q = 0; q < 8; ++q)
                         if (pairs[ci * 8 + q] != 1) return std::printf("R %d S %d A %d: chunk %d pair %d requested %d times\n", R, S, A, ci, q, pairs[ci * 8 + q]), 1;
                 }
-                if (!mcd::stripe_reg_plans_cover(R, S, A)) return std::printf("R %d S %d A %d: stripe_reg_plans_cover\n", R, S, A), 1;
+                if (!mcd::stripe_plans_cover(R, S, A, true)) return std::printf("R %d S %d A %d: stripe_plans_cover\n", R, S, A), 1;
             }
     std::printf("ok: %d plans\n", plans);
     return 0;
