@@ -114,11 +114,11 @@ int eval_gradients(mcd_hmc* m)
 // the dense metric's products are taken across the chains (k_metric_gemm.hip)
 bool across(const mcd_hmc* m) { return m->dev.metric && m->form == MCD_HMC_METRIC_ACROSS_CHAINS; }
 
-// the across-chains workspace holds `slots` right-hand sides per chain (1: leapfrog steps; kNutsRhsMaxSlots: NUTS).  Called by the entry
-// points before their first launch, never inside a round.
+// under the across-chains form the workspace holds `slots` right-hand sides per chain (1: leapfrog steps; kNutsRhsMaxSlots: NUTS).  Called
+// by the entry points before their first launch, never inside a round.
 int across_alloc(mcd_hmc* m, int slots)
 {
-    if (m->wx_slots >= slots) return MCD_OK;
+    if (!across(m) || m->wx_slots >= slots) return MCD_OK;
     HHIP_TRY(hipStreamSynchronize(m->stream));
     for (double* old : {m->wx.X, m->wx.Y})
         if (old) {
@@ -148,6 +148,13 @@ int drift_across(mcd_hmc* m)
 // the largest position a dense metric serves on this handle: the form decides
 int dense_max_dim(const mcd_hmc* m) { return m->form == MCD_HMC_METRIC_ACROSS_CHAINS ? MCD_HMC_DENSE_ACROSS_MAX_DIM : MCD_HMC_DENSE_MAX_DIM; }
 
+// the refusal of a position too long for a dense metric in the handle's form
+int dense_dim_refused(const mcd_hmc* m, const char* who)
+{
+    return hfail(MCD_ERR_UNSUPPORTED, "%s: dim = %d, a dense metric serves positions of up to %s = %d coordinates", who, m->dev.dim,
+                 m->form == MCD_HMC_METRIC_ACROSS_CHAINS ? "MCD_HMC_DENSE_ACROSS_MAX_DIM" : "MCD_HMC_DENSE_MAX_DIM", dense_max_dim(m));
+}
+
 // The metric argument of an entry point: positive inverse masses [dim] -- or NULL while a dense metric is set on the handle, so that
 // no caller runs another metric than the one it names.
 int check_inv_mass(const mcd_hmc* m, const char* who, const double* inv_mass)
@@ -162,10 +169,14 @@ int check_inv_mass(const mcd_hmc* m, const char* who, const double* inv_mass)
     return MCD_OK;
 }
 
-// the diagonal metric's inverse masses go to the device; a dense metric is there already
-int upload_inv_mass(mcd_hmc* m, const double* inv_mass)
+// What an entry point hands over besides positions and momenta goes to the device: step sizes, the diagonal metric's inverse masses (a
+// dense metric is there already), directions of time (null: forwards; a NUTS transition writes its own)
+int upload_step_args(mcd_hmc* m, const double* eps, const double* inv_mass, const double* dir)
 {
+    HHIP_TRY(hipMemcpyAsync(m->d_eps, eps, sizeof(double) * (size_t)m->dev.batch, hipMemcpyHostToDevice, m->stream));
     if (!m->dev.metric) HHIP_TRY(hipMemcpyAsync(m->d_inv_mass, inv_mass, sizeof(double) * m->dev.dim, hipMemcpyHostToDevice, m->stream));
+    if (dir) HHIP_TRY(hipMemcpyAsync(m->d_dir, dir, sizeof(double) * (size_t)m->dev.batch, hipMemcpyHostToDevice, m->stream));
+    m->dev.dir = dir ? m->d_dir : nullptr;
     return MCD_OK;
 }
 
@@ -395,17 +406,9 @@ int mcd_hmc_leapfrog(mcd_hmc_t* m, double* p, const double* eps, const double* d
     const size_t B = (size_t)D.batch, BD = B * (size_t)D.dim;
     if (int rc = check_inv_mass(m, "mcd_hmc_leapfrog", inv_mass)) return rc;
     HHIP_TRY(hipSetDevice(m->device));
-    if (across(m))
-        if (int rc = across_alloc(m, 1)) return rc;
+    if (int rc = across_alloc(m, 1)) return rc;
     HHIP_TRY(hipMemcpyAsync(D.p, p, sizeof(double) * BD, hipMemcpyHostToDevice, m->stream));
-    HHIP_TRY(hipMemcpyAsync(m->d_eps, eps, sizeof(double) * B, hipMemcpyHostToDevice, m->stream));
-    if (int rc = upload_inv_mass(m, inv_mass)) return rc;
-    if (dir) {
-        HHIP_TRY(hipMemcpyAsync(m->d_dir, dir, sizeof(double) * B, hipMemcpyHostToDevice, m->stream));
-        D.dir = m->d_dir;
-    } else {
-        D.dir = nullptr;
-    }
+    if (int rc = upload_step_args(m, eps, inv_mass, dir)) return rc;
     // p += eps/2 g;  [ q += eps Minv p;  g = grad(q);  p += eps g ] x (n - 1);  q += eps Minv p;  g = grad(q);  p += eps/2 g
     // three launches per step (kick + drift fused, prior gradient, likelihood gradient), the closing half kick with the collect
     // (across-chains form of a dense metric: the kick, the product over all chains, the drift)
@@ -436,18 +439,10 @@ int mcd_hmc_step_from(mcd_hmc_t* m, double* q, double* p, double* grad, int have
     const size_t B = (size_t)D.batch, BD = B * (size_t)D.dim;
     if (int rc = check_inv_mass(m, "mcd_hmc_step_from", inv_mass)) return rc;
     HHIP_TRY(hipSetDevice(m->device));
-    if (across(m))
-        if (int rc = across_alloc(m, 1)) return rc;
+    if (int rc = across_alloc(m, 1)) return rc;
     HHIP_TRY(hipMemcpyAsync(D.q, q, sizeof(double) * BD, hipMemcpyHostToDevice, m->stream));
     HHIP_TRY(hipMemcpyAsync(D.p, p, sizeof(double) * BD, hipMemcpyHostToDevice, m->stream));
-    HHIP_TRY(hipMemcpyAsync(m->d_eps, eps, sizeof(double) * B, hipMemcpyHostToDevice, m->stream));
-    if (int rc = upload_inv_mass(m, inv_mass)) return rc;
-    if (dir) {
-        HHIP_TRY(hipMemcpyAsync(m->d_dir, dir, sizeof(double) * B, hipMemcpyHostToDevice, m->stream));
-        D.dir = m->d_dir;
-    } else {
-        D.dir = nullptr;
-    }
+    if (int rc = upload_step_args(m, eps, inv_mass, dir)) return rc;
     HHIP_TRY(mcd::launch_hmc_scatter(D, m->stream));
     if (have_grad) {
         HHIP_TRY(hipMemcpyAsync(D.grad, grad, sizeof(double) * BD, hipMemcpyHostToDevice, m->stream));
@@ -503,6 +498,17 @@ int nuts_alloc(mcd_hmc* m)
     return halloc(m, &m->d_active, 1);
 }
 
+// The end of a round of tree building: the counter is cleared, the round's last kernel counts the chains that go on, the host reads the counter
+template <class Launch>
+int nuts_round_end(mcd_hmc* m, int* active, Launch launch_round_kernel)
+{
+    HHIP_TRY(hipMemsetAsync(m->d_active, 0, sizeof(int), m->stream));
+    HHIP_TRY(launch_round_kernel());
+    HHIP_TRY(hipMemcpyAsync(active, m->d_active, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    HHIP_TRY(hipStreamSynchronize(m->stream));
+    return MCD_OK;
+}
+
 // The tree building of one transition under the across-chains form of a dense metric (k_nuts_across.hip has the sequence): the chains are
 // in lock step, so round r is leaf i of doubling j for every chain still building (nuts_round_position) and the number of products it
 // needs is known here (nuts_rhs_plan).  The counter the host polls after every round is the number of chains that go on, and the kernel
@@ -528,11 +534,9 @@ int nuts_build_across(mcd_hmc* m, int max_depth, uint64_t seed, int64_t chain0, 
         if (int rc = eval_gradients(m)) return rc;
         HHIP_TRY(mcd::launch_nutsx_leaf(D, m->nuts, W.X, m->stream));                                          // (a)
         HHIP_TRY(mcd::launch_metric_gemm_rows(W.X, D.metric, W.Y, (int64_t)plan.count * n, D.dim, false, list, n, B, m->stream));   // (b)
-        HHIP_TRY(hipMemsetAsync(m->d_active, 0, sizeof(int), m->stream));
-        HHIP_TRY(mcd::launch_nutsx_book(D, m->nuts, W.Y, seed, chain0, transition, max_depth, m->d_active, m->d_list, m->stream));   // (c)
         int active = 0;
-        HHIP_TRY(hipMemcpyAsync(&active, m->d_active, sizeof(int), hipMemcpyDeviceToHost, m->stream));
-        HHIP_TRY(hipStreamSynchronize(m->stream));
+        auto book = [&] { return mcd::launch_nutsx_book(D, m->nuts, W.Y, seed, chain0, transition, max_depth, m->d_active, m->d_list, m->stream); };   // (c)
+        if (int rc = nuts_round_end(m, &active, book)) return rc;
         if (active == 0) break;
         list = m->d_list;
         n = active;
@@ -550,11 +554,9 @@ int nuts_build(mcd_hmc* m, int max_depth, uint64_t seed, int64_t chain0, uint64_
     const int64_t max_rounds = (int64_t)1 << max_depth;               // 2^max_depth - 1 leaves at most
     for (int64_t r = 0; r < max_rounds; ++r) {
         if (int rc = eval_gradients(m)) return rc;
-        HHIP_TRY(hipMemsetAsync(m->d_active, 0, sizeof(int), m->stream));
-        HHIP_TRY(mcd::launch_nuts_step(D, m->nuts, seed, chain0, transition, max_depth, m->d_active, m->stream));
         int active = 0;
-        HHIP_TRY(hipMemcpyAsync(&active, m->d_active, sizeof(int), hipMemcpyDeviceToHost, m->stream));
-        HHIP_TRY(hipStreamSynchronize(m->stream));
+        auto step = [&] { return mcd::launch_nuts_step(D, m->nuts, seed, chain0, transition, max_depth, m->d_active, m->stream); };
+        if (int rc = nuts_round_end(m, &active, step)) return rc;
         if (active == 0) break;
     }
     return MCD_OK;
@@ -595,10 +597,8 @@ int mcd_hmc_nuts(mcd_hmc_t* m, const double* eps, const double* inv_mass, int ma
     if (int rc = m->rec.room("mcd_hmc_nuts", 1)) return rc;
     HHIP_TRY(hipSetDevice(m->device));
     if (int rc = nuts_alloc(m)) return rc;
-    if (across(m))
-        if (int rc = across_alloc(m, mcd::kNutsRhsMaxSlots)) return rc;
-    HHIP_TRY(hipMemcpyAsync(m->d_eps, eps, sizeof(double) * B, hipMemcpyHostToDevice, m->stream));
-    if (int rc = upload_inv_mass(m, inv_mass)) return rc;
+    if (int rc = across_alloc(m, mcd::kNutsRhsMaxSlots)) return rc;
+    if (int rc = upload_step_args(m, eps, inv_mass, nullptr)) return rc;
     if (int rc = nuts_transition(m, max_depth, seed, chain_offset, transition)) return rc;
     std::vector<double> a(B);
     std::vector<int> na(B), dp(B);
@@ -657,8 +657,7 @@ int mcd_hmc_cycle_ready_(mcd_hmc* h, const char* who, bool dense)
         return hfail(MCD_ERR_INVALID_ARG, "%s: a dense metric is set on the attached mcd_hmc_t (mcd_hmc_set_metric): the attachment's inv_mass must be NULL", who);
     HHIP_TRY(hipSetDevice(h->device));
     if (int rc = nuts_alloc(h)) return rc;
-    if (across(h))
-        if (int rc = across_alloc(h, mcd::kNutsRhsMaxSlots)) return rc;
+    if (int rc = across_alloc(h, mcd::kNutsRhsMaxSlots)) return rc;
     return MCD_OK;
 }
 
@@ -761,6 +760,10 @@ int nuts_run(mcd_hmc_t* m, int n_transitions, int adapt, double* eps, const doub
     return MCD_OK;
 }
 
+// Both warm-ups shrink a window's (co)variances towards 1e-3 (Stan's regularisation): keep * v, + floor on the diagonal, n_eff positions
+constexpr double shrink_keep(double n_eff) { return n_eff / (n_eff + 5.0); }
+constexpr double shrink_floor(double n_eff) { return 1e-3 * (5.0 / (n_eff + 5.0)); }
+
 // device memory of one call
 struct Scratch {
     double* p = nullptr;
@@ -784,9 +787,7 @@ int mcd_hmc_set_metric(mcd_hmc_t* m, const double* inv_mass_dense)
         metric_clear(m);
         return MCD_OK;
     }
-    if (m->dev.dim > dense_max_dim(m))
-        return hfail(MCD_ERR_UNSUPPORTED, "mcd_hmc_set_metric: dim = %d, a dense metric serves positions of up to %s = %d coordinates", m->dev.dim,
-                     m->form == MCD_HMC_METRIC_ACROSS_CHAINS ? "MCD_HMC_DENSE_ACROSS_MAX_DIM" : "MCD_HMC_DENSE_MAX_DIM", dense_max_dim(m));
+    if (m->dev.dim > dense_max_dim(m)) return dense_dim_refused(m, "mcd_hmc_set_metric");
     std::vector<double> sym, uinv;
     char why[256];
     if (!metric_factors(m->dev.dim, inv_mass_dense, sym, uinv, why, sizeof why)) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_set_metric: %s", why);
@@ -827,9 +828,7 @@ int mcd_hmc_nuts_warmup_dense(mcd_hmc_t* m, int windows, int window, double* eps
     if (!m || !eps || !inv_mass0) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_warmup_dense: NULL argument");
     if (windows < 1 || window < 1) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_warmup_dense: need windows >= 1 and window >= 1");
     const size_t B = (size_t)m->dev.batch, dim = (size_t)m->dev.dim;
-    if (m->dev.dim > dense_max_dim(m))
-        return hfail(MCD_ERR_UNSUPPORTED, "mcd_hmc_nuts_warmup_dense: dim = %d, a dense metric serves positions of up to %s = %d coordinates", m->dev.dim,
-                     m->form == MCD_HMC_METRIC_ACROSS_CHAINS ? "MCD_HMC_DENSE_ACROSS_MAX_DIM" : "MCD_HMC_DENSE_MAX_DIM", dense_max_dim(m));
+    if (m->dev.dim > dense_max_dim(m)) return dense_dim_refused(m, "mcd_hmc_nuts_warmup_dense");
     for (size_t k = 0; k < dim; ++k)
         if (!(inv_mass0[k] > 0) || !std::isfinite(inv_mass0[k])) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_warmup_dense: inverse masses must be positive");
     if (int rc = m->rec.room("mcd_hmc_nuts_warmup_dense", ((int64_t)windows + 1) * (int64_t)window)) return rc;
@@ -862,7 +861,7 @@ int mcd_hmc_nuts_warmup_dense(mcd_hmc_t* m, int windows, int window, double* eps
         HHIP_TRY(hipStreamSynchronize(m->stream));
         phase[1] += since(t0);
         t0 = clk::now();
-        const double n_eff = (double)n, keep = n_eff / (n_eff + 5.0), floor_ = 1e-3 * (5.0 / (n_eff + 5.0));
+        const double keep = shrink_keep((double)n), floor_ = shrink_floor((double)n);
         for (size_t i = 0; i < dim; ++i)
             for (size_t j = 0; j < dim; ++j) cov[i * dim + j] = keep * cov[i * dim + j] + (i == j ? floor_ : 0.0);
         // a chain outside the support leaves NaN positions, a degenerate window no factor: keep the metric
@@ -954,7 +953,7 @@ int mcd_hmc_nuts_warmup(mcd_hmc_t* m, int windows, int window, double* eps, doub
         t += (uint64_t)window;
         const double n_eff = (double)B * (double)window;
         for (size_t k = 0; k < dim; ++k) {
-            const double v = (n_eff / (n_eff + 5.0)) * qv[k] + 1e-3 * (5.0 / (n_eff + 5.0));
+            const double v = shrink_keep(n_eff) * qv[k] + shrink_floor(n_eff);
             inv_mass[k] = (v > 0 && std::isfinite(v)) ? v : inv_mass[k];      // a chain outside the support leaves NaN positions: keep the mass
         }
     }

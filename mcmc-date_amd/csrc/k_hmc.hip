@@ -8,57 +8,34 @@
 // With a dense metric on the handle (D.metric = C = M^-1, mcd_hmc_set_metric) the drift is q += eps (C p), the product of
 // metric_device.hpp by one workgroup per chain; the diagonal kernels and their expressions are untouched.
 // The gradient comes from the batched kernels (k_prior_grad.hip for the prior, k_tree_grad.hip for the likelihood) plus
-// the five-number Jacobian term evaluated here; this file holds the element-wise part: assemble the gradient in the
-// position layout, kick, drift and scatter the new position into the state arrays.  One thread per (chain, coordinate).
+// the five-number Jacobian term (hmc_device.hpp: gradient entry, state slot and ln target of the position layout, shared with
+// the NUTS kernels and the recorder); this file holds the element-wise part: assemble the gradient in the position layout,
+// kick, drift and scatter the new position into the state arrays.  One thread per (chain, coordinate).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
+#include "hmc_device.hpp"
 #include "metric_device.hpp"
 #include "mvn_kernels.h"
 
 namespace mcd {
 
-// d ln target / d q_i for chain b, from the outputs of the two gradient kernels + the Jacobian factor 1 / rootBranch,
-// rootBranch = tH rMu (t_l r_l + t_r r_r)                                             (app/Probability.hs:393-410)
-__device__ __forceinline__ double hmc_grad_entry(const HmcDev& D, int64_t b, int field, int v)
+// eps_b with the direction of time dir_b (+1 / -1 per chain, null = +1)
+__device__ __forceinline__ double hmc_signed_eps(const HmcDev& D, int64_t b) { return D.eps[b] * (D.dir ? D.dir[b] : 1.0); }
+
+// the kick of entry i of chain b with the gradient entry g, which D.grad keeps
+__device__ __forceinline__ void hmc_kick_entry(const HmcDev& D, int64_t i, int64_t b, double kick, double g)
 {
-    const int64_t B = D.batch;
-    const double* H = D.H + b * D.ld;
-    const double* R = D.R + b * D.ld;
-    const int l = 1, r = D.root_right;
-    switch (field) {
-        case 0: return D.gp_sc[0 * B + b];
-        case 1: return D.gp_sc[1 * B + b];
-        case 2: return D.gp_sc[2 * B + b] + D.gl_tH[b] - 1.0 / D.sc[2 * B + b];
-        case 4: return D.gp_sc[3 * B + b] + D.gl_rMu[b] - 1.0 / D.sc[3 * B + b];
-        case 5: return D.gp_sc[4 * B + b];
-        default: break;
-    }
-    const double S = (H[0] - H[l]) * R[l] + (H[0] - H[r]) * R[r];
-    if (field == 3) {
-        double j = 0.0;
-        if (v == l || v == r) j = R[v] / S;                       // d/d h_v of -ln S
-        if (v == 0) j = -(R[l] + R[r]) / S;
-        return D.gp_H[b * D.ld + v] + D.gl_H[b * D.ld + v] + j;
-    }
-    double j = 0.0;
-    if (v == l || v == r) j = -(H[0] - H[v]) / S;
-    return D.gp_R[b * D.ld + v] + D.gl_R[b * D.ld + v] + j;
+    D.p[i] = D.p[i] + kick * hmc_signed_eps(D, b) * g;
+    D.grad[i] = g;
 }
 
-__device__ __forceinline__ double* hmc_state_slot(const HmcDev& D, int64_t b, int field, int v)
+// the position of entry i = (b, k) from the state arrays; coordinate 0 leaves the chain's ln target in D.value
+__device__ __forceinline__ void hmc_collect_entry(const HmcDev& D, int64_t i, int64_t b, int k)
 {
-    const int64_t B = D.batch;
-    switch (field) {
-        case 0: return D.sc + 0 * B + b;
-        case 1: return D.sc + 1 * B + b;
-        case 2: return D.sc + 2 * B + b;
-        case 4: return D.sc + 3 * B + b;
-        case 5: return D.sc + 4 * B + b;
-        case 3: return D.H + b * D.ld + v;
-        default: return D.R + b * D.ld + v;
-    }
+    D.q[i] = *hmc_state_slot(D, b, D.pos_field[k], D.pos_index[k]);
+    if (k == 0) D.value[b] = hmc_ln_target(D, b);
 }
 
 // p += kick * eps_b * dir_b * grad.  `dir` (+1 / -1 per chain, may be null = +1) integrates backwards in time (NUTS-style
@@ -72,11 +49,7 @@ __global__ __launch_bounds__(256) void k_hmc_kick(HmcDev D, double kick, int use
     if (i >= D.batch * D.dim) return;
     const int64_t b = i / D.dim;
     const int k = (int)(i - b * D.dim);
-    const int field = D.pos_field[k], v = D.pos_index[k];
-    const double e = D.eps[b] * (D.dir ? D.dir[b] : 1.0);
-    const double g = use_pos_grad ? D.grad[i] : hmc_grad_entry(D, b, field, v);
-    D.p[i] = D.p[i] + kick * e * g;
-    D.grad[i] = g;
+    hmc_kick_entry(D, i, b, kick, use_pos_grad ? D.grad[i] : hmc_grad_entry(D, b, D.pos_field[k], D.pos_index[k]));
 }
 
 // the state arrays receive the position D.q (masked-out entries keep their values)
@@ -95,10 +68,8 @@ __global__ __launch_bounds__(256) void k_hmc_drift(HmcDev D)
     if (i >= D.batch * D.dim) return;
     const int64_t b = i / D.dim;
     const int k = (int)(i - b * D.dim);
-    const int field = D.pos_field[k], v = D.pos_index[k];
-    const double e = D.eps[b] * (D.dir ? D.dir[b] : 1.0);
-    double* slot = hmc_state_slot(D, b, field, v);
-    const double q = *slot + e * D.inv_mass[k] * D.p[i];
+    double* slot = hmc_state_slot(D, b, D.pos_field[k], D.pos_index[k]);
+    const double q = *slot + hmc_signed_eps(D, b) * D.inv_mass[k] * D.p[i];
     *slot = q;
     D.q[i] = q;
 }
@@ -110,16 +81,8 @@ __global__ __launch_bounds__(256) void k_hmc_collect(HmcDev D)
     if (i >= D.batch * D.dim) return;
     const int64_t b = i / D.dim;
     const int k = (int)(i - b * D.dim);
-    const int field = D.pos_field[k], v = D.pos_index[k];
-    D.q[i] = *hmc_state_slot(D, b, field, v);
-    D.grad[i] = hmc_grad_entry(D, b, field, v);
-    if (k == 0) {
-        const double* H = D.H + b * D.ld;
-        const double* R = D.R + b * D.ld;
-        const int l = 1, r = D.root_right;
-        const double root_branch = D.sc[2 * D.batch + b] * D.sc[3 * D.batch + b] * ((H[0] - H[l]) * R[l] + (H[0] - H[r]) * R[r]);
-        D.value[b] = D.lp[b] + D.ll[b] + log(1.0 / root_branch);
-    }
+    D.grad[i] = hmc_grad_entry(D, b, D.pos_field[k], D.pos_index[k]);
+    hmc_collect_entry(D, i, b, k);
 }
 
 // q += e (C p) for chain b under the dense metric: the chain's momenta D.p are final (a barrier or a launch boundary lies behind)
@@ -148,7 +111,7 @@ __global__ __launch_bounds__(256) void k_hmc_kick_drift(HmcDev D, double kick)
     __shared__ double xs[Dense ? kHmcDenseMaxDim : 1];
     const int64_t b = blockIdx.x;
     const int64_t o = b * D.dim;
-    const double e = D.eps[b] * (D.dir ? D.dir[b] : 1.0);
+    const double e = hmc_signed_eps(D, b);
     for (int k = threadIdx.x; k < D.dim; k += blockDim.x) {
         const double g = hmc_grad_entry(D, b, D.pos_field[k], D.pos_index[k]);
         D.grad[o + k] = g;
@@ -172,7 +135,7 @@ __global__ __launch_bounds__(256) void k_hmc_drift_dense(HmcDev D)
 {
     __shared__ double xs[kHmcDenseMaxDim];
     const int64_t b = blockIdx.x;
-    hmc_drift_dense(D, b, D.eps[b] * (D.dir ? D.dir[b] : 1.0), xs);
+    hmc_drift_dense(D, b, hmc_signed_eps(D, b), xs);
 }
 
 // the drift under a dense metric in the across-chains form: Y = P C is k_metric_gemm.hip's product over all chains, q += e Y elementwise
@@ -182,9 +145,8 @@ __global__ __launch_bounds__(256) void k_hmc_drift_across(HmcDev D, const double
     if (i >= D.batch * D.dim) return;
     const int64_t b = i / D.dim;
     const int k = (int)(i - b * D.dim);
-    const double e = D.eps[b] * (D.dir ? D.dir[b] : 1.0);
     double* slot = hmc_state_slot(D, b, D.pos_field[k], D.pos_index[k]);
-    const double q = *slot + e * Y[i];
+    const double q = *slot + hmc_signed_eps(D, b) * Y[i];
     *slot = q;
     D.q[i] = q;
 }
@@ -196,19 +158,8 @@ __global__ __launch_bounds__(256) void k_hmc_kick_collect(HmcDev D, double kick)
     if (i >= D.batch * D.dim) return;
     const int64_t b = i / D.dim;
     const int k = (int)(i - b * D.dim);
-    const int field = D.pos_field[k], v = D.pos_index[k];
-    const double e = D.eps[b] * (D.dir ? D.dir[b] : 1.0);
-    const double g = hmc_grad_entry(D, b, field, v);
-    D.p[i] = D.p[i] + kick * e * g;
-    D.grad[i] = g;
-    D.q[i] = *hmc_state_slot(D, b, field, v);
-    if (k == 0) {
-        const double* H = D.H + b * D.ld;
-        const double* R = D.R + b * D.ld;
-        const int l = 1, r = D.root_right;
-        const double root_branch = D.sc[2 * D.batch + b] * D.sc[3 * D.batch + b] * ((H[0] - H[l]) * R[l] + (H[0] - H[r]) * R[r]);
-        D.value[b] = D.lp[b] + D.ll[b] + log(1.0 / root_branch);
-    }
+    hmc_kick_entry(D, i, b, kick, hmc_grad_entry(D, b, D.pos_field[k], D.pos_index[k]));
+    hmc_collect_entry(D, i, b, k);
 }
 
 static unsigned hmc_grid(const HmcDev& D) { return (unsigned)((D.batch * D.dim + 255) / 256); }

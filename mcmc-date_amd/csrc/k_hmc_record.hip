@@ -14,6 +14,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "hmc_device.hpp"
 #include "mvn_kernels.h"
 
 namespace mcd {
@@ -38,10 +39,8 @@ __global__ __launch_bounds__(256) void k_hmc_record(HmcDev D, NutsDev N, MhRec R
         v = D.lp[b];
     } else if (tid == 6) {
         v = D.ll[b];
-    } else if (tid == 7) {                                       // ln jacobianRootBranch: the expression of k_nuts_step
-        const int l = 1, r = D.root_right;
-        const double root_branch = D.sc[2 * B + b] * D.sc[3 * B + b] * ((H[0] - H[l]) * Rt[l] + (H[0] - H[r]) * Rt[r]);
-        v = log(1.0 / root_branch);
+    } else if (tid == 7) {                                       // the part of the ln target the kernels add (hmc_device.hpp)
+        v = hmc_ln_root_branch(D, b);
     } else if (tid == 8) {
         v = 1.0;                                                 // beta: these chains are cold
     } else if (tid == 9) {

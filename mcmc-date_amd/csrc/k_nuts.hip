@@ -23,9 +23,14 @@
 // The metric: diagonal inverse masses D.inv_mass, or -- template <Dense>, chosen by the launchers when D.metric is set
 // (mcd_hmc_set_metric) -- a full inverse mass matrix C = U U^T: momenta p = U^-T z from the same normal draws z, kinetic energy
 // 1/2 p^T C p, drift q += eps (C p), U-turn (q+ - q-)^T C r >= 0 at both ends from ONE product w = C (q+ - q-).  The products are
-// metric_device.hpp's; slice, doubling, reservoir, merge, divergence test and random streams are the same code.  The diagonal
-// branches keep their expressions as they were.  The dense metric's other form (mcd_hmc_set_metric_form: the products of all chains as one
-// matrix product, any dim) is k_nuts_across.hip; the helpers both files use are nuts_device.hpp's.
+// metric_device.hpp's.  The dense metric's other form (mcd_hmc_set_metric_form: the products of all chains as one matrix product, any
+// dim) is k_nuts_across.hip.
+//
+// The state machine itself is written once, in nuts_device.hpp, for the kernels of both files: the random streams, the start of a
+// transition (nuts_tree_init, nuts_start), the booking of a leaf (nuts_book_leaf: slice test, divergence flag, reservoir, acceptance
+// statistic) and the decision (nuts_decide: merge, U-turn of the whole tree as a callable, depth stop, write-back).  This file holds what
+// belongs to the per-chain form: momenta, kinetic energy and U-turn products by the chain's own workgroup, the half kick + drift of the
+// next leaf, and the loop over the stack levels, which opens and closes them in one pass.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -85,7 +90,7 @@ __device__ __forceinline__ void nuts_launch_leaf(const HmcDev& D, const NutsDev&
             D.p[o + k] = p;
             D.q[o + k] = q;
             D.grad[o + k] = g;
-            *nuts_state_slot(D, b, D.pos_field[k], D.pos_index[k]) = q;
+            *hmc_state_slot(D, b, D.pos_field[k], D.pos_index[k]) = q;
         }
     } else {
         for (int k = threadIdx.x; k < D.dim; k += blockDim.x) {
@@ -95,7 +100,7 @@ __device__ __forceinline__ void nuts_launch_leaf(const HmcDev& D, const NutsDev&
             D.p[o + k] = p;
             D.q[o + k] = q;
             D.grad[o + k] = g;
-            *nuts_state_slot(D, b, D.pos_field[k], D.pos_index[k]) = q;
+            *hmc_state_slot(D, b, D.pos_field[k], D.pos_index[k]) = q;
         }
     }
     if (threadIdx.x == 0) const_cast<double*>(D.dir)[b] = (double)v;
@@ -114,84 +119,40 @@ __global__ __launch_bounds__(256) void k_nuts_begin(HmcDev D, NutsDev N, uint64_
     double kin = 0.0;
     if constexpr (Dense) {
         double p[kMetricOwned], cp[kMetricOwned];
-        metric_apply(D.metric_uinv, D.dim, true, xs, [&](int k, int) {
-            double ua, ub;
-            philox_block(g, 0x4000u + (uint32_t)(k >> 1), ua, ub);
-            const double rad = sqrt(-2.0 * log(ua)), ang = 6.28318530717958647692 * ub;
-            return (k & 1) ? rad * sin(ang) : rad * cos(ang);
-        }, p);                                                      // p = U^-T z ~ N(0, C^-1) = N(0, M)
+        metric_apply(D.metric_uinv, D.dim, true, xs, [&](int k, int) { return nuts_normal(g, k); }, p);   // p = U^-T z ~ N(0, C^-1) = N(0, M)
         metric_apply(D.metric, D.dim, false, xs, [&](int, int i) { return p[i]; }, cp);
         for (int i = 0; i < kMetricOwned; ++i) {
             const int k = (int)threadIdx.x + 256 * i;
             if (k >= D.dim) break;
             kin += p[i] * cp[i];
-            const double q = D.q[o + k], gr = D.grad[o + k];
-            N.qm[o + k] = q;
-            N.qp[o + k] = q;
-            N.pm[o + k] = p[i];
-            N.pp[o + k] = p[i];
-            N.gm[o + k] = gr;
-            N.gp[o + k] = gr;
-            N.qn[o + k] = q;
-            N.gn[o + k] = gr;
+            nuts_tree_init(D, N, o + k, p[i]);
         }
     } else {
         for (int k = threadIdx.x; k < D.dim; k += blockDim.x) {
-            double ua, ub;
-            philox_block(g, 0x4000u + (uint32_t)(k >> 1), ua, ub);
-            const double rad = sqrt(-2.0 * log(ua)), ang = 6.28318530717958647692 * ub;
-            const double z = (k & 1) ? rad * sin(ang) : rad * cos(ang);
+            const double z = nuts_normal(g, k);
             const double p = z / sqrt(D.inv_mass[k]);                   // p ~ N(0, M)
             kin += p * p * D.inv_mass[k];
-            const double q = D.q[o + k], gr = D.grad[o + k];
-            N.qm[o + k] = q;
-            N.qp[o + k] = q;
-            N.pm[o + k] = p;
-            N.pp[o + k] = p;
-            N.gm[o + k] = gr;
-            N.gp[o + k] = gr;
-            N.qn[o + k] = q;
-            N.gn[o + k] = gr;
+            nuts_tree_init(D, N, o + k, p);
         }
     }
     kin = 0.5 * nuts_block_sum(kin, red);
-    const double joint0 = D.value[b] - kin;
-    double us, ub2;
-    philox_block(g, 1u, us, ub2);
-    const int v = nuts_direction(seed, chain0 + b, transition, 0);
-    if (threadIdx.x == 0) {
-        N.joint0[b] = joint0;
-        N.log_u[b] = joint0 + log(us);
-        N.lpn[b] = D.value[b];
-        N.alpha[b] = 0.0;
-        N.n_alpha[b] = 0;
-        N.n[b] = 1;
-        N.n1[b] = 0;
-        N.s1[b] = 1;
-        N.j[b] = 0;
-        N.v[b] = v;
-        N.i[b] = 0;
-        N.leaf[b] = 0;
-        N.depth[b] = 0;
-        N.done[b] = 0;
-        N.diverged[b] = 0;
-    }
+    const int v = nuts_start(D, N, b, g, kin);
     __syncthreads();
     nuts_launch_leaf<Dense>(D, N, b, v, xs);
 }
 
 // One round: the gradient kernels have run at the position the drift reached.  Finish the leapfrog step (second half kick),
-// book the leaf, decide, and send the next leaf on its way -- or mark the chain done.
+// book the leaf, decide, and send the next leaf on its way -- or mark the chain done (nuts_book_leaf, nuts_decide: nuts_device.hpp).
 template <bool Dense>
 __global__ __launch_bounds__(256) void k_nuts_step(HmcDev D, NutsDev N, uint64_t seed, int64_t chain0, uint64_t transition, int max_depth,
                                                    int* __restrict__ active)
 {
     __shared__ double red[4];
     __shared__ double xs[Dense ? kHmcDenseMaxDim : 1];
-    __shared__ int flag;
     const int64_t b = blockIdx.x;
     if (N.done[b]) return;                                          // workgroup-uniform
     const int64_t o = b * D.dim;
+    const Rng rng = mh_rng(seed, chain0 + b, transition);
     const int v = N.v[b], j = N.j[b], i = N.i[b];
     const double e = D.eps[b] * (double)v;
     double* eq = (v < 0 ? N.qm : N.qp) + o;
@@ -200,7 +161,7 @@ __global__ __launch_bounds__(256) void k_nuts_step(HmcDev D, NutsDev N, uint64_t
     // ---- the new leaf: gradient from the kernels' outputs, second half kick, ln target; it becomes the tree's edge
     double kin = 0.0;
     for (int k = threadIdx.x; k < D.dim; k += blockDim.x) {
-        const double g = nuts_grad_entry(D, b, D.pos_field[k], D.pos_index[k]);
+        const double g = hmc_grad_entry(D, b, D.pos_field[k], D.pos_index[k]);
         const double p = D.p[o + k] + 0.5 * e * g;
         if constexpr (!Dense) kin += p * p * D.inv_mass[k];
         eq[k] = D.q[o + k];
@@ -217,39 +178,7 @@ __global__ __launch_bounds__(256) void k_nuts_step(HmcDev D, NutsDev N, uint64_t
         }
     }
     kin = 0.5 * nuts_block_sum(kin, red);
-    double lp;
-    {
-        const double* H = D.H + b * D.ld;
-        const double* R = D.R + b * D.ld;
-        const int l = 1, r = D.root_right;
-        const double root_branch = D.sc[2 * D.batch + b] * D.sc[3 * D.batch + b] * ((H[0] - H[l]) * R[l] + (H[0] - H[r]) * R[r]);
-        lp = D.lp[b] + D.ll[b] + log(1.0 / root_branch);           // prior x likelihood x jacobianRootBranch (app/Hamiltonian.hs:85-92)
-    }
-    double joint = lp - kin;
-    if (!isfinite(joint)) joint = -INFINITY;                        // left the support / diverged: not admissible
-    const double log_u = N.log_u[b];
-    const bool nl = log_u <= joint;
-    const bool sl = log_u < NUTS_DELTA_MAX + joint;
-    int n1 = N.n1[b] + (nl ? 1 : 0);
-    bool s1 = N.s1[b] != 0 && sl;
-    if (!sl && threadIdx.x == 0) N.diverged[b] = 1;                 // what the sample recorder reports (k_hmc_record.hip)
-    const int leaf = N.leaf[b];
-    if (nl) {                                                       // reservoir over the admissible leaves of the sub tree
-        double ua, ub;
-        philox_block(mh_rng(seed, chain0 + b, transition), 0x100000u + (uint32_t)leaf, ua, ub);
-        if (ua * (double)n1 < 1.0) {
-            for (int k = threadIdx.x; k < D.dim; k += blockDim.x) {
-                N.qc[o + k] = eq[k];
-                N.gc[o + k] = eg[k];
-            }
-            if (threadIdx.x == 0) N.lpc[b] = lp;
-        }
-    }
-    if (threadIdx.x == 0) {
-        const double d = joint - N.joint0[b];
-        N.alpha[b] += fmin(1.0, exp(fmin(0.0, d)));
-        N.n_alpha[b] += 1;
-    }
+    NutsLeaf L = nuts_book_leaf(D, N, b, rng, hmc_ln_target(D, b), kin, eq, eg);
     // ---- aligned sub trees: leaf i opens those of 2^k leaves with i % 2^k == 0 and closes those with (i + 1) % 2^k == 0
     for (int k = 1; k <= j; ++k) {
         const int size = 1 << k;
@@ -260,57 +189,17 @@ __global__ __launch_bounds__(256) void k_nuts_step(HmcDev D, NutsDev N, uint64_t
                 lq[c] = eq[c];
                 lr[c] = ep[c];
             }
-        } else if (((i + 1) & (size - 1)) == 0 && s1) {
+        } else if (((i + 1) & (size - 1)) == 0 && L.s1) {
             __syncthreads();
             // in time order: going forwards the first leaf is the minus end, going backwards the plus end
             const bool ok = v > 0 ? nuts_no_u_turn<Dense>(D, lq, lr, eq, ep, red, xs) : nuts_no_u_turn<Dense>(D, eq, ep, lq, lr, red, xs);
-            s1 = s1 && ok;
+            L.s1 = L.s1 && ok;
         }
     }
     __syncthreads();
-    // ---- decide
-    int done = 0, jn = j, vn = v, in_ = i + 1, n = N.n[b];
-    if (!s1) {
-        done = 1;                                                   // the sub tree is abandoned, the proposal stays
-        jn = j + 1;
-    } else if (in_ == (1 << j)) {                                   // sub tree complete: biased progressive choice, U-turn of the whole tree
-        double ua, ub;
-        philox_block(mh_rng(seed, chain0 + b, transition), 0x11u + 2u * (uint32_t)j, ua, ub);
-        if (n1 > 0 && ua * (double)n < (double)n1) {
-            for (int k = threadIdx.x; k < D.dim; k += blockDim.x) {
-                N.qn[o + k] = N.qc[o + k];
-                N.gn[o + k] = N.gc[o + k];
-            }
-            if (threadIdx.x == 0) N.lpn[b] = N.lpc[b];
-        }
-        n += n1;
-        __syncthreads();
-        const bool s = nuts_no_u_turn<Dense>(D, N.qm + o, N.pm + o, N.qp + o, N.pp + o, red, xs);
-        jn = j + 1;
-        if (!s || jn >= max_depth) {
-            done = 1;
-        } else {
-            vn = nuts_direction(seed, chain0 + b, transition, jn);
-            in_ = 0;
-            n1 = 0;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        N.n[b] = n;
-        N.n1[b] = n1;
-        N.s1[b] = s1 ? 1 : 0;
-        N.j[b] = jn;
-        N.v[b] = vn;
-        N.i[b] = in_;
-        N.leaf[b] = leaf + 1;
-        N.done[b] = done;
-        N.depth[b] = jn;
-        if (!done) atomicAdd(active, 1);
-        flag = done;
-    }
-    __syncthreads();
-    if (!flag) nuts_launch_leaf<Dense>(D, N, b, vn, xs);
+    const int vn = nuts_decide(D, N, b, rng, max_depth, v, j, i, L,
+                               [&] { return nuts_no_u_turn<Dense>(D, N.qm + o, N.pm + o, N.qp + o, N.pp + o, red, xs); }, active, nullptr);
+    if (vn) nuts_launch_leaf<Dense>(D, N, b, vn, xs);
 }
 
 // End of a transition: the proposal becomes the chain's state (position, gradient and ln target with it)
@@ -322,7 +211,7 @@ __global__ __launch_bounds__(256) void k_nuts_end(HmcDev D, NutsDev N)
         const double q = N.qn[o + k];
         D.q[o + k] = q;
         D.grad[o + k] = N.gn[o + k];
-        *nuts_state_slot(D, b, D.pos_field[k], D.pos_index[k]) = q;
+        *hmc_state_slot(D, b, D.pos_field[k], D.pos_index[k]) = q;
     }
     if (threadIdx.x == 0) D.value[b] = N.lpn[b];
 }

@@ -1,7 +1,8 @@
 // k_nuts_across.hip -- the device NUTS (k_nuts.hip) under a dense metric in the across-chains form (mcd_hmc_set_metric_form): k_nuts_begin
 // and k_nuts_step split at the products with C and U^-1, which leave the chain's workgroup and become rows of k_metric_gemm.hip's one
-// product over the lock-step chains.  Definitions, random streams, slice, doubling, reservoir, merge, divergence test and the order of
-// the U-turn tests are k_nuts.hip's; only where a product's numbers come from differs.  One transition (hmc_capi.cpp):
+// product over the lock-step chains.  Random streams, start of a transition, booking of a leaf and the decision are the functions of
+// nuts_device.hpp that k_nuts.hip calls too (nuts_normal, nuts_tree_init, nuts_start, nuts_book_leaf, nuts_decide); here is only where a
+// product's numbers come from, and the stack levels opened in k_nutsx_leaf and closed in k_nutsx_book.  One transition (hmc_capi.cpp):
 //
 //     k_nutsx_draw           Z = the normal draws 0x4000 + k / 2                           (one thread per chain and coordinate)
 //     gemm (lower)           P = Z U^-1 rows, i.e. p = U^-T z
@@ -38,10 +39,7 @@ __global__ __launch_bounds__(256) void k_nutsx_draw(HmcDev D, double* __restrict
     if (i >= D.batch * D.dim) return;
     const int64_t b = i / D.dim;
     const int k = (int)(i - b * D.dim);
-    double ua, ub;
-    philox_block(mh_rng(seed, chain0 + b, transition), 0x4000u + (uint32_t)(k >> 1), ua, ub);
-    const double rad = sqrt(-2.0 * log(ua)), ang = 6.28318530717958647692 * ub;
-    Z[i] = (k & 1) ? rad * sin(ang) : rad * cos(ang);
+    Z[i] = nuts_normal(mh_rng(seed, chain0 + b, transition), k);
 }
 
 // the edge that is extended next: its half-kicked momentum goes to D.p (the right-hand side of the drift's product), its gradient to D.grad
@@ -66,43 +64,14 @@ __global__ __launch_bounds__(256) void k_nutsx_begin(HmcDev D, NutsDev N, const 
     __shared__ double red[4];
     const int64_t b = blockIdx.x;
     const int64_t o = b * D.dim;
-    const Rng g = mh_rng(seed, chain0 + b, transition);
     double kin = 0.0;
     for (int k = threadIdx.x; k < D.dim; k += blockDim.x) {
         const double p = P[o + k];
         kin += p * CP[o + k];
-        const double q = D.q[o + k], gr = D.grad[o + k];
-        N.qm[o + k] = q;
-        N.qp[o + k] = q;
-        N.pm[o + k] = p;
-        N.pp[o + k] = p;
-        N.gm[o + k] = gr;
-        N.gp[o + k] = gr;
-        N.qn[o + k] = q;
-        N.gn[o + k] = gr;
+        nuts_tree_init(D, N, o + k, p);
     }
     kin = 0.5 * nuts_block_sum(kin, red);
-    const double joint0 = D.value[b] - kin;
-    double us, ub2;
-    philox_block(g, 1u, us, ub2);
-    const int v = nuts_direction(seed, chain0 + b, transition, 0);
-    if (threadIdx.x == 0) {
-        N.joint0[b] = joint0;
-        N.log_u[b] = joint0 + log(us);
-        N.lpn[b] = D.value[b];
-        N.alpha[b] = 0.0;
-        N.n_alpha[b] = 0;
-        N.n[b] = 1;
-        N.n1[b] = 0;
-        N.s1[b] = 1;
-        N.j[b] = 0;
-        N.v[b] = v;
-        N.i[b] = 0;
-        N.leaf[b] = 0;
-        N.depth[b] = 0;
-        N.done[b] = 0;
-        N.diverged[b] = 0;
-    }
+    const int v = nuts_start(D, N, b, mh_rng(seed, chain0 + b, transition), kin);
     __syncthreads();
     nutsx_next_edge(D, N, b, v);
 }
@@ -120,7 +89,7 @@ __global__ __launch_bounds__(256) void k_nutsx_drift(HmcDev D, NutsDev N, const 
     const double e = D.eps[b] * (double)v;
     const double q = (v < 0 ? N.qm : N.qp)[i] + e * Y[i];            // q += eps (C p)
     D.q[i] = q;
-    *nuts_state_slot(D, b, D.pos_field[k], D.pos_index[k]) = q;
+    *hmc_state_slot(D, b, D.pos_field[k], D.pos_index[k]) = q;
 }
 
 // (a) of a round: the gradient kernels have run at the position the drift reached.  Second half kick; the leaf becomes the tree's edge and
@@ -136,7 +105,7 @@ __global__ __launch_bounds__(256) void k_nutsx_leaf(HmcDev D, NutsDev N, double*
     const int64_t B = D.batch;
     const int v = N.v[b], j = N.j[b], i = N.i[b];
     const double e = D.eps[b] * (double)v;
-    const double g = nuts_grad_entry(D, b, D.pos_field[k], D.pos_index[k]);
+    const double g = hmc_grad_entry(D, b, D.pos_field[k], D.pos_index[k]);
     const double p = D.p[t] + 0.5 * e * g;
     const double q = D.q[t];
     (v < 0 ? N.qm : N.qp)[t] = q;
@@ -173,15 +142,15 @@ __device__ __forceinline__ bool nutsx_no_u_turn(int dim, const double* w, const 
 }
 
 // (c) of a round: Y holds the products of the right-hand sides k_nutsx_leaf wrote.  Book the leaf, decide, and prepare the next leaf -- or
-// mark the chain done.  A workgroup per chain; k_nuts_step's code with the products read from Y.
+// mark the chain done.  A workgroup per chain; k_nuts_step's round (nuts_book_leaf, nuts_decide: nuts_device.hpp) with the products read from Y.
 __global__ __launch_bounds__(256) void k_nutsx_book(HmcDev D, NutsDev N, const double* __restrict__ Y, uint64_t seed, int64_t chain0, uint64_t transition,
                                                     int max_depth, int* __restrict__ active, int* __restrict__ list)
 {
     __shared__ double red[4];
-    __shared__ int flag;
     const int64_t b = blockIdx.x;
     if (N.done[b]) return;                                          // workgroup-uniform
     const int64_t o = b * D.dim, B = D.batch;
+    const Rng rng = mh_rng(seed, chain0 + b, transition);
     const int v = N.v[b], j = N.j[b], i = N.i[b];
     const double* eq = (v < 0 ? N.qm : N.qp) + o;
     const double* ep = (v < 0 ? N.pm : N.pp) + o;
@@ -190,91 +159,19 @@ __global__ __launch_bounds__(256) void k_nutsx_book(HmcDev D, NutsDev N, const d
     double kin = 0.0;                                               // 1/2 p^T C p
     for (int k = threadIdx.x; k < D.dim; k += blockDim.x) kin += ep[k] * Y[o + k];
     kin = 0.5 * nuts_block_sum(kin, red);
-    double lp;
-    {
-        const double* H = D.H + b * D.ld;
-        const double* R = D.R + b * D.ld;
-        const int l = 1, r = D.root_right;
-        const double root_branch = D.sc[2 * D.batch + b] * D.sc[3 * D.batch + b] * ((H[0] - H[l]) * R[l] + (H[0] - H[r]) * R[r]);
-        lp = D.lp[b] + D.ll[b] + log(1.0 / root_branch);           // prior x likelihood x jacobianRootBranch (app/Hamiltonian.hs:85-92)
-    }
-    double joint = lp - kin;
-    if (!isfinite(joint)) joint = -INFINITY;                        // left the support / diverged: not admissible
-    const double log_u = N.log_u[b];
-    const bool nl = log_u <= joint;
-    const bool sl = log_u < NUTS_DELTA_MAX + joint;
-    int n1 = N.n1[b] + (nl ? 1 : 0);
-    bool s1 = N.s1[b] != 0 && sl;
-    if (!sl && threadIdx.x == 0) N.diverged[b] = 1;
-    const int leaf = N.leaf[b];
-    if (nl) {                                                       // reservoir over the admissible leaves of the sub tree
-        double ua, ub;
-        philox_block(mh_rng(seed, chain0 + b, transition), 0x100000u + (uint32_t)leaf, ua, ub);
-        if (ua * (double)n1 < 1.0) {
-            for (int k = threadIdx.x; k < D.dim; k += blockDim.x) {
-                N.qc[o + k] = eq[k];
-                N.gc[o + k] = eg[k];
-            }
-            if (threadIdx.x == 0) N.lpc[b] = lp;
-        }
-    }
-    if (threadIdx.x == 0) {
-        const double d = joint - N.joint0[b];
-        N.alpha[b] += fmin(1.0, exp(fmin(0.0, d)));
-        N.n_alpha[b] += 1;
-    }
+    NutsLeaf L = nuts_book_leaf(D, N, b, rng, hmc_ln_target(D, b), kin, eq, eg);
     // ---- the aligned sub trees the leaf closes, smallest first
     for (int lvl = 1; lvl <= plan.closes; ++lvl) {
-        if (!s1) break;
+        if (!L.s1) break;
         const double* lr = N.sp + ((int64_t)b * N.max_depth + (lvl - 1)) * D.dim;
         const double* w = Y + ((int64_t)lvl * B + b) * D.dim;
         const bool ok = v > 0 ? nutsx_no_u_turn(D.dim, w, lr, ep, red) : nutsx_no_u_turn(D.dim, w, ep, lr, red);
-        s1 = s1 && ok;
+        L.s1 = L.s1 && ok;
     }
     __syncthreads();
-    // ---- decide
-    int done = 0, jn = j, vn = v, in_ = i + 1, n = N.n[b];
-    if (!s1) {
-        done = 1;                                                   // the sub tree is abandoned, the proposal stays
-        jn = j + 1;
-    } else if (in_ == (1 << j)) {                                   // sub tree complete: biased progressive choice, U-turn of the whole tree
-        double ua, ub;
-        philox_block(mh_rng(seed, chain0 + b, transition), 0x11u + 2u * (uint32_t)j, ua, ub);
-        if (n1 > 0 && ua * (double)n < (double)n1) {
-            for (int k = threadIdx.x; k < D.dim; k += blockDim.x) {
-                N.qn[o + k] = N.qc[o + k];
-                N.gn[o + k] = N.gc[o + k];
-            }
-            if (threadIdx.x == 0) N.lpn[b] = N.lpc[b];
-        }
-        n += n1;
-        __syncthreads();
-        const bool s = nutsx_no_u_turn(D.dim, Y + ((int64_t)(plan.closes + 1) * B + b) * D.dim, N.pm + o, N.pp + o, red);
-        jn = j + 1;
-        if (!s || jn >= max_depth) {
-            done = 1;
-        } else {
-            vn = nuts_direction(seed, chain0 + b, transition, jn);
-            in_ = 0;
-            n1 = 0;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        N.n[b] = n;
-        N.n1[b] = n1;
-        N.s1[b] = s1 ? 1 : 0;
-        N.j[b] = jn;
-        N.v[b] = vn;
-        N.i[b] = in_;
-        N.leaf[b] = leaf + 1;
-        N.done[b] = done;
-        N.depth[b] = jn;
-        if (!done) list[atomicAdd(active, 1)] = (int)b;                // at most batch entries: one per chain
-        flag = done;
-    }
-    __syncthreads();
-    if (!flag) nutsx_next_edge(D, N, b, vn);
+    const int vn = nuts_decide(D, N, b, rng, max_depth, v, j, i, L,
+                               [&] { return nutsx_no_u_turn(D.dim, Y + ((int64_t)(plan.closes + 1) * B + b) * D.dim, N.pm + o, N.pp + o, red); }, active, list);
+    if (vn) nutsx_next_edge(D, N, b, vn);
 }
 
 static unsigned nutsx_grid(const HmcDev& D) { return (unsigned)((D.batch * D.dim + 255) / 256); }
