@@ -42,6 +42,11 @@ module McmcDate.GpuSampler
     GpuSampler,
     withGpuSampler,
     runMetropolisHastingsGreenGpu,
+    -- checkpoint and continue (@Settings ... Save@, @continue@, @--init-from-save@)
+    CheckpointMode (..),
+    saveSampler,
+    loadSampler,
+    continueMetropolisHastingsGreenGpu,
     runMarginalLikelihoodGpu,
     runRecorded,
     recordSummary,
@@ -219,6 +224,17 @@ foreign import ccall unsafe "mcd_mh_detach_hamiltonian"
 
 foreign import ccall unsafe "mcd_mh_hamiltonian_stats"
   c_mh_hamiltonian_stats :: Ptr McdMh -> Ptr Int64 -> Ptr CDouble -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> CInt -> IO CInt
+
+-- checkpoint and continue (@Settings ... Save@ and @continue@, app/Main.hs:494-509; @--init-from-save@, :424-440): the handle between two
+-- runs as one blob
+foreign import ccall unsafe "mcd_mh_save_size"
+  c_mh_save_size :: Ptr McdMh -> Ptr Int64 -> IO CInt
+
+foreign import ccall safe "mcd_mh_save"
+  c_mh_save :: Ptr McdMh -> Ptr Word8 -> Int64 -> Ptr Int64 -> IO CInt
+
+foreign import ccall safe "mcd_mh_load"
+  c_mh_load :: Ptr McdMh -> Ptr Word8 -> Int64 -> CInt -> IO CInt
 
 check :: String -> CInt -> IO ()
 check _ 0 = pure ()
@@ -517,6 +533,41 @@ runMetropolisHastingsGreenGpu s g burnInPeriods iterations period onSample = do
           i <- VSM.read it 0
           when (k == period) (getStates s >>= onSample i)
           go (left - k)
+
+-- | What a load takes from a blob: everything (@continue@, app/Main.hs:494-509) or states, posterior terms and tuning parameters only
+-- (@--init-from-save@, @mhgLoadUnsafe@, :424-440; MCD_CKPT_FULL / MCD_CKPT_STATE_TUNING of the header).
+data CheckpointMode = CheckpointFull | CheckpointStateAndTuning
+
+-- | The sampler between two runs as one blob (mcd_mh_save): state, posterior terms, temperatures, tuning parameters and counters, age sums,
+-- the step counter of the random streams, the recorder's counts.  The host writes it beside its own generator @g@ and iteration count, as
+-- @mcmc@ does with @Settings ... Save@.  The chains do not change.
+saveSampler :: GpuSampler -> IO (VS.Vector Word8)
+saveSampler s = do
+  n <- alloca $ \pn -> (check "mcd_mh_save_size" =<< c_mh_save_size (gsHandle s) pn) >> peek pn
+  buf <- VSM.new (fromIntegral n)
+  VSM.unsafeWith buf $ \p -> alloca $ \pw -> check "mcd_mh_save" =<< c_mh_save (gsHandle s) p n pw
+  VS.unsafeFreeze buf
+
+-- | The blob of 'saveSampler' into a sampler made by the same 'withGpuSampler' call (tree, likelihood, prior, table, chains, seed): no
+-- 'setStates' is needed.  A refused blob (the error names the mismatch) leaves the sampler untouched.
+loadSampler :: GpuSampler -> CheckpointMode -> VS.Vector Word8 -> IO ()
+loadSampler s mode blob =
+  VS.unsafeWith blob $ \p ->
+    check "mcd_mh_load" =<< c_mh_load (gsHandle s) p (fromIntegral (VS.length blob)) (case mode of CheckpointFull -> 0; CheckpointStateAndTuning -> 1)
+
+-- | Counterpart of @continueMetropolisHastingsGreen@ (app/Main.hs:494-509): the sampling phase of 'runMetropolisHastingsGreenGpu' goes on
+-- from a blob saved behind @done@ of its iterations, for the @iterations - done@ that are left, on the generator @g@ the host saved beside
+-- it.  The samples are those of the uninterrupted run, bit for bit.
+continueMetropolisHastingsGreenGpu :: StatefulGen g IO => GpuSampler -> g -> VS.Vector Word8 -> Int -> Int -> Int -> (Int -> [I] -> IO ()) -> IO ()
+continueMetropolisHastingsGreenGpu s g blob done iterations period onSample = do
+  loadSampler s CheckpointFull blob
+  go done
+  where
+    go i = when (i < iterations) $ do
+      let k = min period (iterations - i)
+      runBlock s g k True
+      when (k == period) (getStates s >>= onSample (i + k))
+      go (i + k)
 
 -- | Replacement of @runMarginalLikelihood@ (app/Main.hs:511-543: @marginalLikelihood mlS p l c m i g@) over a sampler of nPoints x
 -- replicates chains: chain b runs at the path point b mod nPoints with the target prior x likelihood^beta (mcd_mh_set_power), all points in

@@ -808,6 +808,95 @@ int mcd_glasso(int n, const double* S, double rho, int penalize_diagonal, double
                int64_t* info);
 
 /* ------------------------------------------------------------------------------------------------
+ * Checkpoint and continue (csrc/ckpt_capi.cpp, csrc/k_checkpoint.hip).  Replaces: `Settings ... Save` and the `continue` command
+ * (app/Main.hs:494-509: `mcmc` writes state, tuning, counters, iteration and generator on exit and reloads all of it) and
+ * `--init-from-save` (app/Main.hs:424-440: `mhgLoadUnsafe`, state and tuning only).  Between two calls of mcd_mh_run a handle is described
+ * by a finite list of arrays and counters, because every run derives its kept quantities afresh when it starts; a blob holds that list.
+ * DEFINITION: "one handle, two calls of mcd_mh_run" and "first call, mcd_mh_save, mcd_mh_destroy, the same mcd_mh_create*, mcd_mh_load
+ * (MCD_CKPT_FULL), second call" give the same bits on every launch structure (MCD_MH_PATH_*).
+ * THE CALLER REBUILDS THE CONFIGURATION, as the reference rebuilds its likelihood closure from <prep>.data at every start: tree,
+ * likelihood operands, prior, proposal table, batch, seed, chain offset -- and mcd_mh_record_begin, mcd_mh_mc3_init,
+ * mcd_mh_attach_hamiltonian where the saved handle had them.  The blob carries a FINGERPRINT of it: n_nodes, parent[], batch, the
+ * likelihood's dimension, dense / sparse, n_prop and every row of the proposal table (the bits of kind, node, n1, n2, jac_root, dim, p0, p1),
+ * seed and chain offset.  The likelihood's operands and the prior are NOT hashed: a changed dataset is the caller's to catch, and the saved
+ * posterior terms are not re-checked against the rebuilt likelihood.
+ * The blob: little-endian 8-byte words; a fixed header (magic, version, header bytes, total bytes, the configuration), a section table of
+ * (id, offset, bytes, checksum), a checksum of the header, then the sections (MCD_CKPT_SEC_*), each a multiple of 8 bytes with zero padding.
+ * It carries: the state sc[5][batch], heights and rates (n_nodes of every row), post[3][batch] and the prior's blocks [batch][3] AS THEY LIE
+ * (never recomputed: on the incremental paths the kept ln likelihood is another rounding of what mcd_mh_set_state would evaluate), the
+ * temperatures and the power-posterior bit, tuning parameters and their counters, the age sums with their sample count, the step counter
+ * (the random streams' position), the recorder's counts, and, where the handle has them, MC3's rank table, swap counters and phase and the
+ * attached Hamiltonian's next transition number, sums, step sizes and inverse masses.  The recorder's ring and an mcd_hmc_t's dense metric
+ * (mcd_hmc_get_metric / mcd_hmc_set_metric) are not in it.  Two saves of an untouched handle give the same bytes.
+ *   mcd_mh_save_size   *bytes of the blob mcd_mh_save would write now: 8 (17 + 4 S) header bytes for S sections + 384 + 8 (12 B + 4 B n_nodes
+ *                      + B P + 2 ceil(B P / 2)) for B chains and P proposals (S = 12); MC3 adds 8 (ceil(total / 2) + 2 (n_chains - 1)) and
+ *                      S + 3, an attachment 8 (5 B [+ dim]) and S + 2 [+ 1].
+ *   mcd_mh_save        ONE launch gathers every section into a staging blob on the device and forms its checksum (k_ckpt_pack), ONE copy
+ *                      brings it to buf; the chains do not change (a handle that saved runs the bits of one that did not).  cap too small:
+ *                      MCD_ERR_INVALID_ARG, the needed size in the message and in *written.  Samples waiting in the recorder's ring: refused
+ *                      (MCD_ERR_INVALID_ARG; fetch them with mcd_mh_record_fetch first); so is a handle without a state.
+ *   mcd_mh_load        flags = MCD_CKPT_FULL: the fingerprint must match; every array and counter above is restored and the handle has a
+ *                      state without mcd_mh_set_state.  A handle with an active recorder of the blob's period continues its period phase
+ *                      (another period is refused; a handle without a recorder ignores the counts).  A blob with MC3 needs mcd_mh_mc3_init
+ *                      done with the same n_chains, total, ladder and seed, a blob with an attachment an attachment of the same max_depth,
+ *                      seed and inv_mass presence; either without the other is refused.
+ *                      flags = MCD_CKPT_STATE_TUNING (`--init-from-save`): only n_nodes, topology, batch and n_prop must match; state,
+ *                      posterior terms and tuning parameters are taken, the tuning counters zeroed; step counter, seed, temperatures, sums,
+ *                      recorder, MC3 and attachment stay the handle's own.
+ *                      One copy to the device, a launch that recomputes every section's checksum (k_ckpt_verify), and only when the host
+ *                      found them equal the launch that scatters the sections (k_ckpt_unpack): EVERY refusal leaves the handle untouched,
+ *                      MCD_ERR_INVALID_ARG with the mismatch named in mcd_last_error() -- bad magic, a truncated buffer, len other than the
+ *                      blob's total bytes, an unknown version, a failed checksum, a configuration that differs.
+ *   mcd_ckpt_inspect   pure host code, no device needed: the header of a blob, after the checks above and every section's checksum.
+ *   mcd_ckpt_checksum  the checksum of n_words 8-byte words: sum_i mix(w_i XOR (i + 1) 0x9E3779B97F4A7C15) mod 2^64, mix the splitmix64
+ *                      finaliser; the host restatement of what the kernels add up with integer atomics (any order, the same word).
+ */
+#define MCD_CKPT_FULL 0
+#define MCD_CKPT_STATE_TUNING 1
+#define MCD_CKPT_MAX_SECTIONS 24
+#define MCD_CKPT_FLAG_DENSE 1u
+#define MCD_CKPT_FLAG_MC3 2u
+#define MCD_CKPT_FLAG_HAMILTONIAN 4u
+#define MCD_CKPT_FLAG_INV_MASS 8u
+#define MCD_CKPT_FLAG_RECORDER 16u
+#define MCD_CKPT_FLAG_POWER 32u
+#define MCD_CKPT_SEC_META 1        /* 48 words: the counters the handle keeps on the host */
+#define MCD_CKPT_SEC_SC 2          /* [5][batch] birth, death, tH, rMu, rVar */
+#define MCD_CKPT_SEC_HEIGHTS 3     /* [batch][n_nodes] */
+#define MCD_CKPT_SEC_RATES 4       /* [batch][n_nodes] */
+#define MCD_CKPT_SEC_POST 5        /* [3][batch] */
+#define MCD_CKPT_SEC_PCOMP 6       /* [batch][3] */
+#define MCD_CKPT_SEC_BETA 7        /* [batch] */
+#define MCD_CKPT_SEC_TUNE 8        /* [batch][n_prop] */
+#define MCD_CKPT_SEC_ACCEPTED 9    /* [batch][n_prop] int32 */
+#define MCD_CKPT_SEC_TRIED 10      /* [batch][n_prop] int32 */
+#define MCD_CKPT_SEC_AGE_SUM 11    /* [batch][n_nodes] */
+#define MCD_CKPT_SEC_AGE_SQ 12     /* [batch][n_nodes] */
+#define MCD_CKPT_SEC_MC3_RANK 13   /* [total] int32 */
+#define MCD_CKPT_SEC_MC3_TRIED 14  /* [n_chains - 1] int64 */
+#define MCD_CKPT_SEC_MC3_ACCEPTED 15
+#define MCD_CKPT_SEC_HAM_SUMS 16   /* [4][batch]: alpha (double), depth, leapfrog steps, divergent (int64) */
+#define MCD_CKPT_SEC_HAM_EPS 17    /* [batch] */
+#define MCD_CKPT_SEC_HAM_INV_MASS 18 /* [dim] */
+typedef struct mcd_ckpt_info {
+    int32_t version, n_sections;
+    int64_t header_bytes, total_bytes;
+    uint32_t flags; /* MCD_CKPT_FLAG_* */
+    int32_t n_nodes, n_prop, dim, dense;
+    int64_t batch, chain0;
+    uint64_t seed, step;
+    uint64_t topology, table, fingerprint; /* hashes of parent[], of the proposal table, of the whole configuration */
+    int32_t section_id[MCD_CKPT_MAX_SECTIONS];
+    int64_t section_offset[MCD_CKPT_MAX_SECTIONS], section_bytes[MCD_CKPT_MAX_SECTIONS];
+    uint64_t section_checksum[MCD_CKPT_MAX_SECTIONS];
+} mcd_ckpt_info_t;
+int mcd_mh_save_size(const mcd_mh_t* m, int64_t* bytes);
+int mcd_mh_save(mcd_mh_t* m, void* buf, int64_t cap, int64_t* written);
+int mcd_mh_load(mcd_mh_t* m, const void* buf, int64_t len, int flags);
+int mcd_ckpt_inspect(const void* buf, int64_t len, mcd_ckpt_info_t* info);
+uint64_t mcd_ckpt_checksum(const void* words, int64_t n_words);
+
+/* ------------------------------------------------------------------------------------------------
  * Multi-GPU.  Chains are independent: every rank (one process per GPU) holds the operands and evaluates its own
  * contiguous block of chains; nothing is exchanged on the likelihood path.  The sampler-level exchange -- the per-chain ln
  * posterior that MC3's swap phase compares (`mc3 (MC3Settings (NChains 4) (SwapPeriod 2) (NSwaps 3))`, app/Main.hs:476-478; in

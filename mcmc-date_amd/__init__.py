@@ -4,7 +4,7 @@ One hot path, hand-written for gfx950, behind the reference's likelihood plugin 
     likelihood_function(lhd, topology)  ~  likelihoodFunction :: LikelihoodData -> LikelihoodFunction I
 (app/Probability.hs:277-281).  See DESIGN.md and include/mcmcdate_mvn.h.
 """
-from . import _capi, diagnostics, monitor
+from . import _capi, checkpoint, diagnostics, monitor
 from ._capi import McdError, NoDevice, NotPositiveDefinite, RootNotBifurcating, get_option, set_option
 from .likelihood import (Full, LikelihoodData, MvnLikelihood, set_logpdf_form, NoData, Sparse, SparseLikelihood, SparseTreeLikelihood, TreeLikelihood, Univariate,
                          jacobian_root_branch, likelihood_function, read_data_file, write_data_file)
@@ -30,7 +30,7 @@ __all__ = [
     "load_braces", "get_mean_root_height",
     "MC3", "Proposal", "Sampler", "cycle_schedule", "init_with", "proposals", "table_arrays", "weight_n_branches",
     "Leapfrog", "hmc_transition", "nuts_transition", "nuts_warmup", "run_cycle_with_nuts", "DualAveraging", "shrunk_covariance", "metric_factors", "get_mask", "to_vector", "from_vector_with", "grad_to_vector", "target_grad",
-    "diagnostics", "Summary", "RecordSummary", "split_rhat", "ess", "summary", "trace_summary",
+    "checkpoint", "diagnostics", "Summary", "RecordSummary", "split_rhat", "ess", "summary", "trace_summary",
     "MarginalLikelihood", "MarginalLikelihoodEstimate", "marginal_likelihood", "marginal_likelihood_device", "power_posterior_points",
     "graphical_lasso", "graphical_lasso_device", "glasso_components",
     "McdError", "NotPositiveDefinite", "RootNotBifurcating", "NoDevice", "set_option", "get_option",

@@ -145,7 +145,31 @@ SYMBOLS = {
     "mcd_hmc_record_end": (C.c_int, [_vp]),
     "mcd_hmc_record_quantities": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "mcd_hmc_record_summary": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64), _dp, _dp, _dp]),
+    "mcd_mh_save_size": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    "mcd_mh_save": (C.c_int, [_vp, _vp, C.c_int64, C.POINTER(C.c_int64)]),
+    "mcd_mh_load": (C.c_int, [_vp, _vp, C.c_int64, C.c_int]),
+    "mcd_ckpt_inspect": (C.c_int, [_vp, C.c_int64, _vp]),
+    "mcd_ckpt_checksum": (C.c_uint64, [_vp, C.c_int64]),
 }
+MCD_CKPT_FULL = 0
+MCD_CKPT_STATE_TUNING = 1
+MCD_CKPT_MAX_SECTIONS = 24
+
+
+class CkptInfo(C.Structure):
+    """mcd_ckpt_info_t (include/mcmcdate_mvn.h): what mcd_ckpt_inspect fills."""
+    _fields_ = [("version", C.c_int32), ("n_sections", C.c_int32), ("header_bytes", C.c_int64), ("total_bytes", C.c_int64), ("flags", C.c_uint32),
+                ("n_nodes", C.c_int32), ("n_prop", C.c_int32), ("dim", C.c_int32), ("dense", C.c_int32), ("batch", C.c_int64), ("chain0", C.c_int64),
+                ("seed", C.c_uint64), ("step", C.c_uint64), ("topology", C.c_uint64), ("table", C.c_uint64), ("fingerprint", C.c_uint64),
+                ("section_id", C.c_int32 * MCD_CKPT_MAX_SECTIONS), ("section_offset", C.c_int64 * MCD_CKPT_MAX_SECTIONS),
+                ("section_bytes", C.c_int64 * MCD_CKPT_MAX_SECTIONS), ("section_checksum", C.c_uint64 * MCD_CKPT_MAX_SECTIONS)]
+
+
+def ckpt_inspect(blob: bytes) -> CkptInfo:
+    """mcd_ckpt_inspect of the C blob (pure host code: no device is needed); raises McdError with the reason for a blob it refuses."""
+    info = CkptInfo()
+    check(lib().mcd_ckpt_inspect(C.c_char_p(bytes(blob)), len(blob), C.byref(info)))
+    return info
 
 
 class McdError(RuntimeError):

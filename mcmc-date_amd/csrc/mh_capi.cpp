@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/mcmcdate_mvn.h"
+#include "ckpt_device.hpp"
 #include "handover_device.hpp"
 #include "mvn_kernels.h"
 #include "nuts_rhs_plan.hpp"
@@ -72,6 +73,7 @@ struct mcd_mh {
     double* d_inc_ll = nullptr;     // [batch] ln likelihood output of the refreshing full products (not used)
     mcd::MhInc inc{};               // incremental likelihood of that path (k_mh_inc.hip): X0, zcur, zprop allocated on first use
     std::vector<mcd::MhRow> rows;   // host copy of the proposal table
+    std::vector<int32_t> dims;      // ... and of its dimension column (the checkpoint's fingerprint, ckpt_capi.cpp)
     double* d_psum = nullptr;           // k_mh_step_wg's kept summands of the ln prior (MhDev::psum, psel)
     int32_t* d_psel = nullptr;
     std::vector<int32_t> sparse_rows;   // per row: 1 = moves at most kMhIncSlots distances (the two-launch path's incremental evaluation)
@@ -89,6 +91,9 @@ struct mcd_mh {
     // Metropolis-coupled MCMC (mcd_mh_mc3_*): temperature ranks of all GLOBAL chains, ladder, counters; phase = swap phases done
     mcd::Mc3Dev mc3{};
     uint64_t mc3_seed = 0, mc3_phase = 0;
+    std::vector<double> mc3_ladder;           // host copy of the ladder (what a checkpoint's MC3 must agree with)
+    void* d_ckpt = nullptr;                   // the checkpoint's staging blob (mcd_mh_save / mcd_mh_load), one of `allocs`
+    size_t ckpt_cap = 0;
     mcd::Recorder rec{"mcd_mh_record"};       // the sample recorder (mcd_mh_record_*, recorder.cpp): it counts iterations
     const int32_t* host_parent = nullptr;     // [n_nodes] the likelihood handle's host copy of the topology (hand-overs compare it)
     mutable hipEvent_t mark = nullptr;        // what another handle's stream waits for (mcd_mh_chains_), created on first use
@@ -339,6 +344,7 @@ int mh_create_impl(mcd_mh_t** out, std::unique_ptr<mcd_mh>& m, const mcd_prior_t
     m->seed = seed;
     m->host_parent = parent;
     for (int i = 0; i < n_prop; ++i) m->rows.push_back(mcd::MhRow{kind[i], node[i], n1[i], n2[i], jac_root[i], p0[i], p1[i]});
+    m->dims.assign(dim, dim + n_prop);
     MHIP_TRY(hipSetDevice(m->device));
     MHIP_TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
     mcd::MhDev& D = m->dev;
@@ -541,6 +547,7 @@ int mcd_mh_mc3_init(mcd_mh_t* m, int n_chains, const double* betas, int64_t tota
     m->dev.lik_only = 0;
     m->mc3_seed = seed;
     m->mc3_phase = 0;
+    m->mc3_ladder.assign(betas, betas + n_chains);
     return MCD_OK;
 }
 
@@ -622,6 +629,56 @@ int mcd_mh_chains_(const mcd_mh* m, mcd::ChainsView* v, hipEvent_t* mark)
         if (!m->mark) MHIP_TRY(hipEventCreateWithFlags(&m->mark, hipEventDisableTiming));
         MHIP_TRY(hipEventRecord(m->mark, m->stream));
         *mark = m->mark;
+    }
+    return MCD_OK;
+}
+
+// ---- what the checkpoint calls need of the handle (ckpt_device.hpp, ckpt_capi.cpp) ------------------------------------------------------
+int mcd_mh_ckpt_view_(const mcd_mh* m, mcd::CkptView* v)
+{
+    if (!m || !v) return mfail(MCD_ERR_INVALID_ARG, "mcd_mh_ckpt_view_: NULL argument");
+    const mcd::RecCounts& rc = m->rec.counts();
+    const mcd_mh::Hamiltonian& A = m->ham;
+    *v = mcd::CkptView{m->device, m->stream, m->dev, m->mvn != nullptr, m->have_state, m->mvn ? m->mvn->n : m->sp->n, m->seed, m->step, m->n_samples,
+                       m->host_parent, m->rows.data(), m->dims.data(), m->rec.active(), rc.period, rc.iter, rc.fetched, m->mc3, m->mc3_ladder.data(),
+                       m->mc3_seed, m->mc3_phase, A.h != nullptr, A.max_depth, A.h ? mcd_hmc_dim(A.h) : 0, A.seed, A.first + A.done, A.counted, A.d_eps,
+                       A.d_inv_mass, A.d_sums};
+    return MCD_OK;
+}
+
+int mcd_mh_ckpt_stage_(mcd_mh* m, size_t bytes, void** p)
+{
+    if (bytes > m->ckpt_cap) {
+        MHIP_TRY(hipSetDevice(m->device));
+        MHIP_TRY(hipStreamSynchronize(m->stream));                // (nothing of an earlier save or load may still read the old blob)
+        if (m->d_ckpt) {
+            m->allocs.erase(std::find(m->allocs.begin(), m->allocs.end(), m->d_ckpt));
+            (void)hipFree(m->d_ckpt);
+            m->d_ckpt = nullptr;
+            m->ckpt_cap = 0;
+        }
+        unsigned char* d = nullptr;
+        if (int rc = dev_alloc(m, &d, bytes, false)) return rc;
+        m->d_ckpt = d;
+        m->ckpt_cap = bytes;
+    }
+    *p = m->d_ckpt;
+    return MCD_OK;
+}
+
+int mcd_mh_ckpt_commit_(mcd_mh* m, const mcd::CkptCommit& c)
+{
+    m->have_state = true;
+    if (!c.full) return MCD_OK;
+    m->step = c.step;
+    m->n_samples = c.n_samples;
+    m->dev.lik_only = c.lik_only;
+    if (c.rec) m->rec.restore(c.rec_iter, c.rec_fetched);
+    if (m->mc3.n_chains != 0) m->mc3_phase = c.mc3_phase;
+    if (m->ham.h) {
+        m->ham.first = c.ham_next;
+        m->ham.done = 0;
+        m->ham.counted = c.ham_counted;
     }
     return MCD_OK;
 }

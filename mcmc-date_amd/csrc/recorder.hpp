@@ -37,6 +37,9 @@ public:
     // what a launch takes: the ring with `iter0` iterations counted before the launch (MhRec::iter0); base null while inactive
     MhRec view(int64_t iter0 = 0) const { return MhRec{ring_, iter0, c_.cap, c_.period}; }
     void advance(int64_t n) { if (ring_) c_.iter += n; }
+    // a checkpoint's counts (mcd_mh_load): `iter` iterations done and every sample of them handed out, so the period phase continues; the
+    // caller has checked that the period is the ring's and that no sample waits on either side
+    void restore(int64_t iter, int64_t fetched) { if (ring_) { c_.iter = iter; c_.fetched = fetched; } }
     bool step() { advance(1); return ring_ && c_.iter % c_.period == 0; }      // one more iteration; true: it is to be recorded
     // tail_doubles: what a sample carries behind post, per chain -- 1 (beta) or kHmcRecDiag (the transition's diagnostics)
     int begin(const char* who, const RecOn& on, int32_t period, int64_t capacity, int tail_doubles);

@@ -71,19 +71,24 @@ def collect(sampler, n_iter: int, period: int = PERIOD, accumulate: bool = False
     return Trace(np.asarray(its, np.int64), *st)
 
 
-def _record_chunks(driver, total: int, period: int, chunk: int, run):
+def _record_chunks(driver, total: int, period: int, chunk: int, run, begun=None, fetched=None):
     """The loop of `record` and `record_nuts`: the driver's recorder holds what one chunk can add at most; run(k, done) advances the driver
-    by the next k of `total` steps (`done` are behind it), one fetch per chunk.  Returns the six arrays of the fetches, concatenated, or
-    None when nothing was recorded."""
+    by the next k of `total` steps (`done` are behind it), one fetch per chunk.  begun(): called once behind record_begin; fetched(i): behind
+    the fetch of chunk i (1, 2, ...), when the ring is empty.  Returns the six arrays of the fetches, concatenated, or None when nothing was
+    recorded."""
     parts: List[tuple] = []
     driver.record_begin(period, (chunk + period - 1) // period)
     try:
+        if begun is not None:
+            begun()
         done = 0
         while done < total:
             k = min(chunk, total - done)
             run(k, done)
             done += k
             parts.append(driver.record_fetch())
+            if fetched is not None:
+                fetched(len(parts))
     finally:
         driver.record_end()
     if sum(len(p[0]) for p in parts) == 0:
@@ -91,15 +96,31 @@ def _record_chunks(driver, total: int, period: int, chunk: int, run):
     return tuple(np.concatenate([p[i] for p in parts]) for i in range(6))
 
 
-def record(sampler, n_iter: int, period: int = PERIOD, accumulate: bool = False, chunk: int = 256) -> Trace:
+def record(sampler, n_iter: int, period: int = PERIOD, accumulate: bool = False, chunk: int = 256, checkpoint: Optional[str] = None,
+           every: int = 1, resume: Optional[str] = None) -> Trace:
     """`collect` without cutting the run into pieces of one monitor period: the sampler's recorder keeps the samples on the device
     while `chunk` iterations run in one call, and they are fetched once per chunk.  The same samples at the same iterations as
     `collect` (the chains do not depend on how a run is cut, up to the rounding of the incremental likelihood, which every call
-    restarts from a full product), with the posterior terms and the temperatures beside them."""
-    if n_iter < 0 or period < 1 or chunk < 1:
-        raise ValueError("record: need n_iter >= 0, period >= 1, chunk >= 1")
-    base = sampler.iterations_done
-    got = _record_chunks(sampler, n_iter, period, chunk, lambda k, done: sampler.run(k, accumulate=accumulate, chunk=k))
+    restarts from a full product), with the posterior terms and the temperatures beside them.
+    checkpoint: a file that `Sampler.checkpoint` rewrites behind the fetch of every `every`-th chunk, when the ring is empty -- a run that
+    loses its process goes on from there: resume = that file, on a fresh sampler over the same configuration, with the same period and chunk
+    and n_iter the iterations still to run, gives the samples the lost run would have given from the next chunk on, bit for bit, at the
+    same iteration numbers (the recorder's period phase, the cycle's generator and the iteration count are in the file)."""
+    if n_iter < 0 or period < 1 or chunk < 1 or every < 1:
+        raise ValueError("record: need n_iter >= 0, period >= 1, chunk >= 1, every >= 1")
+    base = [sampler.iterations_done]
+
+    def begun():
+        if resume is not None:                      # behind record_begin: the load continues the recorder's counts
+            meta = sampler.restore(resume)
+            base[0] = sampler.iterations_done - meta["rec_iter"]
+
+    def fetched(i):
+        if checkpoint is not None and i % every == 0:
+            sampler.checkpoint(checkpoint)
+
+    got = _record_chunks(sampler, n_iter, period, chunk, lambda k, done: sampler.run(k, accumulate=accumulate, chunk=k), begun, fetched)
+    base = base[0]
     if got is None:
         e = np.empty((0,))
         return Trace(np.empty(0, np.int64), e, e, e, e, e, e, e, e, e)

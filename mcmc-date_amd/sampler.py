@@ -16,12 +16,13 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import _capi
+from . import _capi, checkpoint
 from ._arrays import dp, ip
 from .diagnostics import MarginalLikelihoodEstimate
 from .likelihood import TreeLikelihood
@@ -359,6 +360,63 @@ class Sampler(DriverCalls):
     def reset_age_sums(self):
         _capi.check(_capi.lib().mcd_mh_reset_age_sums(self._h))
 
+    # -- checkpoint and continue (mcd_mh_save / mcd_mh_load; `Settings ... Save` and `continue`, app/Main.hs:494-509) ---------------------
+    def save_size(self) -> int:
+        n = C.c_int64(0)
+        _capi.check(_capi.lib().mcd_mh_save_size(self._h, C.byref(n)))
+        return int(n.value)
+
+    def save(self) -> bytes:
+        """Everything this sampler is between two runs: the device handle's blob (mcd_mh_save: state, posterior terms, temperatures, tuning,
+        counters, sums, step counter, recorder counts, MC3 and attachment where present) and, behind it, the host trailer of
+        checkpoint.trailer (the generator that shuffles the cycle, iterations_done).  The chains do not change.  Refused (McdError) while
+        samples wait in the recorder's ring: fetch them first."""
+        buf = C.create_string_buffer(self.save_size())
+        n = C.c_int64(0)
+        _capi.check(_capi.lib().mcd_mh_save(self._h, buf, len(buf), C.byref(n)))
+        return buf.raw[:n.value] + checkpoint.trailer(self._sched_rng, self.iterations_done)
+
+    def load(self, blob: bytes, what: str = "full") -> dict:
+        """Continue from `blob` (of `save`) on a sampler built over the same configuration -- tree, likelihood, prior, table, batch, seed,
+        first_chain; record_begin, an `MC3`, attach_hamiltonian first where the saved sampler had them; no set_state is needed.
+        what="full" (`continue`): the next run gives the bits the saved sampler's next run gave.  what="state+tuning" (`--init-from-save`,
+        app/Main.hs:424-440): states, posterior terms and tuning parameters only, into a sampler that may have another seed; its counters
+        are zeroed and everything else stays its own.  A refused blob (McdError names the mismatch) leaves the sampler untouched.
+        Returns checkpoint.meta_of(blob), the saved handle's host counters."""
+        flags = {"full": _capi.MCD_CKPT_FULL, "state+tuning": _capi.MCD_CKPT_STATE_TUNING}.get(what)
+        if flags is None:
+            raise ValueError('load: what must be "full" or "state+tuning"')
+        blob = bytes(blob)
+        smallest = 8 * (checkpoint.FIXED_WORDS + 1)
+        n = checkpoint.c_bytes(blob) if len(blob) >= smallest else len(blob)
+        if not smallest <= n <= len(blob):
+            n = len(blob)                                              # (a damaged or truncated blob: the library names what is wrong)
+        tail = None
+        if flags == _capi.MCD_CKPT_FULL and len(blob) > n:
+            try:
+                tail = checkpoint.read_trailer(blob[n:])
+            except ValueError:
+                _capi.ckpt_inspect(blob[:n])                           # (the device blob's own fault comes first)
+                raise
+        _capi.check(_capi.lib().mcd_mh_load(self._h, C.c_char_p(blob[:n]), n, flags))
+        if tail is not None:
+            self._sched_rng.bit_generator.state = tail["sched_rng"]
+            self.iterations_done = tail["iterations_done"]
+        return checkpoint.meta_of(blob)
+
+    def checkpoint(self, path: str):
+        """`save` into `path`: written to a temporary file in the same directory and moved into place, so a reader never sees half a file."""
+        tmp = f"{path}.tmp.{os.getpid()}"
+        with open(tmp, "wb") as f:
+            f.write(self.save())
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, path)
+
+    def restore(self, path: str, what: str = "full") -> dict:
+        with open(path, "rb") as f:
+            return self.load(f.read(), what=what)
+
     # -- the sample recorder (mcd_mh_record_*) ------------------------------------------------------------------------------
     _REC_API, _REC_TAIL = "mcd_mh_record", ()        # (the last array of a fetch: beta [n, B])
 
@@ -617,6 +675,21 @@ class MC3:
         if not self.device:
             raise ValueError("MC3.record_summary: the backend is not a Sampler (no device recorder)")
         return self.backend.record_summary_mc3(**kw)
+
+    def checkpoint(self, path: str):
+        """Sampler.checkpoint of the backend between two swap periods: the blob carries the rank table, the swap counters, the phase and
+        the temperatures (device backends only).  A sharded run saves one file per rank, each rank its own shard's chains with the whole
+        rank table -- that path is not exercised by the tests."""
+        if not self.device:
+            raise ValueError("MC3.checkpoint: the backend is not a Sampler")
+        self.backend.checkpoint(path)
+
+    def restore(self, path: str):
+        """Continue from a file of `checkpoint`, on a fresh Sampler with a fresh MC3 of the same n_chains, ladder and seed over it
+        (mcd_mh_load checks them): the swap phases go on where the saved run's ended."""
+        if not self.device:
+            raise ValueError("MC3.restore: the backend is not a Sampler")
+        self.phase = int(self.backend.restore(path)["mc3_phase"])
 
     def swap(self):
         """One swap phase."""

@@ -16,6 +16,9 @@ One JSON line per chain count.  Usage: python tools/bench_mh.py [--name 12-leave
                                   diagnostics.rung_trace + diagnostics.summary on the host (the only route without it); and
                                   Sampler.record_summary of a run WITHOUT MC3 on chains / C chains and the same window -- the device
                                   summary of as many sequences without the gather
+  --checkpoint                    after the timed runs: Sampler.save and Sampler.load (what="full", the blob back into the same handle), each once
+                                  to warm up and then five times: checkpoint_bytes, checkpoint_save_ms and checkpoint_load_ms (medians) beside
+                                  the line's other figures
   --repeat N                      the timed region N times (every value is printed; gpu_steps_per_s and gpu_us_per_lockstep are then the
                                   median of the N runs -- with the default N = 1 the one timed run, as before)"""
 import argparse
@@ -42,6 +45,7 @@ def main():
     ap.add_argument("--repeat", type=int, default=1)
     ap.add_argument("--summary", type=int, default=0)
     ap.add_argument("--mc3", type=int, default=0)
+    ap.add_argument("--checkpoint", action="store_true")
     args = ap.parse_args()
     import mcmc_date_amd as M
 
@@ -65,6 +69,13 @@ def main():
                         "unmonitored_us_per_iteration": float(np.median(out["gpu_us_per_lockstep_runs"])) * S,
                         "recorded_us_per_iteration": 1e6 * float(np.median(rec)) / args.iters,
                         "chopped_us_per_iteration": 1e6 * float(np.median(cut)) / args.iters})
+        if args.checkpoint:
+            blob = smp.save()                                                        # (first call: code object load, staging allocation)
+            smp.load(blob)
+            t_save = [timed(smp.save) for _ in range(5)]
+            t_load = [timed(lambda: smp.load(blob)) for _ in range(5)]
+            out.update({"checkpoint_bytes": len(blob), "checkpoint_save_ms": 1e3 * float(np.median(t_save)), "checkpoint_load_ms": 1e3 * float(np.median(t_load)),
+                        "checkpoint_save_ms_runs": [1e3 * x for x in t_save], "checkpoint_load_ms_runs": [1e3 * x for x in t_load]})
         if args.summary > 0:
             from mcmc_date_amd import monitor
 
@@ -179,7 +190,7 @@ def main():
         print(json.dumps({"metric": "MH proposal steps/sec (chains x steps)", "dataset": args.name, "chains": B, "n_nodes": topo.n_nodes,
                           "steps_per_iteration": S, "gpu_steps_per_s": B * S * args.iters / dt, "gpu_us_per_lockstep": 1e6 * dt / (S * args.iters),
                           "cpu_twin_steps_per_s": B * S * args.cpu_iters / dc, "cpu_threads": os.cpu_count(),
-                          **{k: v for k, v in extra.items() if k.endswith("_runs") or "record" in k or "summary" in k or k.startswith("host_") or k.startswith("order_") or k.endswith("_per_iteration") or k == "path"}}), flush=True)
+                          **{k: v for k, v in extra.items() if k.endswith("_runs") or "checkpoint" in k or "record" in k or "summary" in k or k.startswith("host_") or k.startswith("order_") or k.endswith("_per_iteration") or k == "path"}}), flush=True)
 
 
 if __name__ == "__main__":
