@@ -66,6 +66,9 @@ module McmcDate.GpuSampler
     -- the form of the NUTS driver's dense metric, raw
     c_hmc_set_metric_form,
     c_hmc_get_metric_form,
+    -- where the dense metric's factors are taken, raw
+    c_hmc_set_metric_factor,
+    c_hmc_get_metric_factor,
   )
 where
 
@@ -207,6 +210,14 @@ foreign import ccall unsafe "mcd_hmc_set_metric_form"
 
 foreign import ccall unsafe "mcd_hmc_get_metric_form"
   c_hmc_get_metric_form :: Ptr McdHmc -> Ptr CInt -> IO CInt
+
+-- where the factors of the dense metric are taken: 0 = on the host (the default), 1 = on the device (@csrc/k_metric_factor.hip@; the
+-- window covariance of @mcd_hmc_nuts_warmup_dense@ then never leaves the GPU); allowed at any time, decides the next factorisation
+foreign import ccall unsafe "mcd_hmc_set_metric_factor"
+  c_hmc_set_metric_factor :: Ptr McdHmc -> CInt -> IO CInt
+
+foreign import ccall unsafe "mcd_hmc_get_metric_factor"
+  c_hmc_get_metric_factor :: Ptr McdHmc -> Ptr CInt -> IO CInt
 
 -- the Hamiltonian proposal in the cycle (@--hamiltonian@: 'maybeHamiltonianProposal', app/Definitions.hs:272-278): the chains move between
 -- the two drivers on the device, and an attached @mcd_hmc_t@ makes one NUTS transition in front of every iteration of @mcd_mh_run@

@@ -299,7 +299,7 @@ int mcd_hmc_nuts_warmup(mcd_hmc_t* m, int windows, int window, double* eps, doub
                         int64_t chain_offset, uint64_t first_transition, double* mean_alpha);
 /*
  * The FULL mass matrix (`HTuneAllMasses`): a dense metric set on the handle replaces the vector inv_mass of every entry point.
- * With C = M^-1 = U U^T (U the lower Cholesky factor, taken on the host): momenta p = U^-T z from the normal draws z of the diagonal
+ * With C = M^-1 = U U^T (U the lower Cholesky factor, taken on the host or, by mcd_hmc_set_metric_factor, on the device): momenta p = U^-T z from the normal draws z of the diagonal
  * form (so cov p = C^-1 = M), kinetic energy 1/2 p^T C p, drift q += eps (C p), U-turn test (q+ - q-)^T C r >= 0 at both ends; slice,
  * doubling, reservoir, merge, divergence test and random streams are those of the diagonal form.  Every product v = C x is one
  * workgroup's sum over j ascending with one accumulator per coordinate: a chain's bits depend on nothing but the chain.
@@ -318,6 +318,17 @@ int mcd_hmc_nuts_warmup(mcd_hmc_t* m, int windows, int window, double* eps, doub
  *                        Allowed only while no dense metric is set (else MCD_ERR_INVALID_ARG, the handle untouched; a value that is
  *                        neither form likewise); the form survives mcd_hmc_set_metric(NULL) and is followed by
  *                        mcd_hmc_nuts_warmup_dense.  mcd_hmc_get_metric_form: *form = the handle's form.
+ *   mcd_hmc_set_metric_factor   where the factors are taken.  MCD_HMC_FACTOR_HOST (the default): the host's long double loops, then C and
+ *                        U^-1 are uploaded.  MCD_HMC_FACTOR_DEVICE: mcd_hmc_set_metric keeps its checks of the host array and their
+ *                        messages, uploads C once, and the symmetric part, U and U^-1 are taken on the device (k_metric_factor.hip: a
+ *                        blocked factorisation on the fp64 matrix cores; the same definitions entry by entry, plain double sums in
+ *                        another order, so the factors differ from the host's in the last bits and are the same bits on every call);
+ *                        they become the handle's only when the device reports success, and a refusal names the pivot in the same
+ *                        words.  mcd_hmc_nuts_warmup_dense then shrinks, symmetrises and factors every window's covariance where
+ *                        k_hmc_cov.hip left it, and the host copy of C is fetched when mcd_hmc_get_metric or inv_mass_dense_out asks
+ *                        for it.  A per-handle choice, allowed at any time (it decides the NEXT factorisation); it survives
+ *                        mcd_hmc_set_metric(NULL); any other value is MCD_ERR_INVALID_ARG, the handle untouched.
+ *                        mcd_hmc_get_metric_factor: *where = the handle's choice.
  *   mcd_hmc_get_metric   *is_dense = 0 / 1; inv_mass_dense (may be NULL) receives the stored symmetrised C when dense.
  * While a dense metric is set, mcd_hmc_leapfrog, mcd_hmc_step_from, mcd_hmc_nuts and mcd_hmc_nuts_run require inv_mass == NULL
  * (a vector is MCD_ERR_INVALID_ARG: no caller silently runs the other metric); with none set, NULL stays the error it was.
@@ -340,6 +351,24 @@ int mcd_hmc_get_metric_form(const mcd_hmc_t* m, int* form);
 int mcd_hmc_get_metric(const mcd_hmc_t* m, int* is_dense, double* inv_mass_dense);
 int mcd_hmc_nuts_warmup_dense(mcd_hmc_t* m, int windows, int window, double* eps, const double* inv_mass0, double delta, int max_depth,
                               uint64_t seed, int64_t chain_offset, uint64_t first_transition, double* mean_alpha, double* inv_mass_dense_out);
+#define MCD_HMC_FACTOR_HOST 0
+#define MCD_HMC_FACTOR_DEVICE 1
+int mcd_hmc_set_metric_factor(mcd_hmc_t* m, int where);
+int mcd_hmc_get_metric_factor(const mcd_hmc_t* m, int* where);
+/*
+ * The factors of a dense metric without a handle, on host arrays: C [dim][dim] row-major; sym receives (C + C^T) / 2 with the diagonal of
+ * C, U the lower triangular factor (U U^T = sym), Uinv = U^-1, both with +0.0 above the diagonal, [dim][dim] each; any of the three may be
+ * NULL.  where = MCD_HMC_FACTOR_HOST: what mcd_hmc_set_metric computes by default, no device is touched.  MCD_HMC_FACTOR_DEVICE: the kernels
+ * behind mcd_hmc_set_metric_factor on device_id; without a device MCD_ERR_NO_DEVICE (no fall-back to the host).  Refused as
+ * mcd_hmc_set_metric refuses, with its messages (MCD_ERR_INVALID_ARG, the outputs untouched); dim > MCD_HMC_DENSE_ACROSS_MAX_DIM:
+ * MCD_ERR_UNSUPPORTED.  info [3] (may be NULL): MCD_METRIC_FACTOR_* , then row and column of the offending entry (the pivot twice).
+ */
+#define MCD_METRIC_FACTOR_OK 0
+#define MCD_METRIC_FACTOR_NOT_FINITE 1 /* C[row][col] is NaN or infinite                              */
+#define MCD_METRIC_FACTOR_DIAGONAL 2   /* C[row][row] <= 0                                            */
+#define MCD_METRIC_FACTOR_ASYMMETRIC 3 /* |C[row][col] - C[col][row]| > 1e-10 sqrt(C_rowrow C_colcol) */
+#define MCD_METRIC_FACTOR_PIVOT 4      /* the Cholesky factorisation fails at pivot row                */
+int mcd_metric_factor(int dim, const double* C, int where, int device_id, double* sym, double* U, double* Uinv, int64_t* info);
 /*
  * The sample recorder of the NUTS driver: thinned samples of every chain AND the diagnostics of the transitions behind them kept ON THE
  * DEVICE while mcd_hmc_nuts / _nuts_run / _nuts_warmup run.  Replaces: the `monitor` of app/Definitions.hs:288-417 (`mcmc`'s MonitorFile

@@ -8,7 +8,7 @@ from . import _capi, checkpoint, diagnostics, monitor
 from ._capi import McdError, NoDevice, NotPositiveDefinite, RootNotBifurcating, get_option, set_option
 from .likelihood import (Full, LikelihoodData, MvnLikelihood, set_logpdf_form, NoData, Sparse, SparseLikelihood, SparseTreeLikelihood, TreeLikelihood, Univariate,
                          jacobian_root_branch, likelihood_function, read_data_file, write_data_file)
-from .hmc import DualAveraging, Leapfrog, hmc_transition, metric_factors, nuts_transition, nuts_warmup, run_cycle_with_nuts, shrunk_covariance
+from .hmc import DualAveraging, Leapfrog, factor_metric, hmc_transition, metric_factors, nuts_transition, nuts_warmup, run_cycle_with_nuts, shrunk_covariance
 from .hamiltonian import from_vector_with, get_mask, grad_to_vector, target_grad, to_vector
 from .prepare import glasso_components, graphical_lasso, graphical_lasso_device
 from .prior import (Brace, Calibration, Constraint, PriorFunction, get_mean_root_height, load_braces,
@@ -29,7 +29,7 @@ __all__ = [
     "Calibration", "Constraint", "Brace", "PriorFunction", "prior_function", "load_calibrations", "load_calibrations_from_tree", "load_constraints",
     "load_braces", "get_mean_root_height",
     "MC3", "Proposal", "Sampler", "cycle_schedule", "init_with", "proposals", "table_arrays", "weight_n_branches",
-    "Leapfrog", "hmc_transition", "nuts_transition", "nuts_warmup", "run_cycle_with_nuts", "DualAveraging", "shrunk_covariance", "metric_factors", "get_mask", "to_vector", "from_vector_with", "grad_to_vector", "target_grad",
+    "Leapfrog", "hmc_transition", "nuts_transition", "nuts_warmup", "run_cycle_with_nuts", "DualAveraging", "shrunk_covariance", "metric_factors", "factor_metric", "get_mask", "to_vector", "from_vector_with", "grad_to_vector", "target_grad",
     "checkpoint", "diagnostics", "Summary", "RecordSummary", "split_rhat", "ess", "summary", "trace_summary",
     "MarginalLikelihood", "MarginalLikelihoodEstimate", "marginal_likelihood", "marginal_likelihood_device", "power_posterior_points",
     "graphical_lasso", "graphical_lasso_device", "glasso_components",

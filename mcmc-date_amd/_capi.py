@@ -28,6 +28,13 @@ MCD_HMC_DENSE_MAX_DIM = 512
 MCD_HMC_METRIC_PER_CHAIN = 0
 MCD_HMC_METRIC_ACROSS_CHAINS = 1
 MCD_HMC_DENSE_ACROSS_MAX_DIM = 4098
+MCD_HMC_FACTOR_HOST = 0
+MCD_HMC_FACTOR_DEVICE = 1
+MCD_METRIC_FACTOR_OK = 0
+MCD_METRIC_FACTOR_NOT_FINITE = 1
+MCD_METRIC_FACTOR_DIAGONAL = 2
+MCD_METRIC_FACTOR_ASYMMETRIC = 3
+MCD_METRIC_FACTOR_PIVOT = 4
 MCD_MAT_SIGMA = 0
 MCD_MAT_SIGMA_INV = 1
 
@@ -102,6 +109,9 @@ SYMBOLS = {
     "mcd_hmc_set_metric_form": (C.c_int, [_vp, C.c_int]),
     "mcd_hmc_get_metric_form": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "mcd_hmc_nuts_warmup_dense": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_double, C.c_int, C.c_uint64, C.c_int64, C.c_uint64, _dp, _dp]),
+    "mcd_hmc_set_metric_factor": (C.c_int, [_vp, C.c_int]),
+    "mcd_hmc_get_metric_factor": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "mcd_metric_factor": (C.c_int, [C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_int64)]),
     "mcd_mh_create": (C.c_int, [C.POINTER(_vp), _vp, _vp, C.c_int, _ip, _ip, _ip, _ip, _ip, _ip, _dp, _dp, C.c_int64, C.c_uint64]),
     "mcd_mh_create_sparse": (C.c_int, [C.POINTER(_vp), _vp, _vp, C.c_int, _ip, _ip, _ip, _ip, _ip, _ip, _dp, _dp, C.c_int64, C.c_uint64]),
     "mcd_mh_destroy": (None, [_vp]),

@@ -59,7 +59,14 @@ struct mcd_hmc {
     // the dense metric (mcd_hmc_set_metric): [dim][dim] device buffers behind dev.metric / dev.metric_uinv, allocated by the first
     // metric set; h_metric is the host copy of the stored symmetrised C.  dev.metric == nullptr: the diagonal metric.
     double *d_metric = nullptr, *d_uinv = nullptr;
-    std::vector<double> h_metric;
+    mutable std::vector<double> h_metric;
+    // where the factors are taken (mcd_hmc_set_metric_factor).  MCD_HMC_FACTOR_DEVICE: k_metric_factor.hip writes S, U and U^-1 into the
+    // workspace below ([dim][dim] each, allocated by the first factorisation; d_fc receives a host matrix), and only a factorisation whose
+    // status word reports success is copied into d_metric / d_uinv; h_metric is then fetched when somebody asks for it (h_metric_stale)
+    int factor = MCD_HMC_FACTOR_HOST;
+    double *d_fc = nullptr, *d_fsym = nullptr, *d_fu = nullptr, *d_fw = nullptr;
+    unsigned long long* d_fstatus = nullptr;
+    mutable bool h_metric_stale = false;
     // the form of the dense metric's products (mcd_hmc_set_metric_form) and, for MCD_HMC_METRIC_ACROSS_CHAINS, the workspace of
     // k_metric_gemm.hip's right-hand sides and products: wx_slots x [batch][dim] each, allocated by the first call that needs them
     int form = MCD_HMC_METRIC_PER_CHAIN;
@@ -182,28 +189,54 @@ int upload_step_args(mcd_hmc* m, const double* eps, const double* inv_mass, cons
 
 // C [dim][dim] as a metric: sym = (C + C^T) / 2, uinv = U^-1 of sym = U U^T (lower triangular).  false, with the reason in `why`: a
 // non-finite entry, an asymmetric pair, not positive definite -- the first offender named.
-bool metric_factors(int dim, const double* C, std::vector<double>& sym, std::vector<double>& uinv, char* why, size_t len)
+// What a refusal names besides its message (mcd_metric_factor's info): the kind (MCD_METRIC_FACTOR_*) and the offending entry.
+struct MetricFault {
+    int kind = MCD_METRIC_FACTOR_OK;
+    size_t row = 0, col = 0;
+};
+
+// the checks of a host matrix that need no factor: every entry finite, a positive diagonal, symmetric pairs
+bool metric_checks(int dim, const double* C, char* why, size_t len, MetricFault* fault = nullptr)
 {
     const size_t n = (size_t)dim;
+    auto refuse = [&](int kind, size_t i, size_t j) {
+        if (fault) *fault = MetricFault{kind, i, j};
+        return false;
+    };
     for (size_t i = 0; i < n; ++i)
         for (size_t j = 0; j < n; ++j)
             if (!std::isfinite(C[i * n + j])) {
                 snprintf(why, len, "C[%zu][%zu] = %g is not finite", i, j, C[i * n + j]);
-                return false;
+                return refuse(MCD_METRIC_FACTOR_NOT_FINITE, i, j);
             }
     for (size_t i = 0; i < n; ++i)
         if (!(C[i * n + i] > 0.0)) {
             snprintf(why, len, "C is not positive definite: C[%zu][%zu] = %g", i, i, C[i * n + i]);
-            return false;
+            return refuse(MCD_METRIC_FACTOR_DIAGONAL, i, i);
         }
     for (size_t i = 0; i < n; ++i)
         for (size_t j = i + 1; j < n; ++j) {
             const double a = C[i * n + j], b = C[j * n + i];
             if (std::fabs(a - b) > 1e-10 * std::sqrt(C[i * n + i] * C[j * n + j])) {
                 snprintf(why, len, "C is not symmetric: C[%zu][%zu] = %.17g, C[%zu][%zu] = %.17g", i, j, a, j, i, b);
-                return false;
+                return refuse(MCD_METRIC_FACTOR_ASYMMETRIC, i, j);
             }
         }
+    return true;
+}
+
+// the refusal of a factorisation that stopped at `piv`, on the host or on the device
+void pivot_refused(size_t piv, char* why, size_t len, MetricFault* fault)
+{
+    snprintf(why, len, "C is not positive definite: the Cholesky factorisation fails at pivot %zu", piv);
+    if (fault) *fault = MetricFault{MCD_METRIC_FACTOR_PIVOT, piv, piv};
+}
+
+bool metric_factors(int dim, const double* C, std::vector<double>& sym, std::vector<double>& uinv, char* why, size_t len,
+                    std::vector<double>* factor = nullptr, MetricFault* fault = nullptr)
+{
+    const size_t n = (size_t)dim;
+    if (!metric_checks(dim, C, why, len, fault)) return false;
     sym.resize(n * n);
     for (size_t i = 0; i < n; ++i) {
         sym[i * n + i] = C[i * n + i];
@@ -213,11 +246,26 @@ bool metric_factors(int dim, const double* C, std::vector<double>& sym, std::vec
     if (!mcd::cholesky_lower(dim, sym, U)) {
         size_t piv = 0;                                   // the rows are factored in order: the first row without a diagonal entry failed
         while (piv < n && U[piv * n + piv] > 0.0) ++piv;
-        snprintf(why, len, "C is not positive definite: the Cholesky factorisation fails at pivot %zu", piv);
+        pivot_refused(piv, why, len, fault);
         return false;
     }
     mcd::invert_factor(dim, U, uinv);
+    if (factor) factor->swap(U);
     return true;
+}
+
+// what k_metric_factor.hip's status word says: true for success; else the message and the offender as the host names them
+bool factor_status_ok(unsigned long long st, int dim, char* why, size_t len, MetricFault* fault = nullptr)
+{
+    if (st == mcd::kMfOk) return true;
+    if (st >= mcd::kMfPivot) {
+        pivot_refused((size_t)(st - mcd::kMfPivot), why, len, fault);
+    } else {
+        const size_t i = (size_t)(st / (unsigned long long)dim), j = (size_t)(st % (unsigned long long)dim);
+        snprintf(why, len, "C[%zu][%zu] is not finite", i, j);
+        if (fault) *fault = MetricFault{MCD_METRIC_FACTOR_NOT_FINITE, i, j};
+    }
+    return false;
 }
 
 // the prepared metric becomes the handle's
@@ -233,8 +281,64 @@ int metric_install(mcd_hmc* m, std::vector<double>& sym, const std::vector<doubl
     HHIP_TRY(hipMemcpy(m->d_metric, sym.data(), sizeof(double) * nn, hipMemcpyHostToDevice));
     HHIP_TRY(hipMemcpy(m->d_uinv, uinv.data(), sizeof(double) * nn, hipMemcpyHostToDevice));
     m->h_metric.swap(sym);
+    m->h_metric_stale = false;
     m->dev.metric = m->d_metric;
     m->dev.metric_uinv = m->d_uinv;
+    return MCD_OK;
+}
+
+// The factors of the device matrix d_C (or, d_C == nullptr, of the host matrix h_C uploaded first) into the handle's workspace, on the
+// handle's stream (mcd_hmc_set_metric_factor: MCD_HMC_FACTOR_DEVICE); *st = the status word.  The handle's metric is not touched.
+int metric_factor_device(mcd_hmc* m, const double* d_C, const double* h_C, bool shrink, double keep, double floor_, unsigned long long* st)
+{
+    const size_t nn = (size_t)m->dev.dim * (size_t)m->dev.dim;
+    HHIP_TRY(hipSetDevice(m->device));
+    if (!m->d_fsym) {
+        if (int rc = halloc(m, &m->d_fsym, nn)) return rc;
+        if (int rc = halloc(m, &m->d_fu, nn)) return rc;
+        if (int rc = halloc(m, &m->d_fw, nn)) return rc;
+        if (int rc = halloc(m, &m->d_fstatus, 1)) return rc;
+    }
+    if (!d_C) {
+        if (!m->d_fc)
+            if (int rc = halloc(m, &m->d_fc, nn)) return rc;
+        HHIP_TRY(hipMemcpyAsync(m->d_fc, h_C, sizeof(double) * nn, hipMemcpyHostToDevice, m->stream));
+        d_C = m->d_fc;
+    }
+    HHIP_TRY(mcd::launch_metric_factor(d_C, m->dev.dim, shrink, keep, floor_, m->d_fsym, m->d_fu, m->d_fw, m->d_fstatus, m->stream));
+    HHIP_TRY(hipMemcpyAsync(st, m->d_fstatus, sizeof *st, hipMemcpyDeviceToHost, m->stream));
+    HHIP_TRY(hipStreamSynchronize(m->stream));
+    return MCD_OK;
+}
+
+// the workspace's S and U^-1 (a factorisation that reported success) become the handle's
+int metric_install_device(mcd_hmc* m)
+{
+    const size_t nn = (size_t)m->dev.dim * (size_t)m->dev.dim;
+    if (!m->d_metric) {
+        if (int rc = halloc(m, &m->d_metric, nn)) return rc;
+        if (int rc = halloc(m, &m->d_uinv, nn)) return rc;
+    }
+    HHIP_TRY(hipMemcpyAsync(m->d_metric, m->d_fsym, sizeof(double) * nn, hipMemcpyDeviceToDevice, m->stream));
+    HHIP_TRY(hipMemcpyAsync(m->d_uinv, m->d_fw, sizeof(double) * nn, hipMemcpyDeviceToDevice, m->stream));
+    HHIP_TRY(hipStreamSynchronize(m->stream));
+    m->h_metric.clear();
+    m->h_metric_stale = true;
+    m->dev.metric = m->d_metric;
+    m->dev.metric_uinv = m->d_uinv;
+    return MCD_OK;
+}
+
+// the host copy of the stored C, fetched when it is asked for after a device factorisation
+int metric_host_copy(const mcd_hmc* m)
+{
+    if (!m->h_metric_stale) return MCD_OK;
+    const size_t nn = (size_t)m->dev.dim * (size_t)m->dev.dim;
+    HHIP_TRY(hipSetDevice(m->device));
+    HHIP_TRY(hipStreamSynchronize(m->stream));
+    m->h_metric.resize(nn);
+    HHIP_TRY(hipMemcpy(m->h_metric.data(), m->d_metric, sizeof(double) * nn, hipMemcpyDeviceToHost));
+    m->h_metric_stale = false;
     return MCD_OK;
 }
 
@@ -242,6 +346,7 @@ void metric_clear(mcd_hmc* m)
 {
     m->dev.metric = m->dev.metric_uinv = nullptr;
     m->h_metric.clear();
+    m->h_metric_stale = false;
 }
 
 // the part of mcd_hmc_create / mcd_hmc_create_sparse behind the handles: the likelihood and the prior of `m` are set, `parent` is the host
@@ -790,6 +895,13 @@ int mcd_hmc_set_metric(mcd_hmc_t* m, const double* inv_mass_dense)
     if (m->dev.dim > dense_max_dim(m)) return dense_dim_refused(m, "mcd_hmc_set_metric");
     std::vector<double> sym, uinv;
     char why[256];
+    if (m->factor == MCD_HMC_FACTOR_DEVICE) {
+        if (!metric_checks(m->dev.dim, inv_mass_dense, why, sizeof why)) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_set_metric: %s", why);
+        unsigned long long st = 0;
+        if (int rc = metric_factor_device(m, nullptr, inv_mass_dense, false, 1.0, 0.0, &st)) return rc;
+        if (!factor_status_ok(st, m->dev.dim, why, sizeof why)) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_set_metric: %s", why);
+        return metric_install_device(m);
+    }
     if (!metric_factors(m->dev.dim, inv_mass_dense, sym, uinv, why, sizeof why)) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_set_metric: %s", why);
     return metric_install(m, sym, uinv);
 }
@@ -805,6 +917,22 @@ int mcd_hmc_set_metric_form(mcd_hmc_t* m, int form)
     return MCD_OK;
 }
 
+int mcd_hmc_set_metric_factor(mcd_hmc_t* m, int where)
+{
+    if (!m) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_set_metric_factor: NULL handle");
+    if (where != MCD_HMC_FACTOR_HOST && where != MCD_HMC_FACTOR_DEVICE)
+        return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_set_metric_factor: where = %d is neither MCD_HMC_FACTOR_HOST nor MCD_HMC_FACTOR_DEVICE", where);
+    m->factor = where;
+    return MCD_OK;
+}
+
+int mcd_hmc_get_metric_factor(const mcd_hmc_t* m, int* where)
+{
+    if (!m || !where) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_get_metric_factor: NULL argument");
+    *where = m->factor;
+    return MCD_OK;
+}
+
 int mcd_hmc_get_metric_form(const mcd_hmc_t* m, int* form)
 {
     if (!m || !form) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_get_metric_form: NULL argument");
@@ -816,7 +944,21 @@ int mcd_hmc_get_metric(const mcd_hmc_t* m, int* is_dense, double* inv_mass_dense
 {
     if (!m || !is_dense) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_get_metric: NULL argument");
     *is_dense = m->dev.metric ? 1 : 0;
-    if (m->dev.metric && inv_mass_dense) std::copy(m->h_metric.begin(), m->h_metric.end(), inv_mass_dense);
+    if (m->dev.metric && inv_mass_dense) {
+        if (int rc = metric_host_copy(m)) return rc;
+        std::copy(m->h_metric.begin(), m->h_metric.end(), inv_mass_dense);
+    }
+    return MCD_OK;
+}
+
+// the handle's U^-1 [dim][dim] as the kernels read it, copied to the host (tests; not part of the public header)
+int mcd_hmc_metric_uinv_(const mcd_hmc_t* m, double* out)
+{
+    if (!m || !out) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_metric_uinv_: NULL argument");
+    if (!m->dev.metric) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_metric_uinv_: no dense metric is set on this handle");
+    HHIP_TRY(hipSetDevice(m->device));
+    HHIP_TRY(hipStreamSynchronize(m->stream));
+    HHIP_TRY(hipMemcpy(out, m->d_uinv, sizeof(double) * (size_t)m->dev.dim * (size_t)m->dev.dim, hipMemcpyDeviceToHost));
     return MCD_OK;
 }
 
@@ -834,7 +976,9 @@ int mcd_hmc_nuts_warmup_dense(mcd_hmc_t* m, int windows, int window, double* eps
     if (int rc = m->rec.room("mcd_hmc_nuts_warmup_dense", ((int64_t)windows + 1) * (int64_t)window)) return rc;
     metric_clear(m);
     HHIP_TRY(hipSetDevice(m->device));
-    // where the call's time goes (mcd_hmc_warmup_phases_): 0 factorisations (host) + upload, 1 covariance, 2 window buffer, 3 transitions
+    // where the call's time goes (mcd_hmc_warmup_phases_): 0 factorisations (host, + upload; or on the device), 1 covariance, 2 window
+    // buffer, 3 transitions
+    const bool on_device = m->factor == MCD_HMC_FACTOR_DEVICE;
     using clk = std::chrono::steady_clock;
     double* phase = m->warmup_phase;
     std::fill(phase, phase + 4, 0.0);
@@ -845,7 +989,7 @@ int mcd_hmc_nuts_warmup_dense(mcd_hmc_t* m, int windows, int window, double* eps
     HHIP_TRY(hipMalloc((void**)&Q.p, sizeof(double) * n * dim));
     HHIP_TRY(hipMalloc((void**)&mom.p, sizeof(double) * (dim + dim * dim)));
     phase[2] += since(t0);
-    std::vector<double> alpha(B), cov(dim * dim), sym, uinv;
+    std::vector<double> alpha(B), cov(on_device ? 0 : dim * dim), sym, uinv;
     char why[256];
     uint64_t t = first_transition;
     for (int w = 0; w < windows; ++w) {
@@ -857,11 +1001,20 @@ int mcd_hmc_nuts_warmup_dense(mcd_hmc_t* m, int windows, int window, double* eps
         t0 = clk::now();
         t += (uint64_t)window;
         HHIP_TRY(mcd::launch_hmc_cov(Q.p, (int64_t)n, (int)dim, mom.p, mom.p + dim, m->stream));
-        HHIP_TRY(hipMemcpyAsync(cov.data(), mom.p + dim, sizeof(double) * dim * dim, hipMemcpyDeviceToHost, m->stream));
+        if (!on_device) HHIP_TRY(hipMemcpyAsync(cov.data(), mom.p + dim, sizeof(double) * dim * dim, hipMemcpyDeviceToHost, m->stream));
         HHIP_TRY(hipStreamSynchronize(m->stream));
         phase[1] += since(t0);
         t0 = clk::now();
         const double keep = shrink_keep((double)n), floor_ = shrink_floor((double)n);
+        if (on_device) {                                              // shrinkage, symmetric part, factors: the matrix stays on the device
+            unsigned long long st = 0;
+            if (int rc = metric_factor_device(m, mom.p + dim, nullptr, true, keep, floor_, &st)) return rc;
+            if (st == mcd::kMfOk)                                     // the rule below: a window without a factor keeps the metric
+                if (int rc = metric_install_device(m)) return rc;
+            phase[0] += since(t0);
+            t0 = clk::now();
+            continue;
+        }
         for (size_t i = 0; i < dim; ++i)
             for (size_t j = 0; j < dim; ++j) cov[i * dim + j] = keep * cov[i * dim + j] + (i == j ? floor_ : 0.0);
         // a chain outside the support leaves NaN positions, a degenerate window no factor: keep the metric
@@ -871,10 +1024,17 @@ int mcd_hmc_nuts_warmup_dense(mcd_hmc_t* m, int windows, int window, double* eps
         t0 = clk::now();
     }
     if (!m->dev.metric) {                                             // no window could be used: the starting masses as the dense metric
-        std::fill(cov.begin(), cov.end(), 0.0);
+        cov.assign(dim * dim, 0.0);
         for (size_t k = 0; k < dim; ++k) cov[k * dim + k] = inv_mass0[k];
-        if (!metric_factors((int)dim, cov.data(), sym, uinv, why, sizeof why)) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_warmup_dense: %s", why);
-        if (int rc = metric_install(m, sym, uinv)) return rc;
+        if (on_device) {
+            unsigned long long st = 0;
+            if (int rc = metric_factor_device(m, nullptr, cov.data(), false, 1.0, 0.0, &st)) return rc;
+            if (!factor_status_ok(st, (int)dim, why, sizeof why)) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_warmup_dense: %s", why);
+            if (int rc = metric_install_device(m)) return rc;
+        } else {
+            if (!metric_factors((int)dim, cov.data(), sym, uinv, why, sizeof why)) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_nuts_warmup_dense: %s", why);
+            if (int rc = metric_install(m, sym, uinv)) return rc;
+        }
         phase[0] += since(t0);
         t0 = clk::now();
     }
@@ -882,11 +1042,82 @@ int mcd_hmc_nuts_warmup_dense(mcd_hmc_t* m, int windows, int window, double* eps
     HHIP_TRY(hipStreamSynchronize(m->stream));
     phase[3] += since(t0);
     if (mean_alpha) std::copy(alpha.begin(), alpha.end(), mean_alpha);
-    if (inv_mass_dense_out) std::copy(m->h_metric.begin(), m->h_metric.end(), inv_mass_dense_out);
+    if (inv_mass_dense_out) {
+        if (int rc = metric_host_copy(m)) return rc;
+        std::copy(m->h_metric.begin(), m->h_metric.end(), inv_mass_dense_out);
+    }
     return MCD_OK;
 }
 
-// seconds the last mcd_hmc_nuts_warmup_dense of this handle spent in its four phases: host factorisations and their upload, the window
+// The factors of a dense metric on host arrays, without a handle: where = MCD_HMC_FACTOR_HOST runs metric_factors above (no device is
+// touched), MCD_HMC_FACTOR_DEVICE the kernels of k_metric_factor.hip on device_id.
+int mcd_metric_factor(int dim, const double* C, int where, int device_id, double* sym_out, double* U_out, double* Uinv_out, int64_t* info)
+{
+    auto report = [&](const MetricFault& f) {
+        if (info) {
+            info[0] = f.kind;
+            info[1] = (int64_t)f.row;
+            info[2] = (int64_t)f.col;
+        }
+    };
+    report(MetricFault{});
+    if (dim < 1 || !C) return hfail(MCD_ERR_INVALID_ARG, "mcd_metric_factor: need dim >= 1 and a matrix");
+    if (where != MCD_HMC_FACTOR_HOST && where != MCD_HMC_FACTOR_DEVICE)
+        return hfail(MCD_ERR_INVALID_ARG, "mcd_metric_factor: where = %d is neither MCD_HMC_FACTOR_HOST nor MCD_HMC_FACTOR_DEVICE", where);
+    if (dim > MCD_HMC_DENSE_ACROSS_MAX_DIM)
+        return hfail(MCD_ERR_UNSUPPORTED, "mcd_metric_factor: dim = %d, a dense metric serves positions of up to MCD_HMC_DENSE_ACROSS_MAX_DIM = %d coordinates",
+                     dim, MCD_HMC_DENSE_ACROSS_MAX_DIM);
+    const size_t nn = (size_t)dim * (size_t)dim;
+    char why[256];
+    MetricFault fault;
+    if (where == MCD_HMC_FACTOR_HOST) {
+        std::vector<double> sym, uinv, U;
+        if (!metric_factors(dim, C, sym, uinv, why, sizeof why, &U, &fault)) {
+            report(fault);
+            return hfail(MCD_ERR_INVALID_ARG, "mcd_metric_factor: %s", why);
+        }
+        if (sym_out) std::copy(sym.begin(), sym.end(), sym_out);
+        if (U_out) std::copy(U.begin(), U.end(), U_out);
+        if (Uinv_out) std::copy(uinv.begin(), uinv.end(), Uinv_out);
+        return MCD_OK;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return hfail(MCD_ERR_NO_DEVICE, "mcd_metric_factor: no HIP device (MCD_HMC_FACTOR_DEVICE has no CPU fallback)");
+    if (device_id < 0 || device_id >= ndev) return hfail(MCD_ERR_INVALID_ARG, "mcd_metric_factor: device %d of %d", device_id, ndev);
+    if (!metric_checks(dim, C, why, sizeof why, &fault)) {
+        report(fault);
+        return hfail(MCD_ERR_INVALID_ARG, "mcd_metric_factor: %s", why);
+    }
+    HHIP_TRY(hipSetDevice(device_id));
+    struct Arena {
+        hipStream_t st = nullptr;
+        Scratch c, s, u, w, status;
+        ~Arena()
+        {
+            if (st) (void)hipStreamDestroy(st);
+        }
+    } A;
+    HHIP_TRY(hipStreamCreate(&A.st));
+    for (Scratch* b : {&A.c, &A.s, &A.u, &A.w}) HHIP_TRY(hipMalloc((void**)&b->p, sizeof(double) * nn));
+    HHIP_TRY(hipMalloc((void**)&A.status.p, sizeof(unsigned long long)));
+    unsigned long long st = 0;
+    HHIP_TRY(hipMemcpyAsync(A.c.p, C, sizeof(double) * nn, hipMemcpyHostToDevice, A.st));
+    HHIP_TRY(mcd::launch_metric_factor(A.c.p, dim, false, 1.0, 0.0, A.s.p, A.u.p, A.w.p, (unsigned long long*)A.status.p, A.st));
+    HHIP_TRY(hipMemcpyAsync(&st, A.status.p, sizeof st, hipMemcpyDeviceToHost, A.st));
+    HHIP_TRY(hipStreamSynchronize(A.st));
+    if (!factor_status_ok(st, dim, why, sizeof why, &fault)) {
+        report(fault);
+        return hfail(MCD_ERR_INVALID_ARG, "mcd_metric_factor: %s", why);
+    }
+    if (sym_out) HHIP_TRY(hipMemcpy(sym_out, A.s.p, sizeof(double) * nn, hipMemcpyDeviceToHost));
+    if (U_out) HHIP_TRY(hipMemcpy(U_out, A.u.p, sizeof(double) * nn, hipMemcpyDeviceToHost));
+    if (Uinv_out) HHIP_TRY(hipMemcpy(Uinv_out, A.w.p, sizeof(double) * nn, hipMemcpyDeviceToHost));
+    return MCD_OK;
+}
+
+// seconds the last mcd_hmc_nuts_warmup_dense of this handle spent in its four phases: the factorisations (on the host with their upload,
+// or on the device: mcd_hmc_set_metric_factor), the window
 // covariance (kernel + copy), the window buffer's allocation, the transitions (tools/bench_nuts.py; not part of the public header)
 int mcd_hmc_warmup_phases_(const mcd_hmc_t* m, double* seconds)
 {

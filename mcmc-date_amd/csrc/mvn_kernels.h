@@ -353,6 +353,14 @@ hipError_t launch_hmc_moments(const HmcDev& D, double* s1, double* s2, hipStream
 // cov[i][j] = sum_s (Q[s][i] - mean[i]) (Q[s][j] - mean[j]) / n, both sums in the order s = 0, 1, ...: two passes, no atomics, the same
 // bits on every call
 hipError_t launch_hmc_cov(const double* Q, int64_t n, int dim, double* mean, double* cov, hipStream_t st);
+// The dense metric's factors on the device (k_metric_factor.hip; mcd_hmc_set_metric_factor, mcd_metric_factor).  C, S, U, W: [dim][dim]
+// row-major on the device, all four distinct.  S = the symmetric part of C -- with `shrink` of keep C + floor_ I --, U lower triangular with
+// U U^T = S, W = U^-1, both with +0.0 above the diagonal.  *status (device) afterwards: kMfOk; the row-major index i dim + j of the first
+// non-finite entry of what was symmetrised; or kMfPivot + the first pivot whose sum is not > 0 or not finite.  Unless it is kMfOk, U and
+// W are unfinished and must not be used.  Launches only: the caller synchronises the stream before it reads the word.
+constexpr unsigned long long kMfOk = ~0ull, kMfPivot = 1ull << 40;
+hipError_t launch_metric_factor(const double* C, int dim, bool shrink, double keep, double floor_, double* S, double* U, double* W,
+                                unsigned long long* status, hipStream_t st);
 
 // The choice of form and the public launch_logpdf / launch_grad / launch_tree_logpdf / launch_tree_grad: sweep_launch.cpp.
 int padded_blocks(int n);          // supported R for dimension n, or -1

@@ -55,6 +55,41 @@ def metric_factors(C):
     return U, W
 
 
+_FACTOR_WHERE = {"host": _capi.MCD_HMC_FACTOR_HOST, "device": _capi.MCD_HMC_FACTOR_DEVICE}
+
+
+class MetricRefused(_capi.McdError):
+    """factor_metric refused C: `info` = (MCD_METRIC_FACTOR_* kind, row, column) of the first offender (the pivot twice)."""
+
+    def __init__(self, code: int, message: str, info):
+        _capi.McdError.__init__(self, code, message)
+        self.info = tuple(int(v) for v in info)
+
+
+def factor_metric(C, where: str = "host", device_id: int = 0):
+    """(sym, U, Uinv) of a dense metric C [dim, dim] as the library takes them (mcd_metric_factor): sym = (C + C^T) / 2 with C's diagonal,
+    U lower triangular with U U^T = sym, Uinv = U^-1 -- what a Leapfrog keeps on its device --, zeros above the diagonal.
+    where="host": the long double loops behind set_metric's default, no GPU needed; "device": the kernels behind
+    set_metric_factor("device") on GPU device_id (NoDevice without one: nothing falls back to the host).  Refused as set_metric refuses
+    (MetricRefused with .info naming the offender); dim > 4098: McdError (unsupported)."""
+    if where not in _FACTOR_WHERE:
+        raise _capi.McdError(_capi.MCD_ERR_INVALID_ARG, f"factor_metric: where = {where!r} is none of {sorted(_FACTOR_WHERE)}")
+    C = np.ascontiguousarray(C, dtype=np.float64)
+    if C.ndim != 2 or C.shape[0] != C.shape[1]:
+        raise ValueError("factor_metric: C must be [dim, dim]")
+    dim = C.shape[0]
+    if dim > _capi.MCD_HMC_DENSE_ACROSS_MAX_DIM:            # refused by the library before anything of this size is allocated here
+        sym = U = W = None
+    else:
+        sym, U, W = np.empty((dim, dim)), np.empty((dim, dim)), np.empty((dim, dim))
+    info = (ctypes.c_int64 * 3)()
+    rc = _capi.lib().mcd_metric_factor(dim, dp(C), _FACTOR_WHERE[where], int(device_id), _odp(sym), _odp(U), _odp(W), info)
+    if rc == _capi.MCD_ERR_INVALID_ARG and info[0] != _capi.MCD_METRIC_FACTOR_OK:
+        raise MetricRefused(rc, _capi.lib().mcd_last_error().decode(), info)
+    _capi.check(rc)
+    return sym, U, W
+
+
 class _Metric:
     """M^-1 as the numpy helpers below use it: a vector (diagonal) or a symmetric matrix (dense)."""
 
@@ -120,7 +155,8 @@ class Leapfrog(DriverCalls):
         """C [dim, dim], symmetric positive definite, becomes the handle's metric (momenta p = U^-T z with C = U U^T, kinetic energy
         1/2 p^T C p, drift q += eps C p, U-turn test through C); leapfrog / step_from / nuts / nuts_run then take inv_mass=None.
         Refused (McdError, the handle untouched): a non-finite entry, an asymmetric pair, not positive definite, dim > 512 in the
-        default per-chain form (set_metric_form("across_chains") serves every dim)."""
+        default per-chain form (set_metric_form("across_chains") serves every dim).  The factors are taken on the host, or on the device
+        after set_metric_factor("device")."""
         C = np.ascontiguousarray(C, dtype=np.float64)
         if C.shape != (self.dim, self.dim):
             raise ValueError("set_metric: C must be [dim, dim]")
@@ -142,6 +178,30 @@ class Leapfrog(DriverCalls):
         form = ctypes.c_int(-1)
         _capi.check(_capi.lib().mcd_hmc_get_metric_form(self._h, ctypes.byref(form)))
         return next(name for name, value in self._METRIC_FORMS.items() if value == form.value)
+
+    def set_metric_factor(self, where: str):
+        """Where set_metric and nuts_warmup_dense take the factors of C from now on (mcd_hmc_set_metric_factor): "host" (the default: long
+        double loops on the CPU, C and U^-1 uploaded) or "device" (k_metric_factor.hip: the same definitions on the fp64 matrix cores, the
+        window covariance never leaves the GPU; factors equal to the host's up to the last bits, the same bits on every call).  Allowed
+        at any time; survives clear_metric."""
+        if where not in _FACTOR_WHERE:
+            raise ValueError(f"set_metric_factor: {where!r} is none of {sorted(_FACTOR_WHERE)}")
+        _capi.check(_capi.lib().mcd_hmc_set_metric_factor(self._h, _FACTOR_WHERE[where]))
+
+    @property
+    def metric_factor(self) -> str:
+        """"host" or "device": where the handle takes the factors of a dense metric."""
+        where = ctypes.c_int(-1)
+        _capi.check(_capi.lib().mcd_hmc_get_metric_factor(self._h, ctypes.byref(where)))
+        return next(name for name, value in _FACTOR_WHERE.items() if value == where.value)
+
+    def _metric_uinv(self):
+        """The handle's U^-1 [dim, dim] read back from the device (mcd_hmc_metric_uinv_: for tests)."""
+        f = _capi.lib().mcd_hmc_metric_uinv_
+        f.restype, f.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+        W = np.empty((self.dim, self.dim))
+        _capi.check(f(self._h, dp(W)))
+        return W
 
     def clear_metric(self):
         """Back to the diagonal metric: the handle is what it was before set_metric."""

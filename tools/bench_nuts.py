@@ -17,8 +17,10 @@ One JSON line per run; *_runs hold every repeat, the headline figures are their 
                          tuned step sizes, and the smallest effective sample size over the inner node ages per leapfrog step
                          (Leapfrog.record_summary).
   --metric-form {per_chain,across_chains}   with --metric dense: how the dense metric's products are taken (Leapfrog.set_metric_form); the
-                         line then carries the seconds the warm-up call spent in its four phases (host factorisations, window covariance,
+                         line then carries the seconds the warm-up call spent in its four phases (factorisations, window covariance,
                          window buffer, transitions).
+  --metric-factor {host,device}   with --metric dense: where the factors of every window's covariance are taken
+                         (Leapfrog.set_metric_factor): the host's long double loops, or csrc/k_metric_factor.hip; reported beside the phases.
 
   --cycle {host,library}  instead: --transitions iterations of the reference's `--hamiltonian` mode (the Metropolis-Hastings cycle plus one
                          NUTS transition per iteration) on --name x --chains, from the same start states, step sizes and masses:
@@ -148,6 +150,7 @@ def metric_report(args, topo, lf, eps0, inv_mass0, form):
     t0 = time.perf_counter()
     if dense:
         lf.set_metric_form(args.metric_form)
+        lf.set_metric_factor(args.metric_factor)
         eps, _, alpha_w = lf.nuts_warmup_dense(eps0, inv_mass0, windows=args.windows, window=args.window, **kw)
         inv_mass = None
     else:
@@ -176,6 +179,7 @@ def metric_report(args, topo, lf, eps0, inv_mass0, form):
     ess = summ.ages[inner, 7]
     print(json.dumps({"metric": "NUTS leapfrog steps (all chains in lock step)", "mass_matrix": args.metric,
                       "metric_form": args.metric_form if dense else None, "warmup_phases": phases,
+                      "metric_factor": args.metric_factor if dense else None,
                       "dataset": f"synthetic {args.synthetic} leaves" if args.synthetic else args.name, "likelihood": form, "n_nodes": topo.n_nodes,
                       "dim": lf.dim, "chains": B, "windows": args.windows, "window": args.window, "transitions": T, "max_depth": args.max_depth,
                       "warmup_s": warm_s, "warmup_mean_alpha": float(alpha_w.mean()), "eps_mean": float(eps.mean()), "eps_min": float(eps.min()),
@@ -197,6 +201,7 @@ def main():
     ap.add_argument("--seed", type=int, default=5)
     ap.add_argument("--metric", choices=("diag", "dense"), default=None)
     ap.add_argument("--metric-form", choices=("per_chain", "across_chains"), default="per_chain")
+    ap.add_argument("--metric-factor", choices=("host", "device"), default="host")
     ap.add_argument("--windows", type=int, default=3)
     ap.add_argument("--window", type=int, default=60)
     ap.add_argument("--cycle", choices=("host", "library"), default=None)
@@ -215,6 +220,8 @@ def main():
         return cycle_report(args)
     if args.metric_form != "per_chain" and args.metric != "dense":
         ap.error("--metric-form is valid with --metric dense")
+    if args.metric_factor != "host" and args.metric != "dense":
+        ap.error("--metric-factor is valid with --metric dense")
     B, T = args.chains, args.transitions
     topo, lf, eps, inv_mass, form = synthetic_problem(args.synthetic, B) if args.synthetic else golden_problem(args.name, B)
     if args.metric:
