@@ -1116,6 +1116,96 @@ int mcd_metric_factor(int dim, const double* C, int where, int device_id, double
     return MCD_OK;
 }
 
+namespace {
+
+// device buffers of one of the two entries below, each of exactly the size asked for
+struct TestArena {
+    hipStream_t st = nullptr;
+    std::vector<void*> bufs;
+    ~TestArena()
+    {
+        for (void* p : bufs) (void)hipFree(p);
+        if (st) (void)hipStreamDestroy(st);
+    }
+    hipError_t upload(void** d, const void* h, size_t bytes)           // h == nullptr: allocate only
+    {
+        if (hipError_t e = hipMalloc(d, bytes)) return e;
+        bufs.push_back(*d);
+        return h ? hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
+    }
+};
+
+int test_device(const char* who, int device_id)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return hfail(MCD_ERR_NO_DEVICE, "%s: no HIP device", who);
+    if (device_id < 0 || device_id >= ndev) return hfail(MCD_ERR_INVALID_ARG, "%s: device %d of %d", who, device_id, ndev);
+    return MCD_OK;
+}
+
+}  // namespace
+
+// launch_metric_gemm_rows (k_metric_gemm.hip) on host arrays: X [mem_rows][dim], A [dim][dim], the current contents of Y [mem_rows][dim]
+// and the list [n_list] (or NULL) go to device buffers of exactly these sizes, the launcher runs unchanged, Y comes back.  A list entry
+// or a mapped row outside mem_rows is refused before anything is launched (tests; not part of the public header)
+int mcd_metric_gemm_(const double* X, const double* A, double* Y, int64_t mem_rows, int dim, int lower, const int* list, int n_list, int64_t stride,
+                     int64_t rows, int device_id)
+{
+    const char* who = "mcd_metric_gemm_";
+    if (!X || !A || !Y) return hfail(MCD_ERR_INVALID_ARG, "%s: NULL argument", who);
+    if (mem_rows < 1 || dim < 1 || rows < 0) return hfail(MCD_ERR_INVALID_ARG, "%s: need mem_rows >= 1, dim >= 1 and rows >= 0", who);
+    if (list) {
+        if (n_list < 1 || stride < 0) return hfail(MCD_ERR_INVALID_ARG, "%s: a list needs n_list >= 1 and stride >= 0", who);
+        for (int k = 0; k < n_list; ++k)
+            if (list[k] < 0 || list[k] >= mem_rows) return hfail(MCD_ERR_INVALID_ARG, "%s: list[%d] = %d is no row of %lld", who, k, list[k], (long long)mem_rows);
+        for (int64_t r = 0; r < rows; ++r) {
+            const int64_t slot = r / n_list;
+            if (slot > 0 && stride > (mem_rows - 1 - list[r % n_list]) / slot)      // slot stride + list[..] > mem_rows - 1, without overflow
+                return hfail(MCD_ERR_INVALID_ARG, "%s: product row %lld is memory row %lld x %lld + %d, outside %lld rows", who, (long long)r,
+                             (long long)slot, (long long)stride, list[r % n_list], (long long)mem_rows);
+        }
+    } else if (rows > mem_rows) {
+        return hfail(MCD_ERR_INVALID_ARG, "%s: %lld rows of %lld", who, (long long)rows, (long long)mem_rows);
+    }
+    if (int rc = test_device(who, device_id)) return rc;
+    HHIP_TRY(hipSetDevice(device_id));
+    TestArena T;
+    HHIP_TRY(hipStreamCreate(&T.st));
+    const size_t nx = (size_t)mem_rows * (size_t)dim;
+    double *dX = nullptr, *dA = nullptr, *dY = nullptr;
+    int* dlist = nullptr;
+    HHIP_TRY(T.upload((void**)&dX, X, sizeof(double) * nx));
+    HHIP_TRY(T.upload((void**)&dA, A, sizeof(double) * (size_t)dim * (size_t)dim));
+    HHIP_TRY(T.upload((void**)&dY, Y, sizeof(double) * nx));
+    if (list) HHIP_TRY(T.upload((void**)&dlist, list, sizeof(int) * (size_t)n_list));
+    HHIP_TRY(mcd::launch_metric_gemm_rows(dX, dA, dY, rows, dim, lower != 0, dlist, list ? n_list : 0, list ? stride : 0, T.st));
+    HHIP_TRY(hipMemcpyAsync(Y, dY, sizeof(double) * nx, hipMemcpyDeviceToHost, T.st));
+    HHIP_TRY(hipStreamSynchronize(T.st));
+    return MCD_OK;
+}
+
+// launch_hmc_cov (k_hmc_cov.hip) on the host array Q [n][dim]: mean_out [dim], cov_out [dim][dim] (tests; not part of the public header)
+int mcd_hmc_cov_(const double* Q, int64_t n, int dim, double* mean_out, double* cov_out, int device_id)
+{
+    const char* who = "mcd_hmc_cov_";
+    if (!Q || !mean_out || !cov_out) return hfail(MCD_ERR_INVALID_ARG, "%s: NULL argument", who);
+    if (n < 1 || dim < 1) return hfail(MCD_ERR_INVALID_ARG, "%s: need n >= 1 and dim >= 1", who);
+    if (int rc = test_device(who, device_id)) return rc;
+    HHIP_TRY(hipSetDevice(device_id));
+    TestArena T;
+    HHIP_TRY(hipStreamCreate(&T.st));
+    const size_t nn = (size_t)dim * (size_t)dim;
+    double *dQ = nullptr, *dmean = nullptr, *dcov = nullptr;
+    HHIP_TRY(T.upload((void**)&dQ, Q, sizeof(double) * (size_t)n * (size_t)dim));
+    HHIP_TRY(T.upload((void**)&dmean, nullptr, sizeof(double) * (size_t)dim));
+    HHIP_TRY(T.upload((void**)&dcov, nullptr, sizeof(double) * nn));
+    HHIP_TRY(mcd::launch_hmc_cov(dQ, n, dim, dmean, dcov, T.st));
+    HHIP_TRY(hipMemcpyAsync(mean_out, dmean, sizeof(double) * (size_t)dim, hipMemcpyDeviceToHost, T.st));
+    HHIP_TRY(hipMemcpyAsync(cov_out, dcov, sizeof(double) * nn, hipMemcpyDeviceToHost, T.st));
+    HHIP_TRY(hipStreamSynchronize(T.st));
+    return MCD_OK;
+}
+
 // seconds the last mcd_hmc_nuts_warmup_dense of this handle spent in its four phases: the factorisations (on the host with their upload,
 // or on the device: mcd_hmc_set_metric_factor), the window
 // covariance (kernel + copy), the window buffer's allocation, the transitions (tools/bench_nuts.py; not part of the public header)

@@ -90,6 +90,46 @@ def factor_metric(C, where: str = "host", device_id: int = 0):
     return sym, U, W
 
 
+def _metric_gemm(X, A, Y=None, lower: bool = False, rows: Optional[int] = None, rows_list=None, stride: int = 0, device_id: int = 0):
+    """The product kernel of the across-chains form on host arrays (mcd_metric_gemm_, csrc/k_metric_gemm.hip: for tests).  X [mem_rows, dim],
+    A [dim, dim]; Y [mem_rows, dim] goes to the device as it is (None: zeros) and is returned as the launch left it.  Without rows_list the
+    first `rows` rows (default: all) are multiplied; with it, product row r is memory row (r // n_list) stride + rows_list[r % n_list].
+    The device buffers have exactly the arrays' sizes; a list entry or a mapped row outside mem_rows is refused (McdError), nothing runs."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    if X.ndim != 2 or A.shape != (X.shape[1], X.shape[1]):
+        raise ValueError("_metric_gemm: X must be [mem_rows, dim] and A [dim, dim]")
+    Y = np.zeros_like(X) if Y is None else np.array(Y, dtype=np.float64, order="C")
+    if Y.shape != X.shape:
+        raise ValueError("_metric_gemm: Y must have X's shape")
+    lst = None if rows_list is None else np.ascontiguousarray(rows_list, dtype=np.int32)
+    if rows is None:
+        rows = X.shape[0] if lst is None else lst.size
+    f = _capi.lib().mcd_metric_gemm_
+    f.restype = ctypes.c_int
+    f.argtypes = [ctypes.POINTER(ctypes.c_double)] * 3 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int,
+                  ctypes.c_int64, ctypes.c_int64, ctypes.c_int]
+    _capi.check(f(dp(X), dp(A), dp(Y), X.shape[0], X.shape[1], int(bool(lower)), None if lst is None else ip(lst), 0 if lst is None else lst.size,
+                  int(stride), int(rows), int(device_id)))
+    return Y
+
+
+def _hmc_cov(Q, device_id: int = 0):
+    """(mean [dim], cov [dim, dim]) of the samples Q [n, dim] by the warm-up's covariance kernels (mcd_hmc_cov_, csrc/k_hmc_cov.hip: for
+    tests): cov is the centred covariance divided by n."""
+    Q = np.ascontiguousarray(Q, dtype=np.float64)
+    if Q.ndim != 2:
+        raise ValueError("_hmc_cov: Q must be [n, dim]")
+    n, dim = Q.shape
+    mean, cov = np.empty(dim), np.empty((dim, dim))
+    f = _capi.lib().mcd_hmc_cov_
+    f.restype = ctypes.c_int
+    f.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                  ctypes.c_int]
+    _capi.check(f(dp(Q), n, dim, dp(mean), dp(cov), int(device_id)))
+    return mean, cov
+
+
 class _Metric:
     """M^-1 as the numpy helpers below use it: a vector (diagonal) or a symmetric matrix (dense)."""
 

@@ -139,9 +139,11 @@ def test_one_leapfrog_step_against_numpy(gpu, golden, which, dim):
     one_step(lf, lik, pf, cal, st, C, eps, direction, p0)
 
 
-@pytest.mark.parametrize("B", [15, 16, 17, 33])
+@pytest.mark.parametrize("B", [15, 16, 17, 33, 49, 64, 65, 130])
 def test_row_tiles_and_the_chain_alone(gpu, B):
-    """65 nodes (dim 99): batches around one 16-row operand tile and over two; every chain against itself run alone."""
+    """65 nodes (dim 99): batches around one 16-row operand tile and over two, into the fourth wave's rows (48 ..), up to a full 64-row
+    tile, one row and two tiles and two rows beyond it; every chain against itself run alone (from 49 chains on: the chains at the
+    edges of the waves' rows and of the tiles)."""
     _, lik, pf, st = synthetic_problem(33, B, sparse=True)
     C, eps, direction, p0 = step_inputs(lik, pf, False, st)
     lf = across(lik, pf, False, B)
@@ -153,7 +155,7 @@ def test_row_tiles_and_the_chain_alone(gpu, B):
     q1, p1, g1, v1 = lf.step_from(q0, p0, g0, eps, None, direction=direction, have_grad=True)
     alone = across(lik, pf, False, 1)
     alone.set_metric(C)
-    for b in range(B):
+    for b in (range(B) if B <= 33 else sorted({b for b in (0, 15, 16, 47, 48, 63, 64, B - 1) if b < B})):
         alone.set_state(st.slice(b, b + 1))
         got = alone.step_from(q0[b:b + 1], p0[b:b + 1], g0[b:b + 1], eps[b:b + 1], None, direction=direction[b:b + 1], have_grad=True)
         assert same_bits(got, (q1[b:b + 1], p1[b:b + 1], g1[b:b + 1], v1[b:b + 1])), b
@@ -193,6 +195,88 @@ def test_across_chains_against_per_chain(gpu, golden):
         depths += d2.tolist()
     print(f"across against per chain: depths {depths}")
     assert max(depths) >= 4 and not np.array_equal(q2, q0)
+
+
+def rhs_count(r):
+    """nuts_rhs_plan(j, i).count of round r = 2^j + i - 1 (csrc/nuts_rhs_plan.hpp; pinned by tests/test_nuts_rhs_plan_host.py)."""
+    j = (r + 1).bit_length() - 1
+    i = r + 1 - (1 << j)
+    closes = next(k for k in range(j + 1) if k == j or (i + 1) % (2 << k))
+    return 1 + closes + int(i + 1 == 1 << j)
+
+
+def spread_eps(lik, pf, st, scale, ratio):
+    """Step sizes from `scale` to `scale x ratio` times each chain's safe unit (safe_eps without its ramp), the exponents dealt over the
+    chains by a fixed permutation so that every row tile holds short and long steps."""
+    B = st.heights.shape[0]
+    lf = M.Leapfrog(lik, pf, False, B)
+    lf.set_state(st)
+    q0, _, g0 = lf.position()
+    C = metric_for(q0)
+    unit = 1.0 / np.maximum(1.0, (np.abs(g0) * np.sqrt(np.diag(C))).max(axis=1))
+    u = np.random.default_rng(130).permutation(B) / (B - 1.0)
+    return scale * unit * ratio ** u
+
+
+EPS_130 = dict(scale=1.0, ratio=30.0)
+
+
+def test_across_chains_nuts_at_130_chains(gpu):
+    """The across-chains NUTS at a production row count: 130 chains (two full 64-row tiles and two rows), dim 99, trees of up to 15
+    leaves that end at different leaves, so the rounds' products run over lists of every length.  The per-chain form on the same chains
+    is the reference; the same bits from the same state again and for chains 60 .. 69 (across the 64-row edge) run alone.
+
+    Measured on the MI355X: chains still building per round 130, 120, 118, 101, 101, 97, 95, 70, 69, 67, 66, 65, 65, 63, 60 in the first
+    transition and 130, 120, 116, 103, 101, 99, 96, 82, 82, 81, 78, 76, 74, 72, 71 in the second; depths 1 .. 4 of 10, 19, 31, 70 chains."""
+    B, max_depth, seed, transitions = 130, 4, 20261021, 2
+    _, lik, pf, st = synthetic_problem(33, B, sparse=True)
+    C = step_inputs(lik, pf, False, st)[0]
+    eps = spread_eps(lik, pf, st, **EPS_130)
+    assert eps.max() >= 30 * eps.min()
+    per = M.Leapfrog(lik, pf, False, B)
+    acr = across(lik, pf, False, B)
+    sub = across(lik, pf, False, 10)
+    assert per.dim == 99 and per.metric_form == "per_chain" and acr.metric_form == "across_chains"
+    for lf, s in ((per, st), (acr, st), (sub, st.slice(60, 70))):
+        lf.set_state(s)
+        lf.set_metric(C)
+    q0 = acr.position()[0]
+    per.record_begin(period=1, capacity=transitions)
+    acr.record_begin(period=1, capacity=transitions)
+    runs = []
+    for transition in range(transitions):
+        a1, d1 = per.nuts(eps, None, max_depth=max_depth, seed=seed, transition=transition)
+        a2, d2 = acr.nuts(eps, None, max_depth=max_depth, seed=seed, transition=transition)
+        q1, lp1, _ = per.position()
+        q2, lp2, g2 = acr.position()
+        assert np.array_equal(d1, d2), (transition, np.flatnonzero(d1 != d2))
+        assert np.max(np.abs(a1 - a2)) <= 1e-6
+        assert np.max(np.abs(q1 - q2) / np.maximum(1e-3, np.abs(q1))) <= 1e-6
+        assert np.all(np.abs(lp1 - lp2) <= 1e-6 * np.maximum(1.0, np.abs(lp1)))
+        a_s, d_s = sub.nuts(eps[60:70], None, max_depth=max_depth, seed=seed, transition=transition, chain_offset=60)
+        assert np.array_equal(d_s, d2[60:70]) and np.array_equal(a_s, a2[60:70])
+        assert same_bits(sub.position(), (q2[60:70], lp2[60:70], g2[60:70]))
+        runs.append((a2, d2, q2, lp2, g2))
+    steps = per.record_fetch()[5][:, :, 1]
+    nuts_a = acr.record_fetch()[5]
+    per.record_end()
+    acr.record_end()
+    assert steps.shape == (transitions, B) and np.array_equal(nuts_a[:, :, 1], steps)      # equal leapfrog counts, chain by chain
+    assert np.array_equal(nuts_a[:, :, 0], np.array([r[1] for r in runs]))
+    # the same calls again from the same state, on the handle whose workspace and list the first run has used
+    acr.set_state(st)
+    for transition in range(transitions):
+        a2, d2 = acr.nuts(eps, None, max_depth=max_depth, seed=seed, transition=transition)
+        assert same_bits((a2, d2) + acr.position(), runs[transition]), transition
+    assert np.mean(np.any(runs[-1][2] != q0, axis=1)) > 0.5                                # most chains have moved
+    # what the rounds' products have covered, from the reference's counts: n_r chains are still building in round r
+    n_r = [[int(np.sum(steps[t] > r)) for r in range(1 << max_depth)] for t in range(transitions)]
+    print(f"across-chains NUTS at {B} chains: chains per round {n_r}, depths {np.bincount(runs[0][1], minlength=max_depth + 1).tolist()}")
+    rounds = [(r, n) for per_t in n_r for r, n in enumerate(per_t)]
+    assert any(r >= 1 and n > 64 and n % 64 != 0 for r, n in rounds)                        # a ragged second row tile through the list
+    assert any(0 < n < 64 and n % 16 != 0 for r, n in rounds)                               # a ragged wave of a single tile
+    assert any(rhs_count(r) >= 2 and rhs_count(r) * n > 64 for r, n in rounds)              # several slots, more than one tile of rows
+    assert any(r >= 1 and rhs_count(r) >= 2 and n < B and rhs_count(r) * n > 64 for r, n in rounds)   # ... of a list shorter than the batch
 
 
 @pytest.mark.parametrize("eps_scale", [1.0, 0.25])
