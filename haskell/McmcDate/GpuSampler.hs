@@ -54,6 +54,7 @@ module McmcDate.GpuSampler
     nodeAgeSummary,
     -- the Hamiltonian proposal in the cycle (@--hamiltonian@)
     withHamiltonian,
+    setHamiltonianTransitionForm,
     c_hmc_take_state,
     c_mh_take_state,
     -- the NUTS driver's recorder, raw (the handle comes from 'McmcDate.Gpu')
@@ -69,6 +70,9 @@ module McmcDate.GpuSampler
     -- where the dense metric's factors are taken, raw
     c_hmc_set_metric_factor,
     c_hmc_get_metric_factor,
+    -- how the NUTS driver launches a transition, raw
+    c_hmc_set_transition_form,
+    c_hmc_get_transition_form,
   )
 where
 
@@ -218,6 +222,14 @@ foreign import ccall unsafe "mcd_hmc_set_metric_factor"
 
 foreign import ccall unsafe "mcd_hmc_get_metric_factor"
   c_hmc_get_metric_factor :: Ptr McdHmc -> Ptr CInt -> IO CInt
+
+-- how a transition is launched: 0 = rounds of three launches with a host poll each (the default), 1 = the whole transition as one launch
+-- (@csrc/k_nuts_chain.hip@: dense likelihoods of up to 64 distances, i.e. trees of up to 66 nodes; the same bits); allowed at any time
+foreign import ccall unsafe "mcd_hmc_set_transition_form"
+  c_hmc_set_transition_form :: Ptr McdHmc -> CInt -> IO CInt
+
+foreign import ccall unsafe "mcd_hmc_get_transition_form"
+  c_hmc_get_transition_form :: Ptr McdHmc -> Ptr CInt -> IO CInt
 
 -- the Hamiltonian proposal in the cycle (@--hamiltonian@: 'maybeHamiltonianProposal', app/Definitions.hs:272-278): the chains move between
 -- the two drivers on the device, and an attached @mcd_hmc_t@ makes one NUTS transition in front of every iteration of @mcd_mh_run@
@@ -485,6 +497,7 @@ pourState s at hs rs =
 --   invMass   @Just@ the diagonal inverse masses (length @mcd_hmc_dim@), or @Nothing@: the dense metric set on @hmc@
 --   seed      the sampler's seed xor a constant of the host's, so that the NUTS streams stay apart from the proposals' streams
 -- Returns the action's result and the mean acceptance statistic, mean tree depth and number of divergent transitions per chain.
+-- The transitions are launched as @hmc@'s form says: 'setHamiltonianTransitionForm' beforehand.
 withHamiltonian :: GpuSampler -> Ptr McdHmc -> [Double] -> Maybe [Double] -> Int -> Word64 -> IO a -> IO (a, [(Double, Double, Int)])
 withHamiltonian s hmc eps invMass maxDepth seed act =
   VS.unsafeWith (VS.fromList (map realToFrac eps)) $ \pe ->
@@ -509,6 +522,14 @@ withHamiltonian s hmc eps invMass maxDepth seed act =
     withMass k = case invMass of
       Nothing -> k nullPtr
       Just ms -> VS.unsafeWith (VS.fromList (map realToFrac ms)) k
+
+-- | How the leapfrog handle launches a NUTS transition, for 'withHamiltonian' and every other caller: @False@ the rounds of three
+-- launches (the default), @True@ one launch per transition (@mcd_hmc_set_transition_form@; the datasets of the reference, 9 .. 47
+-- distances, are all eligible).  The library refuses a handle it cannot serve that way (a sparse likelihood, more than 64 distances,
+-- the across-chains form of a dense metric) and leaves it as it was; the chains' bits do not depend on the choice.
+setHamiltonianTransitionForm :: Ptr McdHmc -> Bool -> IO ()
+setHamiltonianTransitionForm hmc oneLaunch =
+  check "mcd_hmc_set_transition_form" =<< c_hmc_set_transition_form hmc (if oneLaunch then 1 else 0)
 
 -- one block of iterations through the shuffled cycle; accumulate: add the node ages to the running sums after every iteration
 runBlock :: StatefulGen g IO => GpuSampler -> g -> Int -> Bool -> IO ()

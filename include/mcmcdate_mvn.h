@@ -260,8 +260,9 @@ int mcd_prior_grad_batch(const mcd_prior_t* p, const double* birth, const double
  * The proposal itself -- `nuts` of the package `mcmc` (`nutsWith`, app/Hamiltonian.hs:95-105; not vendored), restated from the
  * algorithm it implements, Hoffman & Gelman (2014), Algorithm 3 -- runs on the device for all chains in lock step (k_nuts.hip:
  * slice variable, doubling in a random direction, U-turn and divergence stops, uniform choice among the admissible leaves;
- * one round = the two gradient launches + one launch that finishes the leapfrog step, books the leaf and sends the next one
- * on its way; the host only polls a counter):
+ * in the default form of a transition, MCD_HMC_TRANSITION_ROUNDS, one round = the two gradient launches + one launch that finishes
+ * the leapfrog step, books the leaf and sends the next one on its way, and the host only polls a counter; a handle over a small
+ * tree may take the whole transition as one launch instead: mcd_hmc_set_transition_form below):
  *   mcd_hmc_nuts        one transition from the handle's state with per-chain step sizes eps[batch] and inverse masses
  *                       inv_mass[dim]; random streams: Philox (seed, chain_offset + b, transition) -- a chain's draw does not
  *                       depend on the batch it runs in; out: mean acceptance statistic alpha[batch], tree depth[batch].
@@ -355,6 +356,33 @@ int mcd_hmc_nuts_warmup_dense(mcd_hmc_t* m, int windows, int window, double* eps
 #define MCD_HMC_FACTOR_DEVICE 1
 int mcd_hmc_set_metric_factor(mcd_hmc_t* m, int where);
 int mcd_hmc_get_metric_factor(const mcd_hmc_t* m, int* where);
+/*
+ * How a transition is launched, per handle.  MCD_HMC_TRANSITION_ROUNDS (the default): the rounds described above, three launches and one
+ * host poll per leapfrog step of a tree.  MCD_HMC_TRANSITION_ONE_LAUNCH: a whole transition of every chain -- momenta, slice, every
+ * doubling with its gradients, the U-turn and divergence stops, the choice of the proposal, the evaluation at the accepted point -- is
+ * ONE kernel launch (k_nuts_chain.hip: a workgroup per chain, no host poll inside), and the n_steps leapfrog steps of mcd_hmc_leapfrog are
+ * one launch.  It holds for mcd_hmc_nuts, mcd_hmc_nuts_run, mcd_hmc_nuts_warmup, mcd_hmc_nuts_warmup_dense, every transition of a handle
+ * attached to a sampler (mcd_mh_attach_hamiltonian) and mcd_hmc_leapfrog; mcd_hmc_step_from and mcd_hmc_set_state run as they do, and the
+ * recorder's store, the position moments, the covariance and the hand-over stay the launches they are, after the transition's.  The host
+ * still waits once per transition where it does today.
+ *   Eligible: a handle of mcd_hmc_create (dense likelihood) of at most 64 distances -- a tree of at most 66 nodes: one 64-row block of
+ *   the factor, which one workgroup keeps in LDS -- with the diagonal metric or a dense one in MCD_HMC_METRIC_PER_CHAIN.  Refused with
+ *   MCD_ERR_UNSUPPORTED, the handle untouched, the message naming the reason and both numbers: a handle of mcd_hmc_create_sparse, more
+ *   than 64 distances, a handle in MCD_HMC_METRIC_ACROSS_CHAINS -- and mcd_hmc_set_metric_form(MCD_HMC_METRIC_ACROSS_CHAINS) on a
+ *   one-launch handle likewise.  Any other value: MCD_ERR_INVALID_ARG.  The form may be set at any time between calls; it survives
+ *   mcd_hmc_set_state, mcd_hmc_set_metric(NULL), mcd_hmc_take_state and mcd_hmc_record_begin / _end.
+ *   The same bits: every output of those entry points -- state, position, ln target, gradient, alpha, depth, tuned step sizes, masses and
+ *   metric, moments, recorder samples with their diagnostics, mcd_mh_hamiltonian_stats, and the gradient kernels' raw outputs, which
+ *   belong to the accepted point afterwards -- is bit for bit what the rounds form gives WHEN ITS LIKELIHOOD GRADIENT RUNS THE
+ *   SUBSTITUTION SWEEP, which is what the automatic choice takes at a sampler's batch.  From 2048 chains, or under a forced form
+ *   (mcd_mvn_set_form, MCD_FORM), the rounds form's likelihood gradient is the multiply form, with that form's bits; the one-launch
+ *   form does not follow it and keeps the sweep's.
+ *   mcd_hmc_get_transition_form: *form = the handle's form.
+ */
+#define MCD_HMC_TRANSITION_ROUNDS 0      /* the default: what runs today */
+#define MCD_HMC_TRANSITION_ONE_LAUNCH 1
+int mcd_hmc_set_transition_form(mcd_hmc_t* m, int form);
+int mcd_hmc_get_transition_form(const mcd_hmc_t* m, int* form);
 /*
  * The factors of a dense metric without a handle, on host arrays: C [dim][dim] row-major; sym receives (C + C^T) / 2 with the diagonal of
  * C, U the lower triangular factor (U U^T = sym), Uinv = U^-1, both with +0.0 above the diagonal, [dim][dim] each; any of the three may be

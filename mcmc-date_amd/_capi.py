@@ -27,6 +27,8 @@ MCD_GLASSO_MAX_DIM = 2048
 MCD_HMC_DENSE_MAX_DIM = 512
 MCD_HMC_METRIC_PER_CHAIN = 0
 MCD_HMC_METRIC_ACROSS_CHAINS = 1
+MCD_HMC_TRANSITION_ROUNDS = 0
+MCD_HMC_TRANSITION_ONE_LAUNCH = 1
 MCD_HMC_DENSE_ACROSS_MAX_DIM = 4098
 MCD_HMC_FACTOR_HOST = 0
 MCD_HMC_FACTOR_DEVICE = 1
@@ -108,6 +110,8 @@ SYMBOLS = {
     "mcd_hmc_get_metric": (C.c_int, [_vp, C.POINTER(C.c_int), _dp]),
     "mcd_hmc_set_metric_form": (C.c_int, [_vp, C.c_int]),
     "mcd_hmc_get_metric_form": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "mcd_hmc_set_transition_form": (C.c_int, [_vp, C.c_int]),
+    "mcd_hmc_get_transition_form": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "mcd_hmc_nuts_warmup_dense": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_double, C.c_int, C.c_uint64, C.c_int64, C.c_uint64, _dp, _dp]),
     "mcd_hmc_set_metric_factor": (C.c_int, [_vp, C.c_int]),
     "mcd_hmc_get_metric_factor": (C.c_int, [_vp, C.POINTER(C.c_int)]),

@@ -1,6 +1,8 @@
 // hmc_capi.cpp -- C ABI of the device leapfrog (include/mcmcdate_mvn.h, "mcd_hmc_*").  The state of `batch` chains, their
 // momenta and gradients stay on the device; one leapfrog step = kick, drift (k_hmc.hip), prior gradient (k_prior_grad.hip),
 // likelihood gradient (k_tree_grad.hip, or k_sparse_grad.hip over a sparse precision matrix: mcd_hmc_create_sparse).  No CPU path.
+// A handle over a small tree may take a whole NUTS transition, or the steps of mcd_hmc_leapfrog, as one launch instead (k_nuts_chain.hip:
+// mcd_hmc_set_transition_form).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -72,6 +74,9 @@ struct mcd_hmc {
     int form = MCD_HMC_METRIC_PER_CHAIN;
     mcd::MetricAcross wx{};
     int wx_slots = 0;
+    // how a transition is launched (mcd_hmc_set_transition_form): MCD_HMC_TRANSITION_ONE_LAUNCH = k_nuts_chain.hip's one launch per transition
+    // and per mcd_hmc_leapfrog, for the handles the setter admits
+    int transition = MCD_HMC_TRANSITION_ROUNDS;
     double warmup_phase[4] = {0, 0, 0, 0};     // seconds of the last mcd_hmc_nuts_warmup_dense: factorisations, covariance, window buffer, transitions
     bool have_state = false;
     hipStream_t stream = nullptr;
@@ -120,6 +125,9 @@ int eval_gradients(mcd_hmc* m)
 
 // the dense metric's products are taken across the chains (k_metric_gemm.hip)
 bool across(const mcd_hmc* m) { return m->dev.metric && m->form == MCD_HMC_METRIC_ACROSS_CHAINS; }
+
+// a transition, and the steps of mcd_hmc_leapfrog, are one launch (k_nuts_chain.hip); the setters keep the across-chains form off such a handle
+bool one_launch(const mcd_hmc* m) { return m->transition == MCD_HMC_TRANSITION_ONE_LAUNCH; }
 
 // under the across-chains form the workspace holds `slots` right-hand sides per chain (1: leapfrog steps; kNutsRhsMaxSlots: NUTS).  Called
 // by the entry points before their first launch, never inside a round.
@@ -514,6 +522,12 @@ int mcd_hmc_leapfrog(mcd_hmc_t* m, double* p, const double* eps, const double* d
     if (int rc = across_alloc(m, 1)) return rc;
     HHIP_TRY(hipMemcpyAsync(D.p, p, sizeof(double) * BD, hipMemcpyHostToDevice, m->stream));
     if (int rc = upload_step_args(m, eps, inv_mass, dir)) return rc;
+    if (one_launch(m)) {                                  // the same sequence inside one launch, a workgroup per chain
+        HHIP_TRY(mcd::launch_leapfrog_chain(D, *m->mvn, *m->tree, *m->prior, n_steps, m->stream));
+        HHIP_TRY(hipMemcpyAsync(p, D.p, sizeof(double) * BD, hipMemcpyDeviceToHost, m->stream));
+        HHIP_TRY(hipStreamSynchronize(m->stream));
+        return MCD_OK;
+    }
     // p += eps/2 g;  [ q += eps Minv p;  g = grad(q);  p += eps g ] x (n - 1);  q += eps Minv p;  g = grad(q);  p += eps/2 g
     // three launches per step (kick + drift fused, prior gradient, likelihood gradient), the closing half kick with the collect
     // (across-chains form of a dense metric: the kick, the product over all chains, the drift)
@@ -672,6 +686,13 @@ int nuts_transition(mcd_hmc* m, int max_depth, uint64_t seed, int64_t chain0, ui
 {
     mcd::HmcDev& D = m->dev;
     D.dir = m->d_dir;
+    if (one_launch(m)) {
+        // everything below up to the recorder's store as ONE launch: no counter is polled, the gradient kernels' raw outputs are the
+        // accepted point's when it ends
+        HHIP_TRY(mcd::launch_nuts_chain(D, m->nuts, *m->mvn, *m->tree, *m->prior, seed, chain0, transition, max_depth, m->d_active, m->stream));
+        if (m->rec.step()) HHIP_TRY(mcd::launch_hmc_record(D, m->nuts, m->rec.view(), m->rec.counts().taken(), m->stream));
+        return MCD_OK;
+    }
     if (int rc = across(m) ? nuts_build_across(m, max_depth, seed, chain0, transition) : nuts_build(m, max_depth, seed, chain0, transition)) return rc;
     HHIP_TRY(mcd::launch_nuts_end(D, m->nuts, m->stream));
     // k_nuts_end put the accepted point into D.q / D.grad / D.value and the state arrays, but the raw outputs of the gradient
@@ -913,7 +934,43 @@ int mcd_hmc_set_metric_form(mcd_hmc_t* m, int form)
         return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_set_metric_form: form = %d is neither MCD_HMC_METRIC_PER_CHAIN nor MCD_HMC_METRIC_ACROSS_CHAINS", form);
     if (m->dev.metric)
         return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_set_metric_form: a dense metric is set on this handle: clear it first (mcd_hmc_set_metric(NULL))");
+    if (form == MCD_HMC_METRIC_ACROSS_CHAINS && one_launch(m))
+        return hfail(MCD_ERR_UNSUPPORTED,
+                     "mcd_hmc_set_metric_form: the handle's transitions are one launch (MCD_HMC_TRANSITION_ONE_LAUNCH), which takes a dense metric's "
+                     "products per chain only: MCD_HMC_METRIC_ACROSS_CHAINS is refused (mcd_hmc_set_transition_form(MCD_HMC_TRANSITION_ROUNDS) first)");
     m->form = form;
+    return MCD_OK;
+}
+
+int mcd_hmc_set_transition_form(mcd_hmc_t* m, int form)
+{
+    if (!m) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_set_transition_form: NULL handle");
+    if (form != MCD_HMC_TRANSITION_ROUNDS && form != MCD_HMC_TRANSITION_ONE_LAUNCH)
+        return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_set_transition_form: form = %d is neither MCD_HMC_TRANSITION_ROUNDS nor MCD_HMC_TRANSITION_ONE_LAUNCH", form);
+    if (form == MCD_HMC_TRANSITION_ONE_LAUNCH) {
+        if (m->sp)
+            return hfail(MCD_ERR_UNSUPPORTED,
+                         "mcd_hmc_set_transition_form: the handle's likelihood is sparse (mcd_hmc_create_sparse, %d distances): one launch per "
+                         "transition serves dense likelihoods of up to %d distances",
+                         m->sp->n, 64);
+        if (m->mvn->R != 1 || !mcd::nuts_chain_available(*m->mvn, *m->tree, *m->prior))
+            return hfail(MCD_ERR_UNSUPPORTED,
+                         "mcd_hmc_set_transition_form: the likelihood has %d distances (a tree of %d nodes): one launch per transition serves up to "
+                         "%d distances (%d nodes), one 64-row block of the factor",
+                         m->mvn->n, m->dev.n_nodes, 64, mcd::kNutsChainMaxNodes);
+        if (m->form == MCD_HMC_METRIC_ACROSS_CHAINS)
+            return hfail(MCD_ERR_UNSUPPORTED,
+                         "mcd_hmc_set_transition_form: the handle takes a dense metric's products across the chains (MCD_HMC_METRIC_ACROSS_CHAINS); "
+                         "one launch per transition takes them per chain only (mcd_hmc_set_metric_form(MCD_HMC_METRIC_PER_CHAIN) first)");
+    }
+    m->transition = form;
+    return MCD_OK;
+}
+
+int mcd_hmc_get_transition_form(const mcd_hmc_t* m, int* form)
+{
+    if (!m || !form) return hfail(MCD_ERR_INVALID_ARG, "mcd_hmc_get_transition_form: NULL argument");
+    *form = m->transition;
     return MCD_OK;
 }
 

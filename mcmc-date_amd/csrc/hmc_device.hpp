@@ -1,6 +1,7 @@
-// hmc_device.hpp -- the position layout and the ln target of the Hamiltonian side, for every kernel file that needs them (k_hmc.hip,
-// k_nuts.hip and k_nuts_across.hip through nuts_device.hpp, k_hmc_record.hip): the gradient entry and the state slot of a coordinate,
-// ln jacobianRootBranch, ln target.  The build contracts no multiply-add, so one expression here gives every caller the same bits.
+// hmc_device.hpp -- the position layout and the ln target of the Hamiltonian side, for every kernel file that needs them (k_hmc.hip and
+// k_nuts_chain.hip through leapfrog_device.hpp, k_nuts.hip and k_nuts_across.hip through nuts_device.hpp, k_hmc_record.hip): the
+// gradient entry and the state slot of a coordinate, ln jacobianRootBranch, ln target.  The build contracts no multiply-add, so one
+// expression here gives every caller the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

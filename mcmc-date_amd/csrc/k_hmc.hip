@@ -10,33 +10,16 @@
 // The gradient comes from the batched kernels (k_prior_grad.hip for the prior, k_tree_grad.hip for the likelihood) plus
 // the five-number Jacobian term (hmc_device.hpp: gradient entry, state slot and ln target of the position layout, shared with
 // the NUTS kernels and the recorder); this file holds the element-wise part: assemble the gradient in the position layout,
-// kick, drift and scatter the new position into the state arrays.  One thread per (chain, coordinate).
+// kick, drift and scatter the new position into the state arrays.  One thread per (chain, coordinate).  What an entry and a chain's workgroup
+// do is written once, in leapfrog_device.hpp, for the kernels here and for the one-launch form (k_nuts_chain.hip).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
-#include "hmc_device.hpp"
-#include "metric_device.hpp"
+#include "leapfrog_device.hpp"
 #include "mvn_kernels.h"
 
 namespace mcd {
-
-// eps_b with the direction of time dir_b (+1 / -1 per chain, null = +1)
-__device__ __forceinline__ double hmc_signed_eps(const HmcDev& D, int64_t b) { return D.eps[b] * (D.dir ? D.dir[b] : 1.0); }
-
-// the kick of entry i of chain b with the gradient entry g, which D.grad keeps
-__device__ __forceinline__ void hmc_kick_entry(const HmcDev& D, int64_t i, int64_t b, double kick, double g)
-{
-    D.p[i] = D.p[i] + kick * hmc_signed_eps(D, b) * g;
-    D.grad[i] = g;
-}
-
-// the position of entry i = (b, k) from the state arrays; coordinate 0 leaves the chain's ln target in D.value
-__device__ __forceinline__ void hmc_collect_entry(const HmcDev& D, int64_t i, int64_t b, int k)
-{
-    D.q[i] = *hmc_state_slot(D, b, D.pos_field[k], D.pos_index[k]);
-    if (k == 0) D.value[b] = hmc_ln_target(D, b);
-}
 
 // p += kick * eps_b * dir_b * grad.  `dir` (+1 / -1 per chain, may be null = +1) integrates backwards in time (NUTS-style
 // doubling).  The drift is a separate launch (k_hmc_drift): the Jacobian term of one coordinate reads state entries that
@@ -81,24 +64,7 @@ __global__ __launch_bounds__(256) void k_hmc_collect(HmcDev D)
     if (i >= D.batch * D.dim) return;
     const int64_t b = i / D.dim;
     const int k = (int)(i - b * D.dim);
-    D.grad[i] = hmc_grad_entry(D, b, D.pos_field[k], D.pos_index[k]);
-    hmc_collect_entry(D, i, b, k);
-}
-
-// q += e (C p) for chain b under the dense metric: the chain's momenta D.p are final (a barrier or a launch boundary lies behind)
-__device__ __forceinline__ void hmc_drift_dense(const HmcDev& D, int64_t b, double e, double* xs)
-{
-    const int64_t o = b * D.dim;
-    double v[kMetricOwned];
-    metric_apply(D.metric, D.dim, false, xs, [&](int k, int) { return D.p[o + k]; }, v);
-    for (int c = 0; c < kMetricOwned; ++c) {
-        const int k = (int)threadIdx.x + 256 * c;
-        if (k >= D.dim) break;
-        double* slot = hmc_state_slot(D, b, D.pos_field[k], D.pos_index[k]);
-        const double q = *slot + e * v[c];
-        *slot = q;
-        D.q[o + k] = q;
-    }
+    hmc_grad_collect_entry(D, i, b, k);
 }
 
 // kick and drift of one leapfrog step in ONE launch: a workgroup per chain, so that a barrier separates "every gradient entry of
@@ -109,25 +75,7 @@ template <bool Dense>
 __global__ __launch_bounds__(256) void k_hmc_kick_drift(HmcDev D, double kick)
 {
     __shared__ double xs[Dense ? kHmcDenseMaxDim : 1];
-    const int64_t b = blockIdx.x;
-    const int64_t o = b * D.dim;
-    const double e = hmc_signed_eps(D, b);
-    for (int k = threadIdx.x; k < D.dim; k += blockDim.x) {
-        const double g = hmc_grad_entry(D, b, D.pos_field[k], D.pos_index[k]);
-        D.grad[o + k] = g;
-        D.p[o + k] = D.p[o + k] + kick * e * g;
-    }
-    __syncthreads();
-    if constexpr (Dense) {
-        hmc_drift_dense(D, b, e, xs);
-    } else {
-        for (int k = threadIdx.x; k < D.dim; k += blockDim.x) {
-            double* slot = hmc_state_slot(D, b, D.pos_field[k], D.pos_index[k]);
-            const double q = *slot + e * D.inv_mass[k] * D.p[o + k];
-            *slot = q;
-            D.q[o + k] = q;
-        }
-    }
+    hmc_kick_drift_chain<Dense>(D, blockIdx.x, kick, xs);
 }
 
 // the stand-alone drift (k_hmc_drift) under a dense metric: a workgroup per chain
@@ -158,8 +106,7 @@ __global__ __launch_bounds__(256) void k_hmc_kick_collect(HmcDev D, double kick)
     if (i >= D.batch * D.dim) return;
     const int64_t b = i / D.dim;
     const int k = (int)(i - b * D.dim);
-    hmc_kick_entry(D, i, b, kick, hmc_grad_entry(D, b, D.pos_field[k], D.pos_index[k]));
-    hmc_collect_entry(D, i, b, k);
+    hmc_kick_collect_entry(D, i, b, k, kick);
 }
 
 static unsigned hmc_grid(const HmcDev& D) { return (unsigned)((D.batch * D.dim + 255) / 256); }

@@ -3,9 +3,8 @@
 
 namespace mcd {
 
-// Chain rule from g = d ll / d distances back to heights, rates, tH, rMu (SURVEY.md 8a A7:
-// d ll/d r_v = s g t_v, d ll/d h_v = s (sum_children g_c r_c - g_v r_v), d ll/d tH = g.d / tH).  One chain per compute wave;
-// e[v] = s * g[row(v)] * rate[v] is exchanged through the (by then idle) LDS ring, one private
+// Both sweeps, then the chain rule from g = d ll / d distances back to heights, rates, tH, rMu (tree_grad_tail, mvn_device.hpp).  One
+// chain per compute wave; e[v] = s * g[row(v)] * rate[v] is exchanged through the (by then idle) LDS ring, one private
 // region per wave.
 template <int R, int CW, int LW>
 __global__ void __launch_bounds__(64 * (CW + LW)) k_tree_grad(MvnDev M, TreeDev T, const double* __restrict__ H,
@@ -44,43 +43,7 @@ __global__ void __launch_bounds__(64 * (CW + LW)) k_tree_grad(MvnDev M, TreeDev 
     // now d = y = Sigma^-1 (dist - mu); g = -y.  The last barrier of the sweep has passed: the ring
     // is free.  n_nodes_pad <= 64 R + 64 doubles per compute wave fit in it (CW * 8.5 KiB <= 64 KiB).
     if (b0 >= batch) return;               // no barriers below
-    const int64_t b = b0;
-    double* e = reinterpret_cast<double*>(ring) + (size_t)wave * T.n_nodes_pad;
-    const double s = tH[b] * rMu[b];
-    const double* h = H + b * lds;
-    const double* r = Rt + b * lds;
-    double gd = 0.0;
-    if (lane == 0) e[0] = 0.0;
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-        const int row = 64 * k + lane;
-        const int a = T.slot_node[row];
-        const double g = -d[k][0];
-        gd = fma(g, dist[k][0], gd);
-        if (a >= 0) {
-            const int pa = T.slot_parent[row];
-            const double sg = s * g;
-            gR[b * lds + a] = sg * (h[pa] - h[a]);
-            e[a] = sg * r[a];
-            if (row == 0) {
-                const int a2 = T.root_right;
-                gR[b * lds + a2] = sg * (h[0] - h[a2]);
-                e[a2] = sg * r[a2];
-            }
-        }
-    }
-    const double gdot = wave_sum(gd);
-    if (lane == 0) {
-        gR[b * lds] = gdot == gdot ? 0.0 : gdot;   // stem rate: unused by the likelihood (a NaN chain: NaN, as every other entry)
-        gtH[b] = gdot / tH[b];
-        grMu[b] = gdot / rMu[b];
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's e[] writes have landed (wave-private region)
-    for (int v = lane; v < T.n_nodes; v += 64) {
-        double acc = (v == 0) ? 0.0 : -e[v];
-        for (int ci = T.child_ptr[v]; ci < T.child_ptr[v + 1]; ++ci) acc += e[T.child_idx[ci]];
-        gH[b * lds + v] = acc;
-    }
+    tree_grad_tail<R>(d, dist, T, H, Rt, lds, tH, rMu, b0, reinterpret_cast<double*>(ring) + (size_t)wave * T.n_nodes_pad, lane, gH, gR, gtH, grMu);
 }
 
 template <int R>

@@ -925,6 +925,52 @@ __device__ __forceinline__ void finish_ll(const double (&d)[R][BT], const MvnVie
     }
 }
 
+// Chain rule from g = d ll / d distances back to heights, rates, tH, rMu (SURVEY.md 8a A7:
+// d ll/d r_v = s g t_v, d ll/d h_v = s (sum_children g_c r_c - g_v r_v), d ll/d tH = g.d / tH) for chain b by the wave that
+// holds d = y = Sigma^-1 (dist - mu), g = -y, after both sweeps.  e[v] = s * g[row(v)] * rate[v] is exchanged through e: n_nodes_pad
+// doubles of LDS private to the wave.  No barriers.  (k_tree_grad.hip; the one-launch NUTS transition, k_nuts_chain.hip)
+template <int R>
+__device__ __forceinline__ void tree_grad_tail(const double (&d)[R][1], const double (&dist)[R][1], const TreeDev& T, const double* H, const double* Rt,
+                                               int64_t lds, const double* tH, const double* rMu, int64_t b, double* e, int lane, double* gH,
+                                               double* gR, double* gtH, double* grMu)
+{
+    const double s = tH[b] * rMu[b];
+    const double* h = H + b * lds;
+    const double* r = Rt + b * lds;
+    double gd = 0.0;
+    if (lane == 0) e[0] = 0.0;
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+        const int row = 64 * k + lane;
+        const int a = T.slot_node[row];
+        const double g = -d[k][0];
+        gd = fma(g, dist[k][0], gd);
+        if (a >= 0) {
+            const int pa = T.slot_parent[row];
+            const double sg = s * g;
+            gR[b * lds + a] = sg * (h[pa] - h[a]);
+            e[a] = sg * r[a];
+            if (row == 0) {
+                const int a2 = T.root_right;
+                gR[b * lds + a2] = sg * (h[0] - h[a2]);
+                e[a2] = sg * r[a2];
+            }
+        }
+    }
+    const double gdot = wave_sum(gd);
+    if (lane == 0) {
+        gR[b * lds] = gdot == gdot ? 0.0 : gdot;   // stem rate: unused by the likelihood (a NaN chain: NaN, as every other entry)
+        gtH[b] = gdot / tH[b];
+        grMu[b] = gdot / rMu[b];
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's e[] writes have landed (wave-private region)
+    for (int v = lane; v < T.n_nodes; v += 64) {
+        double acc = (v == 0) ? 0.0 : -e[v];
+        for (int ci = T.child_ptr[v]; ci < T.child_ptr[v + 1]; ++ci) acc += e[T.child_idx[ci]];
+        gH[b * lds + v] = acc;
+    }
+}
+
 // ---------------------------------------------------------------------------------------
 // Kernel skeleton.  Waves 0 .. CW-1 compute, waves CW .. CW+LW-1 load.  Every wave of a
 // workgroup takes part in every barrier, also compute waves whose chains lie beyond the batch

@@ -316,6 +316,15 @@ hipError_t launch_nuts_begin(const HmcDev& D, const NutsDev& N, uint64_t seed, i
 hipError_t launch_nuts_step(const HmcDev& D, const NutsDev& N, uint64_t seed, int64_t chain0, uint64_t transition, int max_depth, int* active,
                             hipStream_t st);
 hipError_t launch_nuts_end(const HmcDev& D, const NutsDev& N, hipStream_t st);
+// The one-launch form (k_nuts_chain.hip; mcd_hmc_set_transition_form): a whole transition of every chain -- launch_nuts_begin, the rounds
+// of gradients and launch_nuts_step, launch_nuts_end, the gradients at the accepted point and launch_hmc_collect -- or n_steps leapfrog
+// steps with their closing kick and collect (n_steps == 0: the collect alone) as ONE launch, a workgroup per chain.  For the dense
+// likelihoods of one 64-row block (M.R == 1), the diagonal metric or D.metric in the per-chain form.
+constexpr int kNutsChainMaxNodes = 66;     // N <= 64 distances
+bool nuts_chain_available(const MvnDev& M, const TreeDev& T, const PriorDev& P);
+hipError_t launch_nuts_chain(const HmcDev& D, const NutsDev& N, const MvnDev& M, const TreeDev& T, const PriorDev& P, uint64_t seed, int64_t chain0,
+                             uint64_t transition, int max_depth, int* active, hipStream_t st);
+hipError_t launch_leapfrog_chain(const HmcDev& D, const MvnDev& M, const TreeDev& T, const PriorDev& P, int n_steps, hipStream_t st);
 // The dense metric's second form (mcd_hmc_set_metric_form, MCD_HMC_METRIC_ACROSS_CHAINS): the products with C and U^-1 are rows of one
 // matrix product over the lock-step chains (k_metric_gemm.hip) instead of one workgroup's matvec per chain (metric_device.hpp), so no
 // bound on dim comes from a workgroup's registers and LDS.  Y[r][k] = sum_j X[r][j] A[j dim + k], X and Y [rows][dim], A [dim][dim];

@@ -235,6 +235,25 @@ class Leapfrog(DriverCalls):
         _capi.check(_capi.lib().mcd_hmc_get_metric_factor(self._h, ctypes.byref(where)))
         return next(name for name, value in _FACTOR_WHERE.items() if value == where.value)
 
+    _TRANSITION_FORMS = {"rounds": _capi.MCD_HMC_TRANSITION_ROUNDS, "one_launch": _capi.MCD_HMC_TRANSITION_ONE_LAUNCH}
+
+    def set_transition_form(self, form: str):
+        """How a transition is launched (mcd_hmc_set_transition_form): "rounds" (the default: three launches and one host poll per leapfrog
+        step of a tree) or "one_launch" (csrc/k_nuts_chain.hip: a whole transition of every chain, and the steps of leapfrog(), as ONE
+        kernel launch; the same bits as "rounds" with the substitution sweep as its likelihood gradient).  "one_launch" serves dense
+        likelihoods of up to 64 distances (trees of up to 66 nodes) with the diagonal metric or a dense one in the per-chain form;
+        refused otherwise (McdError, Unsupported, the handle untouched).  Allowed at any time between calls."""
+        if form not in self._TRANSITION_FORMS:
+            raise ValueError(f"set_transition_form: {form!r} is none of {sorted(self._TRANSITION_FORMS)}")
+        _capi.check(_capi.lib().mcd_hmc_set_transition_form(self._h, self._TRANSITION_FORMS[form]))
+
+    @property
+    def transition_form(self) -> str:
+        """"rounds" or "one_launch": how the handle launches a transition."""
+        form = ctypes.c_int(-1)
+        _capi.check(_capi.lib().mcd_hmc_get_transition_form(self._h, ctypes.byref(form)))
+        return next(name for name, value in self._TRANSITION_FORMS.items() if value == form.value)
+
     def _metric_uinv(self):
         """The handle's U^-1 [dim, dim] read back from the device (mcd_hmc_metric_uinv_: for tests)."""
         f = _capi.lib().mcd_hmc_metric_uinv_

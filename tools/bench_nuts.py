@@ -27,7 +27,13 @@ One JSON line per run; *_runs hold every repeat, the headline figures are their 
                          host      hmc.run_cycle_with_nuts -- the states cross the host twice per iteration between the two handles;
                          library   Sampler.attach_hamiltonian + Sampler.run -- mcd_mh_run with the attached handle, hand-overs on the device.
                          Milliseconds per iteration (median, every repeat, maximum - minimum of the repeats), mean tree depth and leapfrog
-                         steps per transition.  The measurement runs in a child process under --limit seconds."""
+                         steps per transition.  The measurement runs in a child process under --limit seconds.
+
+  --transition-form {rounds,one_launch}   how the leapfrog handle launches a transition (Leapfrog.set_transition_form): rounds of three
+                         launches with a host poll each, or the whole transition as one launch (csrc/k_nuts_chain.hip; dense likelihoods
+                         of up to 64 distances).  It applies to the plain run, --metric, --record and --cycle library (the attached
+                         handle); the plain run's line carries milliseconds per transition (median and maximum - minimum of the
+                         repeats), the mean tree depth and microseconds per leapfrog step (transition time / mean leapfrog steps)."""
 import argparse
 import ctypes
 import json
@@ -81,6 +87,7 @@ def cycle_report(args):
     topo, smp, lf, eps, inv_mass = golden_setup(args.name, B)
     start = smp.state()
     library = args.cycle == "library"
+    lf.set_transition_form(args.transition_form)
     if library:
         smp.attach_hamiltonian(lf, eps, inv_mass, max_depth=args.max_depth)
 
@@ -114,7 +121,7 @@ def cycle_report(args):
         depth, leaves, divergent = float(nuts[:, :, 0].mean()), float(nuts[:, :, 1].mean()), int(nuts[:, :, 3].sum())
     print(json.dumps({"metric": "Metropolis-Hastings cycle + one NUTS transition per iteration", "cycle": args.cycle, "dataset": args.name,
                       "n_nodes": topo.n_nodes, "chains": B, "iterations": T, "steps_per_iteration": int(sum(p.weight for p in smp.table)),
-                      "max_depth": args.max_depth, "path": smp.last_path(), "ms_per_iteration": float(np.median(runs)), "ms_per_iteration_runs": runs,
+                      "max_depth": args.max_depth, "transition_form": lf.transition_form, "path": smp.last_path(), "ms_per_iteration": float(np.median(runs)), "ms_per_iteration_runs": runs,
                       "spread_ms": max(runs) - min(runs), "mean_depth": depth, "leapfrog_steps_per_transition": leaves, "divergent": divergent}),
           flush=True)
 
@@ -179,7 +186,7 @@ def metric_report(args, topo, lf, eps0, inv_mass0, form):
     ess = summ.ages[inner, 7]
     print(json.dumps({"metric": "NUTS leapfrog steps (all chains in lock step)", "mass_matrix": args.metric,
                       "metric_form": args.metric_form if dense else None, "warmup_phases": phases,
-                      "metric_factor": args.metric_factor if dense else None,
+                      "metric_factor": args.metric_factor if dense else None, "transition_form": lf.transition_form,
                       "dataset": f"synthetic {args.synthetic} leaves" if args.synthetic else args.name, "likelihood": form, "n_nodes": topo.n_nodes,
                       "dim": lf.dim, "chains": B, "windows": args.windows, "window": args.window, "transitions": T, "max_depth": args.max_depth,
                       "warmup_s": warm_s, "warmup_mean_alpha": float(alpha_w.mean()), "eps_mean": float(eps.mean()), "eps_min": float(eps.min()),
@@ -205,6 +212,7 @@ def main():
     ap.add_argument("--windows", type=int, default=3)
     ap.add_argument("--window", type=int, default=60)
     ap.add_argument("--cycle", choices=("host", "library"), default=None)
+    ap.add_argument("--transition-form", choices=("rounds", "one_launch"), default="rounds")
     ap.add_argument("--limit", type=int, default=300, help="seconds the child process of --cycle may take")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -224,6 +232,7 @@ def main():
         ap.error("--metric-factor is valid with --metric dense")
     B, T = args.chains, args.transitions
     topo, lf, eps, inv_mass, form = synthetic_problem(args.synthetic, B) if args.synthetic else golden_problem(args.name, B)
+    lf.set_transition_form(args.transition_form)
     if args.metric:
         return metric_report(args, topo, lf, eps, inv_mass, form)
     start = lf.state()
@@ -250,11 +259,22 @@ def main():
         ends["recorded"] = lf.state()
         runs["cut"].append(timed(cut))
         ends["cut"] = lf.state()
+    lf.set_state(start)                                                # one more pass, untimed, for the trees' sizes
+    # (monitor.record_nuts above ends its own recording before it returns, so no recorder is active here)
+    lf.record_begin(period=1, capacity=T)
+    lf.nuts_run(T, eps, inv_mass, adapt=False, **kw)
+    nuts = lf.record_fetch()[-1]                                       # [T, B, 6] = Leapfrog.NUTS_FIELDS
+    lf.record_end()
+    ms = [1e3 * v / T for v in runs["unrecorded"]]
+    steps = float(nuts[:, :, 1].mean())
     same = all(np.array_equal(ends["unrecorded"].heights, ends[k].heights) and np.array_equal(ends["unrecorded"].rates, ends[k].rates) for k in ends)
     rate = {k: T / float(np.median(v)) for k, v in runs.items()}
     spread = {k: (max(v) - min(v)) / float(np.median(v)) for k, v in runs.items()}
     print(json.dumps({"metric": "NUTS transitions/s (all chains in lock step)", "dataset": f"synthetic {args.synthetic} leaves" if args.synthetic else args.name,
                       "likelihood": form, "n_nodes": topo.n_nodes, "chains": B, "transitions": T, "max_depth": args.max_depth, "record_period": args.record,
+                      "transition_form": lf.transition_form, "ms_per_transition": float(np.median(ms)), "ms_per_transition_runs": ms,
+                      "spread_ms": max(ms) - min(ms), "mean_depth": float(nuts[:, :, 0].mean()), "leapfrog_steps_per_transition": steps,
+                      "us_per_leapfrog_step": 1e3 * float(np.median(ms)) / max(1.0, steps),
                       "unrecorded_transitions_per_s": rate["unrecorded"], "recorded_transitions_per_s": rate["recorded"],
                       "cut_transitions_per_s": rate["cut"], "recorded_over_cut": rate["recorded"] / rate["cut"],
                       "recorded_over_unrecorded": rate["recorded"] / rate["unrecorded"], "same_end_state": bool(same),
